@@ -427,6 +427,19 @@ def reinforce_main(args, world, rank):
     return 0
 
 
+def dump_outputs(out_dir, eng):
+    """--dump-outputs: what the timed path hands its caller after its last step -- that step's losses (float64) and the fp32 master
+    parameters of every network (float32, the whole tensors: ~7 MB for DDPG, ~10 MB for TD3) -- as out_dir/<name>.npy."""
+    from recnn_amd.nn.engine import NET_NAMES_DDPG, NET_NAMES_TD3
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in eng.losses().items():                     # (synchronises the engine's stream)
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), np.array([v], dtype=np.float64))
+    torch.cuda.synchronize()
+    for net, ni in (NET_NAMES_TD3 if eng.td3 else NET_NAMES_DDPG).items():
+        for p, t in eng.param_views(ni).items():
+            np.save(os.path.join(out_dir, f"{net}.{p}.npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,7 +467,12 @@ def main():
                          "sustained region, no sub-records: the child's kernel trace then holds the replayed schedule and nothing else")
     ap.add_argument("--preflight", action="store_true",
                     help="N > 1 diagnostics instead of the benchmark: one JSON object per stage (tools/multigpu_preflight.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step computed (its losses, every network's parameters) "
+                         "as DIR/<name>.npy (rank 0; ddpg / td3)")
     args = ap.parse_args()
+    if args.dump_outputs and args.algo == "reinforce":
+        raise SystemExit("--dump-outputs: supported for --algo ddpg / td3")
 
     if args.preflight:
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -633,6 +651,8 @@ def main():
             run(args.warmup + r * args.steps, args.steps)
             barrier()
             samples.append(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eng)
     # the same path over ONE long region (whole policy cycles per run graph): the short timed regions above carry ~100 us of fixed cost each
     # (graph launch, loss read-back), which a 20-step region does not amortise -- both figures go into the line
     sustained = None

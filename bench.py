@@ -9,6 +9,12 @@ all inside librecnn_hip.so (hipGraph replay), inputs resident in HBM.  Nothing i
 Contract (driver): python bench.py --gpus N --steps K --warmup W  -> ONE JSON line on rank 0.
 value = total update steps/s over all ranks (weak scaling: every rank runs its own B=2048 step on its own shard
 of the replay users; gradients are all-reduced over RCCL when N > 1).
+
+A plain run does only what that line's headline needs: set up, warm up, time the `--repeats` regions of K steps, write
+--dump-outputs, print.  --full adds everything else the line has carried: the sustained 2000-step region, the per-launch
+profile and rooflines (with two rocprofv3 child runs for PMC traffic), the sub-records (parity mode, other configs, loss-curve
+deviation from the CPU oracle), the CPU baseline and, for N > 1, the timing of both collectives; --no-traffic / --no-extras /
+--no-cpu-baseline then leave out their part of it.
 """
 import argparse
 import json
@@ -450,8 +456,11 @@ def main():
                     help="td3 --rows 4096 = BASELINE.json configs[2]; reinforce = configs[4]: Top-K REINFORCE at a 100k-item catalogue, the catalogue "
                          "dimension sharded over --gpus ranks (tools/reinforce_bench.py)")
     ap.add_argument("--rows", type=int, default=B_ROWS, help="transition rows per step per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child runs behind roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: sustained region, per-launch profile and rooflines, PMC traffic child runs, sub-records "
+                         "(parity_mode, other_configs, loss-curve deviation), CPU baseline, N > 1 collective A/B")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) skip the two rocprofv3 --pmc child runs behind roofline.traffic")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank steps on its own --rows rows (headline); strong: the GLOBAL batch is --rows rows, "
                          "each rank takes rows/N of it")
@@ -461,7 +470,7 @@ def main():
                          "the peers cannot be mapped) or host-issued RCCL all-reduces")
     ap.add_argument("--force-dp", action="store_true", help="run the data-parallel stepper even with one rank (tests the N>1 path)")
     ap.add_argument("--repeats", type=int, default=5, help="timed regions of `--steps` steps each; value = their median")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sub-records (parity_mode, other_configs, loss-curve deviation)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the sub-records (parity_mode, other_configs, loss-curve deviation)")
     ap.add_argument("--child-trace", action="store_true",
                     help="(internal: the rocprofv3 child runs behind roofline.traffic) the timed regions only -- no eager per-launch profile, no "
                          "sustained region, no sub-records: the child's kernel trace then holds the replayed schedule and nothing else")
@@ -654,9 +663,9 @@ def main():
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, eng)
     # the same path over ONE long region (whole policy cycles per run graph): the short timed regions above carry ~100 us of fixed cost each
-    # (graph launch, loss read-back), which a 20-step region does not amortise -- both figures go into the line
+    # (graph launch, loss read-back), which a 20-step region does not amortise -- with --full both figures go into the line
     sustained = None
-    if not use_dp and args.steps < 2000 and not args.child_trace:
+    if args.full and not use_dp and args.steps < 2000 and not args.child_trace:
         with torch.cuda.stream(stream):
             first = args.warmup + reps * args.steps
             run(first, 200)
@@ -674,7 +683,7 @@ def main():
     elapsed = float(np.median(samples))
     losses = eng.losses()
     collective_ab = None
-    if use_dp and world > 1 and not args.child_trace:
+    if args.full and use_dp and world > 1 and not args.child_trace:
         # ---- ONE run decides between the collectives: per-collective latency at the two gradient sizes, and the
         # same data-parallel steps with the OTHER exchange (host-issued RCCL all-reduces between phase graphs), timed like the headline
         single = bool(os.environ.get("RECNN_BENCH_SINGLE_DEVICE"))
@@ -780,6 +789,7 @@ def main():
             if world > 1:
                 out["config"]["workload"] += (f"; N = {world}: value = rank-steps/s (every rank steps on its own {rows}-row batch, one gradient "
                                               "all-reduce per optimizer step), global_updates_per_s = synchronised updates/s")
+    if rank == 0 and args.full:
         # ---- per-launch times, measured live with HIP events around every launch (eager replays of the same steps on the stream
         # the kernels run on), and the rooflines they imply.  Two schedules exist and agree bit for bit (profiles/NOTES_r01_r05.md 5c):
         #   "fused": one row-panel launch for all networks of a step (csrc/mlps.hip) -- eager steps and run graphs shorter than

@@ -23,8 +23,8 @@ def _run(cmd, extra_env, timeout=600):
 
 
 def test_bench_two_ranks_on_one_gpu_prints_the_multi_gpu_record(cuda):
-    out, lines = _run(["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "2", "--no-extras", "--no-cpu-baseline",
-                       "--no-traffic"], {})
+    out, lines = _run(["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "2", "--full", "--no-extras",
+                       "--no-cpu-baseline", "--no-traffic"], {})
     assert out["n_gpus"] == 2 and out["metric"].startswith("DDPG update steps/sec") and out["scaling"] == "weak"
     mg = out["multi_gpu"]
     assert mg["world_size"] == 2 and mg["backend"] == "gloo" and mg["ranks_share_one_gpu"] is True

@@ -1,6 +1,6 @@
 import csv, sys, collections
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    rows = list(csv.DictReader(open(f"gpurun_out/pmc_{c}/p_counter_collection.csv")))
+    rows = list(csv.DictReader(open(f"{sys.argv[1]}/pmc_{c}/p_counter_collection.csv")))     # usage: python tools/pmc.py DIR
     agg = collections.defaultdict(list)
     for r in rows:
         agg[r["Kernel_Name"][:60]].append(float(r["Counter_Value"]))

@@ -58,7 +58,8 @@ enum {
 int recnn_abi_version(void);
 const char* recnn_last_error(void);
 /* sizeof() of an ABI struct: 0 recnn_gemm_args, 1 recnn_engine_config, 2 recnn_hyper,
- * 3 recnn_engine_sizes, 4 recnn_sampler, 5 recnn_engine_tuning, 6 recnn_shadow_out (lets a binding verify its declarations);
+ * 3 recnn_engine_sizes, 4 recnn_sampler, 5 recnn_engine_tuning, 6 recnn_shadow_out, 7 recnn_ae_params, 8 recnn_ae_grads (lets a
+ * binding verify its declarations);
  * -1 if unknown. */
 int64_t recnn_abi_sizeof(int which);
 /* =====================================================================================
@@ -624,6 +625,55 @@ int recnn_topk_workspace_bytes(int n_queries, int k, int64_t* h_bytes);
 int recnn_topk_search(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
                       int metric, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
                       void* stream);
+
+/* =====================================================================================
+ * 6. Anomaly detector: the reference's debugging autoencoder (recnn/nn/models.py:7-38)
+ *    x[128] -> Linear(128,64) ReLU BN(64) -> Linear(64,32) ReLU BN(32) -> Linear(32,64) ReLU BN(64)
+ *           -> Linear(64,128) ReLU;  rec_error(x) = sum((x - ae(x))^2, 1).
+ *    Widths are fixed.  fp32 throughout (exact-f32 MFMA), every reduction in a fixed order: two identical calls give
+ *    bit-identical outputs, gradients and running statistics.
+ *
+ *    Layouts: x is [rows, 128] with row stride ldx (unit column stride; any ldx >= 128); out is [rows, 128] (ldo), err is
+ *    float[rows].  Weights are nn.Linear's [out, in] row-major arrays, contiguous and 16-byte aligned.  BatchNorm i (i = 0, 1, 2)
+ *    normalises the output of Linear i.  act (train-style forward / backward) holds the activations backward needs,
+ *    recnn_ae_act_floats(rows) floats, 16-byte aligned.  workspace: recnn_ae_workspace_bytes(rows) bytes, 16-byte aligned.
+ *    Errors: RECNN_E_INVALID for a null pointer, a misaligned operand, rows < 0, or rows < 2 in train mode.
+ * ===================================================================================== */
+typedef struct recnn_ae_params {
+  const float* w[4];              /* [64,128] [32,64] [64,32] [128,64] */
+  const float* b[4];              /* [64] [32] [64] [128] */
+  const float* gamma[3];          /* BatchNorm weight [64] [32] [64] */
+  const float* beta[3];           /* BatchNorm bias */
+  float* running_mean[3];         /* read in eval mode; updated in train mode (momentum, unbiased variance) */
+  float* running_var[3];
+  int64_t* num_batches_tracked[3];  /* incremented once per train-mode forward */
+  float eps[3];
+  float momentum[3];
+} recnn_ae_params;
+
+typedef struct recnn_ae_grads {  /* outputs of recnn_ae_backward, shaped like the parameters */
+  float* w[4];
+  float* b[4];
+  float* gamma[3];
+  float* beta[3];
+} recnn_ae_grads;
+
+int recnn_ae_act_floats(int rows, int64_t* h_floats);
+int recnn_ae_workspace_bytes(int rows, int64_t* h_bytes);
+/* Eval mode (running statistics), ONE launch: exactly one of out (forward) and err (rec_error; the 128-wide output is never
+ * stored) is non-NULL.  rows == 0 launches nothing. */
+int recnn_ae_eval(const recnn_ae_params* h_p, const float* x, int64_t ldx, int rows, float* out, int64_t ldo, float* err,
+                  void* stream);
+/* Segmented forward, four launches (one per BatchNorm seam).  train = 1: batch statistics (biased variance), running statistics
+ * and num_batches_tracked updated; train = 0: running statistics.  Writes a0..a2 (post-ReLU) into act always and the normalised
+ * h0..h2 plus the statistics used only when keep != 0 (what recnn_ae_backward reads).  Exactly one of out / err non-NULL. */
+int recnn_ae_forward(const recnn_ae_params* h_p, int train, const float* x, int64_t ldx, int rows, float* out, int64_t ldo,
+                     float* err, float* act, int keep, void* workspace, void* stream);
+/* Gradients of sum(dout * out) for the forward that filled act (keep = 1) with the same train flag: every field of h_g is
+ * written; dx (may be NULL) gets d/dx.  dout: [rows, 128] (ld_dout), out: that forward's output (ldo). */
+int recnn_ae_backward(const recnn_ae_params* h_p, const recnn_ae_grads* h_g, int train, const float* x, int64_t ldx, int rows,
+                      const float* out, int64_t ldo, const float* dout, int64_t ld_dout, const float* act, float* dx,
+                      int64_t lddx, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

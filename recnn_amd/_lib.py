@@ -54,6 +54,18 @@ class ShadowOut(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("cols", C.c_int), ("ld", C.c_int64), ("bf16", C.c_int)]
 
 
+class AeParams(C.Structure):
+    """include/recnn_hip.h recnn_ae_params (the anomaly detector's parameters and BatchNorm state)"""
+    _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3),
+                ("running_mean", C.c_void_p * 3), ("running_var", C.c_void_p * 3), ("num_batches_tracked", C.c_void_p * 3),
+                ("eps", C.c_float * 3), ("momentum", C.c_float * 3)]
+
+
+class AeGrads(C.Structure):
+    """include/recnn_hip.h recnn_ae_grads"""
+    _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [
         ("algo", C.c_int), ("dtype", C.c_int), ("state_dim", C.c_int), ("action_dim", C.c_int),
@@ -192,6 +204,11 @@ SIGNATURES = {
     "recnn_topk_item_aux": (_I, [_P, _I, _I, _I, _P, _P]),
     "recnn_topk_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
     "recnn_topk_search": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "recnn_ae_act_floats": (_I, [_I, C.POINTER(_L)]),
+    "recnn_ae_workspace_bytes": (_I, [_I, C.POINTER(_L)]),
+    "recnn_ae_eval": (_I, [C.POINTER(AeParams), _P, _L, _I, _P, _L, _P, _P]),
+    "recnn_ae_forward": (_I, [C.POINTER(AeParams), _I, _P, _L, _I, _P, _L, _P, _P, _I, _P, _P]),
+    "recnn_ae_backward": (_I, [C.POINTER(AeParams), C.POINTER(AeGrads), _I, _P, _L, _I, _P, _L, _P, _L, _P, _P, _L, _P, _P]),
     "recnn_engine_buffer": (_P, [_P, C.c_char_p, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
 }
 
@@ -228,7 +245,8 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    for which, st in enumerate((GemmArgs, EngineConfig, Hyper, EngineSizes, Sampler, EngineTuning, ShadowOut)):
+    for which, st in enumerate((GemmArgs, EngineConfig, Hyper, EngineSizes, Sampler, EngineTuning, ShadowOut,
+                                     AeParams, AeGrads)):
         if lib.recnn_abi_sizeof(which) != C.sizeof(st):
             raise RecnnHipError(f"ABI mismatch for {st.__name__}: C={lib.recnn_abi_sizeof(which)} py={C.sizeof(st)}")
     _lib = lib

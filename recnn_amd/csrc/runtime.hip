@@ -30,6 +30,8 @@ extern "C" int64_t recnn_abi_sizeof(int which) {
     case 4: return (int64_t)sizeof(recnn_sampler);
     case 5: return (int64_t)sizeof(recnn_engine_tuning);
     case 6: return (int64_t)sizeof(recnn_shadow_out);
+    case 7: return (int64_t)sizeof(recnn_ae_params);
+    case 8: return (int64_t)sizeof(recnn_ae_grads);
     default: return -1;
   }
 }

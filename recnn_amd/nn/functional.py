@@ -937,3 +937,146 @@ def mlp_onehot(state, idx, n_state, module, train: bool):
     return MLPFunction.apply(state.float(), w_state, module.linear1.bias, module.linear2.weight, module.linear2.bias,
                              module.linear3.weight, module.linear3.bias, train, torch.initial_seed(),
                              _take_forced_masks(module, train), cols)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The reference's debugging autoencoder (recnn/nn/models.py:7-38, `AnomalyDetector`) over csrc/anomaly.hip.
+# Replaces the Sequential's addmm / relu / batch_norm chain, `sum((x - ae(x)) ** 2, 1)` and their autograd backward.
+
+_AE_WIDTHS = ((128, 64), (64, 32), (32, 64), (64, 128))
+
+
+def _ae_layers(ae):
+    """(the four Linear modules, the three BatchNorm1d modules) of the reference's Sequential, checked."""
+    lins, bns = [ae[0], ae[3], ae[6], ae[9]], [ae[2], ae[5], ae[8]]
+    for lin, (i, o) in zip(lins, _AE_WIDTHS):
+        if lin.in_features != i or lin.out_features != o or lin.bias is None:
+            raise ValueError(f"AnomalyDetector: expected Linear({i}, {o}) with bias, got {lin}")
+    for bn in bns:
+        if bn.momentum is None:
+            raise NotImplementedError("AnomalyDetector: BatchNorm1d(momentum=None) (cumulative average) is not supported")
+        if not bn.affine:
+            raise NotImplementedError("AnomalyDetector: BatchNorm1d(affine=False) is not supported")
+        if not bn.track_running_stats:
+            raise NotImplementedError("AnomalyDetector: BatchNorm1d(track_running_stats=False) is not supported")
+    return lins, bns
+
+
+def _ae_params(lins, bns, tensors=None):
+    """recnn_ae_params for the modules; `tensors` (w0, b0, ..., w3, b3, g0, be0, ..., g2, be2) overrides the parameters."""
+    if tensors is None:
+        tensors = [t for lin in lins for t in (lin.weight, lin.bias)] + [t for bn in bns for t in (bn.weight, bn.bias)]
+    for t in tensors:
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+            raise L.RecnnHipError("recnn_amd AnomalyDetector: parameters must be contiguous float32 GPU tensors")
+    p = L.AeParams()
+    for i in range(4):
+        p.w[i], p.b[i] = tensors[2 * i].data_ptr(), tensors[2 * i + 1].data_ptr()
+    for i, bn in enumerate(bns):
+        p.gamma[i], p.beta[i] = tensors[8 + 2 * i].data_ptr(), tensors[9 + 2 * i].data_ptr()
+        for name in ("running_mean", "running_var"):
+            buf = getattr(bn, name)
+            if not buf.is_cuda or buf.dtype != torch.float32 or not buf.is_contiguous():
+                raise L.RecnnHipError(f"recnn_amd AnomalyDetector: BatchNorm {name} must be a contiguous float32 GPU tensor")
+            getattr(p, name)[i] = buf.data_ptr()
+        p.num_batches_tracked[i] = bn.num_batches_tracked.data_ptr()
+        p.eps[i], p.momentum[i] = float(bn.eps), float(bn.momentum)
+    return p
+
+
+def _ae_input(x):
+    if not x.is_cuda:
+        raise L.RecnnHipError("recnn_amd AnomalyDetector: needs GPU tensors (no CPU fallback)")
+    if x.dim() != 2 or x.shape[1] != 128 or x.dtype != torch.float32:
+        raise ValueError(f"AnomalyDetector: input must be float32 [rows, 128], got {tuple(x.shape)} {x.dtype}")
+    if x.stride(1) != 1 or x.stride(0) < 128 or x.data_ptr() % 16 or x.stride(0) % 4:
+        x = x.contiguous()
+    return x
+
+
+def _ae_buffers(rows, device):
+    n_act, n_ws = C.c_int64(), C.c_int64()
+    L.call("recnn_ae_act_floats", rows, C.byref(n_act))
+    L.call("recnn_ae_workspace_bytes", rows, C.byref(n_ws))
+    return torch.empty(n_act.value, device=device), torch.empty((n_ws.value + 3) // 4, device=device)
+
+
+def _ae_run(x, lins, bns, train, want_err, keep, tensors=None):
+    """(out or err, act, workspace): one eval launch, or the four-launch forward when training or keeping activations."""
+    rows = x.shape[0]
+    if train and rows < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    p = _ae_params(lins, bns, tensors)
+    res = torch.empty(rows, device=x.device) if want_err else torch.empty(rows, 128, device=x.device)
+    err, out = (res, None) if want_err else (None, res)
+    if rows == 0:
+        return res, None, None
+    if not train and not keep:
+        L.call("recnn_ae_eval", C.byref(p), L.ptr(x), x.stride(0), rows, L.ptr(out), 128, L.ptr(err), L.current_stream())
+        return res, None, None
+    act, ws = _ae_buffers(rows, x.device)
+    L.call("recnn_ae_forward", C.byref(p), int(train), L.ptr(x), x.stride(0), rows, L.ptr(out), 128, L.ptr(err), L.ptr(act),
+           int(keep), L.ptr(ws), L.current_stream())
+    return res, act, ws
+
+
+class AnomalyDetectorFunction(torch.autograd.Function):
+    """out = ae(x) for the reference's autoencoder Sequential `ae`; train mode normalises with batch statistics and updates the
+    running ones (as BatchNorm1d does, with or without grad), eval mode uses the running statistics."""
+
+    @classmethod
+    def apply(cls, x, ae, train, *tensors):
+        # (Function.forward runs with grad mode off: whether a backward can exist is decided here)
+        return super().apply(x, ae, train, torch.is_grad_enabled(), *tensors)
+
+    @staticmethod
+    def forward(ctx, x, ae, train, grad_mode, *tensors):
+        lins, bns = _ae_layers(ae)
+        xin = _ae_input(x)
+        keep = bool(grad_mode and (x.requires_grad or any(t.requires_grad for t in tensors)))
+        out, act, ws = _ae_run(xin, lins, bns, train, False, keep and xin.shape[0] > 0, tensors)
+        ctx.train, ctx.bns = bool(train), bns
+        if keep:
+            ctx.save_for_backward(xin, out, act, ws, *tensors)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xin, out, act, ws, *tensors = ctx.saved_tensors
+        rows = xin.shape[0]
+        grads = [torch.empty_like(t) for t in tensors]
+        dx = torch.empty(rows, 128, device=xin.device) if ctx.needs_input_grad[0] else None
+        if rows == 0:
+            return (None if dx is None else dx, None, None, None, *[g.zero_() for g in grads])
+        dout = dout.float()
+        if dout.stride(1) != 1 or dout.stride(0) < 128:
+            dout = dout.contiguous()
+        p = _ae_params(None, ctx.bns, tensors)
+        g = L.AeGrads()
+        for i in range(4):
+            g.w[i], g.b[i] = grads[2 * i].data_ptr(), grads[2 * i + 1].data_ptr()
+        for i in range(3):
+            g.gamma[i], g.beta[i] = grads[8 + 2 * i].data_ptr(), grads[9 + 2 * i].data_ptr()
+        L.call("recnn_ae_backward", C.byref(p), C.byref(g), int(ctx.train), L.ptr(xin), xin.stride(0), rows, L.ptr(out), 128,
+               L.ptr(dout), dout.stride(0), L.ptr(act), L.ptr(dx), 128, L.ptr(ws), L.current_stream())
+        need = ctx.needs_input_grad[4:]
+        return (dx, None, None, None, *[gr if nd else None for gr, nd in zip(grads, need)])
+
+
+def _ae_tensors(lins, bns):
+    return [t for lin in lins for t in (lin.weight, lin.bias)] + [t for bn in bns for t in (bn.weight, bn.bias)]
+
+
+def anomaly_forward(x, ae, train: bool):
+    """ae(x) for the reference's AnomalyDetector Sequential on the HIP kernels (differentiable)."""
+    lins, bns = _ae_layers(ae)
+    return AnomalyDetectorFunction.apply(x, ae, bool(train), *_ae_tensors(lins, bns))
+
+
+def anomaly_rec_error(x, ae, train: bool):
+    """sum((x - ae(x)) ** 2, 1), fused: the 128-wide output is never stored.  Not differentiable (the reference detaches it);
+    in train mode the running statistics are updated, as the reference's train-mode call does."""
+    lins, bns = _ae_layers(ae)
+    xin = _ae_input(x)
+    err, _, _ = _ae_run(xin, lins, bns, bool(train), True, False)
+    return err

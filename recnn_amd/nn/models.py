@@ -1,4 +1,4 @@
-"""Actor / Critic / DiscreteActor / bcqPerturbator / bcqGenerator
+"""AnomalyDetector (reference: recnn/nn/models.py:7-38), Actor / Critic / DiscreteActor / bcqPerturbator / bcqGenerator
 (reference: recnn/nn/models.py:41-73, :187-213, :76-184, :216-242, :245-295) and the Soft Actor-Critic networks of the
 reference's `examples/1. Vanilla RL/4. SAC.ipynb` (StateCritic, SoftQ, StochasticActor: code cells 5-7).
 
@@ -15,7 +15,33 @@ import torch.nn as nn
 
 from . import functional as F_hip
 
-__all__ = ["Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor"]
+__all__ = ["AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor"]
+
+
+class AnomalyDetector(nn.Module):
+    """The reference's debugging autoencoder (models.py:7-38): 128 -> 64 -> 32 -> 64 -> 128, each hidden Linear followed by ReLU
+    then BatchNorm1d, the output by ReLU.  `self.ae` is the same plain nn.Sequential (state_dict keys `ae.0.weight` ... `ae.9.bias`,
+    constructor RNG consumption, `load_state_dict(torch.load('anomaly.pt'))`); `forward` and `rec_error` run on the HIP kernels
+    (`functional.anomaly_forward` / `anomaly_rec_error`, csrc/anomaly.hip), in train mode with batch statistics and running-statistic
+    updates as BatchNorm1d has them.  Input: float32 [rows, 128] on the GPU."""
+
+    def __init__(self):
+        super().__init__()
+        self.ae = nn.Sequential(
+            nn.Linear(128, 64), nn.ReLU(), nn.BatchNorm1d(64),
+            nn.Linear(64, 32), nn.ReLU(), nn.BatchNorm1d(32),
+            nn.Linear(32, 64), nn.ReLU(), nn.BatchNorm1d(64),
+            nn.Linear(64, 128), nn.ReLU(),
+        )
+
+    def forward(self, x):
+        return F_hip.anomaly_forward(x, self.ae, self.training)
+
+    def rec_error(self, x):
+        error = F_hip.anomaly_rec_error(x, self.ae, self.training)
+        if x.size(1) != 1:
+            return error.detach()
+        return error.item()
 
 
 class Actor(nn.Module):

@@ -78,3 +78,34 @@ class Plotter:
                 ax.plot(self.loss["test"]["step"], self.loss["test"][key], "r-.", label="test")
             plt.legend()
         plt.show()
+
+    @staticmethod
+    def kde_reconstruction_error(ad, gen_actions, true_actions, device=torch.device("cpu")):
+        """Densities of the anomaly detector's reconstruction errors of generated and of true actions (plot.py:96-122): both sets
+        scored with `ad.rec_error`, a Gaussian KDE fitted to each, evaluated on linspace(0, 1000, 100).  Inputs: numpy arrays or
+        tensors (on any device)."""
+        import matplotlib
+        matplotlib.use("Agg", force=False)
+        import matplotlib.pyplot as plt
+        from scipy import stats
+
+        def rec_score(actions):
+            t = torch.as_tensor(actions).to(device).float()
+            return ad.rec_error(t).detach().cpu().numpy()
+
+        true_scores = rec_score(true_actions)
+        gen_scores = rec_score(gen_actions)
+        true_kernel = stats.gaussian_kde(true_scores)
+        gen_kernel = stats.gaussian_kde(gen_scores)
+        x = np.linspace(0, 1000, 100)
+        fig = plt.figure(figsize=(16, 10))
+        ax = fig.add_subplot(111)
+        ax.plot(x, true_kernel(x), "-b", label="true dist")
+        ax.plot(x, gen_kernel(x), "-r", label="generated dist")
+        ax.legend()
+        return fig
+
+    @staticmethod
+    def plot_kde_reconstruction_error(*args, **kwargs):
+        fig = Plotter.kde_reconstruction_error(*args, **kwargs)
+        fig.show()

@@ -612,8 +612,8 @@ const void* recnn_engine_buffer(recnn_engine* e, const char* name, int64_t* h_ro
 /* =====================================================================================
  * 5. Batched exact top-K action scoring ("next" row)
  *    replaces the retrieval step after the actor: faiss IndexFlatL2 / IndexFlatIP / IP on normalised rows
- *    (examples/streamlit_demo.py:190-204), the per-item scipy loop `rank` (streamlit_demo.py:207-231) and
- *    MilvusConnection.search (recnn/data/db_con.py:45-56).
+ *    (examples/streamlit_demo.py:190-204) and MilvusConnection.search (recnn/data/db_con.py:45-56).  The per-item
+ *    scipy loop `rank` (streamlit_demo.py:207-231) and its metrics are section 7.
  *    metric: 0 = IP (q.t, descending), 1 = L2 (|q-t|^2, ascending), 2 = COS (q.t/|t|, descending).
  *    Ties are broken towards the smaller item id.  emb_dim must be 128, k <= 64.
  * ===================================================================================== */
@@ -674,6 +674,37 @@ int recnn_ae_forward(const recnn_ae_params* h_p, int train, const float* x, int6
 int recnn_ae_backward(const recnn_ae_params* h_p, const recnn_ae_grads* h_g, int train, const float* x, int64_t ldx, int rows,
                       const float* out, int64_t ldo, const float* dout, int64_t ld_dout, const float* act, float* dx,
                       int64_t lddx, void* workspace, void* stream);
+
+/* =====================================================================================
+ * 7. Ranking under scipy's distance metrics: the reference's per-item scipy loop `rank`
+ *    (examples/streamlit_demo.py:207-231; examples/[Results]/1. Ranking.ipynb).  Each metric is
+ *    scipy.spatial.distance.cdist's (scipy 1.15), computed in fp32 with a fixed summation order over the 128 elements
+ *    (DESIGN.md 11): a pair's distance does not depend on the batch, the tile or the call, and recnn_dist_topk reports
+ *    bit for bit what recnn_dist_matrix stores.  minkowski needs p >= 1 (p = inf allowed); p = 1, 2, inf give the bits of
+ *    cityblock, euclidean, chebyshev.  NaN distances (cosine against a zero row, correlation against a constant row,
+ *    braycurtis(0, 0)) are reported as NaN and rank after every number; ties go to the smaller item id.
+ *    Limits: emb_dim == 128, k <= 64 and k <= n_items, ld_q % 4 == 0, queries / table / aux / workspace 16-byte aligned.
+ *    Errors: RECNN_E_INVALID, before any HIP call, for an unknown metric, p < 1 or NaN for minkowski, a null pointer, a
+ *    misaligned operand, a missing aux (cosine / correlation) and the limits above.
+ * ===================================================================================== */
+enum {
+  RECNN_DIST_SQEUCLIDEAN = 0, RECNN_DIST_EUCLIDEAN = 1, RECNN_DIST_CITYBLOCK = 2, RECNN_DIST_CHEBYSHEV = 3,
+  RECNN_DIST_MINKOWSKI = 4, RECNN_DIST_CANBERRA = 5, RECNN_DIST_BRAYCURTIS = 6, RECNN_DIST_COSINE = 7,
+  RECNN_DIST_CORRELATION = 8
+};
+/* floats of the per-table aux array: n_items * 128 for cosine / correlation (normalised, centred rows), else 0 */
+int recnn_dist_item_aux_floats(int n_items, int emb_dim, int metric, int64_t* h_floats);
+/* builds the aux rows of `table` (cosine / correlation only); once per table */
+int recnn_dist_item_aux(const float* table, int n_items, int emb_dim, int metric, float* aux, void* stream);
+/* workspace of one call: k = 0 for recnn_dist_matrix, else the k of recnn_dist_topk */
+int recnn_dist_workspace_bytes(int n_queries, int n_items, int metric, int k, int64_t* h_bytes);
+/* out float[n_queries, n_items] with row stride ld_out >= n_items */
+int recnn_dist_matrix(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                      int metric, double p, const float* item_aux, float* out, int64_t ld_out, void* workspace, void* stream);
+/* out_dist float[n_queries, k] ascending, out_ids int64[n_queries, k] (table row ids) */
+int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                    int metric, double p, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
+                    void* stream);
 
 #ifdef __cplusplus
 }

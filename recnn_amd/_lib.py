@@ -204,6 +204,11 @@ SIGNATURES = {
     "recnn_topk_item_aux": (_I, [_P, _I, _I, _I, _P, _P]),
     "recnn_topk_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
     "recnn_topk_search": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "recnn_dist_item_aux_floats": (_I, [_I, _I, _I, C.POINTER(_L)]),
+    "recnn_dist_item_aux": (_I, [_P, _I, _I, _I, _P, _P]),
+    "recnn_dist_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_dist_matrix": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _L, _P, _P]),
+    "recnn_dist_topk": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P]),
     "recnn_ae_act_floats": (_I, [_I, C.POINTER(_L)]),
     "recnn_ae_workspace_bytes": (_I, [_I, C.POINTER(_L)]),
     "recnn_ae_eval": (_I, [C.POINTER(AeParams), _P, _L, _I, _P, _L, _P, _P]),

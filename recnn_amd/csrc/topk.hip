@@ -1,10 +1,10 @@
 // topk.hip -- batched exact top-K scoring of action vectors against the item-embedding table (gfx950).
 //
-// SURVEY.md 8(f2) "next": replaces the three external retrieval paths the reference uses to turn a generated action
-// into recommended items -- faiss IndexFlatL2 / IndexFlatIP / IP-on-normalised rows (examples/streamlit_demo.py:190-204),
-// the per-item scipy distance loop (examples/streamlit_demo.py:207-231, `rank`) and the Milvus service
-// (recnn/data/db_con.py:45-56, `MilvusConnection.search`) -- by one exact-fp32 MFMA scoring GEMM fused with a
-// per-query top-K selection.
+// SURVEY.md 8(f2) "next": replaces faiss IndexFlatL2 / IndexFlatIP / IP-on-normalised rows (examples/streamlit_demo.py:190-204)
+// and the Milvus service (recnn/data/db_con.py:45-56, `MilvusConnection.search`), two of the external retrieval paths the
+// reference uses to turn a generated action into recommended items, by one exact-fp32 MFMA scoring GEMM fused with a
+// per-query top-K selection.  It gives the order of scipy's euclidean (and of cosine up to the query's norm) but not the
+// scipy metrics of the per-item loop (examples/streamlit_demo.py:207-231, `rank`): those are rank.hip.
 //
 //   score(q, t):  IP  = q.t          (larger is better)
 //                 L2  = |q - t|^2    (smaller is better; squared distance, as faiss IndexFlatL2 reports)

@@ -706,6 +706,50 @@ int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries, const flo
                     int metric, double p, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
                     void* stream);
 
+/* =====================================================================================
+ * 8. Dueling DQN of the embeddings notebook (examples/0. Embeddings Generation/1. (proof of concept) DQN.ipynb): the catalogue-wide
+ *    head Q[b, n] = V_b + A[b, n] - mean(A), A = h W^T + c (W [n_items, 128]), its learn step without the [B, N] matrix, the
+ *    deterministic scatter-sums of the embedding / head gradients, the clip_grad_norm_ coefficient on the device and torch's RAdam.
+ *    Algebra, layouts and error bounds: DESIGN.md 12.  Every float sum has a fixed order (no float atomics): repeated calls are
+ *    bit-identical.  Hidden width 128.  h rows and W rows 16-byte aligned.  Ids outside their range are dropped (scatter) or give NaN
+ *    (row dot); nothing is read or written out of bounds.
+ * ===================================================================================== */
+/* the catalogue GEMM.  Exactly one of out / rowmax is non-NULL:
+ *   out    float[B, ldo]: out[b, n] = h_b . W_n + c_n + V_b - *mu                (DuelDQN.forward)
+ *   rowmax int32[B]    : the order-preserving integer image of max_n (h_b . W_n + c_n); [B, N] is never stored (target network).
+ * W is fp32 (w_bf16 = 0, exact-f32 MFMA) or bfloat16 (w_bf16 = 1: h rounded to bf16 on load, fp32 accumulation). */
+int recnn_dqn_head(const float* h, int64_t ldh, int B, const void* W, int64_t ldw, int w_bf16, const float* c, int N, const float* V,
+                   const float* mu, float* out, int64_t ldo, int32_t* rowmax, void* stream);
+/* out[b] = x_b . w[idx_b] + bias[idx_b] over 128 columns (idx NULL: row 0 of w, bias[0]; bias may be NULL) */
+int recnn_dqn_row_dot(const float* x, int64_t ldx, int rows, const float* w, int64_t ldw, const int64_t* idx, int n_w, const float* bias,
+                      float* out, void* stream);
+/* out[col] = scale * sum over rows of x[row, col] (cols <= 256), rows in fixed chunks added in chunk order */
+int recnn_dqn_colsum_workspace_floats(int rows, int cols, int64_t* h_floats);
+int recnn_dqn_colsum(const float* x, int64_t ldx, int rows, int cols, float scale, float* out, float* workspace, void* stream);
+/* *mu = (sh . sw) / (B N) + *sc / N: mean(A) from the column sums sh = sum_b h_b, sw = sum_n W_n and sc = sum_n c_n */
+int recnn_dqn_mean(const float* sh, const float* sw, const float* sc, int B, int N, float* mu, void* stream);
+/* TD step of the notebook's loss: q = V + adv - mu, y = reward + gamma (Vt + max' - mu') (1 - done), g = 2 (q - y) / B.
+ * adv = h_b . W[a_b] + c[a_b] (recnn_dqn_row_dot), rowmax from recnn_dqn_head.  q / g may be NULL.
+ * stats float[8]: loss = mean (q - y)^2, G = sum g, G / (B N), G / N, mu, mu'. */
+int recnn_dqn_td(const float* V, const float* adv, const float* Vt, const int32_t* rowmax, const float* reward, const float* done,
+                 float gamma, int B, int N, const float* sh, const float* sw, const float* sc, const float* sht, const float* swt,
+                 const float* sct, float* q, float* g, float* stats, void* stream);
+/* dh [B, 256] = [ [ha > 0] (g_b W[a_b] - stats[2] sw) | [hv > 0] g_b wv ] for h2 = [ha | hv] (ldh >= 256) */
+int recnn_dqn_dh(const float* h2, int64_t ldh, int B, const float* W, int64_t ldw, int N, const int64_t* act, const float* sw,
+                 const float* wv, const float* g, const float* stats, float* dh, void* stream);
+/* out[d, 0:128] = sum over contributions j with id d, in j order, of scale[j / per_row] * src[(j / per_row) ld_src + (j % per_row) 128 ...]
+ * (scale NULL: 1), minus coef[0] * rank1 when rank1 is given; out_s[d] (may be NULL) = the sum of the weights minus coef[1] (coef NULL: 0).
+ * Contribution j reads its id at ids[(j / per_row) ld_ids + j % per_row].  Every one of the n_dest rows is written (dense gradient). */
+int recnn_dqn_scatter_workspace_bytes(int64_t contributions, int n_dest, int64_t* h_bytes);
+int recnn_dqn_scatter_sum(const float* src, int64_t ld_src, int rows, int per_row, const int64_t* ids, int64_t ld_ids, const float* scale,
+                          int n_dest, float* out, float* out_s, const float* rank1, const float* coef, void* workspace, void* stream);
+/* clip_grad_norm_(max_norm, norm_type = 1) on a flat gradient whose L1 norm is *norm (device): g *= min(max_norm / (*norm + 1e-6), 1) */
+int recnn_dqn_clip(float* g, int64_t n, const float* norm, float max_norm, void* stream);
+/* One torch.optim.RAdam step over a flat fp32 array (foreach arithmetic; L2 weight decay; step_t 1-based).  clip_norm (device, may be
+ * NULL): the gradient is first scaled by the recnn_dqn_clip coefficient and the scaled gradient written back to g. */
+int recnn_radam_flat(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                     int step_t, const float* clip_norm, float max_norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,17 @@ SIGNATURES = {
     "recnn_ae_eval": (_I, [C.POINTER(AeParams), _P, _L, _I, _P, _L, _P, _P]),
     "recnn_ae_forward": (_I, [C.POINTER(AeParams), _I, _P, _L, _I, _P, _L, _P, _P, _I, _P, _P]),
     "recnn_ae_backward": (_I, [C.POINTER(AeParams), C.POINTER(AeGrads), _I, _P, _L, _I, _P, _L, _P, _L, _P, _P, _L, _P, _P]),
+    "recnn_dqn_head": (_I, [_P, _L, _I, _P, _L, _I, _P, _I, _P, _P, _P, _L, _P, _P]),
+    "recnn_dqn_row_dot": (_I, [_P, _L, _I, _P, _L, _P, _I, _P, _P, _P]),
+    "recnn_dqn_colsum_workspace_floats": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_dqn_colsum": (_I, [_P, _L, _I, _I, _F, _P, _P, _P]),
+    "recnn_dqn_mean": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "recnn_dqn_td": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "recnn_dqn_dh": (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "recnn_dqn_scatter_workspace_bytes": (_I, [_L, _I, C.POINTER(_L)]),
+    "recnn_dqn_scatter_sum": (_I, [_P, _L, _I, _I, _P, _L, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "recnn_dqn_clip": (_I, [_P, _L, _P, _F, _P]),
+    "recnn_radam_flat": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _F, _P]),
     "recnn_engine_buffer": (_P, [_P, C.c_char_p, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
 }
 

@@ -11,7 +11,7 @@ import torch
 from .. import _lib as L
 from .pandas_backend import pd
 
-__all__ = ["rolling_window", "get_irsu", "batch_tensor_embeddings", "batch_contstate_discaction", "prepare_batch_static_size", "make_items_tensor",
+__all__ = ["rolling_window", "get_irsu", "batch_tensor_embeddings", "batch_contstate_discaction", "batch_no_embeddings", "prepare_batch_static_size", "make_items_tensor",
            "sort_users_itemwise", "get_base_batch", "packed_ld", "FrameBatch"]
 
 
@@ -127,6 +127,31 @@ def batch_contstate_discaction(batch, item_embeddings_tensor, frame_size, num_it
     last = torch.as_tensor(batch["items"])[:, -1].to(dev)
     res["action"] = onehot_rows(last, int(num_items))
     return res
+
+
+def batch_no_embeddings(batch, frame_size, *args, **kwargs):
+    """Embed Batch: discrete state, discrete action (utils.py:23-48), the index batch the embeddings notebook's DQN learns from:
+    items / next_items int[B, F] (the window without its last / first item), ratings / next_ratings float[B, F], action = the item id
+    at the end of the window, reward = its rating, done = 1 on each user's last window (cumsum(sizes - F) - 1).  Host-side slicing
+    like the reference; `dqn_update` moves the tensors to the GPU and gathers the embeddings there.
+
+    Deliberate difference: the reference keys the ratings with the TENSOR (`ratings: "ratings"`, a typo); here the key is the string
+    "ratings"."""
+    items_t, ratings_t, sizes_t, users_t = get_irsu(batch)
+    items_t, ratings_t, sizes_t = torch.as_tensor(items_t), torch.as_tensor(ratings_t), torch.as_tensor(sizes_t)
+    b_size = ratings_t.size(0)
+    done = torch.zeros(b_size)
+    done[torch.cumsum(sizes_t - frame_size, dim=0) - 1] = 1
+    return {
+        "items": items_t[:, :-1],
+        "next_items": items_t[:, 1:],
+        "ratings": ratings_t[:, :-1],
+        "next_ratings": ratings_t[:, 1:],
+        "action": items_t[:, -1],
+        "reward": ratings_t[:, -1],
+        "done": done,
+        "meta": {"users": users_t, "sizes": sizes_t},
+    }
 
 
 def prepare_batch_static_size(batch, item_embeddings_tensor, frame_size=10, embed_batch=batch_tensor_embeddings):

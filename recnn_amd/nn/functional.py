@@ -1080,3 +1080,186 @@ def anomaly_rec_error(x, ae, train: bool):
     xin = _ae_input(x)
     err, _, _ = _ae_run(xin, lins, bns, bool(train), True, False)
     return err
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Dueling DQN of the embeddings notebook (csrc/dqn.hip): Q = V + A - mean(A) with A = h W^T + c over the catalogue.
+# The trunk (feature, advantage.0 and value.0 as ONE stacked [256, 128] layer) runs on the GEMM kernels; the catalogue head, the mean
+# and the head's gradients on csrc/dqn.hip.  The learn step itself (recnn_amd/nn/update/dqn.py) reuses these pieces.
+DQN_HIDDEN = 128
+
+
+def dqn_colsum(x, rows, cols, scale=1.0, out=None):
+    """float[cols]: scale * column sums of x[:rows, :cols] (row stride x.stride(0)) in a fixed order."""
+    ws_n = C.c_int64()
+    L.call("recnn_dqn_colsum_workspace_floats", rows, cols, C.byref(ws_n))
+    ws = torch.empty(ws_n.value, dtype=torch.float32, device=x.device)
+    out = torch.empty(cols, dtype=torch.float32, device=x.device) if out is None else out
+    L.call("recnn_dqn_colsum", L.ptr(x), x.stride(0) if x.dim() == 2 else 1, rows, cols, float(scale), L.ptr(out), L.ptr(ws),
+           L.current_stream())
+    return out
+
+
+def dqn_row_dot(x, w, idx=None, bias=None, out=None):
+    """float[rows]: x_b . w[idx_b] + bias[idx_b] over 128 columns (idx None: row 0 of w)."""
+    rows = x.shape[0]
+    out = torch.empty(rows, dtype=torch.float32, device=x.device) if out is None else out
+    L.call("recnn_dqn_row_dot", L.ptr(x), x.stride(0), rows, L.ptr(w), w.stride(0), L.ptr(idx), w.shape[0], L.ptr(bias), L.ptr(out),
+           L.current_stream())
+    return out
+
+
+def dqn_head_weight(w):
+    """(operand, is_bf16) of the catalogue weight [N, 128] in the current catalogue compute type (bf16: a copy per weight version)."""
+    if _catalogue_dtype == "bf16":
+        return _derived_of(w, "bf16_dqn", lambda t: t.to(torch.bfloat16).contiguous()), 1
+    return w.detach(), 0
+
+
+def dqn_head(h, w, c, V=None, mu=None, rowmax=False):
+    """The catalogue GEMM: Q [B, N] = h W^T + c + V - mu (store), or the int32 order-preserving image of max_n (h W^T + c)_n."""
+    B, N = h.shape[0], w.shape[0]
+    wop, bf = dqn_head_weight(w)
+    s = L.current_stream()
+    if rowmax:
+        out = torch.empty(B, dtype=torch.int32, device=h.device)
+        L.call("recnn_dqn_head", L.ptr(h), h.stride(0), B, L.ptr(wop), wop.stride(0), bf, L.ptr(c), N, None, None, None, 0, L.ptr(out), s)
+    else:
+        out = torch.empty(B, N, dtype=torch.float32, device=h.device)
+        L.call("recnn_dqn_head", L.ptr(h), h.stride(0), B, L.ptr(wop), wop.stride(0), bf, L.ptr(c), N, L.ptr(V), L.ptr(mu), L.ptr(out), N,
+               None, s)
+    return out
+
+
+def ord_to_float(t):
+    """Decode recnn_dqn_head's row-max image (int32) to float32."""
+    i = t.to(torch.int32)
+    return torch.where(i >= 0, i, i ^ 0x7FFFFFFF).view(torch.float32)
+
+
+def dqn_check_net(net):
+    """(feature Linear, stacked (advantage.0, value.0), advantage.2, value.2) of a DuelDQN-shaped module, checked."""
+    try:
+        l0, la0, la2, lv0, lv2 = net.feature[0], net.advantage[0], net.advantage[2], net.value[0], net.value[2]
+    except (AttributeError, IndexError, TypeError):
+        raise ValueError("expected a DuelDQN-shaped module (feature / advantage / value Sequentials)") from None
+    if l0.out_features != DQN_HIDDEN or la0.in_features != DQN_HIDDEN or la0.out_features != DQN_HIDDEN or \
+            lv0.out_features != DQN_HIDDEN or lv2.out_features != 1 or la2.in_features != DQN_HIDDEN:
+        raise ValueError(f"DuelDQN kernels need hidden width {DQN_HIDDEN}")
+    for p in net.parameters():
+        if not p.is_cuda:
+            raise L.RecnnHipError("recnn_amd DuelDQN runs on the GPU only (no CPU fallback): move the module and its inputs to 'cuda'")
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise L.RecnnHipError("recnn_amd DuelDQN: parameters must be contiguous float32")
+    return l0, la0, la2, lv0, lv2
+
+
+def dqn_trunk(net, x, K, Kp):
+    """(f [B, 128], h2 = [ha | hv] [B, 256], padded feature weight [128, Kp], stacked weight [256, 128]) for x [B, >= Kp] whose
+    columns K .. Kp are zero."""
+    l0, la0, _, lv0, _ = dqn_check_net(net)
+    B = x.shape[0]
+    dev = x.device
+    w0p = _derived_of(l0.weight, f"dqn_pad{Kp}", lambda w: _pad(w, DQN_HIDDEN, Kp))
+    w12 = torch.cat([la0.weight.detach(), lv0.weight.detach()], 0)
+    b12 = torch.cat([la0.bias.detach(), lv0.bias.detach()], 0)
+    f = torch.empty(B, DQN_HIDDEN, device=dev)
+    h2 = torch.empty(B, 2 * DQN_HIDDEN, device=dev)
+    if B:
+        _fwd(x, Kp, w0p, l0.bias.detach(), f, DQN_HIDDEN, DQN_HIDDEN, True, None)
+        _fwd(f, DQN_HIDDEN, w12, b12, h2, 2 * DQN_HIDDEN, 2 * DQN_HIDDEN, True, None)
+    return f, h2, w0p, w12
+
+
+def dqn_head_stats(h2, B, w, c):
+    """(sum_b ha_b, sum_n W_n, sum_n c_n): the three column sums mean(A) is made of."""
+    N = w.shape[0]
+    return dqn_colsum(h2, B, DQN_HIDDEN), dqn_colsum(w.detach(), N, DQN_HIDDEN), dqn_colsum(c.detach().view(N, 1), N, 1)
+
+
+def dqn_trunk_backward(dh, f, x, K, Kp, w0p, w12, gw0, gb0, gw12, gb12, want_dx):
+    """Gradients of the trunk from dh = d[ha | hv] (pre-activation, [B, 256]): written into gw0 [128, K], gb0, gw12 [256, 128], gb12;
+    returns d x [B, Kp] (or None)."""
+    B = dh.shape[0]
+    dev = dh.device
+    _dw(dh, 2 * DQN_HIDDEN, f, DQN_HIDDEN, gw12)
+    dqn_colsum(dh, B, 2 * DQN_HIDDEN, out=gb12)
+    df = torch.empty(B, DQN_HIDDEN, device=dev)
+    _dx(dh, 2 * DQN_HIDDEN, w12, DQN_HIDDEN, df, f, 1.0, None)
+    dw0 = torch.empty(DQN_HIDDEN, Kp, device=dev)
+    _dw(df, DQN_HIDDEN, x, Kp, dw0)
+    gw0.copy_(dw0[:, :K])
+    dqn_colsum(df, B, DQN_HIDDEN, out=gb0)
+    if not want_dx:
+        return None
+    dx = torch.empty(B, Kp, device=dev)
+    _dx(df, DQN_HIDDEN, w0p, Kp, dx, None, 1.0, None)
+    return dx
+
+
+class DuelDQNFunction(torch.autograd.Function):
+    """Q = DuelDQN(x) [B, N] and its backward for any upstream dQ: dV = rowsum(dQ), dA = dQ - sum(dQ) / (B N)."""
+
+    @staticmethod
+    def forward(ctx, x, net, *params):
+        if not x.is_cuda:
+            raise L.RecnnHipError("recnn_amd DuelDQN runs on the GPU only (no CPU fallback): move the module and its inputs to 'cuda'")
+        _, _, la2, _, lv2 = dqn_check_net(net)
+        B, K = x.shape
+        Kp = _r64(K)
+        xp = _pad(x, B, Kp)
+        f, h2, w0p, w12 = dqn_trunk(net, xp, K, Kp)
+        W, c = la2.weight.detach(), la2.bias.detach()
+        N = W.shape[0]
+        V = dqn_row_dot(h2[:, DQN_HIDDEN:], lv2.weight.detach(), None, lv2.bias.detach())
+        sh, sw, sc = dqn_head_stats(h2, B, W, c)
+        mu = torch.empty(1, device=x.device)
+        if B:
+            L.call("recnn_dqn_mean", L.ptr(sh), L.ptr(sw), L.ptr(sc), B, N, L.ptr(mu), L.current_stream())
+        Q = dqn_head(h2, W, c, V, mu)
+        ctx.net = net
+        ctx.params = params
+        ctx.dims = (B, K, Kp, N)
+        ctx.save_for_backward(xp, f, h2, w0p, w12, sh, sw)
+        return Q
+
+    @staticmethod
+    def backward(ctx, dQ):
+        xp, f, h2, w0p, w12, sh, sw = ctx.saved_tensors
+        B, K, Kp, N = ctx.dims
+        net = ctx.net
+        l0, la0, la2, lv0, lv2 = dqn_check_net(net)
+        dev = dQ.device
+        H = DQN_HIDDEN
+        N4 = _r4(N)
+        dQp = torch.zeros(B, N4, device=dev)
+        dQp[:, :N] = dQ
+        s = dQp.sum() / (B * N)                      # d mean(A) seed, on the device
+        dV = dQp.sum(1)
+        ha, hv = h2[:, :H], h2[:, H:]
+        W = la2.weight.detach()
+        gW = torch.empty(N, H, device=dev)
+        _dw(dQp, N, ha, H, gW)                       # dQ^T ha: contraction over the batch
+        gW -= s * sh[None, :]
+        gc = dQp[:, :N].sum(0) - s * B
+        Wp = _pad(W, N4, H)
+        dha = torch.empty(B, H, device=dev)
+        _dx(dQp, N4, Wp, H, dha, None, 1.0, None)    # dQ W: contraction over the catalogue
+        dh = torch.empty(B, 2 * H, device=dev)
+        dh[:, :H] = (dha - s * sw[None, :]) * (ha > 0)
+        wv = lv2.weight.detach()
+        dh[:, H:] = dV[:, None] * wv * (hv > 0)
+        gwv = (dV[:, None] * hv).sum(0, keepdim=True)
+        gbv = dV.sum().reshape(1)
+        gw0, gb0 = torch.empty(H, K, device=dev), torch.empty(H, device=dev)
+        gw12, gb12 = torch.empty(2 * H, H, device=dev), torch.empty(2 * H, device=dev)
+        dx = dqn_trunk_backward(dh, f, xp, K, Kp, w0p, w12, gw0, gb0, gw12, gb12, ctx.needs_input_grad[0])
+        grads = {id(l0.weight): gw0, id(l0.bias): gb0, id(la0.weight): gw12[:H], id(la0.bias): gb12[:H], id(lv0.weight): gw12[H:],
+                 id(lv0.bias): gb12[H:], id(la2.weight): gW, id(la2.bias): gc, id(lv2.weight): gwv, id(lv2.bias): gbv}
+        pg = tuple(grads.get(id(p)) for p in ctx.params)
+        return (dx[:, :K] if dx is not None else None, None) + pg
+
+
+def duel_dqn_forward(x, net):
+    """DuelDQN(x) on the kernels, differentiable in x and in every parameter of `net`."""
+    return DuelDQNFunction.apply(x, net, *net.parameters())

@@ -15,7 +15,24 @@ import torch.nn as nn
 
 from . import functional as F_hip
 
-__all__ = ["AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor"]
+__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor"]
+
+
+class DuelDQN(nn.Module):
+    """The dueling DQN of the embeddings notebook (examples/0. Embeddings Generation/1. (proof of concept) DQN.ipynb): feature =
+    Linear(input_dim, 128) ReLU, advantage = Linear(128, 128) ReLU Linear(128, action_dim), value = Linear(128, 128) ReLU Linear(128, 1),
+    forward(x) = value + advantage - advantage.mean(), the mean ONE scalar over the whole [B, action_dim] matrix.  Same sub-modules,
+    state_dict keys and default initialisation as the notebook's class; `forward` runs on the HIP kernels (csrc/dqn.hip and the GEMM
+    kernels) and is differentiable.  Input: float32 [B, input_dim] on the GPU."""
+
+    def __init__(self, input_dim, action_dim):
+        super().__init__()
+        self.feature = nn.Sequential(nn.Linear(input_dim, 128), nn.ReLU())
+        self.advantage = nn.Sequential(nn.Linear(128, 128), nn.ReLU(), nn.Linear(128, action_dim))
+        self.value = nn.Sequential(nn.Linear(128, 128), nn.ReLU(), nn.Linear(128, 1))
+
+    def forward(self, x):
+        return F_hip.duel_dqn_forward(x, self)
 
 
 class AnomalyDetector(nn.Module):

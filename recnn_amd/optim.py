@@ -12,6 +12,8 @@
            against it ("parity unpinned").  What IS pinned: with weight_decay = 0 the RAdam part equals
            torch.optim.RAdam (same rectification term, same threshold, eps outside the sqrt), and Lookahead is three lines
            (tests/test_gpu_optim.py); `Ranger.reference_step` is the same algorithm in plain torch ops.
+`RAdam` -- torch.optim.RAdam's arithmetic (its foreach form; L2 weight decay) on the HIP kernel `recnn_radam_flat`, which can take the
+           clip_grad_norm_ coefficient from a device scalar (`dqn_update`: the clip costs no host read and no extra pass).
 """
 import math
 
@@ -21,7 +23,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["Adam", "Ranger", "adam_config", "fused_config"]
+__all__ = ["Adam", "RAdam", "Ranger", "adam_config", "fused_config"]
 
 
 def _shadow_of(p):
@@ -104,6 +106,50 @@ class Adam(torch.optim.Optimizer):
         if stepped:
             self._step_dev.add_(1)
         return loss
+
+
+class RAdam(torch.optim.Optimizer):
+    """torch.optim.RAdam (weight_decay as torch's L2 form; decoupled_weight_decay is not supported) on `recnn_radam_flat`."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
+            raise ValueError("invalid RAdam hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.step_clipped(None, 0.0)
+        return loss
+
+    @torch.no_grad()
+    def step_clipped(self, clip_norm, max_norm):
+        """One step; with `clip_norm` (a device float[1] holding the L1 norm of all gradients of this optimizer) every gradient is first
+        multiplied by min(max_norm / (norm + 1e-6), 1) -- clip_grad_norm_(params, max_norm, 1) -- and `.grad` keeps the clipped value."""
+        stream = None
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise L.RecnnHipError("recnn_amd.optim.RAdam: parameters must live on the GPU (no CPU fallback)")
+                if p.dtype != torch.float32 or not p.data.is_contiguous() or not p.grad.is_contiguous():
+                    raise L.RecnnHipError("recnn_amd.optim.RAdam: parameters and gradients must be contiguous float32")
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p.data)
+                    st["exp_avg_sq"] = torch.zeros_like(p.data)
+                st["step"] = int(st["step"]) + 1
+                stream = stream or L.current_stream()
+                L.call("recnn_radam_flat", L.ptr(p.data), L.ptr(p.grad), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), p.numel(),
+                       float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(st["step"]),
+                       L.ptr(clip_norm), float(max_norm), stream)
+                torch.autograd.graph.increment_version(p)
 
 
 def adam_config(opt):

@@ -750,6 +750,23 @@ int recnn_dqn_clip(float* g, int64_t n, const float* norm, float max_norm, void*
 int recnn_radam_flat(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                      int step_t, const float* clip_norm, float max_norm, void* stream);
 
+/* =====================================================================================
+ * 9. Statistics of a top-K result (csrc/divstats.hip): what the reference's diversity / distances notebooks compute on the host
+ *    from the ids and distances of a search (np.unique(ids, return_counts=True), D.mean(axis=1).mean(), D.std(axis=1).mean()).
+ *    dist float[n_queries, k] and ids int64[n_queries, k], both contiguous and 16-byte aligned, are what recnn_topk_search /
+ *    recnn_dist_topk write.  x = (double)dist, or sqrt((double)dist) when take_sqrt.  Per row, in float64, two passes, both sums in
+ *    index order: mean = (sum x) / k, std = sqrt(sum (x - mean)^2 / k) (ddof = 0); NaN entries propagate as in numpy.  Integer atomics
+ *    for the counts, no float atomics: totals are summed in a fixed order that depends on n_queries alone, equal calls give equal bits.
+ *    Limits: 0 < k <= 64.  Errors: RECNN_E_INVALID, before any HIP call, for a null pointer, k out of range, n_items <= 0,
+ *    n_queries < 0 or a misaligned operand.  n_queries == 0 launches nothing.  DESIGN.md 13.
+ * ===================================================================================== */
+int recnn_topk_stats_workspace_bytes(int n_queries, int k, int64_t* h_bytes);
+/* counts int32[n_items]: ACCUMULATED into (the caller zeroes it once); ids outside [0, n_items) are not counted.
+ * row_mean, row_std double[n_queries]: written.
+ * totals double[4]: ACCUMULATED into: sum of row_mean, sum of row_std, rows seen, ids outside [0, n_items). */
+int recnn_topk_stats(const float* dist, const int64_t* ids, int n_queries, int k, int n_items, int take_sqrt, int32_t* counts,
+                     double* row_mean, double* row_std, double* totals, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

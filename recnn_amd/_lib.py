@@ -226,6 +226,8 @@ SIGNATURES = {
     "recnn_dqn_clip": (_I, [_P, _L, _P, _F, _P]),
     "recnn_radam_flat": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _F, _P]),
     "recnn_engine_buffer": (_P, [_P, C.c_char_p, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
+    "recnn_topk_stats_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_topk_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

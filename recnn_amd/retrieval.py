@@ -151,3 +151,112 @@ def cdist(queries: torch.Tensor, table: torch.Tensor, metric="euclidean", p=None
 
 
 __all__ = ["FlatIndex", "cdist", "METRICS", "DIST_METRICS", "metric_name", "minkowski_p"]
+
+
+# ---- statistics of a search result (csrc/divstats.hip): what the reference's diversity and distances
+# notebooks compute on the host from `[B, k]` ids and distances, kept on the GPU and accumulated over the test loader's batches.
+
+class TopkStats:
+    """Device tensors of one `topk_stats` call: `row_mean`, `row_std` (float64 [B]), `counts` (int32 [n_items]) and `totals`
+    (float64 [4]: sum of row_mean, sum of row_std, rows seen, ids outside [0, n_items))."""
+    __slots__ = ("row_mean", "row_std", "counts", "totals")
+
+    def __init__(self, row_mean, row_std, counts, totals):
+        self.row_mean, self.row_std, self.counts, self.totals = row_mean, row_std, counts, totals
+
+
+def _dense16(t, dtype, what):
+    _on_gpu(t, what)
+    if t.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}, got {t.dtype}")
+    t = t.detach().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def topk_stats(dist, ids, n_items, sqrt=False, counts=None, totals=None):
+    """Per-row mean and population std (float64, `np.sqrt` of the distances first when `sqrt`) of `dist` float32 [B, k], and
+    how often each item of [0, n_items) appears in `ids` int64 [B, k]: one pass over what `FlatIndex.search` or
+    `SearchResult.dist / id` returned, on the GPU.  `counts` and `totals` are accumulated into when given (else fresh zeros);
+    ids out of range are not counted but tallied in `totals[3]`."""
+    dist, ids = _dense16(dist, torch.float32, "topk_stats: dist"), _dense16(ids, torch.int64, "topk_stats: ids")
+    if dist.dim() != 2 or dist.shape != ids.shape:
+        raise ValueError(f"topk_stats: dist and ids must both be [B, k], got {tuple(dist.shape)} and {tuple(ids.shape)}")
+    B, k = dist.shape
+    dev = dist.device
+    if counts is None:
+        counts = torch.zeros(n_items, dtype=torch.int32, device=dev)
+    if totals is None:
+        totals = torch.zeros(4, dtype=torch.float64, device=dev)
+    for t, dtype, shape, what in ((counts, torch.int32, (n_items,), "counts"), (totals, torch.float64, (4,), "totals")):
+        _on_gpu(t, f"topk_stats: {what}")
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"topk_stats: {what} must be a contiguous {dtype} tensor of shape {shape}")
+    row_mean = torch.empty(B, dtype=torch.float64, device=dev)
+    row_std = torch.empty(B, dtype=torch.float64, device=dev)
+    nbytes = C.c_int64()
+    L.call("recnn_topk_stats_workspace_bytes", B, k, C.byref(nbytes))
+    if B == 0:                                                       # an empty batch has no storage to point at
+        return TopkStats(row_mean, row_std, counts, totals)
+    ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
+    L.call("recnn_topk_stats", L.ptr(dist), L.ptr(ids), B, k, n_items, int(bool(sqrt)), L.ptr(counts), L.ptr(row_mean),
+           L.ptr(row_std), L.ptr(totals), L.ptr(ws), L.current_stream())
+    return TopkStats(row_mean, row_std, counts, totals)
+
+
+class DiversityMeter:
+    """Accumulates `topk_stats` over any number of `update(dist, ids)` calls (one per batch of the test loader).
+
+    `mean` / `std` are the notebooks' `D.mean(axis=1).mean()` / `D.std(axis=1).mean()` over all rows seen, `recommended()`
+    what `np.unique(ids, return_counts=True)` gives, `counts_of_counts()` what `pd.Series(counts).value_counts()` holds.
+    Reading any of them synchronises once and raises ValueError if an id was outside [0, n_items)."""
+
+    def __init__(self, n_items, sqrt=False, device="cuda"):
+        self.n_items, self.sqrt = int(n_items), bool(sqrt)
+        device = torch.device(device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise L.RecnnHipError("DiversityMeter: the accumulators live on the GPU (no CPU fallback)")
+        self.counts = torch.zeros(self.n_items, dtype=torch.int32, device=device)
+        self.totals = torch.zeros(4, dtype=torch.float64, device=device)
+
+    def update(self, dist, ids):
+        """Adds one batch; returns its `TopkStats` (the per-row tensors of this batch, the shared accumulators)."""
+        return topk_stats(dist, ids, self.n_items, self.sqrt, self.counts, self.totals)
+
+    def reset(self):
+        self.counts.zero_()
+        self.totals.zero_()
+
+    def _totals(self):
+        t = self.totals.tolist()
+        if t[3] != 0:
+            raise ValueError(f"DiversityMeter: {int(t[3])} ids were outside [0, {self.n_items}) and were not counted")
+        return t
+
+    @property
+    def rows(self):
+        return int(self._totals()[2])
+
+    @property
+    def mean(self):
+        t = self._totals()
+        return t[0] / t[2]
+
+    @property
+    def std(self):
+        t = self._totals()
+        return t[1] / t[2]
+
+    def recommended(self):
+        """(uniques, counts) as numpy int64 arrays: the ids with a non-zero count, ascending, and their counts."""
+        self._totals()
+        uniques = torch.nonzero(self.counts).flatten()
+        return uniques.cpu().numpy(), self.counts[uniques].to(torch.int64).cpu().numpy()
+
+    def counts_of_counts(self):
+        """(n_recommended, how_many_items) as numpy int64 arrays, sorted by n_recommended, over the recommended items."""
+        self._totals()
+        n, how_many = torch.unique(self.counts[self.counts > 0], return_counts=True)
+        return n.to(torch.int64).cpu().numpy(), how_many.cpu().numpy()
+
+
+__all__ += ["topk_stats", "DiversityMeter"]

@@ -709,7 +709,8 @@ int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries, const flo
 /* =====================================================================================
  * 8. Dueling DQN of the embeddings notebook (examples/0. Embeddings Generation/1. (proof of concept) DQN.ipynb): the catalogue-wide
  *    head Q[b, n] = V_b + A[b, n] - mean(A), A = h W^T + c (W [n_items, 128]), its learn step without the [B, N] matrix, the
- *    deterministic scatter-sums of the embedding / head gradients, the clip_grad_norm_ coefficient on the device and torch's RAdam.
+ *    deterministic scatter-sums of the embedding / head gradients (csrc/dqn.hip), the clip_grad_norm_ coefficient on the device and
+ *    torch's RAdam (csrc/optim.hip).
  *    Algebra, layouts and error bounds: DESIGN.md 12.  Every float sum has a fixed order (no float atomics): repeated calls are
  *    bit-identical.  Hidden width 128.  h rows and W rows 16-byte aligned.  Ids outside their range are dropped (scatter) or give NaN
  *    (row dot); nothing is read or written out of bounds.

@@ -287,6 +287,16 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def workspace(query: str, *args, device):
+    """Scratch tensor (uint8) of the size the entry point `query` (a `recnn_*_workspace_bytes` or `*_floats`) reports for `args`,
+    never empty: a zero-size request still gets storage to point at."""
+    import torch
+    n = C.c_int64()
+    call(query, *args, C.byref(n))
+    nbytes = n.value * (4 if query.endswith("_floats") else 1)
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
 def current_stream():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

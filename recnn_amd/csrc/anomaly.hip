@@ -565,11 +565,9 @@ int cu_count() {
   return cached[dev];
 }
 
-inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 int check_params(const recnn_ae_params* p, bool writes_stats) {
   RECNN_REQUIRE(p, "anomaly: null params");
-  for (int l = 0; l < 4; ++l) RECNN_REQUIRE(p->w[l] && p->b[l] && al16(p->w[l]), "anomaly: weight %d null or not 16-byte aligned", l);
+  for (int l = 0; l < 4; ++l) RECNN_REQUIRE(p->w[l] && p->b[l] && aligned16(p->w[l]), "anomaly: weight %d null or not 16-byte aligned", l);
   for (int i = 0; i < 3; ++i) {
     RECNN_REQUIRE(p->gamma[i] && p->beta[i] && p->running_mean[i] && p->running_var[i], "anomaly: BatchNorm %d: null pointer", i);
     RECNN_REQUIRE(!writes_stats || p->num_batches_tracked[i], "anomaly: BatchNorm %d: null num_batches_tracked", i);
@@ -621,7 +619,7 @@ int recnn_ae_eval(const recnn_ae_params* h_p, const float* x, int64_t ldx, int r
   RECNN_REQUIRE(x && rows >= 0 && ldx >= 128 && ((out != nullptr) != (err != nullptr)), "ae_eval: bad arguments (x, rows, ldx, out xor err)");
   RECNN_REQUIRE(!out || ldo >= 128, "ae_eval: ldo < 128");
   if (rows == 0) return 0;
-  const int xvec = al16(x) && (ldx % 4) == 0;
+  const int xvec = aligned16(x) && (ldx % 4) == 0;
   const int P = (rows + BMR - 1) / BMR;
   const int grid = P < cu_count() ? P : cu_count();
   hipStream_t s = (hipStream_t)stream;
@@ -644,11 +642,11 @@ int recnn_ae_forward(const recnn_ae_params* h_p, int train, const float* x, int6
                 "ae_forward: bad arguments (x, act, workspace, rows, ldx, out xor err)");
   RECNN_REQUIRE(!out || ldo >= 128, "ae_forward: ldo < 128");
   RECNN_REQUIRE(!train || rows >= 2, "ae_forward: train mode needs at least 2 rows (got %d)", rows);
-  RECNN_REQUIRE(al16(act) && al16(workspace), "ae_forward: act / workspace not 16-byte aligned");
+  RECNN_REQUIRE(aligned16(act, workspace), "ae_forward: act / workspace not 16-byte aligned");
   if (rows == 0) return 0;
   const recnn_ae_params& p = *h_p;
   const WsLayout wl = ws_layout(rows);
-  const int xvec = al16(x) && (ldx % 4) == 0;
+  const int xvec = aligned16(x) && (ldx % 4) == 0;
   float* ws = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
   int rc = launch_fwd_seg<0, 0>(p, train, x, ldx, xvec, rows, out, ldo, err, act, keep, ws, wl.fpart, wl.P, s);
@@ -670,7 +668,7 @@ int recnn_ae_backward(const recnn_ae_params* h_p, const recnn_ae_grads* h_g, int
                 "ae_backward: bad arguments");
   RECNN_REQUIRE(!dx || lddx >= 128, "ae_backward: lddx < 128");
   RECNN_REQUIRE(!train || rows >= 2, "ae_backward: train mode needs at least 2 rows");
-  RECNN_REQUIRE(al16(x) && ldx % 4 == 0 && al16(act) && al16(workspace), "ae_backward: x / act / workspace not 16-byte aligned");
+  RECNN_REQUIRE(aligned16(x, act, workspace) && ldx % 4 == 0, "ae_backward: x / act / workspace not 16-byte aligned");
   const recnn_ae_params& p = *h_p;
   const recnn_ae_grads& g = *h_g;
   const WsLayout wl = ws_layout(rows);

@@ -110,6 +110,55 @@ __device__ inline float wave_sum(float v) {
   v += dpp_take<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3: lane 63 holds the total
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// max over the wave, returned in every lane
+__device__ inline float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
+  return v;
+}
+
+// Workgroup reductions, result in every thread; `red` holds one float per wave.  All of them meet at a barrier on entry (red may be
+// reused at once, and the caller's own LDS and global stores are ordered before what follows the call) and after the wave results land.
+// The order of the cross-wave step is part of each one's contract: results are compared bit for bit.
+// 256 threads, the four wave sums added pairwise
+__device__ inline float block_sum256(float v, float* red /*[4]*/) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// NWAVE waves, the wave sums added left to right.  (vae.hip's former copy had its second barrier after the read and none on entry;
+// this is the stricter placement: categorical_kernel relies on the entry barrier.)
+template <int NWAVE> __device__ inline float block_sum(float v, float* red /*[NWAVE]*/) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < NWAVE; ++i) t += red[i];
+  return t;
+}
+template <int NWAVE> __device__ inline float block_max(float v, float* red /*[NWAVE]*/) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = red[0];
+#pragma unroll
+  for (int i = 1; i < NWAVE; ++i) t = fmaxf(t, red[i]);
+  return t;
+}
+
+// ---------------------------------------------------------------- launch helpers (host)
+// whether every pointer is 16-byte aligned
+template <class... T> inline bool aligned16(const T*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
+// workgroups for `elems` elements at `per_wg` each: at least 1, at most `cap`
+inline int grid_for(int64_t elems, int per_wg, int cap) {
+  const int64_t g = (elems + per_wg - 1) / per_wg;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
 
 // Pull `BYTES` bytes of the kernel-argument segment, starting `dyn_offset` bytes in, into the scalar cache -- every 64-byte line touched
 // by one s_load_dword, all in flight together, waited for once.  A kernel that reads the fields of a by-value argument block one dependent

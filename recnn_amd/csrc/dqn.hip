@@ -1,4 +1,5 @@
-// dqn.hip -- the dueling DQN of the embeddings notebook (section 8 of include/recnn_hip.h).
+// dqn.hip -- the dueling DQN of the embeddings notebook (section 8 of include/recnn_hip.h; its norm clip and RAdam:
+// optim.hip).
 //
 // Q[b, n] = V_b + A[b, n] - mean(A), A = h W^T + c over the whole catalogue.  The algebra of DESIGN.md 12 keeps the [B, N] matrix out of
 // the learn step: the mean is (sum_b h_b) . (sum_n W_n) / (B N) + mean(c), the online Q at the action is one gathered-row dot, and the
@@ -10,7 +11,6 @@
 #include <type_traits>
 
 #include "common.h"
-#include "optim.h"
 
 namespace {
 
@@ -220,10 +220,8 @@ __global__ __launch_bounds__(256) void dqn_colsum_final_kernel(const float* __re
   const int col = blockIdx.x;
   float s = 0.f;
   for (int k = threadIdx.x; k < chunks; k += 256) s += part[(int64_t)k * cols + col];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[col] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+  s = block_sum256(s, red);
+  if (threadIdx.x == 0) out[col] = s * scale;
 }
 
 // mu = (sh . sw) / (B N) + sc / N: the mean of A = h W^T + c over [B, N]
@@ -262,15 +260,8 @@ __global__ __launch_bounds__(256) void dqn_td_kernel(const float* __restrict__ V
     l += d * d;
     gs += g;
   }
-  l = wave_sum(l);
-  gs = wave_sum(gs);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
-  __syncthreads();
-  const float lt = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = gs;
-  __syncthreads();
-  const float gt = (red[0] + red[1]) + (red[2] + red[3]);
+  const float lt = block_sum256(l, red);
+  const float gt = block_sum256(gs, red);
   if (threadIdx.x == 0) {
     stats[0] = lt / (float)B;
     stats[1] = gt;
@@ -469,60 +460,13 @@ __global__ __launch_bounds__(256) void scatter_merge_kernel(const int* __restric
   if (out_s && lane == 0) out_s[d] = coef ? as - coef[1] : as;
 }
 
-// ---------------------------------------------------------------- clip, RAdam
-// clip_grad_norm_(max_norm, norm_type=1) on a flat gradient whose L1 norm is *norm: g *= min(max_norm / (norm + 1e-6), 1)
-__device__ inline float clip_coef(const float* norm, float max_norm) { return fminf(max_norm / (norm[0] + 1e-6f), 1.f); }
-__global__ __launch_bounds__(256) void dqn_clip_kernel(float* __restrict__ g, int64_t n, const float* __restrict__ norm, float max_norm) {
-  const float cf = clip_coef(norm, max_norm);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) g[i] *= cf;
-}
-// torch.optim.RAdam (foreach form): m = lerp(m, g, 1 - b1); v = b2 v + (1 - b2) g g; p += m (1 / ((sqrt(v) + eps) / S) + U) with
-// S = -lr rect sqrt(bc2) / bc1 (0 unrectified), U = -lr / bc1 when unrectified (else 0).  gscale: a device clip norm (see above); the
-// scaled gradient is written back, so .grad holds what clip_grad_norm_ leaves there.
-__global__ __launch_bounds__(256) void radam_flat_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, int64_t n, float beta1w, float beta2, float omb2, float eps,
-                                                         float wd, float S, float U, int rect, const float* __restrict__ norm,
-                                                         float max_norm) {
-#pragma clang fp contract(off)
-  const float cf = norm ? clip_coef(norm, max_norm) : 1.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float gi = g[i];
-    if (norm) {
-      gi *= cf;
-      g[i] = gi;
-    }
-    float pi = p[i];
-    if (wd != 0.f) gi = gi + wd * pi;
-    float mi = m[i], vi = v[i];
-    mi = mi + beta1w * (gi - mi);
-    vi = vi * beta2 + omb2 * gi * gi;
-    float step;
-    if (rect) {
-      step = (sqrtf(vi) + eps) / S;
-      step = 1.f / step;
-    } else {
-      step = U;
-    }
-    pi = pi + step * mi;
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
-int grid_for(int64_t n, int cap) {
-  int64_t gr = (n + 255) / 256;
-  if (gr > cap) gr = cap;
-  return (int)(gr < 1 ? 1 : gr);
-}
-
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int recnn_dqn_head(const float* h, int64_t ldh, int B, const void* W, int64_t ldw, int w_bf16, const float* c, int N,
                               const float* V, const float* mu, float* out, int64_t ldo, int32_t* rowmax, void* stream) {
   RECNN_REQUIRE(h && W && c && B >= 0 && N >= 1 && (out != nullptr) != (rowmax != nullptr), "dqn_head: bad arguments");
   RECNN_REQUIRE(!out || (V && mu && ldo >= N), "dqn_head: store mode needs V, mu and ldo >= N");
-  RECNN_REQUIRE(al16(h) && ldh % 4 == 0 && ldh >= HK && al16(W) && ldw >= HK && ldw % (w_bf16 ? 8 : 4) == 0,
+  RECNN_REQUIRE(aligned16(h, W) && ldh % 4 == 0 && ldh >= HK && ldw >= HK && ldw % (w_bf16 ? 8 : 4) == 0,
                 "dqn_head: h / W rows must be 16-byte aligned, 128 wide");
   if (B == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -635,33 +579,4 @@ extern "C" int recnn_dqn_scatter_sum(const float* src, int64_t ld_src, int rows,
   hipLaunchKernelGGL(scatter_merge_kernel, dim3((n_dest + 3) / 4), dim3(256), 0, s, w.start, n_dest, w.part, w.part_s, out, out_s, rank1,
                      coef);
   return recnn_check_hip(hipGetLastError(), "dqn_scatter_sum");
-}
-
-extern "C" int recnn_dqn_clip(float* g, int64_t n, const float* norm, float max_norm, void* stream) {
-  RECNN_REQUIRE(g && norm && n >= 0, "dqn_clip: bad arguments");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(dqn_clip_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, g, n, norm, max_norm);
-  return recnn_check_hip(hipGetLastError(), "dqn_clip");
-}
-
-extern "C" int recnn_radam_flat(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, int step_t, const float* clip_norm, float max_norm, void* stream) {
-  RECNN_REQUIRE(p && g && m && v && n >= 0 && step_t >= 1, "radam_flat: bad arguments");
-  if (n == 0) return 0;
-  // host scalars in double, as torch computes them from the Python floats (betas: recnn_snap7, optim.h)
-  const double b1 = recnn_snap7(beta1), b2 = recnn_snap7(beta2), t = step_t;
-  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-  const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
-  const double rho_t = rho_inf - 2.0 * t * pow(b2, t) / bc2;
-  const int rect = rho_t > 5.0;
-  double S = 0.0, U = 0.0;
-  if (rect) {
-    const double r = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
-    S = sqrt(bc2) * (lr * r / bc1) * -1.0;
-  } else {
-    U = (lr * 1.0 / bc1) * -1.0;
-  }
-  hipLaunchKernelGGL(radam_flat_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - b1), (float)b2,
-                     (float)(1.0 - b2), eps, weight_decay, (float)S, (float)U, rect, clip_norm, max_norm);
-  return recnn_check_hip(hipGetLastError(), "radam_flat");
 }

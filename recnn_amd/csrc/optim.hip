@@ -1,4 +1,5 @@
-// optim.hip -- gradient reduction, the clip quirk, Adam, soft target update, shadow refresh (gfx950).
+// optim.hip -- gradient reduction, the clip quirk, Adam, soft target update, shadow refresh; the flat optimizer passes (Adam, Ranger,
+// RAdam, soft update, norm clip) over one element walk (gfx950).
 //
 // Replaces:
 //   torch.optim.Adam.step  as injected by the reference's users   recnn/nn/update/misc.py:44, ddpg.py:93,
@@ -8,6 +9,8 @@
 // Flat chunks of each parameter tensor per workgroup (optim.h) over a flat fp32 arena; the same pass writes the compute-type
 // "shadow" copy of the weights (zero-padded, 16-byte aligned rows; critic W1 columns rotated to the
 // packed [action | state] batch layout) that the MFMA GEMMs read, and optionally the soft-updated target.
+#include <type_traits>
+
 #include "optim.h"
 #include "x3.h"
 #include "comm_dev.h"
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(256) void scale_grads_kernel(const NetLayout L, flo
                                                           float grad_scale) {
   __shared__ float red[4];
   float gs = grad_scale;
-  if (n_l1 > 0) gs *= clip_coef(l1part, n_l1, grad_scale, red);
+  if (n_l1 > 0) gs *= quirk_clip_coef(l1part, n_l1, grad_scale, red);
   const int b = blockIdx.x;
   const TensorSeg& T = L.t[find_tensor(L, b)];
   const Own o = own_elems(T, b - T.blk0);
@@ -138,18 +141,52 @@ int scale_grads_launch(const NetLayout& L, float* gflat, const float* l1part, in
   return recnn_check_hip(hipGetLastError(), "scale_grads_kernel");
 }
 
-// ---------------------------------------------------------------- flat entry points (C ABI section 3)
+// ---------------------------------------------------------------- flat entry points (C ABI sections 3 and 8)
+// The element walk of every flat pass: body(i, width) once per run of `width` consecutive elements starting at i, each element in exactly
+// one run.  VEC = 4: 16 bytes per lane and load over the n >> 2 whole quads (catalogue-sized tensors -- REINFORCE at 100k items -- are
+// bound by bytes in flight, not by HBM, with 4-byte lanes), then the n % 4 tail one by one; VEC = 1 (unaligned callers): one by one
+// throughout.  The body is written once for both widths (flat_ld / flat_st take the width from their array): element by element the same
+// arithmetic.  Floating-point contraction follows the body's own pragma, not this function's.
+template <int W> using Width = std::integral_constant<int, W>;
+template <int VEC, class Body> __device__ __forceinline__ void flat_walk(int64_t n, Body body) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  int64_t done = 0;
+  if constexpr (VEC == 4) {
+    const int64_t n4 = n >> 2;
+    for (int64_t q = gid; q < n4; q += stride) body(q << 2, Width<4>());
+    done = n4 << 2;
+  }
+  for (int64_t i = done + gid; i < n; i += stride) body(i, Width<1>());
+}
+template <int W> __device__ __forceinline__ void flat_ld(const float* a, int64_t i, float (&x)[W]) {
+  if constexpr (W == 4) {
+    const float4 t = *(const float4*)(a + i);
+    x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+  } else {
+    x[0] = a[i];
+  }
+}
+template <int W> __device__ __forceinline__ void flat_st(float* a, int64_t i, const float (&x)[W]) {
+  if constexpr (W == 4) *(float4*)(a + i) = make_float4(x[0], x[1], x[2], x[3]);
+  else a[i] = x[0];
+}
+// Launches a flat pass that comes in <SH, VEC> instantiations: go(SH, VEC, grid) is called once, with SH (the pass rewrites a shadow copy)
+// and VEC (4 when the flat arrays are 16-byte aligned; the copy is handled by ShadowDst::quad) as integral constants.
+template <class Go> static void flat_dispatch(int64_t n, bool shadow, bool vec4, Go go) {
+  // (measured: 4096 / 8192 workgroups and non-temporal loads / stores are all 4-10 % slower)
+  const dim3 grid(grid_for(vec4 ? (n + 3) / 4 : n, 256, 2048));
+  if (shadow) { if (vec4) go(std::true_type(), Width<4>(), grid); else go(std::true_type(), Width<1>(), grid); }
+  else { if (vec4) go(std::false_type(), Width<4>(), grid); else go(std::false_type(), Width<1>(), grid); }
+}
+
 __global__ __launch_bounds__(256) void soft_update_flat_kernel(float* __restrict__ t, const float* __restrict__ p, int64_t n,
                                                                float tau) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    t[i] = t[i] * (1.0f - tau) + p[i] * tau;
+  flat_walk<1>(n, [&](int64_t i, Width<1>) { t[i] = t[i] * (1.0f - tau) + p[i] * tau; });
 }
 extern "C" int recnn_soft_update_flat(float* target, const float* net, int64_t n, float tau, void* stream) {
   RECNN_REQUIRE(target && net && n >= 0, "soft_update_flat: bad arguments");
   if (n == 0) return 0;
-  int grid = (int)((n + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(soft_update_flat_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, target, net, n, tau);
+  hipLaunchKernelGGL(soft_update_flat_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, target, net, n, tau);
   return recnn_check_hip(hipGetLastError(), "soft_update_flat");
 }
 
@@ -157,16 +194,16 @@ extern "C" int recnn_soft_update_flat(float* target, const float* net, int64_t n
 // a [rows, cols] weight whose rows are not 16-byte aligned or not in the compute type), rewritten by the optimizer pass that has the
 // new value in a register anyway: element i of the flat array is (i / cols, i % cols) of the copy.
 struct ShadowDst { void* dst; int cols; int64_t ld; int bf16; int quad; };
-__device__ __forceinline__ void shadow_put(const ShadowDst& sh, int64_t i, float v) {
+__device__ __forceinline__ void shadow_put(const ShadowDst& sh, int64_t i, const float (&x)[1]) {
   const int64_t r = i / sh.cols;
   const int c = (int)(i - r * sh.cols);
-  if (sh.bf16) ((bf16_t*)sh.dst)[r * sh.ld + c] = f2bf(v);
-  else ((float*)sh.dst)[r * sh.ld + c] = v;
+  if (sh.bf16) ((bf16_t*)sh.dst)[r * sh.ld + c] = f2bf(x[0]);
+  else ((float*)sh.dst)[r * sh.ld + c] = x[0];
 }
 // Four consecutive flat elements i .. i + 3 (i a multiple of 4) with ONE division.  sh.quad (shadow_arg): 4 = the quad lies in one row and
 // its destination is 8- / 16-byte aligned (cols and ld multiples of 4): one store; 2 = cols and ld even: a PAIR never straddles a row and is
 // 4- / 8-byte aligned (the catalogue-sized weights of REINFORCE: [2048, 101290], [100000, 1290]): two stores; 1 = element by element.
-__device__ __forceinline__ void shadow_put4(const ShadowDst& sh, int64_t i, const float (&x)[4]) {
+__device__ __forceinline__ void shadow_put(const ShadowDst& sh, int64_t i, const float (&x)[4]) {
   int64_t r;
   if (i < (int64_t)0x7fffffff) r = (uint32_t)i / (uint32_t)sh.cols;   // (a 64-bit division is ~100 instructions)
   else r = i / sh.cols;
@@ -190,12 +227,6 @@ __device__ __forceinline__ void shadow_put4(const ShadowDst& sh, int64_t i, cons
       if (++c == sh.cols) { c = 0; ++r; }
     }
   }
-}
-// whether the flat passes may take 16 bytes per lane and instruction (the flat arrays 16-byte aligned; the copy is handled by sh.quad)
-static bool flat_vec4(std::initializer_list<const void*> ptrs) {
-  for (const void* q : ptrs)
-    if ((uintptr_t)q & 15) return false;
-  return true;
 }
 static int shadow_arg(const recnn_shadow_out* h, int64_t n, ShadowDst* out) {
   out->dst = nullptr; out->cols = 1; out->ld = 0; out->bf16 = 0; out->quad = 1;
@@ -222,37 +253,28 @@ __device__ __forceinline__ void adam_elem(float& pi, float& mi, float& vi, float
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
   pi -= step_size * (mi / denom);
 }
-// VEC = 4: 16 bytes per lane and load (catalogue-sized tensors -- REINFORCE at 100k items -- are bound by bytes in flight, not by HBM, with
-// 4-byte lanes); the n % 4 tail and unaligned callers take the scalar form.  Element by element the same arithmetic.
+// the pass itself, shared by the host-step and the device-step kernel: a captured step and an eager one stay bit-identical
+template <bool SH, int VEC>
+__device__ __forceinline__ void adam_flat_pass(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                               int64_t n, float beta2, float eps, float wd, float step_size, float bc2_sqrt, float gs,
+                                               float omb1, float omb2, const ShadowDst& sh) {
+  flat_walk<VEC>(n, [&](int64_t i, auto w) {
+#pragma clang fp contract(off)      // (every instantiation must round alike: which products fuse into FMAs is the compiler's choice per body)
+    constexpr int W = decltype(w)::value;
+    float P[W], G[W], M[W], V[W];
+    flat_ld(p, i, P); flat_ld(g, i, G); flat_ld(m, i, M); flat_ld(v, i, V);
+#pragma unroll
+    for (int j = 0; j < W; ++j) adam_elem(P[j], M[j], V[j], G[j], beta2, eps, wd, step_size, bc2_sqrt, gs, omb1, omb2);
+    flat_st(p, i, P); flat_st(m, i, M); flat_st(v, i, V);
+    if (SH) shadow_put(sh, i, P);
+  });
+}
 template <bool SH, int VEC>
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, int64_t n, float lr, float beta1, float beta2,
                                                         float eps, float wd, float step_size, float bc2_sqrt, float gs, float omb1,
                                                         float omb2, const ShadowDst sh) {
-#pragma clang fp contract(off)      // (both instantiations must round alike: which products fuse into FMAs is the compiler's choice per body)
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-  int64_t done = 0;
-  if (VEC == 4) {
-    const int64_t n4 = n >> 2;
-    for (int64_t q = gid; q < n4; q += stride) {
-      const float4 P = ((const float4*)p)[q], G = ((const float4*)g)[q], M = ((const float4*)m)[q], V = ((const float4*)v)[q];
-      float x[4] = {P.x, P.y, P.z, P.w}, mm[4] = {M.x, M.y, M.z, M.w}, vv[4] = {V.x, V.y, V.z, V.w};
-      const float gg[4] = {G.x, G.y, G.z, G.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) adam_elem(x[j], mm[j], vv[j], gg[j], beta2, eps, wd, step_size, bc2_sqrt, gs, omb1, omb2);
-      ((float4*)p)[q] = make_float4(x[0], x[1], x[2], x[3]);
-      ((float4*)m)[q] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-      ((float4*)v)[q] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-      if (SH) shadow_put4(sh, q << 2, x);
-    }
-    done = n4 << 2;
-  }
-  for (int64_t i = done + gid; i < n; i += stride) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    adam_elem(pi, mi, vi, g[i], beta2, eps, wd, step_size, bc2_sqrt, gs, omb1, omb2);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    if (SH) shadow_put(sh, i, pi);
-  }
+  adam_flat_pass<SH, VEC>(p, g, m, v, n, beta2, eps, wd, step_size, bc2_sqrt, gs, omb1, omb2, sh);
 }
 extern "C" int recnn_adam_flat_shadow(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                                       float eps, float weight_decay, int step_t, float grad_scale, const recnn_shadow_out* h_shadow,
@@ -264,15 +286,11 @@ extern "C" int recnn_adam_flat_shadow(float* p, const float* g, float* m, float*
   if (rc) return rc;
   const double b1 = recnn_snap7(beta1), b2 = recnn_snap7(beta2);
   const double bc1 = 1.0 - pow(b1, (double)step_t), bc2 = 1.0 - pow(b2, (double)step_t);
-  const bool v4 = flat_vec4({p, g, m, v});
-  int grid = (int)(((v4 ? (n + 3) / 4 : n) + 255) / 256);
-  if (grid > 2048) grid = 2048;
-#define ADAM_FLAT_GO(SH, VEC)                                                                                                             \
-  hipLaunchKernelGGL((adam_flat_kernel<SH, VEC>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,  \
-                     weight_decay, (float)((double)lr / bc1), (float)sqrt(bc2), grad_scale, (float)(1.0 - b1), (float)(1.0 - b2), sh)
-  if (sh.dst) { if (v4) ADAM_FLAT_GO(true, 4); else ADAM_FLAT_GO(true, 1); }
-  else { if (v4) ADAM_FLAT_GO(false, 4); else ADAM_FLAT_GO(false, 1); }
-#undef ADAM_FLAT_GO
+  flat_dispatch(n, sh.dst, aligned16(p, g, m, v), [&](auto SH, auto VEC, dim3 grid) {
+    hipLaunchKernelGGL((adam_flat_kernel<decltype(SH)::value, decltype(VEC)::value>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                       lr, beta1, beta2, eps, weight_decay, (float)((double)lr / bc1), (float)sqrt(bc2), grad_scale, (float)(1.0 - b1),
+                       (float)(1.0 - b2), sh);
+  });
   return recnn_check_hip(hipGetLastError(), "adam_flat");
 }
 extern "C" int recnn_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
@@ -286,31 +304,18 @@ __global__ __launch_bounds__(256) void adam_flat_at_kernel(float* __restrict__ p
                                                            float* __restrict__ v, int64_t n, float lr, float beta2, float eps, float wd,
                                                            double b1, double b2, const int32_t* __restrict__ t_ptr, int t_add, float gs,
                                                            float omb1, float omb2) {
-#pragma clang fp contract(off)      // the same roundings as adam_flat_kernel: a captured step and an eager one stay bit-identical
   const double t = (double)(*t_ptr + t_add);
   const float step_size = (float)((double)lr / (1.0 - pow(b1, t)));
   const float bc2_sqrt = (float)sqrt(1.0 - pow(b2, t));
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float pi = p[i];
-    float gi = g[i] * gs;
-    if (wd != 0.f) gi += wd * pi;
-    float mi = m[i], vi = v[i];
-    mi += omb1 * (gi - mi);
-    vi = beta2 * vi + omb2 * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
+  adam_flat_pass<false, 1>(p, g, m, v, n, beta2, eps, wd, step_size, bc2_sqrt, gs, omb1, omb2, ShadowDst());
 }
 extern "C" int recnn_adam_flat_at(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                                   float eps, float weight_decay, const int32_t* step_dev, int step_add, float grad_scale, void* stream) {
   RECNN_REQUIRE(p && g && m && v && n >= 0 && step_dev, "adam_flat_at: bad arguments");
   if (n == 0) return 0;
   const double b1 = recnn_snap7(beta1), b2 = recnn_snap7(beta2);
-  int grid = (int)((n + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(adam_flat_at_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta2, eps, weight_decay, b1,
-                     b2, step_dev, step_add, grad_scale, (float)(1.0 - b1), (float)(1.0 - b2));
+  hipLaunchKernelGGL(adam_flat_at_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta2, eps,
+                     weight_decay, b1, b2, step_dev, step_add, grad_scale, (float)(1.0 - b1), (float)(1.0 - b2));
   return recnn_check_hip(hipGetLastError(), "adam_flat_at");
 }
 
@@ -330,12 +335,82 @@ __global__ __launch_bounds__(256) void l1_final_kernel(const float* __restrict__
 }
 extern "C" int recnn_l1_norm_flat(const float* g, int64_t n, float* scratch, float* out, void* stream) {
   RECNN_REQUIRE(g && scratch && out && n >= 0, "l1_norm_flat: bad arguments");
-  int grid = (int)((n + 255) / 256);
-  if (grid > 1024) grid = 1024;
-  if (grid < 1) grid = 1;
+  const int grid = grid_for(n, 256, 1024);
   hipLaunchKernelGGL(l1_part_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, n, scratch);
   hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, grid, out);
   return recnn_check_hip(hipGetLastError(), "l1_norm_flat");
+}
+
+namespace {   // (these kernels keep the internal linkage, hence the profiler names, they had in dqn.hip)
+// clip_grad_norm_(max_norm, norm_type=1) on a flat gradient whose L1 norm is *norm: g *= min(max_norm / (norm + 1e-6), 1).  (The engine's
+// pass has the reference's max_norm = -1 quirk over L1 partials instead: quirk_clip_coef, optim_dev.h.)
+__device__ inline float norm_clip_coef(const float* norm, float max_norm) { return fminf(max_norm / (norm[0] + 1e-6f), 1.f); }
+__global__ __launch_bounds__(256) void dqn_clip_kernel(float* __restrict__ g, int64_t n, const float* __restrict__ norm, float max_norm) {
+  const float cf = norm_clip_coef(norm, max_norm);
+  flat_walk<1>(n, [&](int64_t i, Width<1>) { g[i] *= cf; });
+}
+// One element of torch.optim.RAdam (foreach form): m = lerp(m, g, 1 - b1); v = b2 v + (1 - b2) g g; p += m (1 / ((sqrt(v) + eps) / S) + U)
+// with S = -lr rect sqrt(bc2) / bc1 (0 unrectified), U = -lr / bc1 when unrectified (else 0); fp contraction off.
+__device__ __forceinline__ void radam_elem(float& pi, float& mi, float& vi, float gi, float beta1w, float beta2, float omb2, float eps,
+                                           float wd, float S, float U, int rect) {
+#pragma clang fp contract(off)
+  if (wd != 0.f) gi = gi + wd * pi;
+  mi = mi + beta1w * (gi - mi);
+  vi = vi * beta2 + omb2 * gi * gi;
+  float step;
+  if (rect) {
+    step = (sqrtf(vi) + eps) / S;
+    step = 1.f / step;
+  } else {
+    step = U;
+  }
+  pi = pi + step * mi;
+}
+// norm: a device clip norm (norm_clip_coef); the scaled gradient is written back, so .grad holds what clip_grad_norm_ leaves there.
+__global__ __launch_bounds__(256) void radam_flat_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, int64_t n, float beta1w, float beta2, float omb2, float eps,
+                                                         float wd, float S, float U, int rect, const float* __restrict__ norm,
+                                                         float max_norm) {
+  const float cf = norm ? norm_clip_coef(norm, max_norm) : 1.f;
+  flat_walk<1>(n, [&](int64_t i, Width<1>) {
+#pragma clang fp contract(off)
+    float gi = g[i];
+    if (norm) {
+      gi *= cf;
+      g[i] = gi;
+    }
+    float pi = p[i], mi = m[i], vi = v[i];
+    radam_elem(pi, mi, vi, gi, beta1w, beta2, omb2, eps, wd, S, U, rect);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  });
+}
+}  // namespace
+extern "C" int recnn_dqn_clip(float* g, int64_t n, const float* norm, float max_norm, void* stream) {
+  RECNN_REQUIRE(g && norm && n >= 0, "dqn_clip: bad arguments");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(dqn_clip_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, g, n, norm, max_norm);
+  return recnn_check_hip(hipGetLastError(), "dqn_clip");
+}
+extern "C" int recnn_radam_flat(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int step_t, const float* clip_norm, float max_norm, void* stream) {
+  RECNN_REQUIRE(p && g && m && v && n >= 0 && step_t >= 1, "radam_flat: bad arguments");
+  if (n == 0) return 0;
+  // host scalars in double, as torch computes them from the Python floats (betas: recnn_snap7, optim.h)
+  const double b1 = recnn_snap7(beta1), b2 = recnn_snap7(beta2), t = step_t;
+  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+  const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
+  const double rho_t = rho_inf - 2.0 * t * pow(b2, t) / bc2;
+  const int rect = rho_t > 5.0;
+  double S = 0.0, U = 0.0;
+  if (rect) {
+    const double r = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
+    S = sqrt(bc2) * (lr * r / bc1) * -1.0;
+  } else {
+    U = (lr * 1.0 / bc1) * -1.0;
+  }
+  hipLaunchKernelGGL(radam_flat_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - b1),
+                     (float)b2, (float)(1.0 - b2), eps, weight_decay, (float)S, (float)U, rect, clip_norm, max_norm);
+  return recnn_check_hip(hipGetLastError(), "radam_flat");
 }
 
 // One element of the flat Ranger pass (RAdam + Lookahead: torch_optimizer.Ranger, the third-party optimizer recnn/nn/algo.py:84-90 constructs;
@@ -357,42 +432,23 @@ __global__ __launch_bounds__(256) void ranger_flat_kernel(float* __restrict__ p,
                                                           int rect, float step, float gs, float omb1, float omb2, const ShadowDst sh) {
 #pragma clang fp contract(off)
   const float sl_lr = step * lr;
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-  int64_t done = 0;
-  if (VEC == 4) {      // (see adam_flat_kernel)
-    const int64_t n4 = n >> 2;
-    for (int64_t q = gid; q < n4; q += stride) {
-      const float4 P = ((const float4*)p)[q], G = ((const float4*)g)[q], M = ((const float4*)m)[q], V = ((const float4*)v)[q];
-      float x[4] = {P.x, P.y, P.z, P.w}, mm[4] = {M.x, M.y, M.z, M.w}, vv[4] = {V.x, V.y, V.z, V.w};
-      const float gg[4] = {G.x, G.y, G.z, G.w};
+  flat_walk<VEC>(n, [&](int64_t i, auto w) {
+#pragma clang fp contract(off)
+    constexpr int W = decltype(w)::value;
+    float P[W], G[W], M[W], V[W];
+    flat_ld(p, i, P); flat_ld(g, i, G); flat_ld(m, i, M); flat_ld(v, i, V);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) ranger_elem(x[j], mm[j], vv[j], gg[j], lr, beta1, beta2, eps, wd, rect, sl_lr, gs, omb1, omb2);
-      if (la_sync) {
-        const float4 S = ((const float4*)slow)[q];
-        float ss[4] = {S.x, S.y, S.z, S.w};
+    for (int j = 0; j < W; ++j) ranger_elem(P[j], M[j], V[j], G[j], lr, beta1, beta2, eps, wd, rect, sl_lr, gs, omb1, omb2);
+    if (la_sync) {      // Lookahead: slow += alpha (p - slow); p = slow
+      float S[W];
+      flat_ld(slow, i, S);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { ss[j] += la_alpha * (x[j] - ss[j]); x[j] = ss[j]; }
-        ((float4*)slow)[q] = make_float4(ss[0], ss[1], ss[2], ss[3]);
-      }
-      ((float4*)p)[q] = make_float4(x[0], x[1], x[2], x[3]);
-      ((float4*)m)[q] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-      ((float4*)v)[q] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-      if (SH) shadow_put4(sh, q << 2, x);
+      for (int j = 0; j < W; ++j) { S[j] += la_alpha * (P[j] - S[j]); P[j] = S[j]; }
+      flat_st(slow, i, S);
     }
-    done = n4 << 2;
-  }
-  for (int64_t i = done + gid; i < n; i += stride) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    ranger_elem(pi, mi, vi, g[i], lr, beta1, beta2, eps, wd, rect, sl_lr, gs, omb1, omb2);
-    if (la_sync) {
-      float si = slow[i];
-      si += la_alpha * (pi - si);
-      pi = si;
-      slow[i] = si;
-    }
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    if (SH) shadow_put(sh, i, pi);
-  }
+    flat_st(p, i, P); flat_st(m, i, M); flat_st(v, i, V);
+    if (SH) shadow_put(sh, i, P);
+  });
 }
 extern "C" int recnn_ranger_flat_shadow(float* p, const float* g, float* m, float* v, float* slow, int64_t n, float lr, float beta1,
                                         float beta2, float eps, float weight_decay, float la_alpha, int la_k, float nsma_threshold,
@@ -404,16 +460,12 @@ extern "C" int recnn_ranger_flat_shadow(float* p, const float* g, float* m, floa
   if (rc) return rc;
   const double b1 = recnn_snap7(beta1), b2 = recnn_snap7(beta2);
   const RadamScalars rs = radam_scalars(step_t, log(b1), log(b2), b2, (double)nsma_threshold);
-  const bool v4 = flat_vec4({p, g, m, v, slow});
-  int grid = (int)(((v4 ? (n + 3) / 4 : n) + 255) / 256);
-  if (grid > 2048) grid = 2048;     // (measured: 4096 / 8192 workgroups and non-temporal loads / stores are all 4-10 % slower)
   const int sync = (la_k > 0 && step_t % la_k == 0) ? 1 : 0;
-#define RANGER_FLAT_GO(SH, VEC)                                                                                                             \
-  hipLaunchKernelGGL((ranger_flat_kernel<SH, VEC>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, slow, n, lr, beta1, beta2, \
-                     eps, weight_decay, la_alpha, sync, rs.rect, rs.step, grad_scale, (float)(1.0 - b1), (float)(1.0 - b2), sh)
-  if (sh.dst) { if (v4) RANGER_FLAT_GO(true, 4); else RANGER_FLAT_GO(true, 1); }
-  else { if (v4) RANGER_FLAT_GO(false, 4); else RANGER_FLAT_GO(false, 1); }
-#undef RANGER_FLAT_GO
+  flat_dispatch(n, sh.dst, aligned16(p, g, m, v, slow), [&](auto SH, auto VEC, dim3 grid) {
+    hipLaunchKernelGGL((ranger_flat_kernel<decltype(SH)::value, decltype(VEC)::value>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       slow, n, lr, beta1, beta2, eps, weight_decay, la_alpha, sync, rs.rect, rs.step, grad_scale, (float)(1.0 - b1),
+                       (float)(1.0 - b2), sh);
+  });
   return recnn_check_hip(hipGetLastError(), "ranger_flat");
 }
 extern "C" int recnn_ranger_flat(float* p, const float* g, float* m, float* v, float* slow, int64_t n, float lr, float beta1,

@@ -1,6 +1,6 @@
 // optim_dev.h -- device-side pieces of the flat optimizer pass shared by optim.hip (apply_kernel) and dwadam.hip (the weight-gradient
 // GEMM with the optimizer in its epilogue): workgroup -> element map, fixed-order slab sums, the clip coefficient, the data-parallel
-// exchange and apply_body itself.  Include after optim.h; device code only.
+// exchange and apply_body itself (block_sum256: common.h).  Include after optim.h; device code only.
 #pragma once
 #include "optim.h"
 #include "x3.h"
@@ -12,14 +12,6 @@ __device__ inline int find_tensor(const NetLayout& L, int b) {
   for (int i = 1; i < 6; ++i)
     if (b >= L.t[i].blk0) ti = i;
   return ti;
-}
-
-__device__ inline float block_sum256(float v, float* red /*[4]*/) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // ---- which elements of tensor T this thread owns (see optim.h for the mapping) -------------------------------
@@ -131,11 +123,12 @@ __device__ inline void slab_grads(const TensorSeg& T, int bt, const Own& o, floa
   }
 }
 
-__device__ inline float clip_coef(const float* l1part, int n, float grad_scale, float* red) {
+// The reference's clip_grad_norm_(max_norm=-1, norm_type=1) quirk over per-workgroup L1 partials: coef = -1/(total+1e-6), clamped to <= 1.
+// (The general rule from a finished norm is optim.hip's norm_clip_coef.)
+__device__ inline float quirk_clip_coef(const float* l1part, int n, float grad_scale, float* red) {
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += l1part[i];
   const float total = block_sum256(s, red) * grad_scale;
-  // clip_grad_norm_(max_norm=-1, norm_type=1): coef = -1/(total+1e-6), clamped to <= 1
   return fminf(-1.0f / (total + 1e-6f), 1.0f);
 }
 
@@ -230,7 +223,7 @@ __device__ __forceinline__ void apply_body(const NetLayout& L, const ApplyArgs& 
   }
   float gs = a.grad_scale;
   if (a.n_l1 > 0) {
-    const float coef = clip_coef(a.l1part, a.n_l1, a.grad_scale, red);
+    const float coef = quirk_clip_coef(a.l1part, a.n_l1, a.grad_scale, red);
     if (a.coef_out && b == 0 && threadIdx.x == 0) a.coef_out[0] = coef;
     gs *= coef;
   }

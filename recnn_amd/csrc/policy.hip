@@ -18,34 +18,6 @@ constexpr int PT = 1024;        // threads per row workgroup
 constexpr int NWAVE = PT / WAVE;
 constexpr float CAT_EPS = 1.1920928955078125e-07f;  // torch.finfo(float32).eps: Categorical clamps probs to [eps, 1-eps]
 
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-  return v;
-}
-
-// sum over the workgroup, result in every thread.  `red` holds NWAVE floats.
-__device__ inline float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < NWAVE; ++i) t += red[i];
-  return t;
-}
-__device__ inline float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = red[0];
-#pragma unroll
-  for (int i = 1; i < NWAVE; ++i) t = fmaxf(t, red[i]);
-  return t;
-}
-
 __device__ inline float4 load4_tail(const float* row, int i4, int n, float fill) {
   // element 4*i4 + c exists iff < n; rows are 16-byte aligned and padded to a multiple of 4 floats in memory
   float4 v = *(const float4*)(row + 4 * (int64_t)i4);
@@ -85,9 +57,9 @@ __global__ __launch_bounds__(PT) void categorical_kernel(float* __restrict__ x, 
       if (vm > m) { s *= expf(m - vm); m = vm; }
       s += expf(v.x - m) + expf(v.y - m) + expf(v.z - m) + expf(v.w - m);
     }
-    mx = block_max(m, red);
+    mx = block_max<NWAVE>(m, red);
     s = (m == -INFINITY) ? 0.f : s * expf(m - mx);
-    denom = block_sum(s, red);
+    denom = block_sum<NWAVE>(s, red);
   }
 
   // normalising pass (row now comes from L2): write p, accumulate this thread's share of sum(p)
@@ -102,7 +74,7 @@ __global__ __launch_bounds__(PT) void categorical_kernel(float* __restrict__ x, 
     mine += (v.x + v.y) + (v.z + v.w);
   }
   part[tid] = mine;
-  const float psum = block_sum(mine, red);   // (also orders part[] and the p stores before what follows)
+  const float psum = block_sum<NWAVE>(mine, red);   // (also orders part[] and the p stores before what follows)
 
   int64_t a = -1;
   if (sample) {
@@ -282,7 +254,7 @@ __global__ __launch_bounds__(PT) void softmax_bwd_kernel(const float* __restrict
   float* dr = d + (int64_t)row * ldd;
   float dot = 0.f;
   for (int j = tid; j < n; j += PT) dot += pr[j] * gr[j];
-  dot = block_sum(dot, red);
+  dot = block_sum<NWAVE>(dot, red);
   const int npad = (n + 3) & ~3;
   for (int j = tid; j < npad; j += PT) dr[j] = j < n ? pr[j] * (gr[j] - dot) : 0.f;
 }
@@ -303,8 +275,6 @@ __global__ __launch_bounds__(256) void onehot_kernel(const int64_t* __restrict__
     *(float4*)(out + (int64_t)r * ld + 4 * (int64_t)i4) = v;
   }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // dst[c][r] = src[r][c]: fp32 [R, C] -> fp32 or bf16 [C, ldt].  The backward of the policy head contracts d logits [rows, n_items]
 // with W2 [n_items, hidden] over the CATALOGUE -- W2 is k-strided for that product; its transpose (made once per weight version)
@@ -346,7 +316,7 @@ __global__ __launch_bounds__(PT) void shard_rowmax_kernel(const float* __restric
     const float4 v = load4_tail(xr, i, n, -INFINITY);
     mx = fmaxf(mx, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
   }
-  mx = block_max(mx, red);
+  mx = block_max<NWAVE>(mx, red);
   if (threadIdx.x == 0) m[blockIdx.x] = mx;
 }
 __global__ __launch_bounds__(PT) void shard_exp_rowsum_kernel(float* __restrict__ x, int64_t ld, int n, const float* __restrict__ m,
@@ -362,7 +332,7 @@ __global__ __launch_bounds__(PT) void shard_exp_rowsum_kernel(float* __restrict_
     *(float4*)(xr + 4 * (int64_t)i) = v;
     mine += (v.x + v.y) + (v.z + v.w);
   }
-  const float tot = block_sum(mine, red);
+  const float tot = block_sum<NWAVE>(mine, red);
   if (threadIdx.x == 0) ssum[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(PT) void shard_norm_pick_kernel(float* __restrict__ x, int64_t ld, int n, const float* __restrict__ ssum,
@@ -422,7 +392,7 @@ int recnn_categorical_rows(float* x, int64_t ld, int rows, int n, int flags, uin
 int recnn_logprob_bwd(const float* p, int64_t ldp, int rows, int n, const int64_t* actions, const float* g, const float* rowstat,
                       void* dlogits, int64_t ldd, int flags, float* colsum, float* scratch, void* stream) {
   RECNN_REQUIRE(p && actions && rowstat && dlogits && rows >= 0 && n > 0, "logprob_bwd: bad arguments");
-  RECNN_REQUIRE(aligned16(p) && aligned16(dlogits) && ldp % 4 == 0 && ldd % 4 == 0 && ldp >= ((n + 3) & ~3) && ldd >= ((n + 3) & ~3),
+  RECNN_REQUIRE(aligned16(p, dlogits) && ldp % 4 == 0 && ldd % 4 == 0 && ldp >= ((n + 3) & ~3) && ldd >= ((n + 3) & ~3),
                 "logprob_bwd: rows must be 16-byte aligned and padded to 4 floats");
   RECNN_REQUIRE(!colsum || scratch, "logprob_bwd: column sums need the scratch buffer (ceil(rows/32) * round4(n) floats)");
   if (rows == 0) return 0;
@@ -472,7 +442,7 @@ int recnn_shard_softmax_pass(float* x, int64_t ld, int rows, int n, int pass, fl
 int recnn_shard_logprob_bwd(const float* p, int64_t ldp, int rows, int n, const int64_t* local, const float* g, float* dlogits, int64_t ldd,
                             void* stream) {
   RECNN_REQUIRE(p && local && g && dlogits && rows >= 0 && n > 0, "shard_logprob_bwd: bad arguments");
-  RECNN_REQUIRE(aligned16(p) && aligned16(dlogits) && ldp % 4 == 0 && ldd % 4 == 0 && ldp >= ((n + 3) & ~3) && ldd >= ((n + 3) & ~3),
+  RECNN_REQUIRE(aligned16(p, dlogits) && ldp % 4 == 0 && ldd % 4 == 0 && ldp >= ((n + 3) & ~3) && ldd >= ((n + 3) & ~3),
                 "shard_logprob_bwd: rows must be 16-byte aligned and padded to 4 floats");
   if (rows == 0) return 0;
   const int n4 = (n + 3) >> 2;

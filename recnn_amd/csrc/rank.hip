@@ -265,12 +265,6 @@ __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict_
   }
 }
 
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // cosine: x / |x|;  correlation: (x - mean) / |x - mean|.  A zero row (cosine) or a constant row (correlation: its centred row is
 // exactly zero in exact arithmetic) becomes a NaN row.  One wave per row, two elements per lane, fixed-order sums.
 __global__ __launch_bounds__(256) void dist_prep_kernel(const float* __restrict__ x, int64_t ldx, int rows, int centre,
@@ -365,7 +359,7 @@ int check_common(const char* fn, const float* q, int64_t ld_q, int B, const floa
   RECNN_REQUIRE(!needs_aux(metric) || aux, "%s: cosine / correlation need the item aux rows (recnn_dist_item_aux)", fn);
   RECNN_REQUIRE(B >= 0 && N > 0, "%s: need n_queries >= 0 and n_items > 0", fn);
   RECNN_REQUIRE(emb_dim == E, "%s: emb_dim must be 128 (the reference's embedding width)", fn);
-  RECNN_REQUIRE((((uintptr_t)q | (uintptr_t)table | (uintptr_t)aux) & 15) == 0 && ld_q % 4 == 0 && ld_q >= E,
+  RECNN_REQUIRE(aligned16(q, table, aux) && ld_q % 4 == 0 && ld_q >= E,
                 "%s: 16-byte alignment (rows and ld_q)", fn);
   return 0;
 }
@@ -396,7 +390,7 @@ extern "C" int recnn_dist_item_aux_floats(int n_items, int emb_dim, int metric, 
 extern "C" int recnn_dist_item_aux(const float* table, int n_items, int emb_dim, int metric, float* aux, void* stream) {
   RECNN_REQUIRE(needs_aux(metric), "dist_item_aux: only cosine / correlation have an item aux");
   RECNN_REQUIRE(table && aux && n_items > 0 && emb_dim == E, "dist_item_aux: bad arguments");
-  RECNN_REQUIRE((((uintptr_t)table | (uintptr_t)aux) & 15) == 0, "dist_item_aux: 16-byte alignment");
+  RECNN_REQUIRE(aligned16(table, aux), "dist_item_aux: 16-byte alignment");
   hipLaunchKernelGGL(dist_prep_kernel, dim3((n_items + 3) / 4), dim3(256), 0, (hipStream_t)stream, table, (int64_t)E, n_items,
                      (int)(metric == CORRELATION), aux);
   return recnn_check_hip(hipGetLastError(), "dist_prep_kernel");
@@ -417,7 +411,7 @@ extern "C" int recnn_dist_matrix(const float* queries, int64_t ld_q, int n_queri
   if (int rc = check_common("dist_matrix", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
   RECNN_REQUIRE((out || n_queries == 0) && ld_out >= n_items, "dist_matrix: null output or ld_out < n_items");
   RECNN_REQUIRE(workspace || !needs_aux(metric) || n_queries == 0, "dist_matrix: cosine / correlation need the workspace");
-  RECNN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dist_matrix: 16-byte alignment (workspace)");
+  RECNN_REQUIRE(aligned16(workspace), "dist_matrix: 16-byte alignment (workspace)");
   if (n_queries == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   DistArgs a;
@@ -434,7 +428,7 @@ extern "C" int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries
   if (int rc = check_common("dist_topk", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
   RECNN_REQUIRE((out_dist && out_ids && workspace) || n_queries == 0, "dist_topk: null pointer");
   RECNN_REQUIRE(k > 0 && k <= KMAX && k <= n_items, "dist_topk: need 0 < k <= min(64, n_items)");
-  RECNN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dist_topk: 16-byte alignment (workspace)");
+  RECNN_REQUIRE(aligned16(workspace), "dist_topk: 16-byte alignment (workspace)");
   if (n_queries == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   DistArgs a;

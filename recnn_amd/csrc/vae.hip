@@ -52,17 +52,6 @@ __global__ __launch_bounds__(VT) void vae_latent_bwd_kernel(const float* __restr
   }
 }
 
-__device__ inline float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < VT / WAVE; ++i) t += red[i];
-  __syncthreads();
-  return t;
-}
-
 // parts[b] = (sum (u - a)^2, sum (1 + log(std^2) - mean^2 - std^2)) over workgroup b's elements
 __global__ __launch_bounds__(VT) void vae_loss_part_kernel(const float* __restrict__ u, int64_t ldu, const float* __restrict__ a, int64_t lda,
                                                            const float* __restrict__ mean, int64_t ldm, const float* __restrict__ sd,
@@ -80,8 +69,8 @@ __global__ __launch_bounds__(VT) void vae_loss_part_kernel(const float* __restri
     const float m = mean[r * ldm + c], s = sd[r * lds_ + c];
     kl += 1.f + logf(s * s) - m * m - s * s;
   }
-  se = block_sum(se, red);
-  kl = block_sum(kl, red);
+  se = block_sum<VT / WAVE>(se, red);
+  kl = block_sum<VT / WAVE>(kl, red);
   if (threadIdx.x == 0) {
     parts[2 * blockIdx.x] = se;
     parts[2 * blockIdx.x + 1] = kl;
@@ -128,11 +117,6 @@ __global__ __launch_bounds__(VT) void vae_loss_bwd_kernel(const float* __restric
   }
 }
 
-inline int grid_for(int64_t elems) {
-  int64_t g = (elems + VT - 1) / VT;
-  return (int)(g < 1 ? 1 : (g > MAX_PARTS ? MAX_PARTS : g));
-}
-
 }  // namespace
 
 extern "C" {
@@ -142,7 +126,7 @@ int recnn_vae_latent_fwd(const float* ml, int64_t ld_ml, const float* eps, int64
   RECNN_REQUIRE(ml && eps && z && std_out && rows >= 0 && latent > 0, "vae_latent_fwd: bad arguments");
   RECNN_REQUIRE(ld_ml >= 2 * latent && ld_eps >= latent && ldz >= latent && ld_std >= latent, "vae_latent_fwd: row strides too small");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(vae_latent_fwd_kernel, dim3(grid_for((int64_t)rows * latent)), dim3(VT), 0, (hipStream_t)stream, ml, ld_ml, eps, ld_eps,
+  hipLaunchKernelGGL(vae_latent_fwd_kernel, dim3(grid_for((int64_t)rows * latent, VT, MAX_PARTS)), dim3(VT), 0, (hipStream_t)stream, ml, ld_ml, eps, ld_eps,
                      rows, latent, z, ldz, std_out, ld_std);
   return recnn_check_hip(hipGetLastError(), "vae_latent_fwd launch");
 }
@@ -155,7 +139,7 @@ int recnn_vae_latent_bwd(const float* ml, int64_t ld_ml, const float* eps, int64
   RECNN_REQUIRE((!dz || ld_dz >= latent) && (!dmean || ld_dmean >= latent) && (!dstd || ld_dstd >= latent),
                 "vae_latent_bwd: gradient row strides too small");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(vae_latent_bwd_kernel, dim3(grid_for((int64_t)rows * latent)), dim3(VT), 0, (hipStream_t)stream, ml, ld_ml, eps, ld_eps,
+  hipLaunchKernelGGL(vae_latent_bwd_kernel, dim3(grid_for((int64_t)rows * latent, VT, MAX_PARTS)), dim3(VT), 0, (hipStream_t)stream, ml, ld_ml, eps, ld_eps,
                      std_in, ld_std, dz, ld_dz, dmean, ld_dmean, dstd, ld_dstd, rows, latent, dml, ld_dml);
   return recnn_check_hip(hipGetLastError(), "vae_latent_bwd launch");
 }
@@ -166,7 +150,7 @@ int recnn_vae_loss_fwd(const float* recon, int64_t ld_recon, const float* action
   RECNN_REQUIRE(recon && action && mean && std_in && out3 && scratch && rows > 0 && action_dim > 0 && latent > 0,
                 "vae_loss_fwd: bad arguments (scratch: 2 * 256 floats)");
   const int64_t na = (int64_t)rows * action_dim, nl = (int64_t)rows * latent;
-  const int nparts = grid_for(na > nl ? na : nl);
+  const int nparts = grid_for(na > nl ? na : nl, VT, MAX_PARTS);
   hipLaunchKernelGGL(vae_loss_part_kernel, dim3(nparts), dim3(VT), 0, (hipStream_t)stream, recon, ld_recon, action, ld_action, mean, ld_mean,
                      std_in, ld_std, rows, action_dim, latent, scratch);
   hipLaunchKernelGGL(vae_loss_final_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, scratch, nparts, 1.f / (float)na, 1.f / (float)nl,
@@ -180,7 +164,7 @@ int recnn_vae_loss_bwd(const float* recon, int64_t ld_recon, const float* action
   RECNN_REQUIRE(recon && action && mean && std_in && gout && d_recon && d_mean && d_std && rows > 0 && action_dim > 0 && latent > 0,
                 "vae_loss_bwd: bad arguments");
   const int64_t na = (int64_t)rows * action_dim, nl = (int64_t)rows * latent;
-  hipLaunchKernelGGL(vae_loss_bwd_kernel, dim3(grid_for(na > nl ? na : nl)), dim3(VT), 0, (hipStream_t)stream, recon, ld_recon, action,
+  hipLaunchKernelGGL(vae_loss_bwd_kernel, dim3(grid_for(na > nl ? na : nl, VT, MAX_PARTS)), dim3(VT), 0, (hipStream_t)stream, recon, ld_recon, action,
                      ld_action, mean, ld_mean, std_in, ld_std, rows, action_dim, latent, gout, kl_weight, d_recon, ld_drecon, d_mean, ld_dmean,
                      d_std, ld_dstd);
   return recnn_check_hip(hipGetLastError(), "vae_loss_bwd launch");

@@ -94,9 +94,7 @@ def csr_from_ratings_device(user_ids, item_keys, ratings, timestamps, key_to_id=
         vals = np.fromiter(key_to_id.values(), dtype=np.int64, count=len(key_to_id))
         o = np.argsort(keys)
         mk, mv, n_map = up(keys[o], np.int64), up(vals[o], np.int64), len(keys)
-    need = C.c_int64(0)
-    L.call("recnn_csr_workspace_bytes", n, C.byref(need))
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws = L.workspace("recnn_csr_workspace_bytes", n, device=dev)
     items = torch.empty(n, dtype=torch.int64, device=dev)
     rates = torch.empty(n, dtype=torch.float64, device=dev)
     users = torch.empty(n, dtype=torch.int64, device=dev)
@@ -105,7 +103,7 @@ def csr_from_ratings_device(user_ids, item_keys, ratings, timestamps, key_to_id=
     counts = (C.c_int64 * 3)()
     with torch.cuda.device(dev):
         L.call("recnn_csr_build", L.ptr(d_user), L.ptr(d_item), L.ptr(d_rating), L.ptr(d_ts), n, L.ptr(mk), L.ptr(mv), n_map,
-               L.ptr(items), L.ptr(rates), L.ptr(users), L.ptr(off), None, L.ptr(mapped), counts, L.ptr(ws), need.value,
+               L.ptr(items), L.ptr(rates), L.ptr(users), L.ptr(off), None, L.ptr(mapped), counts, L.ptr(ws), ws.numel(),
                L.current_stream())
     n_users, missing = int(counts[0]), int(counts[1])
     if missing:

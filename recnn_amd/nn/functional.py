@@ -994,13 +994,6 @@ def _ae_input(x):
     return x
 
 
-def _ae_buffers(rows, device):
-    n_act, n_ws = C.c_int64(), C.c_int64()
-    L.call("recnn_ae_act_floats", rows, C.byref(n_act))
-    L.call("recnn_ae_workspace_bytes", rows, C.byref(n_ws))
-    return torch.empty(n_act.value, device=device), torch.empty((n_ws.value + 3) // 4, device=device)
-
-
 def _ae_run(x, lins, bns, train, want_err, keep, tensors=None):
     """(out or err, act, workspace): one eval launch, or the four-launch forward when training or keeping activations."""
     rows = x.shape[0]
@@ -1014,7 +1007,8 @@ def _ae_run(x, lins, bns, train, want_err, keep, tensors=None):
     if not train and not keep:
         L.call("recnn_ae_eval", C.byref(p), L.ptr(x), x.stride(0), rows, L.ptr(out), 128, L.ptr(err), L.current_stream())
         return res, None, None
-    act, ws = _ae_buffers(rows, x.device)
+    act = L.workspace("recnn_ae_act_floats", rows, device=x.device)
+    ws = L.workspace("recnn_ae_workspace_bytes", rows, device=x.device)
     L.call("recnn_ae_forward", C.byref(p), int(train), L.ptr(x), x.stride(0), rows, L.ptr(out), 128, L.ptr(err), L.ptr(act),
            int(keep), L.ptr(ws), L.current_stream())
     return res, act, ws
@@ -1091,9 +1085,7 @@ DQN_HIDDEN = 128
 
 def dqn_colsum(x, rows, cols, scale=1.0, out=None):
     """float[cols]: scale * column sums of x[:rows, :cols] (row stride x.stride(0)) in a fixed order."""
-    ws_n = C.c_int64()
-    L.call("recnn_dqn_colsum_workspace_floats", rows, cols, C.byref(ws_n))
-    ws = torch.empty(ws_n.value, dtype=torch.float32, device=x.device)
+    ws = L.workspace("recnn_dqn_colsum_workspace_floats", rows, cols, device=x.device)
     out = torch.empty(cols, dtype=torch.float32, device=x.device) if out is None else out
     L.call("recnn_dqn_colsum", L.ptr(x), x.stride(0) if x.dim() == 2 else 1, rows, cols, float(scale), L.ptr(out), L.ptr(ws),
            L.current_stream())

@@ -17,7 +17,6 @@ catalogue-wide parts on csrc/dqn.hip: the online Q at the action is one gathered
 max_n is the only catalogue GEMM (row-max epilogue, [B, N] never stored), and the head / embedding gradients are deterministic
 scatter-sums.  The loss is the only value read back to the host.
 """
-import ctypes as C
 
 import torch
 
@@ -162,9 +161,7 @@ def dqn_update(batch, params, nets, optimizer, device=torch.device("cuda"), debu
     gw12 = flat[offs[id(la0.weight)]:offs[id(la0.weight)] + 2 * H * H].view(2 * H, H)
     gb12 = flat[offs[id(la0.bias)]:offs[id(la0.bias)] + 2 * H]
 
-    ws_n = C.c_int64()
-    L.call("recnn_dqn_scatter_workspace_bytes", B * F, max(N, emb.num_embeddings), C.byref(ws_n))
-    ws = torch.empty((ws_n.value + 3) // 4, dtype=torch.float32, device=dev)
+    ws = L.workspace("recnn_dqn_scatter_workspace_bytes", B * F, max(N, emb.num_embeddings), device=dev)
     # head: dW = sum_{a_b = n} g_b ha_b - kappa sum_b ha_b, dc = sum_{a_b = n} g_b - G / N; value head: sum_b g_b hv_b, G
     L.call("recnn_dqn_scatter_sum", L.ptr(h2), h2.stride(0), B, 1, L.ptr(action), 1, L.ptr(g), N, L.ptr(views[id(la2.weight)]),
            L.ptr(views[id(la2.bias)]), L.ptr(sh), L.ptr(stats[2:4]), L.ptr(ws), s)

@@ -12,7 +12,8 @@
            against it ("parity unpinned").  What IS pinned: with weight_decay = 0 the RAdam part equals
            torch.optim.RAdam (same rectification term, same threshold, eps outside the sqrt), and Lookahead is three lines
            (tests/test_gpu_optim.py); `Ranger.reference_step` is the same algorithm in plain torch ops.
-`RAdam` -- torch.optim.RAdam's arithmetic (its foreach form; L2 weight decay) on the HIP kernel `recnn_radam_flat`, which can take the
+`RAdam` -- torch.optim.RAdam's arithmetic (its foreach form; L2 weight decay) on the HIP kernel `recnn_radam_flat` (csrc/optim.hip, like
+           the other two), which can take the
            clip_grad_norm_ coefficient from a device scalar (`dqn_update`: the clip costs no host read and no extra pass).
 """
 import math

@@ -68,12 +68,6 @@ def _item_aux(table, name):
     return aux
 
 
-def _workspace(B, n, name, k, device):
-    nbytes = C.c_int64()
-    L.call("recnn_dist_workspace_bytes", B, n, DIST_METRICS[name], k, C.byref(nbytes))
-    return torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=device)
-
-
 class FlatIndex:
     """Exact search over the rows of `table` (float32 [N, 128] on the GPU).
 
@@ -117,13 +111,11 @@ class FlatIndex:
         dist = torch.empty(B, k, dtype=torch.float32, device=q.device)
         ids = torch.empty(B, k, dtype=torch.int64, device=q.device)
         if self.metric in DIST_METRICS:
-            ws = _workspace(B, self.n_items, self.metric, k, q.device)
+            ws = L.workspace("recnn_dist_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], k, device=q.device)
             L.call("recnn_dist_topk", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
                    DIST_METRICS[self.metric], self.p, L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream())
             return dist, ids
-        nbytes = C.c_int64()
-        L.call("recnn_topk_workspace_bytes", B, k, C.byref(nbytes))
-        ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=q.device)
+        ws = L.workspace("recnn_topk_workspace_bytes", B, k, device=q.device)
         L.call("recnn_topk_search", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim, METRICS[self.metric],
                L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream())
         return dist, ids
@@ -144,7 +136,7 @@ def cdist(queries: torch.Tensor, table: torch.Tensor, metric="euclidean", p=None
     B, (N, dim) = q.shape[0], t.shape
     aux = _item_aux(t, name)
     out = torch.empty(B, N, dtype=torch.float32, device=t.device)
-    ws = _workspace(B, N, name, 0, t.device)
+    ws = L.workspace("recnn_dist_workspace_bytes", B, N, DIST_METRICS[name], 0, device=t.device)
     L.call("recnn_dist_matrix", L.ptr(q), q.stride(0), B, L.ptr(t), N, dim, DIST_METRICS[name], pp, L.ptr(aux), L.ptr(out), N,
            L.ptr(ws), L.current_stream())
     return out
@@ -193,11 +185,9 @@ def topk_stats(dist, ids, n_items, sqrt=False, counts=None, totals=None):
             raise ValueError(f"topk_stats: {what} must be a contiguous {dtype} tensor of shape {shape}")
     row_mean = torch.empty(B, dtype=torch.float64, device=dev)
     row_std = torch.empty(B, dtype=torch.float64, device=dev)
-    nbytes = C.c_int64()
-    L.call("recnn_topk_stats_workspace_bytes", B, k, C.byref(nbytes))
+    ws = L.workspace("recnn_topk_stats_workspace_bytes", B, k, device=dev)     # (also refuses a k the kernel cannot take)
     if B == 0:                                                       # an empty batch has no storage to point at
         return TopkStats(row_mean, row_std, counts, totals)
-    ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
     L.call("recnn_topk_stats", L.ptr(dist), L.ptr(ids), B, k, n_items, int(bool(sqrt)), L.ptr(counts), L.ptr(row_mean),
            L.ptr(row_std), L.ptr(totals), L.ptr(ws), L.current_stream())
     return TopkStats(row_mean, row_std, counts, totals)

@@ -76,8 +76,8 @@ def cdist_into(q, t, metric, p, aux, out):
     """recnn_dist_matrix into a preallocated [B, N] (the scoring loop with the store epilogue)."""
     import ctypes as C
     from recnn_amd import _lib as L
-    from recnn_amd.retrieval import DIST_METRICS, _workspace, minkowski_p
-    ws = _workspace(q.shape[0], t.shape[0], metric, 0, q.device)
+    from recnn_amd.retrieval import DIST_METRICS, minkowski_p
+    ws = L.workspace("recnn_dist_workspace_bytes", q.shape[0], t.shape[0], DIST_METRICS[metric], 0, device=q.device)
     L.call("recnn_dist_matrix", L.ptr(q), q.stride(0), q.shape[0], L.ptr(t), t.shape[0], t.shape[1], DIST_METRICS[metric],
            C.c_double(minkowski_p(metric, p)), L.ptr(aux), L.ptr(out), t.shape[0], L.ptr(ws), L.current_stream())
 

@@ -17,6 +17,7 @@
 // g(k) = (k & 3) | (((k >> 3) & 1) << 2): the 8 rows x 32 bytes of a half-wave transpose read hit 8 distinct
 // 32-byte bank groups.
 #include "bwd.h"
+#include "lds_stream.h"
 
 namespace {
 constexpr int NW = 16;
@@ -25,17 +26,6 @@ constexpr int SLAB_BYTES = 128 * 512;       // 128 k rows x 256 columns bf16
 constexpr int PANEL_OFF = 2 * SLAB_BYTES;   // dz2 panel: two k halves of 32 rows x 256 B (chunk c of row r at c ^ (r & 15))
 constexpr int PANEL_HALF = BWD_ROWS * 256;
 constexpr int LDS_TOTAL = PANEL_OFF + 2 * PANEL_HALF;
-
-typedef short v4s16 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst_uniform)
-      : "memory");
-}
 
 // k rows [k0, k0 + 128) of W2 (row pitch ld elements, 256 columns) -> LDS slab; 2 rows per wave instruction
 __device__ __forceinline__ void dma_w2_slab(const void* W2, int64_t ld, int k0, int k_max, unsigned lds_dst, int wave, int lane) {
@@ -171,10 +161,10 @@ __global__ __launch_bounds__(NW * 64) void bwd_panel_kernel(const BwdPanelBatch 
         b[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
             (__attribute__((address_space(3))) v4s16*)(sbm + k * 512 + ((wave ^ g) * 32) + (fr & 3) * 8));
       }
-      struct { v4s16 lo, hi; } bv = {b[0], b[1]};
+      const TrFrag bv = {b[0], b[1]};
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm)
-        acc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[tm]), __builtin_bit_cast(bf16x8, bv), acc[tm], 0, 0, 0);
+        acc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[tm]), bv.to_bf16x8(), acc[tm], 0, 0, 0);
     }
   }
 
@@ -253,10 +243,10 @@ __device__ __forceinline__ void ch_mma(const unsigned char* panel, int half, con
       b[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
           (__attribute__((address_space(3))) v4s16*)(slab + k * row_bytes + ((wave ^ g) * 32) + (fr & 3) * 8));
     }
-    struct { v4s16 lo, hi; } bv = {b[0], b[1]};
+    const TrFrag bv = {b[0], b[1]};
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
-      acc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[tm]), __builtin_bit_cast(bf16x8, bv), acc[tm], 0, 0, 0);
+      acc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[tm]), bv.to_bf16x8(), acc[tm], 0, 0, 0);
   }
 }
 }  // namespace

@@ -165,7 +165,7 @@ inline int grid_for(int64_t elems, int per_wg, int cap) {
 // batch after the other pays a scalar-cache miss (~0.5 us) per first touch of a line; after this they are hits (measured: l1gemm.hip, round
 // 3; x3_fwd_ws_kernel -0.5 us, round 5).
 #if defined(__HIPCC__)
-template <int BYTES> __device__ __forceinline__ void kernarg_prefetch(int dyn_offset = 0) {
+template <int BYTES> __device__ __forceinline__ void kernarg_prefetch(size_t dyn_offset = 0) {
   unsigned touch = 0;
   const char __attribute__((address_space(4)))* pa =
       (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + dyn_offset;

@@ -11,17 +11,7 @@
 // (rows {0..3} and {8..11} of a k step, same 16 columns) fall on 8 different 32-byte bank groups.
 #pragma once
 #include "gemm.h"
-
-typedef short v4s16 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dw_dma16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst_uniform)
-      : "memory");
-}
+#include "lds_stream.h"
 
 // acc += dZ[kbeg..kend, m0..m0+63]^T * X[kbeg..kend, n0..n0+63] for the calling workgroup of 256 * NWK threads: 4 * NWK waves as
 // NWK k-groups x (2 x 2) wave tiles of 32 x 32.  k-group kq takes the 32-row k steps ks with ks % NWK == kq of every stage, so
@@ -67,7 +57,7 @@ __device__ __forceinline__ void dw_tile_accumulate(const GemmProb& P, const int 
       const int row = min(k0 + rg * 8 + d_row, kend - 1);  // clamped rows are masked out of the A fragments below
       const char* src = op == 0 ? (const char*)G.A + ((int64_t)row * G.lda + m0) * 2 + c * 16
                                 : (const char*)G.B + ((int64_t)row * G.ldb + n0) * 2 + c * 16;
-      if (!(probe & 4)) dw_dma16(src, sbase + op * OP_BYTES + rg * 1024);
+      if (!(probe & 4)) dma16(src, sbase + op * OP_BYTES + rg * 1024);
     }
   };
 
@@ -159,8 +149,8 @@ __device__ __forceinline__ void dw_tile_accumulate(const GemmProb& P, const int 
       for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
-          struct { v4s16 lo, hi; } av = {a[tm][0], a[tm][1]}, bv = {b[tn][0], b[tn][1]};
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv),
+          const TrFrag av = {a[tm][0], a[tm][1]}, bv = {b[tn][0], b[tn][1]};
+          acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av.to_bf16x8(), bv.to_bf16x8(),
                                                                 acc[tm][tn], 0, 0, 0);
         }
     }

@@ -30,8 +30,7 @@
 #include "optim_dev.h"
 #include "x3.h"
 #include "recnn_hip_debug.h"
-
-typedef short v4s16 __attribute__((ext_vector_type(4)));
+#include "lds_stream.h"
 
 namespace {
 constexpr int NC = 8, NL = 4;                    // consumer / loader waves
@@ -48,13 +47,7 @@ constexpr int PER = (CH_X + CH_Z) / 1024 * (NC / NL);   // DMA instructions per 
 static_assert(16 * PART <= RING, "16 partial tiles must fit the idle ring");
 static_assert(sizeof(OptScalars) <= 64, "scalar block");
 
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "m0");
-}
-
 struct Pair { float2 p, m, v, tp; };
-
-#define DWA_STAMP(i) do { if (trow) trow[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
 
 // ---- split bf16 (x3.h): the tile's operands are 64 physical columns of dZ (one [hi 32 | lo 32] group = 32 logical) and 128 of X (two
 // groups = 64 logical); three MFMAs per 32-row k step and 16 x 16 block (x3_mfma: lo.hi, hi.lo, hi.hi -- x3.hip x3_dw_kernel's order).
@@ -64,20 +57,7 @@ struct Pair { float2 p, m, v, tp; };
 // through LDS only to reach the row-contiguous quads of the shared epilogue.
 constexpr int X3_ROWS = 128;                     // batch rows per stage
 constexpr int X3_XB = X3_ROWS * 256;             // 32 KB of X rows, then 16 KB of dZ rows
-__device__ __forceinline__ int swz32(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }   // (x3.hip: 32-byte chunk c of a 256-byte row at c ^ swz32)
-struct TrFrag { v4s16 lo, hi; };
-// transpose-read fragment of 16 physical columns [col0, col0 + 16) over the 32 rows of k step `ks` of the X image (256-byte rows)
-__device__ __forceinline__ bf16x8 x3_frag_x(const unsigned char* s, int col0, int fr, int fg) {
-  TrFrag f;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int row = fg * 8 + half * 4 + (fr >> 2);
-    const v4s16 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) v4s16*)(s + row * 256 + (((col0 >> 4) ^ swz32(row)) << 5) + (fr & 3) * 8));
-    if (half == 0) f.lo = v; else f.hi = v;
-  }
-  return __builtin_bit_cast(bf16x8, f);
-}
+// (the X image, 256-byte rows: tr_frag_swz, lds_stream.h)
 // ... of the dZ image (128-byte rows, dw_tile.h's pair swizzle p ^ f(row))
 __device__ __forceinline__ bf16x8 x3_frag_z(const unsigned char* s, int col0, int fr, int fg) {
   TrFrag f;
@@ -90,7 +70,7 @@ __device__ __forceinline__ bf16x8 x3_frag_z(const unsigned char* s, int col0, in
     const v4s16 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16*)(s + row * 128 + slot * 16 + (fr & 1) * 8));
     if (half == 0) f.lo = v; else f.hi = v;
   }
-  return __builtin_bit_cast(bf16x8, f);
+  return f.to_bf16x8();
 }
 
 // SPW = slabs per consumer wave (nslab / 8); X3: split-bf16 operands and shadows
@@ -254,7 +234,7 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
     const OptScalars S = opt_scalars(a);
     if (lane == 0) *(OptScalars*)(lds + SCAL_OFF) = S;
   }
-  DWA_STAMP(1);
+  TRACE_STAMP(trow, 1);
 
   float g[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (X3) {
@@ -273,19 +253,19 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
       for (int st = 0; st < sps; ++st) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (first) { DWA_STAMP(2); first = false; }
+        if (first) { TRACE_STAMP(trow, 2); first = false; }
         const unsigned char* sx = lds + slot * STAGE;
         const unsigned char* sz = sx + X3_XB;
 #pragma unroll
         for (int kk = 0; kk < X3_ROWS / 32; ++kk) {
           const bf16x8 ah = x3_frag_z(sz + kk * 32 * 128, tm * 16, fr, fg), al = x3_frag_z(sz + kk * 32 * 128, 32 + tm * 16, fr, fg);
-          const bf16x8 bh = x3_frag_x(sx + kk * 32 * 256, xcol, fr, fg), bl = x3_frag_x(sx + kk * 32 * 256, xcol + 32, fr, fg);
+          const bf16x8 bh = tr_frag_swz(sx + kk * 32 * 256, xcol, fr, fg), bl = tr_frag_swz(sx + kk * 32 * 256, xcol + 32, fr, fg);
           acc[sl] = x3_mfma(ah, al, bh, bl, acc[sl]);
         }
         slot = slot + 1 == NS ? 0 : slot + 1;
       }
     }
-    DWA_STAMP(3);
+    TRACE_STAMP(trow, 3);
     // slab sums in apply_kernel's order, per lane: acc[.][r] = dW[m0 + 16 tm + 4 fg + r][n0 + 16 tn + fr]
     f32x4 gsum = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -302,7 +282,7 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    DWA_STAMP(4);
+    TRACE_STAMP(trow, 4);
     const f32x4 gv = *(const f32x4*)((const float*)lds + em * TP + enq);
 #pragma unroll
     for (int k = 0; k < 4; ++k) g[k] = gv[k];
@@ -339,7 +319,7 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
     for (int s = 0; s < SPW; ++s) {
       for (int tt = 0; tt < per_slab; ++tt) {
         __builtin_amdgcn_s_barrier();              // stage t is in LDS (every loader waited for its part)
-        if (s == 0 && tt == 0) DWA_STAMP(2);
+        if (s == 0 && tt == 0) TRACE_STAMP(trow, 2);
         const unsigned char* ch = lds + slot * STAGE + cw * CHUNK;
         v4s16 fa[2][2], fb[4][2];
   #pragma unroll
@@ -355,13 +335,13 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
         for (int tm = 0; tm < 2; ++tm)
   #pragma unroll
           for (int tn = 0; tn < 4; ++tn) {
-            struct { v4s16 lo, hi; } av = {fa[tm][0], fa[tm][1]}, bv = {fb[tn][0], fb[tn][1]};
-            acc[s][tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc[s][tm][tn], 0, 0, 0);
+            const TrFrag av = {fa[tm][0], fa[tm][1]}, bv = {fb[tn][0], fb[tn][1]};
+            acc[s][tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av.to_bf16x8(), bv.to_bf16x8(), acc[s][tm][tn], 0, 0, 0);
           }
         slot = slot + 1 == NS ? 0 : slot + 1;
       }
     }
-    DWA_STAMP(3);
+    TRACE_STAMP(trow, 3);
     // ---- the partial tiles meet in LDS (the ring is idle once every consumer has read its last stage)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -380,7 +360,7 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    DWA_STAMP(4);
+    TRACE_STAMP(trow, 4);
     constexpr int NG = NC * SPW;
     {
       const float* pe = (const float*)lds + em * TP + enq;
@@ -425,7 +405,7 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
       if (a_tp) *(float2*)(a_tp + idx[h]) = make_float2(tp[0], tp[1]);
     }
   }
-  DWA_STAMP(5);
+  TRACE_STAMP(trow, 5);
   if (X3 && t_sh_off >= 0) {                      // split-bf16 shadow(s): hi at the mapped column, lo 32 elements further (x3.h)
     const int c0 = n0 + enq;
     const int64_t se = t_sh_off + (int64_t)row * t_sh_ld;
@@ -450,7 +430,7 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
       if (a_tp && a_tsh) *(uint32_t*)(a_tsh + se) = pack_bf2(tn4[0], tn4[1]);
     }
   }
-  DWA_STAMP(6);
+  TRACE_STAMP(trow, 6);
   if (trow) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); trow[7] = __builtin_amdgcn_s_memtime(); }
 }
 
@@ -459,9 +439,8 @@ __global__ __launch_bounds__((NC + NL) * 64) void dw_adam_kernel(const DwAdamBat
   const DwAdamNet& N = batch.n[blockIdx.y];
   const int nwg = N.nsmall + N.ntile[0] + N.ntile[1];
   if ((int)blockIdx.x >= nwg) return;
-  unsigned long long* trow = (trace && threadIdx.x == 0) ? trace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 : nullptr;
-  asm volatile("" : "+v"(trow));
-  DWA_STAMP(0);
+  unsigned long long* trow = TRACE_ROW(trace, (int64_t)blockIdx.y * gridDim.x + blockIdx.x, 8);
+  TRACE_STAMP(trow, 0);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lid = xcd_remap(blockIdx.x, nwg);    // consecutive logical ids share an XCD: the tiles of one X column block read it from one L2
   if (lid < N.nsmall) {

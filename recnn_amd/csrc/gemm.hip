@@ -525,15 +525,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_kernel(const GemmBatch batch) {
 // insertion, which would otherwise drain every DMA before each ds_read).  A k stage is 256 bytes per tile row;
 // the 16-byte chunk c of row r sits at chunk position c ^ (r & 15) of its LDS row (the DMA writes lane-linear,
 // so the XOR is applied to each lane's SOURCE address), which makes the 16 rows x one chunk of an MFMA fragment
-// read hit 16 different bank quads.
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst_uniform)
-      : "memory");
-}
+// read hit 16 different bank quads.  (dma16, lds_stream.h)
 
 // X3 (x3.h): the operands are split-bf16 rows; a 256-byte stage row is two logical 32-k groups [hi 32 | lo 32 | hi 32 | lo 32], each
 // contracted with three MFMAs (hi hi + hi lo + lo hi); K / lda / ldb are physical, the epilogue writes split columns.
@@ -1027,23 +1019,24 @@ __global__ __launch_bounds__((WR * WC + NL) * 64) void x3_fwd_ws_kernel(const Ge
     const int es = P.c_f32 ? 4 : 2;
     const bool st = m0 + BM <= P.M && n0 + BN <= P.N && !(((int64_t)P.ldc * es) & 15) && !((uintptr_t)P.C & 15) && !((uintptr_t)P.bias & 15) &&
                     BM * TPF <= NS * STAGE_BYTES && !P.dot_part && !(probe & 64);
+    // (row pointer without TRACE_ROW's pin: a consumer wave has no DMA in flight that a stamp could drain)
     unsigned long long* trow = (trace && tid == 0) ? trace + (int64_t)blockIdx.x * 8 : nullptr;
-    if (trow) trow[0] = __builtin_amdgcn_s_memtime();
+    TRACE_STAMP(trow, 0);
     if (!st) {
       epilogue_fwd_x3<TM, TN, false>(P, acc, m0, n0, wm0, wn0, lane, lid * NC + wave);
       return;
     }
     __builtin_amdgcn_s_barrier();          // every consumer is done reading the last k stage
-    if (trow) trow[1] = __builtin_amdgcn_s_memtime();
+    TRACE_STAMP(trow, 1);
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
         *(f32x4*)(dsmem + (wm0 + tm * 16 + fr) * TPF + (wn0 + tn * 16 + fg * 4) * 4) = acc[tm][tn];
-    if (trow) trow[2] = __builtin_amdgcn_s_memtime();
+    TRACE_STAMP(trow, 2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's part of the image is IN LDS (s_barrier alone does not wait for LDS writes)
     __builtin_amdgcn_s_barrier();
-    if (trow) trow[3] = __builtin_amdgcn_s_memtime();
+    TRACE_STAMP(trow, 3);
     constexpr int CPR = BN / 4;            // 4-column groups per tile row
     static_assert((NC * 64) % CPR == 0, "a lane keeps its column group");
     const int ch = (wave * 64 + lane) % CPR;
@@ -1103,23 +1096,23 @@ __global__ __launch_bounds__((WR * WC + NL) * 64) void x3_fwd_ws_kernel(const Ge
         asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(dst), "v"(o));
       }
     }
-    if (trow) { trow[4] = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); trow[5] = __builtin_amdgcn_s_memtime(); }
+    if (trow) { TRACE_STAMP(trow, 4); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TRACE_STAMP(trow, 5); }
     return;
   }
   constexpr int TP = BN * 4 + X3_TILE_PITCH_PAD;            // bytes per tile row: 2 BN bf16 + a 16-byte skew against bank conflicts
   const bool staged = !P.c_f32 && !P.yref && m0 + BM <= P.M && n0 + BN <= P.N && !(P.ldc & 7) && !((uintptr_t)P.C & 15) && BM * TP <= NS * STAGE_BYTES &&
                       !(probe & 64);
   unsigned long long* trow = (trace && tid == 0) ? trace + (int64_t)blockIdx.x * 8 : nullptr;
-  if (trow) trow[0] = __builtin_amdgcn_s_memtime();
+  TRACE_STAMP(trow, 0);
   if (staged) __builtin_amdgcn_s_barrier();                 // every consumer is done reading the last k stage: the tile image may overwrite it
-  if (trow) trow[1] = __builtin_amdgcn_s_memtime();
+  TRACE_STAMP(trow, 1);
   if (staged && !((uintptr_t)P.bias & 15) && !((uintptr_t)P.dot_w & 15) && !(probe & 1024)) epilogue_x3_full_tile<TM, TN>(P, acc, m0, n0, wm0, wn0, lane, lid * NC + wave, dsmem, TP);
   else epilogue_fwd_x3<TM, TN>(P, acc, m0, n0, wm0, wn0, lane, lid * NC + wave, staged ? dsmem : nullptr, TP);
-  if (trow) trow[2] = __builtin_amdgcn_s_memtime();
+  TRACE_STAMP(trow, 2);
   if (staged) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's part of the image is IN LDS (s_barrier alone does not wait for LDS writes)
     __builtin_amdgcn_s_barrier();
-    if (trow) trow[3] = __builtin_amdgcn_s_memtime();
+    TRACE_STAMP(trow, 3);
     constexpr int CPR2 = BN * 4 / 16;                          // 16-byte chunks per tile row
     bf16_t* C = (bf16_t*)P.C + (int64_t)m0 * P.ldc + x3_col(n0);
     for (int idx = wave * 64 + lane; idx < BM * CPR2; idx += NC * 64) {
@@ -1131,7 +1124,7 @@ __global__ __launch_bounds__((WR * WC + NL) * 64) void x3_fwd_ws_kernel(const Ge
              asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(vv) : "memory"); }   // write-through: the tile drains while the
                                                                                                  // launch runs, not at its end (guide: publish-large)
     }
-    if (trow) { trow[4] = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); trow[5] = __builtin_amdgcn_s_memtime(); }
+    if (trow) { TRACE_STAMP(trow, 4); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TRACE_STAMP(trow, 5); }
   }
 }
 

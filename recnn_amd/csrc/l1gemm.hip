@@ -16,36 +16,19 @@
 // is 256 workgroups of 393 KB each instead of 128 of 1.0 MB) and 128 x 128 / 128 x 64 (2- / 3-slot rings: the cycle-batched
 // launches of the frozen networks, M >= 16k rows).
 #include "split.h"
+#include "lds_stream.h"
 
 namespace {
-
-// One LDS-DMA instruction: 64 lanes x 16 bytes from (uniform base + per-lane 32-bit byte offset) to LDS at lds_dst + 16 lane.
-// M0 is written directly (the kernel has no other M0 consumer); no "memory" clobber: the ordering points are the waits and
-// barriers of the consumer.  (mlps.hip's lean issue: the saddr form keeps a stage's address arithmetic to scalar adds.)
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "m0");
-}
-
-template <int N> __device__ __forceinline__ void wait_vm_const() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // TM x TN 16 x 16 MFMA tiles per wave, WM x WN waves per workgroup, NS ring slots
 template <int TM, int TN, int WM, int WN, int NS>
 __global__ __launch_bounds__(WM * WN * 64) void l1_gemm_kernel(const L1Batch batch, unsigned long long* trace) {
   constexpr int NW = WM * WN;
-  unsigned long long* trow = (trace && threadIdx.x == 0) ? trace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 : nullptr;
-  asm volatile("" : "+v"(trow));
-  if (trow) trow[0] = __builtin_amdgcn_s_memtime();
+  unsigned long long* trow = TRACE_ROW(trace, (int64_t)blockIdx.y * gridDim.x + blockIdx.x, 16);
+  TRACE_STAMP(trow, 0);
   // pull the kernel-argument cache lines of this workgroup's problem into the scalar cache NOW, all in flight together (a first
   // touch costs a scalar-cache miss of ~0.5 us and the fields are otherwise fetched one dependent batch after the other)
-  unsigned touch = 0;
-  {
-    const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-    const char __attribute__((address_space(4)))* pa = ka + blockIdx.y * sizeof(L1Prob);
-#pragma unroll
-    for (int i = 0; i < (int)((sizeof(L1Prob) + 63) / 64); ++i) asm volatile("s_load_dword %0, %1, %2" : "+s"(touch) : "s"(pa), "n"(i * 64));
-    asm volatile("s_load_dword %0, %1, %2" : "+s"(touch) : "s"(pa), "n"((int)sizeof(L1Prob) - 4));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(touch));
-  }
+  kernarg_prefetch<sizeof(L1Prob)>(blockIdx.y * sizeof(L1Prob));
   constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
   constexpr int KB = 128;                                  // k elements per stage (256-byte rows)
   constexpr int D = NS - 1;                                // prefetch distance
@@ -125,9 +108,9 @@ __global__ __launch_bounds__(WM * WN * 64) void l1_gemm_kernel(const L1Batch bat
   }
   // the device step counter through the SCALAR cache (a plain load of this uniform global becomes a vector load + vmcnt(0))
   int32_t step_now = 0;
-  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(step_now) : "s"(P.step_ptr));
+  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) sload_dword(step_now, P.step_ptr);
 
-  if (trow) trow[1] = __builtin_amdgcn_s_memtime();
+  TRACE_STAMP(trow, 1);
   for (int t = 0; t < nt; ++t) {
     // stage t has landed once at most the loads of the (up to D - 1) younger stages are still outstanding
     const int younger = min(D - 1, nt - 1 - t);
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(WM * WN * 64) void l1_gemm_kernel(const L1Batch bat
     }
   }
 
-  if (trow) trow[2] = __builtin_amdgcn_s_memtime();
+  TRACE_STAMP(trow, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(step_now));
   const int32_t step0 = step_now + P.step_add;
   // ---- epilogue: acc[tm][tn][r] = C[row m0 + wm0 + 16 tm + fr][column n0 + wn0 + 16 tn + 4 fg + r]
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(WM * WN * 64) void l1_gemm_kernel(const L1Batch bat
       if (m < P.rows) *(uint2*)((bf16_t*)P.h1 + (int64_t)m * P.ldh + n) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
     }
   }
-  if (trow) trow[3] = __builtin_amdgcn_s_memtime();
+  TRACE_STAMP(trow, 3);
 }
 
 template <int TM, int TN, int WM, int WN, int NS> constexpr int lds_bytes() { return NS * (16 * TM * WM + 16 * TN * WN) * 256; }
@@ -276,7 +259,7 @@ __global__ __launch_bounds__((WS_NL + WS_NC) * 64) void l1_gemm_ws_kernel(const 
   const int nb = n0 + wn0 + fg * 4;
   const f32x4 bias = (nb + 3 < P.H) ? *(const f32x4*)(P.b1 + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
   int32_t step_now = 0;
-  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(step_now) : "s"(P.step_ptr));
+  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) sload_dword(step_now, P.step_ptr);
   for (int t = 0; t < nt; ++t) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (this wave's reads of stage t - 1 have returned: its slot may be refilled)
     __builtin_amdgcn_s_barrier();

@@ -1,21 +1,36 @@
-// mlp_panel.h -- pieces shared by the fused row-panel forward kernels (mlp.hip, mlps.hip): the LDS-DMA primitive, the
-// 32 x 256 bf16 activation panel (the next layer's A operand) and the hidden-layer epilogue that fills it.
+// mlp_panel.h -- pieces shared by the fused row-panel kernels (mlps.hip, mlpt.hip, mlpf.hip): the 32 x 256 bf16 activation panel (the
+// next layer's A operand), the hidden-layer epilogue that fills it and the panel x weight-slab product (mlps.hip, mlpt.hip).
 #pragma once
 #include <type_traits>
 #include "mlp.h"
+#include "lds_stream.h"
 
 namespace {
 constexpr int BM = 32;            // rows per workgroup
 constexpr int HP = 256;           // hidden width handled
 constexpr int PANEL_HALF = BM * 256;          // one k half (128 columns) of the 32 x 256 activation panel
+constexpr int KB1 = 64;           // k elements per weight-slab row
+constexpr int SLAB_PITCH = 2 * KB1;           // ... = 128 bytes
+constexpr int OW = 8;             // waves of the actor's 128-column output layer
 
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst_uniform))   // (under SGPR pressure the compiler may hold it in a VGPR)
-      : "memory");
+// acc += panel(k quarter q: columns 64 q .. 64 q + 63 of the 32 x 256 activation panel; rows of 256 bytes per 128-column half, chunk c
+// of row r at c ^ (r & 15)) * W(rows wrow0 + fr, 64 k of a ring slab: rows of SLAB_PITCH bytes, chunk c of row r at c ^ ((r >> 1) & 7))^T.
+// Operands swapped: acc[tm][0][r] = C[row 16 tm + fr][column wrow0 + 4 fg + r].  two = false: 16-row panel, only the first row block exists.
+__device__ __forceinline__ void mma_panel(const unsigned char* panel, int q, const unsigned char* sb, f32x4 (&acc)[2][1], int wrow0, int fr, int fg,
+                                          const bool two) {
+  const int sw = (fr >> 1) & 7;
+  const unsigned char* sa = panel + (q >> 1) * PANEL_HALF;
+#pragma unroll
+  for (int ks = 0; ks < KB1 / 32; ++ks) {
+    const int posa = ((((q & 1) * 8) + ks * 4 + fg) ^ fr) * 16;
+    const int posb = ((ks * 4 + fg) ^ sw) * 16;
+    uint4 a[2], b;
+    a[0] = *(const uint4*)(sa + fr * 256 + posa);
+    if (two) a[1] = *(const uint4*)(sa + (16 + fr) * 256 + posa);
+    b = *(const uint4*)(sb + (wrow0 + fr) * SLAB_PITCH + posb);
+    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a[0]), acc[0][0], 0, 0, 0);
+    if (two) acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a[1]), acc[1][0], 0, 0, 0);
+  }
 }
 
 // hidden-layer epilogue: bias + relu + dropout -> bf16 into the LDS panel (the next layer's A operand).  Kept lean on purpose

@@ -42,10 +42,6 @@ template <int FR> struct FrozenPlan {
   static_assert(CONST_OFF + 3 * 1024 <= LDS_TOTAL && PANEL_BYTES + 3 * W_BYTES <= LDS_TOTAL, "the two LDS plans share one allocation");
   static_assert(CONST_OFF >= WR_OFF + 2 * W_BYTES, "the constants must survive the later layers' first two slabs");
 };
-
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "m0");
-}
 }  // namespace
 
 template <int FR>
@@ -56,21 +52,13 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   const int m0 = blockIdx.x * FR;
   if (m0 >= P.rows) return;
   // pull this problem's kernel-argument lines into the scalar cache, all in flight together
-  unsigned touch = 0;
-  {
-    const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-    const char __attribute__((address_space(4)))* pa = ka + blockIdx.y * sizeof(FrozenProb);
-#pragma unroll
-    for (int i = 0; i < (int)((sizeof(FrozenProb) + 63) / 64); ++i) asm volatile("s_load_dword %0, %1, %2" : "+s"(touch) : "s"(pa), "n"(i * 64));
-    asm volatile("s_load_dword %0, %1, %2" : "+s"(touch) : "s"(pa), "n"((int)sizeof(FrozenProb) - 4));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(touch));
-  }
+  kernarg_prefetch<sizeof(FrozenProb)>(blockIdx.y * sizeof(FrozenProb));
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const unsigned lds0 = (unsigned)(size_t)lds;
   const int tid = threadIdx.x, lane = tid & 63;
   // (debug: phase stamps by thread 0 -- tools/frozen_trace.py)
   unsigned long long* const trw = batch.trace ? batch.trace + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 : nullptr;
-  auto stamp = [&](int k) { if (trw && tid == 0) trw[k] = __builtin_amdgcn_s_memtime(); };
+  auto stamp = [&](int k) { if (trw && tid == 0) TRACE_STAMP(trw, k); };
   stamp(0);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WNG, wn = wave % WNG;    // rows 32 wm .. + 31, hidden columns 16 TNH wn .. + 16 TNH - 1
@@ -88,9 +76,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
     dma_s((unsigned)(min(lane * 4, nvalid - 4) * 4), src, lds0 + CONST_OFF + wave * 1024);
   }
   float b3s = 0.f;                                // critic: b3 through the scalar cache
-  if (!actor) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(b3s) : "s"(P.b3));
+  if (!actor) sload_dword(b3s, P.b3);
   int32_t step_now = 0;
-  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(step_now) : "s"(P.step_ptr));
+  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) sload_dword(step_now, P.step_ptr);
 
   // ------------------------------------------------------------------ layer 1
   // slab = A rows (one instruction per wave: rows 8 wave .. + 7) + 256 W1 rows (two per wave: rows l_row, l_row + 128); chunk c

@@ -21,7 +21,6 @@
 
 namespace {
 constexpr int NW = 16;
-constexpr int KB1 = 64;                       // k elements per slab row (128 bytes)
 constexpr int A1_BYTES = BM * 128;            // 4 KB
 constexpr int W1_BYTES = HP * 128;            // 32 KB
 constexpr int STAGE1 = A1_BYTES + W1_BYTES;   // 36 KB
@@ -29,28 +28,7 @@ constexpr int NST = 4;
 constexpr int PANEL_OFF = NST * STAGE1;       // 144 KB
 constexpr int LDS_TOTAL = PANEL_OFF + 2 * PANEL_HALF;  // 160 KB
 
-constexpr int OW = 8;                         // waves of the actor's 128-column output layer
 constexpr int RW = BM / NW;                   // critic head rows per wave
-
-// One LDS-DMA instruction: 64 lanes x 16 bytes from (uniform base + per-lane byte offset) to LDS at lds_dst + 16 lane.
-// M0 is written directly (the kernel uses no other M0 consumer: no movrel, no GWS, no LDS-direct loads); no "memory"
-// clobber: the ordering points are the waits and barriers of the consumer, and the argument block stays in registers.
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "m0");
-}
-
-// wait until at most `n` of this wave's vector-memory operations are outstanding (n is wave-uniform, 0 .. 2 (NIW + 1))
-__device__ __forceinline__ void wait_vm(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory"); break;
-  }
-}
 
 // acc += A(32 x 64 k) * W(rows wrow0 + 16 tn + fr, 64 k)^T, both operands from a ring stage (rows of 128 bytes).  Operands
 // swapped as in mlp.hip: acc[tm][tn][r] = C[row 16 tm + fr][column .. + 4 fg + r].
@@ -68,32 +46,7 @@ __device__ __forceinline__ void mma_stage(const unsigned char* sa, const unsigne
       acc[tm][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a[tm]), acc[tm][0], 0, 0, 0);
   }
 }
-// the same with A = k quarter q (columns 64 q .. 64 q + 63) of the activation panel (rows of 256 bytes per 128-column half,
-// chunk c of row r at c ^ (r & 15))
-__device__ __forceinline__ void mma_panel(const unsigned char* panel, int q, const unsigned char* sb, f32x4 (&acc)[2][1], int wrow0, int fr,
-                                          int fg) {
-  const int sw = (fr >> 1) & 7;
-  const unsigned char* sa = panel + (q >> 1) * PANEL_HALF;
-#pragma unroll
-  for (int ks = 0; ks < KB1 / 32; ++ks) {
-    const int posa = ((((q & 1) * 8) + ks * 4 + fg) ^ fr) * 16;
-    const int posb = ((ks * 4 + fg) ^ sw) * 16;
-    uint4 a[2], b;
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) a[tm] = *(const uint4*)(sa + (tm * 16 + fr) * 256 + posa);
-    b = *(const uint4*)(sb + (wrow0 + fr) * 128 + posb);
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-      acc[tm][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a[tm]), acc[tm][0], 0, 0, 0);
-  }
-}
-typedef short v4s16 __attribute__((ext_vector_type(4)));
 }  // namespace
-
-// (the row pointer is computed ONCE, before any DMA is in flight: gridDim.x is a load from the dispatch packet, and the compiler's
-// vmcnt(0) for it inside a stamp drained the whole DMA queue of wave 0 at every stamp -- the first traces of this kernel charged
-// that drain to whatever phase a stamp followed)
-#define MLPS_STAMP(i) do { if (trow) trow[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
 
 // PROBE (timing experiments, recnn_debug_mlp_probe): 1 = no MFMA work, 2 = no DMA
 template <int PROBE>
@@ -113,15 +66,15 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int row_max = P.rows - 1;
-  unsigned long long* trow = (trace && threadIdx.x == 0) ? trace + ((int64_t)by * panels + bx) * 32 : nullptr;
-  asm volatile("" : "+v"(trow));
-  MLPS_STAMP(0);
+  unsigned long long* trow = TRACE_ROW(trace, (int64_t)by * panels + bx, 32);
+  TRACE_STAMP(trow, 0);
 
   // ---- pull every kernel-argument cache line this workgroup will read into the scalar cache NOW.  The argument block is
   // 3.7 KB; a first touch of one of its 64-byte lines costs a scalar-cache miss (in-kernel trace: 1.1-1.4k ticks, ~0.6 us, on
   // the first DMA issue of W3 / of a chained critic's weights, against 260 for a touched line) -- a dozen of those sat on
   // the dependent chain after layer 1.  One dword per line, all in flight together, waited for once (below, where the
-  // workgroup waits for its first slabs anyway).
+  // workgroup waits for its first slabs anyway).  (Written out, not two kernarg_prefetch calls: the second range is seven whole lines
+  // with no closing dword and the wait comes after the first slabs are requested -- the template would add a load and an early wait.)
   unsigned touch = 0;   // (one SGPR, threaded through every load so that it stays allocated until the wait)
   {
     // (through the kernarg segment pointer: taking the address of the by-value argument would make the compiler copy it to scratch)
@@ -251,9 +204,9 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
     if (y >= 2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     else if (y == 1) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (stamp >= 0) MLPS_STAMP(stamp);
+    if (stamp >= 0) TRACE_STAMP(trow, stamp);
     __builtin_amdgcn_s_barrier();  // slab c landed for every wave; everybody is done with slab c - 1 and with its LDS writes so far
-    if (stamp >= 0) MLPS_STAMP(stamp + 1);
+    if (stamp >= 0) TRACE_STAMP(trow, stamp + 1);
     issue_post(issued - nt);
     return lds + (c & (NST - 1)) * STAGE1;
   };
@@ -309,7 +262,7 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
   asm volatile("" : "+v"(b1v[0]), "+v"(b2v[0]), "+v"(h_rew), "+v"(h_done), "+v"(h_tq));
 #pragma unroll
   for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(v3[r]));
-  MLPS_STAMP(1);
+  TRACE_STAMP(trow, 1);
 
   // ------------------------------------------------------------------ layer 1
   // slab t has landed for this wave once only the DMAs of the two younger slabs are outstanding (3 instructions per slab on
@@ -332,37 +285,37 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
     const unsigned char* st = lds + (consumed++ & (NST - 1)) * STAGE1;
     if constexpr (!(PROBE & 1)) mma_stage(st, st + A1_BYTES, acc, wave * 16, fr, fg);
   }
-  MLPS_STAMP(2);
+  TRACE_STAMP(trow, 2);
   if (P.part_out) {
     // producer of a chained critic: hand the raw pre-activation part to the consumer workgroup of this panel
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm) *(f32x4*)(P.part_out + (int64_t)(m0 + tm * 16 + fr) * HP + n0) = acc[tm][0];
     __syncthreads();  // every thread's stores have completed (the barrier is preceded by s_waitcnt vmcnt(0))
     if (tid == 0 && (batch.fault & 3) != 1) __hip_atomic_store(P.part_flag + bx, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    MLPS_STAMP(9);
+    TRACE_STAMP(trow, 9);
     return;
   }
   unsigned char* panel = lds + PANEL_OFF;
   uint32_t gate1 = 0;  // relu/dropout gate of h1 for this lane's accumulator elements (bit tm*4 + r)
   hidden_epilogue<1>(acc, b1v, P.H, P.rows, m0, wave, fr, fg, P.mask_mode, P.mask1, P.ld_mask, key1, panel, &gate1);
-  MLPS_STAMP(3);
+  TRACE_STAMP(trow, 3);
 
   // ------------------------------------------------------------------ layer 2
   acc[0][0] = acc[1][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int w2_first = consumed;                               // stream index of W2's k-slab 0 (= nt)
   for (int q = 0; q < 4; ++q) {
     const unsigned char* st = next_post(q == 1 ? 22 : -1);     // (its barrier also completes the h1 panel for q = 0)
-    MLPS_STAMP(10 + q);
+    TRACE_STAMP(trow, 10 + q);
     if (q == 0 && P.h1) panel_to_global<NW>(panel, (bf16_t*)P.h1, P.ldh, m0, P.rows, tid);
-    if (q == 0) MLPS_STAMP(24);
-    if constexpr (!(PROBE & 1)) mma_panel(panel, q, st + A1_BYTES, acc, wave * 16, fr, fg);
-    if (q == 0) MLPS_STAMP(25);
+    if (q == 0) TRACE_STAMP(trow, 24);
+    if constexpr (!(PROBE & 1)) mma_panel(panel, q, st + A1_BYTES, acc, wave * 16, fr, fg, true);
+    if (q == 0) TRACE_STAMP(trow, 25);
   }
-  MLPS_STAMP(4);
+  TRACE_STAMP(trow, 4);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();  // everyone is done reading the h1 panel
   hidden_epilogue<1>(acc, b2v, P.H, P.rows, m0, wave, fr, fg, P.mask_mode, P.mask2, P.ld_mask, key2, panel);
-  MLPS_STAMP(5);
+  TRACE_STAMP(trow, 5);
 
   if (P.W3) {
     // ---------------------------------------------------------------- layer 3 (actor): 32 x 128 outputs on waves 0..7
@@ -370,14 +323,14 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
     o[0][0] = o[1][0] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < 2; ++p) {
       const unsigned char* st = next_post();                   // (completes the h2 panel for p = 0)
-      MLPS_STAMP(14 + p);
+      TRACE_STAMP(trow, 14 + p);
       if (p == 0 && P.h2) panel_to_global<NW>(panel, (bf16_t*)P.h2, P.ldh, m0, P.rows, tid);
       if (wave < OW) {
-        if constexpr (!(PROBE & 1)) mma_panel(panel, 2 * p, st + A1_BYTES, o, wave * 16, fr, fg);
-        if constexpr (!(PROBE & 1)) mma_panel(panel, 2 * p + 1, st + A1_BYTES, o, 128 + wave * 16, fr, fg);
+        if constexpr (!(PROBE & 1)) mma_panel(panel, 2 * p, st + A1_BYTES, o, wave * 16, fr, fg, true);
+        if constexpr (!(PROBE & 1)) mma_panel(panel, 2 * p + 1, st + A1_BYTES, o, 128 + wave * 16, fr, fg, true);
       }
     }
-    MLPS_STAMP(16);
+    TRACE_STAMP(trow, 16);
     if (wave < OW) {
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm) {
@@ -414,7 +367,7 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
           *(uint2*)(lds + ((ps0 + 1 + (no >> 6)) & (NST - 1)) * STAGE1 + row * 128 + (((((no & 63) >> 3)) ^ ((fr >> 1) & 7)) << 4) + (no & 7) * 2) = packed;
       }
     }
-    MLPS_STAMP(6);
+    TRACE_STAMP(trow, 6);
     // ---------------------------------------------------------------- chained critics (target critic on the new action)
     float* qscratch = (float*)(lds + ps0 * STAGE1 + 3072);     // last KB of an A part the constants never touch
 #pragma unroll
@@ -422,7 +375,7 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
       if (ti >= n_tail) break;
       const MlpTail& T = batch.tail[ti];
       const unsigned char* tc = next_post();                   // the producer's layer-1 part (fp32 rows of 1 KB) + b1 | b2 | w3
-      if (ti == 0) MLPS_STAMP(17);
+      if (ti == 0) TRACE_STAMP(trow, 17);
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm) acc[tm][0] = *(const f32x4*)(tc + A1_BYTES + (tm * 16 + fr) * 1024 + n0 * 4);
       f32x4 tbv[1];
@@ -430,25 +383,25 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
         const unsigned char* st = next_post();                 // (the action slabs are complete after the part slab's barrier)
         if constexpr (!(PROBE & 1)) mma_stage(lds + ((ps0 + 1 + q) & (NST - 1)) * STAGE1, st + A1_BYTES, acc, wave * 16, fr, fg);
       }
-      if (ti == 0) MLPS_STAMP(18);
+      if (ti == 0) TRACE_STAMP(trow, 18);
       if (ti > 0) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // the previous critic's q dots are done with the panel
       }
       tbv[0] = *(const f32x4*)(tc + n0 * 4);
       hidden_epilogue<1>(acc, tbv, P.H, P.rows, m0, wave, fr, fg, RECNN_MASK_NONE, nullptr, 0, 0u, panel);
-      if (ti == 0) MLPS_STAMP(19);
+      if (ti == 0) TRACE_STAMP(trow, 19);
       acc[0][0] = acc[1][0] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int q = 0; q < 4; ++q) {
         const unsigned char* st = next_post();
-        if constexpr (!(PROBE & 1)) mma_panel(panel, q, st + A1_BYTES, acc, wave * 16, fr, fg);
+        if constexpr (!(PROBE & 1)) mma_panel(panel, q, st + A1_BYTES, acc, wave * 16, fr, fg, true);
       }
-      if (ti == 0) MLPS_STAMP(20);
+      if (ti == 0) TRACE_STAMP(trow, 20);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // everyone is done reading the h1 panel
       tbv[0] = *(const f32x4*)(tc + 1024 + n0 * 4);
       hidden_epilogue<1>(acc, tbv, P.H, P.rows, m0, wave, fr, fg, RECNN_MASK_NONE, nullptr, 0, 0u, panel);
-      if (ti == 0) MLPS_STAMP(21);
+      if (ti == 0) TRACE_STAMP(trow, 21);
       const f32x4 tw = *(const f32x4*)(tc + 2048 + lane * 16);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // h2 panel complete
@@ -468,7 +421,7 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
         }
       }
     }
-    MLPS_STAMP(7);
+    TRACE_STAMP(trow, 7);
     // ---------------------------------------------------------------- head of the learning critic(s)
     if (batch.head.n_critic > 0 && n_tail > 0) {
       const MlpHead& Hd = batch.head;
@@ -535,7 +488,7 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
           __hip_atomic_store((uint32_t*)batch.cbwd[P.cbwd_idx].q_slot + m0 + row, __builtin_bit_cast(uint32_t, qv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    MLPS_STAMP(6);
+    TRACE_STAMP(trow, 6);
     if (P.cbwd_idx >= 0) {
       const MlpCriticBwd& B = batch.cbwd[P.cbwd_idx];
       // ---- u2 = w3 * scale * [h2 > 0], in place in the panel (it becomes the A operand) and to global
@@ -585,10 +538,10 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
           b[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
               (__attribute__((address_space(3))) v4s16*)(wslab + k * 128 + (((cpair + ((fr & 3) >> 1)) ^ ((k >> 1) & 7)) * 16) + (fr & 1) * 8));
         }
-        struct { v4s16 lo, hi; } bv = {b[0], b[1]};
+        const TrFrag bv = {b[0], b[1]};
 #pragma unroll
         for (int tm = 0; tm < 2; ++tm)
-          dacc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bv), __builtin_bit_cast(bf16x8, a[tm]), dacc[tm], 0, 0, 0);
+          dacc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bv.to_bf16x8(), __builtin_bit_cast(bf16x8, a[tm]), dacc[tm], 0, 0, 0);
       }
       // (operands swapped: dacc[tm][r] = U[row 16 tm + fr][column 16 wave + 4 fg + r], the layout of gate1)
 #pragma unroll
@@ -625,7 +578,7 @@ __global__ __launch_bounds__(NW * 64) void mlps_fwd_kernel(const MlpBatch batch,
       }
     }
   }
-  MLPS_STAMP(9);
+  TRACE_STAMP(trow, 9);
 }
 
 // ---- debug hooks (recnn_hip_debug.h: not part of the public ABI; process-wide by nature -- a trace buffer, a fault to inject)

@@ -23,39 +23,13 @@
 
 namespace {
 constexpr int NW = 16;
-constexpr int KB1 = 64;                       // k elements per slab row (128 bytes)
 constexpr int W_BYTES = HP * 128;             // 32 KB: one k-slab of a 256-row matrix
 constexpr int NST = 4;
 constexpr int PANEL_OFF = NST * W_BYTES;      // 128 KB
 constexpr int SCR_OFF = PANEL_OFF + 2 * PANEL_HALF;   // per-row scalars: q, e, d, y (fp32 [32] each)
 constexpr int COL_OFF = SCR_OFF + 512;        // column-sum partials: fp32 [2][4][256]
 constexpr int LDS_TOTAL = COL_OFF + 8192;     // 152.5 KB
-constexpr int OW = 8;                         // waves of the actor's 128-column output layer
 constexpr int RW = BM / NW;                   // critic head rows per wave
-
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "m0");
-}
-
-// acc += panel(k quarter q: columns 64 q .. 64 q + 63 of the 32 x 256 activation panel) * W(rows wrow0 + fr, 64 k)^T; operands
-// swapped as in mlps.hip: acc[tm][0][r] = C[row 16 tm + fr][column wrow0 + 4 fg + r]
-__device__ __forceinline__ void mma_panel(const unsigned char* panel, int q, const unsigned char* sb, f32x4 (&acc)[2][1], int wrow0, int fr, int fg,
-                                          const bool two = true) {   // two = false: 16-row panel, only the first row block exists
-  const int sw = (fr >> 1) & 7;
-  const unsigned char* sa = panel + (q >> 1) * PANEL_HALF;
-#pragma unroll
-  for (int ks = 0; ks < KB1 / 32; ++ks) {
-    const int posa = ((((q & 1) * 8) + ks * 4 + fg) ^ fr) * 16;
-    const int posb = ((ks * 4 + fg) ^ sw) * 16;
-    uint4 a[2], b;
-    a[0] = *(const uint4*)(sa + fr * 256 + posa);
-    if (two) a[1] = *(const uint4*)(sa + (16 + fr) * 256 + posa);
-    b = *(const uint4*)(sb + (wrow0 + fr) * 128 + posb);
-    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a[0]), acc[0][0], 0, 0, 0);
-    if (two) acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a[1]), acc[1][0], 0, 0, 0);
-  }
-}
-typedef short v4s16 __attribute__((ext_vector_type(4)));
 
 // The critics' layer 2 once ALL four W2 slabs have landed: the same eight 32-k steps in the same order per accumulator as four
 // mma_panel calls, but the fragment reads of four steps are issued together, ahead of their MFMAs (round 6: the step-by-step form read,
@@ -110,9 +84,9 @@ __device__ __forceinline__ void mma_u_all(const unsigned char* panel, const unsi
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      struct { v4s16 lo, hi; } bv = {b[j][0], b[j][1]};
-      dacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bv), __builtin_bit_cast(bf16x8, a0[j]), dacc[0], 0, 0, 0);
-      if (TWO) dacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bv), __builtin_bit_cast(bf16x8, a1[j]), dacc[1], 0, 0, 0);
+      const TrFrag bv = {b[j][0], b[j][1]};
+      dacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bv.to_bf16x8(), __builtin_bit_cast(bf16x8, a0[j]), dacc[0], 0, 0, 0);
+      if (TWO) dacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bv.to_bf16x8(), __builtin_bit_cast(bf16x8, a1[j]), dacc[1], 0, 0, 0);
     }
   }
 }
@@ -124,7 +98,6 @@ __device__ __forceinline__ float panel_at(const unsigned char* panel, int row, i
 }
 }  // namespace
 
-#define MLPT_STAMP(i) do { if (trow) trow[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
 __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch, unsigned long long* trace) {
   const TailProb& P = batch.p[blockIdx.y];
   // rows per workgroup: 32, or 16 for a learning critic with P.half_panels (round 6: every phase behind layer 2 is bound by the VALU
@@ -143,18 +116,10 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     else if (threadIdx.x == 0) trow = tbase + wg * 16;
   }
   asm volatile("" : "+v"(trow));
-  MLPT_STAMP(0);
+  TRACE_STAMP(trow, 0);
   // pull the kernel-argument cache lines of this workgroup's problem into the scalar cache NOW, all in flight together (a first
   // touch costs a scalar-cache miss of ~0.5 us and the fields are otherwise fetched one dependent batch after the other)
-  unsigned touch = 0;
-  {
-    const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-    const char __attribute__((address_space(4)))* pa = ka + blockIdx.y * sizeof(TailProb);
-#pragma unroll
-    for (int i = 0; i < (int)((sizeof(TailProb) + 63) / 64); ++i) asm volatile("s_load_dword %0, %1, %2" : "+s"(touch) : "s"(pa), "n"(i * 64));
-    asm volatile("s_load_dword %0, %1, %2" : "+s"(touch) : "s"(pa), "n"((int)sizeof(TailProb) - 4));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(touch));
-  }
+  kernarg_prefetch<sizeof(TailProb)>(blockIdx.y * sizeof(TailProb));
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const unsigned lds0 = (unsigned)(size_t)lds;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -211,7 +176,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
   // the device step counter through the SCALAR cache (hipcc turns a plain load of this uniform global into a vector load + an
   // immediate vmcnt(0)): requested here, waited for where the dropout key is hashed
   int32_t step_now = 0;
-  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(step_now) : "s"(P.step_ptr));
+  if (P.mask_mode == RECNN_MASK_HASH && P.step_ptr) sload_dword(step_now, P.step_ptr);
 
   // ---- request EVERYTHING the workgroup will multiply: the h1 panel (one instruction per wave: 4 rows x 256 bytes of one
   // k half; LDS position p of row r holds source chunk p ^ (r & 15)) and W2's four k-slabs (ring stages 0..3; rows l_row and
@@ -260,7 +225,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();             // slab q (and the h1 panel) landed for every wave; everybody is done with slab q - 1
     }
-    if (q == 0) MLPT_STAMP(1);
+    if (q == 0) TRACE_STAMP(trow, 1);
     if (actor && q >= 1 && q <= 2) issue_w3(q - 1);   // W2's slab q - 1 is done with: W3's slab q - 1 takes its stage
     if (q == 0 && learn) {
       // (row blocks as compile-time constants: a loop that BREAKS on a run-time flag is not unrolled, and indexing registers with its
@@ -283,7 +248,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     if (two) mma_panel_all<true>(panel, lds, acc, wave * 16, fr, fg);
     else mma_panel_all<false>(panel, lds, acc, wave * 16, fr, fg);
   }
-  MLPT_STAMP(2);
+  TRACE_STAMP(trow, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                 // everyone is done reading the h1 panel
   // (hidden_epilogue hashes the dropout word from the row's index INSIDE its batch: m0 -> mrow0)
@@ -301,11 +266,11 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     if (wave < OW) {
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        mma_panel(panel, 2 * p, lds + p * W_BYTES, o, wave * 16, fr, fg);
-        mma_panel(panel, 2 * p + 1, lds + p * W_BYTES, o, 128 + wave * 16, fr, fg);
+        mma_panel(panel, 2 * p, lds + p * W_BYTES, o, wave * 16, fr, fg, true);
+        mma_panel(panel, 2 * p + 1, lds + p * W_BYTES, o, 128 + wave * 16, fr, fg, true);
       }
     }
-    MLPT_STAMP(3);
+    TRACE_STAMP(trow, 3);
     if (P.h2) panel_to_global<NW>(panel, (bf16_t*)P.h2, P.ldh, m0, P.rows, tid);
     if (wave < OW) {
 #pragma unroll
@@ -340,7 +305,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
         }
       }
     }
-    MLPT_STAMP(10);
+    TRACE_STAMP(trow, 10);
     return;
   }
 
@@ -363,7 +328,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     y = fminf(fmaxf(y, kLo), kHi);
     ys[lane] = y;
   }
-  MLPT_STAMP(3);
+  TRACE_STAMP(trow, 3);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                 // h2 panel complete (and the TD targets are in LDS)
   if (kH2) panel_to_global<NW>(panel, (bf16_t*)kH2, kLdh, m0, min(kRows, m0 + PR), tid);
@@ -425,13 +390,13 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
   if (!learn) {
     __syncthreads();
     if (tid < PR && m0 + tid < kRows && kQ) kQ[m0 + tid] = qs[tid];
-    MLPT_STAMP(4);
+    TRACE_STAMP(trow, 4);
     return;
   }
-  MLPT_STAMP(4);
+  TRACE_STAMP(trow, 4);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                 // e and d of all 32 rows are in LDS; every thread has read the h2 values it needs
-  MLPT_STAMP(5);
+  TRACE_STAMP(trow, 5);
   if (cell_on) *(uint4*)cell = packed;          // the u2 panel (the A operand of the next product) takes h2's place
   if (wave == 1 && lane < PR && m0 + lane < kRows) {       // (wave 0 has the loss sums)
     if (kQ) kQ[m0 + lane] = qs[lane];
@@ -480,10 +445,10 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     colp[cc * 256 + ck] = s3;
     colp[1024 + cc * 256 + ck] = s2;
   }
-  MLPT_STAMP(6);
+  TRACE_STAMP(trow, 6);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                 // u2 panel complete, the column partials are in LDS
-  MLPT_STAMP(7);
+  TRACE_STAMP(trow, 7);
   if (kDw3 && tid < kH) {
     // (16-row panel: the sum of ITS two chunks; the consumer adds the two halves of a 32-row panel first -- optim_dev.h slab_grads, pair)
     kDw3[(int64_t)blockIdx.x * kH + tid] = two ? (colp[tid] + colp[256 + tid]) + (colp[512 + tid] + colp[768 + tid]) : colp[tid] + colp[256 + tid];
@@ -502,7 +467,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     else mma_u_all<false>(panel, wslab, cpair, dacc, fr, fg);
   }
   // (operands swapped: dacc[tm][r] = U[row 16 tm + fr][column 16 wave + 4 fg + r], the layout of gate1)
-  MLPT_STAMP(8);
+  TRACE_STAMP(trow, 8);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                 // every wave is done with the u2 panel (MFMA A operand): U takes its place
   {
@@ -527,7 +492,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     u_block(std::integral_constant<int, 0>{});
     if (two) u_block(std::integral_constant<int, 1>{});
   }
-  MLPT_STAMP(9);
+  TRACE_STAMP(trow, 9);
   if (kDb1) {                             // db1[k] = sum_r d_r U[r][k], same four-chunk order
     __syncthreads();                            // U panel complete
     if (ck < kH && col_on) {
@@ -539,7 +504,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_tail_kernel(const TailBatch batch
     __syncthreads();
     if (tid < kH) kDb1[(int64_t)blockIdx.x * kH + tid] = two ? (colp[tid] + colp[256 + tid]) + (colp[512 + tid] + colp[768 + tid]) : colp[tid] + colp[256 + tid];
   }
-  MLPT_STAMP(10);
+  TRACE_STAMP(trow, 10);
 }
 
 static unsigned long long* g_mlpt_trace = nullptr;

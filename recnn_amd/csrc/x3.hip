@@ -12,45 +12,11 @@
 // 32-row k step): these launches are a small part of the step (profiles/NOTES_r01_r05.md 5d).
 #include "gemm.h"
 #include "x3.h"
-
-typedef short v4s16 __attribute__((ext_vector_type(4)));
+#include "lds_stream.h"
 
 namespace {
 
 constexpr int X3_LO_LO = 0;   // 1: also add a_lo * b_lo (a fourth MFMA per block; tests/x3_numerics.py "x4")
-
-struct Frag { v4s16 lo, hi; };   // two transpose reads = the 8 k values of a lane (k = 8 fg + 0..3 | 4..7)
-
-// transpose-read fragment of 16 physical columns [col0, col0 + 16) over k rows 0..31 of an LDS image with `pitch` bytes per row
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* s, int pitch, int col0, int fr, int fg) {
-  Frag f;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int row = fg * 8 + half * 4 + (fr >> 2);
-    const v4s16 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) v4s16*)(s + row * pitch + (col0 + (fr & 3) * 4) * 2));
-    if (half == 0) f.lo = v; else f.hi = v;
-  }
-  return __builtin_bit_cast(bf16x8, f);
-}
-
-// The same fragment from a SWIZZLED image (pitch 256 bytes, no padding): the 32-byte chunk c of row r lives at chunk c ^ g(r),
-// g(r) = (r & 3) | ((r >> 3) & 1) << 2.  A transpose read's lane group touches rows {0..3, 8..11} (+4, +16) and 32 bytes of
-// each: with a plain pitch of 256 + 16 (the dW kernel's first layout) neighbouring rows overlap in 4 of their 8 banks -- a third
-// of that kernel's LDS cycles were conflicts (SQ_LDS_BANK_CONFLICT, profiles/r04_x3_pmc.txt); g maps the 8 rows to the 8 disjoint
-// bank windows.
-__device__ __forceinline__ int swz32(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-__device__ __forceinline__ bf16x8 tr_frag_swz(const unsigned char* s, int col0, int fr, int fg) {
-  Frag f;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int row = fg * 8 + half * 4 + (fr >> 2);
-    const v4s16 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) v4s16*)(s + row * 256 + (((col0 >> 4) ^ swz32(row)) << 5) + (fr & 3) * 8));
-    if (half == 0) f.lo = v; else f.hi = v;
-  }
-  return __builtin_bit_cast(bf16x8, f);
-}
 
 __device__ __forceinline__ f32x4 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x4 acc) {
   if (X3_LO_LO) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bl, acc, 0, 0, 0);

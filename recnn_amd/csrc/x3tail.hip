@@ -13,6 +13,7 @@
 // 128-column blocks of 32 rows x 256 bytes (chunk c of row r at c ^ (r & 15)): the layouts of mlps.hip / mlp_panel.h.
 #include "x3tail.h"
 #include "x3.h"
+#include "lds_stream.h"
 
 namespace {
 constexpr int NW = 16, BM = 32;
@@ -23,10 +24,6 @@ constexpr int PANEL_OFF = NST * SLAB;        // 128 KB
 constexpr int LDS_TOTAL = PANEL_OFF + 4 * PBLK;   // 160 KB
 constexpr int OW = 8;                        // waves of the actor's 128-column output layer
 constexpr int RW = BM / NW;                  // critic rows per wave
-
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "m0");
-}
 
 // acc[tm] += A(panel slab q: physical k 64 q .. 64 q + 63 = logical k 32 q .. + 31 as [hi | lo]) * W(rows wrow0 + fr of the ring
 // slab)^T, three MFMAs; weights first: acc[tm][r] = C[row 16 tm + fr][column .. + 4 fg + r]

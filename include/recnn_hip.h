@@ -586,6 +586,10 @@ typedef struct recnn_engine_tuning {
   int frozen_half;          /* 1: a cycle segment's frozen-network launch (csrc/mlpf.hip) runs 64-row workgroups instead of 128-row ones while
                                it then still fits one round of workgroups (short segments: a request that starts or ends inside a policy
                                cycle); 0: always 128 rows.  Bit-identical */
+  int frozen_window;        /* 1 (default): bf16 cycle mode with frozen_fused does not materialise next_state rows for the frozen networks -- the
+                               cycle gather writes state rows, action rows and the ten next ratings only, and the target networks' layer 1 reads s'
+                               as shifted windows of those (csrc/mlpf.hip: up to four contraction segments); the packed next rows of the cycle are
+                               then not allocated.  0: the gather also writes a next_state row per transition.  Bit-identical */
   int reserved[3];
 } recnn_engine_tuning;
 void recnn_engine_tuning_init(recnn_engine_tuning* h_t);
@@ -605,7 +609,9 @@ int recnn_engine_read_losses(recnn_engine* e, float* h_out, void* stream);
  * loss seed "delta1" is applied by the consumers inside the dW launch), 0 if they hold dz itself. */
 int recnn_engine_unit_backward(recnn_engine* e);
 /* Debug / test access to intermediate device buffers by name
- * ("next_action", "expected", "q1", "gen_action", ...).  Returns NULL if unknown. */
+ * ("next_action", "expected", "q1", "gen_action", ...).  Returns NULL if unknown.  Cycle mode's arrays (MSET_MAX x max_rows rows each):
+ * "cycle_gen_action", "cycle_target_q1" / "2", "cycle_next_action0" / "1" (the target actor's output of window mode, per copy) and
+ * "cycle_xn0" / "1" (the packed next rows whose action slot holds it otherwise: the engine's own allocation, NULL while it has none). */
 const void* recnn_engine_buffer(recnn_engine* e, const char* name, int64_t* h_rows, int64_t* h_cols,
                                 int64_t* h_ld, int* h_is_f32);
 

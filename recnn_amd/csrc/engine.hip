@@ -115,11 +115,18 @@ int64_t carve(recnn_engine* e, char* base) {
   }
   if (e->bf16) {
     const int64_t MB = (int64_t)recnn_engine::MSET_MAX * Bc;
+    // (the cycle's packed next rows m_xn_b[] are not carved: window mode does not have them, ensure_mxn allocates them for the rest)
+    // state = frame x (emb | rating), action = emb: frame * emb embedding columns, the rest of the padded row is the next ratings' array
+    const int64_t FE = e->S % (A + 1) == 0 ? (e->S / (A + 1)) * A : 0;
+    e->win_tail = (FE > A && FE % 64 == 0 && A % 64 == 0 && e->K1a > FE && (e->K1a - FE) % 64 == 0) ? (int)(e->K1a - FE) : 0;
     for (int b = 0; b < 2; ++b) {
-      e->m_xs_b[b] = c.take(MB * e->ldx * 2); e->m_xn_b[b] = c.take(MB * e->ldx * 2);
+      e->m_xs_b[b] = c.take(MB * e->ldx * 2);
       e->m_reward_b[b] = (float*)c.take(MB * 4); e->m_done_b[b] = (float*)c.take(MB * 4);
+      if (e->win_tail) { e->m_tail_n_b[b] = c.take(MB * e->win_tail * 2); e->m_na_b[b] = c.take(MB * Ap * 2); }
     }
-    e->m_xs = e->m_xs_b[0]; e->m_xn = e->m_xn_b[0]; e->m_reward = e->m_reward_b[0]; e->m_done = e->m_done_b[0];
+    if (e->win_tail) e->m_xn_short = c.take((int64_t)recnn_engine::SHORT_SETS * Bc * e->ldx * 2);
+    e->m_xs = e->m_xs_b[0]; e->m_reward = e->m_reward_b[0]; e->m_done = e->m_done_b[0];
+    e->m_tail_n = e->m_tail_n_b[0]; e->m_na = e->m_na_b[0];
     e->m_ga = c.take(MB * Ap * 2);
     e->m_tp_h1 = c.take(MB * Hp * 2); e->m_tp_h2 = c.take(MB * Hp * 2); e->m_pa_h1 = c.take(MB * Hp * 2); e->m_pa_h2 = c.take(MB * Hp * 2);
     for (int i = 0; i < e->n_critic; ++i) { e->m_tq[i] = (float*)c.take(MB * 4); e->m_tq_h1[i] = c.take(MB * Hp * 2); }
@@ -280,6 +287,7 @@ extern "C" void recnn_engine_destroy(recnn_engine* e) {
   if (!e) return;
   drop_graphs(e);
   if (e->h_stage) (void)hipHostFree(e->h_stage);
+  if (e->m_xn_own) (void)hipFree(e->m_xn_own);
   delete e;
 }
 
@@ -515,6 +523,23 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
       {"dze2", e->dze2, e->H, Hp, 0},              {"dze1", e->dze1, e->H, Hp, 0},
       {"dzp2", e->dzp2, e->H, Hp, 0},              {"dzp1", e->dzp1, e->H, Hp, 0},            {"noise", e->noise_buf, e->A, e->A, 1},
   };
+  // cycle mode's arrays (all MSET_MAX * Bc rows; the two copies alternate between the segments of a run graph): the target actor's
+  // output is the action slot of the packed next rows "cycle_xn<b>", or -- window mode, which has no such rows (NULL) -- its own array
+  const int64_t MB = (int64_t)recnn_engine::MSET_MAX * e->Bc;
+  const Ent cyc[] = {
+      {"cycle_xn0", e->m_xn_b[0], e->ldx, e->ldx, 0},              {"cycle_xn1", e->m_xn_b[1], e->ldx, e->ldx, 0},
+      {"cycle_next_action0", e->m_na_b[0], e->A, e->Ap, 0},        {"cycle_next_action1", e->m_na_b[1], e->A, e->Ap, 0},
+      {"cycle_target_q1", e->m_tq[0], 1, 1, 1},                    {"cycle_target_q2", e->m_tq[1], 1, 1, 1},
+      {"cycle_gen_action", e->m_ga, e->A, e->Ap, 0},
+  };
+  for (const Ent& t : cyc)
+    if (!strcmp(t.n, name)) {
+      if (rows) *rows = MB;
+      if (cols) *cols = t.c;
+      if (ld) *ld = t.l;
+      if (is_f32) *is_f32 = t.f;
+      return t.p;
+    }
   for (const Ent& t : tab)
     if (!strcmp(t.n, name)) {
       if (rows) *rows = (!strcmp(name, "losses") || !strcmp(name, "clip_coef")) ? 1 : (!strcmp(name, "loss_ring") ? LOSS_RING : e->cfg.max_rows);

@@ -28,8 +28,8 @@ extern "C" int recnn_engine_profile(recnn_engine* e, int rows, int policy_steps,
       // the first step of the cycle (an ordinary step) on the split forward
       RECNN_REQUIRE(cycle_ok(e, rows), "profile: cycle mode is not available for this engine / batch size");
       const int n = e->hy.policy_every < recnn_engine::MSET_MAX ? e->hy.policy_every : recnn_engine::MSET_MAX;
-      select_mbuf(e, 0);
-      rc = ph_gather_cycle(e, rows, n, 0, 0, s);
+      rc = begin_cycle_mode(e, rows);
+      if (!rc) rc = ph_gather_cycle(e, rows, n, 0, 0, s, true);
       if (!rc) rc = ph_frozen_batched(e, rows, n, 0, s);
       if (!rc) {
         use_mset(e, 0, rows);
@@ -82,10 +82,11 @@ int capture_run(recnn_engine* e, int rows, hipStream_t s, int phase, int len, hi
   const bool look = lookahead_ok(e) && len > 1;
   hipGraph_t graph = nullptr;
   int rc = 0;
+  const bool cyc = len > 1 && (e->tune.split_fwd >= 2 || len >= e->tune.cycle_min_len) && cycle_ok(e, rows);
+  if (cyc && (rc = begin_cycle_mode(e, rows))) return rc;      // (may allocate: before the capture starts)
   RECNN_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   e->use_sampler = e->has_sampler;
   int n_pol = 0;
-  const bool cyc = !rc && len > 1 && (e->tune.split_fwd >= 2 || len >= e->tune.cycle_min_len) && cycle_ok(e, rows);
   auto is_pol = [&](int i) { return phase >= 0 && ((phase + i) % pe) == 0; };
   if (cyc) {
     // segments = the steps up to and including the next policy step (the frozen networks change right after it)
@@ -96,7 +97,8 @@ int capture_run(recnn_engine* e, int rows, hipStream_t s, int phase, int len, hi
       seg0[nseg] = i0; seg1[nseg] = i1; ++nseg;
       i0 = i1 + 1;
     }
-    rc = ph_gather_cycle(e, rows, seg1[0] - seg0[0] + 1, seg0[0], 0, s);
+    auto seg_batched = [&](int k) { return seg1[k] - seg0[k] + 1 >= e->tune.cycle_min_seg; };
+    rc = ph_gather_cycle(e, rows, seg1[0] - seg0[0] + 1, seg0[0], 0, s, seg_batched(0));
     for (int k = 0; k < nseg && !rc; ++k) {
       const int i0 = seg0[k], i1 = seg1[k], n = i1 - i0 + 1, buf = k & 1;
       select_mbuf(e, buf);
@@ -107,7 +109,7 @@ int capture_run(recnn_engine* e, int rows, hipStream_t s, int phase, int len, hi
       // us/step against 67.8-68.3 all-fused -- inside the noise, so short graphs stayed on the fused schedule: cycle_min_len 30.
       //  Round 5, after the kernel-argument prefetches: the same command 67.6-68.2 in cycle mode against 69.3-69.4 fused, A/B inside one
       //  call -- cycle_min_len is 20 now.)
-      const bool batched = n >= e->tune.cycle_min_seg;
+      const bool batched = seg_batched(k);
       if (batched) rc = ph_frozen_batched(e, rows, n, i0, s);
       for (int i = i0; i <= i1 && !rc; ++i) {
         const bool pol = is_pol(i);
@@ -125,7 +127,7 @@ int capture_run(recnn_engine* e, int rows, hipStream_t s, int phase, int len, hi
         rc = step_impl(e, rows, true, pol, s, true, false, defer, batched);
       }
       // (the next segment's batches go into the other copy of the cycle arrays: this segment's deferred forwards still read theirs)
-      if (!rc && k + 1 < nseg) rc = ph_gather_cycle(e, rows, seg1[k + 1] - seg0[k + 1] + 1, seg0[k + 1], buf ^ 1, s);
+      if (!rc && k + 1 < nseg) rc = ph_gather_cycle(e, rows, seg1[k + 1] - seg0[k + 1] + 1, seg0[k + 1], buf ^ 1, s, seg_batched(k + 1));
     }
     select_mbuf(e, 0);
   }

@@ -113,6 +113,17 @@ struct recnn_engine {
   float *m_reward = nullptr, *m_done = nullptr;    // [MSET_MAX * Bc]                  steps on one, a side branch of the run graph
   char *m_xs_b[2] = {nullptr, nullptr}, *m_xn_b[2] = {nullptr, nullptr};            //  gathers the next cycle's batches into the other)
   float *m_reward_b[2] = {nullptr, nullptr}, *m_done_b[2] = {nullptr, nullptr};
+  // tuning.frozen_window: the frozen networks read s' as shifted windows of m_xs (+ the next ratings), so batched segments have no next
+  // rows at all.  m_xn_b[] is then NOT part of the workspace: it is the engine's own allocation, made the first time a capture needs
+  // it (window mode off or not eligible: ensure_mxn).  Segments too short for the batched launches step through the fused forward,
+  // which reads whole next rows: theirs (at most SHORT_SETS batches) go to m_xn_short.
+  static constexpr int SHORT_SETS = 3;
+  bool win = false;                                // the capture / profile being issued runs in window mode (window_ok)
+  int win_tail = 0;                                // columns of m_tail_n: K1a - frame * emb (0: the dims do not allow window mode)
+  char *m_tail_n = nullptr, *m_tail_n_b[2] = {nullptr, nullptr};   // bf16 [MSET_MAX * Bc, win_tail]: r1..rF, then zeros
+  char *m_na = nullptr, *m_na_b[2] = {nullptr, nullptr};           // the target actor's output, bf16 [MSET_MAX * Bc, Ap]
+  char* m_xn_short = nullptr;                      // bf16 [SHORT_SETS * Bc, ldx]
+  char* m_xn_own = nullptr;                        // hipMalloc'ed backing of m_xn_b[] (NULL until needed)
   char* m_ga = nullptr;                            // actor outputs, bf16 [MSET_MAX * Bc, Ap]
   float* m_tq[2] = {nullptr, nullptr};             // Q'(s', pi'(s')) per target critic, fp32 [MSET_MAX * Bc]
   float* m_noise = nullptr;                        // TD3 target-action noise, fp32 [MSET_MAX * Bc, A]
@@ -233,7 +244,11 @@ void select_mbuf(recnn_engine* e, int b);
 int stage_batch(recnn_engine* e, int rows, hipStream_t s);
 int frame_gather_packed(recnn_engine* e, int rows, hipStream_t s);
 GatherArgs gather_args(const recnn_engine* e, int rows, int set, int cursor_add);
-int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipStream_t s);
+// batched: the segment runs the cycle-batched frozen launches (window mode: its gather writes no next rows)
+int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipStream_t s, bool batched);
+bool window_ok(const recnn_engine* e, int rows);
+// decides e->win for the capture / profile about to be issued and makes sure the next rows it will write exist; NOT inside a capture
+int begin_cycle_mode(recnn_engine* e, int rows);
 int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s);
 int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool value_bwd, hipStream_t s);
 int ph_value_backward(recnn_engine* e, int rows, bool reduce, hipStream_t s, bool dx_only = false);

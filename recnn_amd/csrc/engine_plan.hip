@@ -269,6 +269,7 @@ extern "C" void recnn_engine_tuning_init(recnn_engine_tuning* t) {
   t->sampler_f32_rows = 0; t->dw_splits = 8; t->comm_fused = 1; t->l1_big = 1;
   t->gemm_variant = -1; t->gemm_v0_threshold = 512; t->gemm_dma = 1; t->gemm_dma_depth = 1; t->gemm_dma_waves = 8;
   t->gemm_waves = 8; t->dw_dma = 2; t->x3_tail = 1; t->x3_fwd = 2; t->dw_fuse = 1; t->tail_half = 1; t->l1_ws = 1; t->frozen_half = 1;
+  t->frozen_window = 1;
 }
 extern "C" int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* t) {
   RECNN_REQUIRE(e && t, "set_tuning: null pointer");
@@ -1445,12 +1446,45 @@ bool cycle_ok(const recnn_engine* e, int rows) {
 // target actor -> next_action (+ TD3 noise) -> target critics -> Q', and the actor -> gen_action (+ its activations for the
 // policy step's backward).  recnn/nn/update/misc.py:28-31, td3.py:73-81 (target side), ddpg.py:66-69 / td3.py:104-110 (actor).
 void select_mbuf(recnn_engine* e, int b) {
-  e->m_xs = e->m_xs_b[b]; e->m_xn = e->m_xn_b[b]; e->m_reward = e->m_reward_b[b]; e->m_done = e->m_done_b[b];
+  e->m_xs = e->m_xs_b[b]; e->m_reward = e->m_reward_b[b]; e->m_done = e->m_done_b[b];
+  // window mode: only a segment that steps through the fused forward has next rows (its steps' e->xcn); nothing of a batched
+  // segment reads e->xcn -- the frozen launches take m_tail_n / m_na, the per-step launches the state rows
+  e->m_xn = e->win ? e->m_xn_short : e->m_xn_b[b];
+  e->m_tail_n = e->m_tail_n_b[b]; e->m_na = e->m_na_b[b];
 }
+
+// tuning.frozen_window applies to the bf16 cycle schedule with the fused frozen launches.  Every reader of the cycle's next rows is
+// covered: the batched frozen launches (ph_frozen_batched: windows) -- their tiled form (frozen_fused 0) reads whole rows and makes the
+// mode ineligible --; the fused forward of segments shorter than cycle_min_seg (m_xn_short: they must fit it); the per-step launches of
+// a batched segment, the data-parallel exchange and TD3's noise addend (indexed by row) do not read them.
+bool window_ok(const recnn_engine* e, int rows) {
+  return e->tune.frozen_window && e->bf16 && e->tune.frozen_fused && e->win_tail > 0 && cycle_ok(e, rows) && e->has_sampler &&
+         e->smp.emb_dim == e->A && e->smp.frame * e->smp.emb_dim == e->K1a - e->win_tail && e->tune.cycle_min_seg - 1 <= recnn_engine::SHORT_SETS;
+}
+// the cycle's packed next rows for everything that is not window mode: allocated (and zeroed, like the workspace) on first use
+static int ensure_mxn(recnn_engine* e) {
+  if (e->m_xn_own || !e->bf16) return 0;
+  const size_t each = (size_t)ru((int64_t)recnn_engine::MSET_MAX * e->Bc * e->ldx * 2, 256);
+  RECNN_HIP(hipMalloc((void**)&e->m_xn_own, 2 * each));
+  RECNN_HIP(hipMemset(e->m_xn_own, 0, 2 * each));
+  e->m_xn_b[0] = e->m_xn_own; e->m_xn_b[1] = e->m_xn_own + each;
+  return 0;
+}
+int begin_cycle_mode(recnn_engine* e, int rows) {
+  e->win = window_ok(e, rows);
+  const int rc = e->win ? 0 : ensure_mxn(e);
+  select_mbuf(e, 0);
+  return rc;
+}
+
 // the batches of run steps run_off0 .. run_off0 + n - 1 into copy `b` of the cycle arrays: one launch
-int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipStream_t s) {
+int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipStream_t s, bool batched) {
   GatherArgs g = gather_args(e, rows, 0, run_off0);
-  g.state_h = (bf16_t*)e->m_xs_b[b] + e->A; g.next_h = (bf16_t*)e->m_xn_b[b] + e->A; g.action_h = (bf16_t*)e->m_xs_b[b];
+  g.state_h = (bf16_t*)e->m_xs_b[b] + e->A; g.action_h = (bf16_t*)e->m_xs_b[b];
+  RECNN_REQUIRE(e->win || e->m_xn_b[b], "cycle gather: the packed next rows are not allocated (begin_cycle_mode)");
+  if (!e->win) g.next_h = (bf16_t*)e->m_xn_b[b] + e->A;
+  else if (!batched) { RECNN_REQUIRE(n <= recnn_engine::SHORT_SETS, "cycle gather: %d batches of a short segment", n); g.next_h = (bf16_t*)e->m_xn_short + e->A; }
+  else { g.next_h = nullptr; g.tail_n = (bf16_t*)e->m_tail_n_b[b]; g.ld_tail = e->win_tail; }
   g.reward = e->m_reward_b[b]; g.done = e->m_done_b[b];
   return slot(e, "frame_gather_cycle", 0, s, [&] { return frame_gather_multi_launch(g, n, s); });
 }
@@ -1515,10 +1549,22 @@ int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_
       p->h1 = e->m_pa_h1 + r0 * e->Hp * 2; p->h2 = e->m_pa_h2 + r0 * e->Hp * 2;
       p->out = e->m_ga + r0 * e->Ap * 2; p->ldo = e->Ap;
     };
+    // Window mode (tuning.frozen_window): no next rows exist.  s' = [e1..eF | r1..rF | 0] of a transition is, column for column,
+    // [state row from its second embedding on | action row | next ratings]: three contraction segments with constant offsets into
+    // m_xs and m_tail_n, against the same W1 columns in the same ascending k order -- the same bits as the materialised row.
+    const bool win = e->win;
+    const int FE = e->K1a - e->win_tail;                             // frame x emb embedding columns of a state
+    auto window = [&](FrozenProb* p, int col0) {
+      p->A[0] = e->m_xs + aoff + (int64_t)A * 2; p->lda[0] = e->ldx; p->K[0] = FE - A; p->w1_col[0] = col0;            // e1..e(F-1)
+      p->A[1] = e->m_xs; p->lda[1] = e->ldx; p->K[1] = A; p->w1_col[1] = col0 + FE - A;                               // eF = the action
+      p->A[2] = e->m_tail_n; p->lda[2] = e->win_tail; p->K[2] = e->win_tail; p->w1_col[2] = col0 + FE;                // r1..rF, zeros
+      p->nseg = 3;
+    };
     FrozenBatch fb;
     int np = 0;
     fill(&fb.p[np], TPOL, e->m_xn + aoff, e->K1a, 0, -1);            // target actor on s' -> next_action into the rows' action slot
     fb.p[np].out = e->m_xn; fb.p[np].ldo = e->ldx;
+    if (win) { window(&fb.p[np], 0); fb.p[np].out = e->m_na; fb.p[np].ldo = e->Ap; }    // ... or into its own compact array
     if (e->td3) { fb.p[np].addend = e->m_noise; fb.p[np].ld_add = A; fb.p[np].add_clip = e->hy.noise_clip; }
     ++np;
     if (sets_a > 0) actor_part(&fb.p[np++], 0, sets_a);              // actor on s -> gen_action, activations kept for the policy step
@@ -1528,6 +1574,10 @@ int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_
     for (int c = 0; c < nc; ++c) {                                  // target critics on [s' | next_action]: state part first
       fill(&fc.p[nq], TVAL[c], e->m_xn + aoff, e->K1a, A, -1);
       fc.p[nq].A[1] = e->m_xn; fc.p[nq].lda[1] = e->ldx; fc.p[nq].K[1] = e->Ap; fc.p[nq].w1_col[1] = 0; fc.p[nq].nseg = 2;
+      if (win) {
+        window(&fc.p[nq], A);
+        fc.p[nq].A[3] = e->m_na; fc.p[nq].lda[3] = e->Ap; fc.p[nq].K[3] = e->Ap; fc.p[nq].w1_col[3] = 0; fc.p[nq].nseg = 4;
+      }
       fc.p[nq].q = e->m_tq[c];
       ++nq;
     }

@@ -29,6 +29,10 @@ struct GatherArgs {
   bf16_t* action_h;
   int64_t ld_h;
   int x3;   // the twins are split-bf16 rows (x3.h): ld_h physical, every value stored as hi (mapped column) + lo (32 further)
+  // bf16 twins without next rows (next_h == NULL, cycle gather only): a next_state row is columns E.. of the state row followed by the
+  // action row, so only its F ratings r1..rF are new -- they go to columns 0..F-1 of tail_n (row stride ld_tail, the rest stays zero)
+  bf16_t* tail_n;
+  int64_t ld_tail;
 };
 
 

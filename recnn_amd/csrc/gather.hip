@@ -208,7 +208,9 @@ __global__ __launch_bounds__(256) void frame_gather_multi_kernel(const GatherArg
   const int j = blockIdx.y;
   const int64_t r0 = (int64_t)j * a.rows;
   a.cursor_add += j;
-  a.state_h += r0 * a.ld_h; a.next_h += r0 * a.ld_h; a.action_h += r0 * a.ld_h;
+  a.state_h += r0 * a.ld_h; a.action_h += r0 * a.ld_h;
+  if (a.next_h) a.next_h += r0 * a.ld_h;            // (NULL: no next rows, the next ratings go to tail_n -- gather.h)
+  else a.tail_n += r0 * a.ld_tail;
   a.reward += r0; a.done += r0;
   frame_gather_body<4, 4>(a, blockIdx.x, smem_raw);
 }
@@ -218,6 +220,10 @@ int frame_gather_multi_launch(const GatherArgs& a, int n_sets, hipStream_t s) {
   if (lds > 48 * 1024 || !a.state_h || a.state || (a.emb % 4) || a.rows <= 0 || n_sets <= 0 || n_sets > 65535) {
     recnn_set_error("frame_gather_multi: needs the bf16-only gather with a tile that fits 48 KB of LDS");
     return RECNN_E_UNSUPPORTED;
+  }
+  if (!a.next_h && (!a.tail_n || a.x3 || a.ld_tail < a.frame)) {
+    recnn_set_error("frame_gather_multi: without next rows the next ratings need a bf16 array of at least `frame` columns");
+    return RECNN_E_INVALID;
   }
   hipLaunchKernelGGL(frame_gather_multi_kernel, dim3((a.rows + 3) / 4, n_sets), dim3(256), lds, s, a);
   return recnn_check_hip(hipGetLastError(), "frame_gather_multi");
@@ -294,6 +300,7 @@ int frame_gather_launch(GatherArgs a, hipStream_t stream) {
     return RECNN_E_INVALID;
   }
   if (emb_dim % W) W = 1;
+  if (a.state_h && !a.next_h) { recnn_set_error("frame_gather: the per-batch gather writes next rows"); return RECNN_E_INVALID; }
   if (a.state_h && W != 4) { recnn_set_error("frame_gather: bf16 twin rows need 16-byte aligned fp32 rows"); return RECNN_E_INVALID; }
   // (4 rows per workgroup: 2 and 8 were measured in round 2 -- 7.0 / 9.6 us against 7.2 -- and are gone)
   return launch_gather<4>(a, W, stream);

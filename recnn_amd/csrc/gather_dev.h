@@ -170,7 +170,10 @@ __device__ __forceinline__ void frame_gather_body(const GatherArgs& a, const int
         if (jj >= 1) x3_store(a.next_h + row * a.ld_h, FE + jj - 1, v);
       } else if (a.state_h) {
         if (jj < F) a.state_h[row * a.ld_h + FE + jj] = f2bf(v);
-        if (jj >= 1) a.next_h[row * a.ld_h + FE + jj - 1] = f2bf(v);
+        if (jj >= 1) {
+          if (a.next_h) a.next_h[row * a.ld_h + FE + jj - 1] = f2bf(v);
+          else if (a.tail_n) a.tail_n[row * a.ld_tail + jj - 1] = f2bf(v);
+        }
       }
     }
   }
@@ -225,7 +228,7 @@ __device__ __forceinline__ void frame_gather_body(const GatherArgs& a, const int
             if (jj == F) { bf16_t* d = a.action_h + row * a.ld_h + x3_col(ee[u]); *(uint2*)d = h; *(uint2*)(d + 32) = hl; }
           } else if (a.state_h) {
             if (jj < F) *(uint2*)(a.state_h + row * a.ld_h + jj * E + ee[u]) = h;
-            if (jj >= 1) *(uint2*)(a.next_h + row * a.ld_h + (jj - 1) * E + ee[u]) = h;
+            if (jj >= 1 && a.next_h) *(uint2*)(a.next_h + row * a.ld_h + (jj - 1) * E + ee[u]) = h;
             if (jj == F) *(uint2*)(a.action_h + row * a.ld_h + ee[u]) = h;
           }
         }

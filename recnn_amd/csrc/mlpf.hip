@@ -13,7 +13,8 @@
 //             64 KB, W2's four and W3's two 32 KB slabs stream through a 3-slot ring in the other 96 KB;
 //   critic    q dots from the h2 panel (8 rows per wave).
 // Per output element the arithmetic is the per-step kernels' (l1gemm.hip + mlpt.hip = mlps.hip): k ascending in MFMA steps of
-// 32 from a zero accumulator, segment 0 before segment 1, weights as the first MFMA operand, the same epilogues
+// 32 from a zero accumulator, the segments in order (up to four: [s' | a'] of a target critic is three shifted windows of the
+// cycle's state / action / next-rating arrays and the target actor's output), weights as the first MFMA operand, the same epilogues
 // (mlp_panel.h), the same q-dot lane map and reduction tree -- so `run()` in cycle mode equals the eager step loop bit for bit.
 #include <cstddef>
 #include "mlp_panel.h"
@@ -83,8 +84,12 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   // ------------------------------------------------------------------ layer 1
   // slab = A rows (one instruction per wave: rows 8 wave .. + 7) + 256 W1 rows (two per wave: rows l_row, l_row + 128); chunk c
   // of slab row r at position c ^ ((r >> 1) & 7)
-  const int nt0 = P.K[0] / 64;
-  const int nt = nt0 + (P.nseg > 1 ? P.K[1] / 64 : 0);
+  // up to four contraction segments: slab t belongs to the segment whose cumulative slab count first exceeds t.  The boundaries are
+  // scalars (an absent segment's equals nt, which no issue reaches); the segment table stays in the kernel arguments
+  const int nb1 = P.K[0] / 64;
+  const int nb2 = nb1 + (P.nseg > 1 ? P.K[1] / 64 : 0);
+  const int nb3 = nb2 + (P.nseg > 2 ? P.K[2] / 64 : 0);
+  const int nt = nb3 + (P.nseg > 3 ? P.K[3] / 64 : 0);
   const int l_row = wave * 8 + (lane >> 3);
   const int l_c = ((lane & 7) ^ ((l_row >> 1) & 7)) * 16;
   const int gr_a = min(m0 + l_row, P.rows - 1);
@@ -96,10 +101,13 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   const unsigned wave_kb = wave * 1024;
   int issued = 0;
   auto issue_l1 = [&]() {
-    if (issued == nt0) {                          // second contraction segment
-      voff_a = (unsigned)(gr_a * (int)P.lda[1] * 2 + l_c);
-      a_base = (const char*)P.A[1];
-      w_base = (const char*)P.W1 + (int64_t)P.w1_col[1] * 2;
+    if (issued == nb1 || issued == nb2 || issued == nb3) {   // next contraction segment: re-base the three streams
+      const bool g1 = issued == nb1, g2 = issued == nb2;     // (segments have at least one slab each: at most one boundary matches)
+      const int lda = (int)(g1 ? P.lda[1] : (g2 ? P.lda[2] : P.lda[3]));
+      const int col = g1 ? P.w1_col[1] : (g2 ? P.w1_col[2] : P.w1_col[3]);
+      voff_a = (unsigned)(gr_a * lda * 2 + l_c);
+      a_base = (const char*)(g1 ? P.A[1] : (g2 ? P.A[2] : P.A[3]));
+      w_base = (const char*)P.W1 + (int64_t)col * 2;
     }
     const unsigned sb = lds0 + (issued % NST1) * STAGE1 + wave_kb;
     ++issued;
@@ -368,11 +376,11 @@ int mlpf_launch(const FrozenBatch& b, int nprob, hipStream_t s, int panel_rows) 
     const FrozenProb& p = b.p[i];
     if (p.rows > rows) rows = p.rows;
     RECNN_REQUIRE(p.rows > 0 && p.H >= 8 && p.H <= HP && (p.H & 7) == 0 && p.out_dim <= 128, "mlp_frozen: hidden <= 256 (multiple of 8), out_dim <= 128");
-    RECNN_REQUIRE(p.nseg >= 1 && p.nseg <= 2 && p.W1 && p.W2 && p.b1 && p.b2 && p.b3, "mlp_frozen: bad problem");
+    RECNN_REQUIRE(p.nseg >= 1 && p.nseg <= FROZEN_MAX_SEG && p.W1 && p.W2 && p.b1 && p.b2 && p.b3, "mlp_frozen: bad problem");
     int k64 = 0;
     for (int g = 0; g < p.nseg; ++g) {
-      RECNN_REQUIRE(p.K[g] > 0 && p.K[g] % 64 == 0 && p.lda[g] % 8 == 0 && (((uintptr_t)p.A[g]) & 15) == 0 && (p.w1_col[g] & 7) == 0 &&
-                        (int64_t)p.rows * p.lda[g] * 2 < (1ll << 31),
+      RECNN_REQUIRE(p.A[g] && p.K[g] > 0 && p.K[g] % 64 == 0 && p.lda[g] % 8 == 0 && (((uintptr_t)p.A[g]) & 15) == 0 && (p.w1_col[g] & 7) == 0 &&
+                        p.w1_col[g] >= 0 && p.w1_col[g] + p.K[g] <= p.ldw1 && (int64_t)p.rows * p.lda[g] * 2 < (1ll << 31),
                     "mlp_frozen: segment %d must be 16-byte aligned with K a multiple of 64 (and < 2 GB)", g);
       k64 += p.K[g] / 64;
     }

@@ -109,11 +109,12 @@ int qdot_launch(const void* h2, int64_t ldh, const float* w3row, const float* b3
 // ---------------------------------------------------------------------------------------------- frozen networks, cycle-wide
 // One whole network (all three layers) on 128-row panels of M = cycle x rows rows (mlpf.hip): the target actor, the target
 // critics on its output, the actor between its optimizer steps.
+constexpr int FROZEN_MAX_SEG = 4;
 struct FrozenProb {
-  const void* A[2];               // layer-1 input: up to two k-contiguous bf16 segments, contracted in order
-  int64_t lda[2];
-  int K[2];                       // multiples of 64
-  int w1_col[2];
+  const void* A[FROZEN_MAX_SEG];  // layer-1 input: up to four k-contiguous bf16 segments, contracted in order (a target network's s' as
+  int64_t lda[FROZEN_MAX_SEG];    // shifted windows of the cycle's state / action rows + the next ratings, then the target actor's output)
+  int K[FROZEN_MAX_SEG];          // multiples of 64
+  int w1_col[FROZEN_MAX_SEG];
   int nseg;
   const void* W1; int64_t ldw1;
   const void* W2; int64_t ldw2;

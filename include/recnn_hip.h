@@ -774,6 +774,44 @@ int recnn_topk_stats_workspace_bytes(int n_queries, int k, int64_t* h_bytes);
 int recnn_topk_stats(const float* dist, const int64_t* ids, int n_queries, int k, int n_items, int take_sqrt, int32_t* counts,
                      double* row_mean, double* row_std, double* totals, void* workspace, void* stream);
 
+/* =====================================================================================
+ * 10. Dynamic-length user batches (csrc/seq.hip): the padded gathers behind recnn.data.utils.padder /
+ *    prepare_batch_dynamic_size, an LSTM state encoder over whole user histories, and the replay-buffer collect of SeqEnv.
+ *    The replay store is the CSR triple of section 2 (items int32, ratings float, user_off int64) and `slots` int32[n_users] names
+ *    the batch's users.  table float[n_items, emb_dim], 16-byte aligned rows.  An item id outside [0, n_items) gives NaN in whatever
+ *    is derived from it; nothing is read or written out of bounds.  No atomics: equal calls give equal bits.
+ *    Errors: RECNN_E_INVALID with a message, before any launch, for a null pointer, an unsupported shape or a misaligned operand.
+ *    DESIGN.md 14.
+ * ===================================================================================== */
+/* out_items int64[n_users, l_max], out_ratings float[n_users, l_max], out_emb float[n_users, l_max, emb_dim] (may be NULL).
+ * Positions past a user's history hold id 0, rating 0 and therefore table row 0 (the reference's quirk).  emb_dim % 4 == 0. */
+int recnn_seq_gather(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                     int l_max, const float* table, int n_items, int emb_dim, int64_t* out_items, float* out_ratings,
+                     float* out_emb, void* stream);
+/* the same rows from an already padded id tensor: out_emb float[n, emb_dim] = table[idx[i]] */
+int recnn_seq_gather_idx(const int64_t* idx, int64_t n, const float* table, int n_items, int emb_dim, float* out_emb,
+                         void* stream);
+/* torch.nn.LSTM(emb_dim + 1, hidden), one layer, one direction, gate order i, f, g, o, weights read in place:
+ * w_ih float[4 hidden, emb_dim + 1], w_hh float[4 hidden, hidden], b_ih / b_hh float[4 hidden].  The input of step t of user u is
+ * [table[items_u[t]] | ratings_u[t]]; steps t0 .. t0 + T - 1 run from the state (h0, c0) float[n_users, hidden] (both NULL: zeros).
+ * h_out float[n_users, T, hidden]; h_T, c_T float[n_users, hidden] (may alias h0, c0).  Every history must hold t0 + T elements
+ * (positions past an end are clamped to the last element).  fp32 state and accumulation (exact-f32 MFMA); a user's result does not
+ * depend on the other users of the batch or on how its steps are cut into calls.  emb_dim: multiple of 8 up to 128; hidden:
+ * multiple of 16 up to 256.  variant 0: input projection fused into the step; variant 1: projected per chunk of steps into
+ * `workspace` (recnn_lstm_workspace_bytes; 16-byte aligned) by a grid-wide launch -- the same bits. */
+int recnn_lstm_workspace_bytes(int n_users, int T, int hidden, int variant, int64_t* h_bytes);
+int recnn_lstm_encode(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                      int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
+                      const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, const float* c0, float* h_out,
+                      float* h_T, float* c_T, int variant, void* workspace, void* stream);
+/* Rows k n_users + u (k < n_steps) of the four replay-buffer tensors, each pointer already offset to the first row to write, from
+ * h float[n_users, T, hidden] of an encode call with t0 = 0 and the kept steps steps int32[n_steps] (device; 1 <= step < T):
+ * state = h[u, step - 1], next_state = h[u, step], action = table[items_u[step]], reward = ratings_u[step].
+ * state / next_state rows hidden floats, action rows emb_dim floats, reward one float; all contiguous.  hidden, emb_dim % 4 == 0. */
+int recnn_seq_collect(const float* h, int n_users, int T, int hidden, const int32_t* steps, int n_steps, const int32_t* items,
+                      const float* ratings, const int64_t* user_off, const int32_t* slots, const float* table, int n_items,
+                      int emb_dim, float* state, float* action, float* reward, float* next_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

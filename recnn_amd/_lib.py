@@ -229,6 +229,11 @@ SIGNATURES = {
     "recnn_engine_buffer": (_P, [_P, C.c_char_p, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
     "recnn_topk_stats_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
     "recnn_topk_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "recnn_seq_gather": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "recnn_seq_gather_idx": (_I, [_P, _L, _P, _I, _I, _P, _P]),
+    "recnn_lstm_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_lstm_encode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "recnn_seq_collect": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

@@ -16,7 +16,7 @@ from . import utils
 from .pandas_backend import pd
 from .store import ReplayStore
 
-__all__ = ["UserDataset", "EnvBase", "DataPath", "Env", "FrameEnv", "FrameLoader"]
+__all__ = ["UserDataset", "EnvBase", "DataPath", "Env", "FrameEnv", "FrameLoader", "SeqEnv", "SeqLoader"]
 
 
 class UserDataset:
@@ -134,7 +134,55 @@ class FrameLoader:
             yield self.env.collate_users([users[j] for j in order[i:i + self.batch_size]])
 
 
-class FrameEnv(Env):
+class StoreEnv(Env):
+    """An Env whose user histories live on the GPU as one CSR replay store (`recnn_amd.data.store`), next to the embedding
+    table: what FrameEnv and SeqEnv build their batches from.  Subclasses set `device` and implement `_make_loaders`."""
+    _store = None
+    _table = None
+    _csr = None
+
+    def _fill_from_user_dict(self, embeddings, user_dict, train_users, test_users):
+        self.base.embeddings = embeddings
+        n = embeddings.shape[0]
+        self.base.key_to_id = {i: i for i in range(n)}
+        self.base.id_to_key = {i: i for i in range(n)}
+        self.base.train_user_dataset = UserDataset(list(train_users), user_dict)
+        self.base.test_user_dataset = UserDataset(list(test_users), user_dict)
+        self._make_loaders()
+
+    def _fill_from_csr(self, embeddings, items, ratings, user_off, test_fraction):
+        self.base.embeddings = embeddings
+        n_users = len(user_off) - 1
+        n_test = int(n_users * test_fraction)
+        ids = list(range(n_users))
+        self._csr = (np.asarray(items), np.asarray(ratings), np.asarray(user_off, dtype=np.int64))
+        self.base.train_user_dataset = UserDataset(ids[: n_users - n_test], None)
+        self.base.test_user_dataset = UserDataset(ids[n_users - n_test:], None)
+        self._make_loaders()
+
+    @property
+    def store(self) -> ReplayStore:
+        if self._store is None:
+            if self.device.type != "cuda" or not torch.cuda.is_available():
+                from .. import _lib as L
+                raise L.RecnnHipError(f"{type(self).__name__} batches are built on the GPU; device {self.device} is not usable "
+                                      "(no CPU fallback)")
+            if getattr(self, "_csr", None) is not None:
+                self._store = ReplayStore.from_arrays(*self._csr, self.device)
+            else:
+                user_dict = self.base.train_user_dataset.user_dict
+                ids = list(self.base.train_user_dataset.users) + list(self.base.test_user_dataset.users)
+                self._store = ReplayStore(ids, user_dict, self.device)
+            self._table = self.base.embeddings.to(self.device, torch.float32).contiguous()
+        return self._store
+
+    @property
+    def table(self) -> torch.Tensor:
+        self.store
+        return self._table
+
+
+class FrameEnv(StoreEnv):
     """Static length user environment (env.py:190-256).
 
     Extra keyword arguments (extensions, all optional):
@@ -164,13 +212,7 @@ class FrameEnv(Env):
                        **kwargs):
         """Build an env from in-memory data (the output contract of `prepare_dataset`) without csv / pickle files."""
         self = cls(None, frame_size, batch_size, **kwargs)
-        self.base.embeddings = embeddings
-        n = embeddings.shape[0]
-        self.base.key_to_id = {i: i for i in range(n)}
-        self.base.id_to_key = {i: i for i in range(n)}
-        self.base.train_user_dataset = UserDataset(list(train_users), user_dict)
-        self.base.test_user_dataset = UserDataset(list(test_users), user_dict)
-        self._make_loaders()
+        self._fill_from_user_dict(embeddings, user_dict, train_users, test_users)
         return self
 
     @classmethod
@@ -179,41 +221,12 @@ class FrameEnv(Env):
         """Build an env straight from CSR arrays (items int[sum L], ratings float[sum L], user_off int64[U+1]): the
         replay-store form of the reference's `user_dict`, for data that never existed as per-user python objects."""
         self = cls(None, frame_size, batch_size, **kwargs)
-        self.base.embeddings = embeddings
-        n_users = len(user_off) - 1
-        n_test = int(n_users * test_fraction)
-        ids = list(range(n_users))
-        self._csr = (np.asarray(items), np.asarray(ratings), np.asarray(user_off, dtype=np.int64))
-        self.base.train_user_dataset = UserDataset(ids[: n_users - n_test], None)
-        self.base.test_user_dataset = UserDataset(ids[n_users - n_test:], None)
-        self._make_loaders()
+        self._fill_from_csr(embeddings, items, ratings, user_off, test_fraction)
         return self
 
     def _make_loaders(self):
         self.train_dataloader = FrameLoader(self, self.base.train_user_dataset, self.batch_size, shuffle=True)
         self.test_dataloader = FrameLoader(self, self.base.test_user_dataset, self.batch_size, shuffle=True)
-
-    # ------------------------------------------------------------------ device store
-    @property
-    def store(self) -> ReplayStore:
-        if self._store is None:
-            if self.device.type != "cuda" or not torch.cuda.is_available():
-                from .. import _lib as L
-                raise L.RecnnHipError(f"FrameEnv batches are built on the GPU; device {self.device} is not usable "
-                                      "(no CPU fallback)")
-            if getattr(self, "_csr", None) is not None:
-                self._store = ReplayStore.from_arrays(*self._csr, self.device)
-            else:
-                user_dict = self.base.train_user_dataset.user_dict
-                ids = list(self.base.train_user_dataset.users) + list(self.base.test_user_dataset.users)
-                self._store = ReplayStore(ids, user_dict, self.device)
-            self._table = self.base.embeddings.to(self.device, torch.float32).contiguous()
-        return self._store
-
-    @property
-    def table(self) -> torch.Tensor:
-        self.store
-        return self._table
 
     # ------------------------------------------------------------------ batches
     def collate_users(self, user_ids):
@@ -276,3 +289,156 @@ class FrameEnv(Env):
 
     def test_batch(self):
         return next(iter(self.test_dataloader))
+
+
+class SeqLoader:
+    """What `SeqEnv.train_dataloader` is: a re-iterable, len()-able stream of batches of `batch_size` USERS in dataset order
+    (the reference's DataLoader(shuffle=False, collate_fn=padder + prepare_batch_dynamic_size)).  Each batch is the
+    `prepare_batch_dynamic_size` dict, built on the GPU from the replay store in one launch."""
+
+    def __init__(self, env, dataset: UserDataset, batch_size: int):
+        self.env = env
+        self.dataset = dataset
+        self.batch_size = batch_size
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def user_batches(self):
+        users = self.dataset.users
+        for i in range(0, len(users), self.batch_size):
+            yield list(users[i:i + self.batch_size])
+
+    def __iter__(self):
+        for ids in self.user_batches():
+            yield self.env.collate_users(ids)
+
+
+class SeqEnv(StoreEnv):
+    """Dynamic-length user environment: whole user histories run through a recurrent state encoder, and a replay buffer of
+    (state, action, reward, next_state) rows is filled from a random 5 % of the steps (the design sketched, and left disabled, in
+    the reference's env.py).  `train_batch()` / `test_batch()` are infinite generators of full buffers.
+
+    Per batch of U users (dataset order; the datasets are sorted by length, so a batch holds users of similar length):
+    T = min(sizes) - 1 steps; the input of step t is [embedding(item_t) | rating_t]; next_state = h_t, state = h_{t-1},
+    action = embedding(item_t), reward = rating_t.  One `np.random.random()` draw per step, in step order; step t is kept when its
+    draw is > 0.95 and t >= 1.  Each kept step appends U rows, meta["step"] receives t, meta["sizes"] / meta["users"] describe the
+    current user batch.  When the buffer holds `max_buf_size` rows, or the next U rows would not fit, the buffers are yielded as
+    {"state", "action", "reward", "next_state", "done", "meta"} (full tensors, zeros beyond meta["rows"]; `done` is all zeros, added
+    so that `recnn.nn.ddpg_update` runs on the batch unchanged) and the buffer starts over.
+
+    All T steps of a user batch are ONE HIP launch chain (`recnn_amd.nn.functional.lstm_encode`), the kept rows one more
+    (`seq_collect`); the padded [U, Lmax, E] tensor is not built on this path.  `state_encoder` must be a single-layer
+    unidirectional `torch.nn.LSTM(E + 1, H)` on the GPU; its `batch_first` is ignored (users are always the batch).
+
+    The encoder is a FROZEN feature extractor here: the states in the buffer carry no autograd graph, and the encoder's weights
+    are read live, so a caller may change them between batches, but training the encoder through the buffer is a follow-up.
+
+    Default layout: [max_buf_size, H], [max_buf_size, E], [max_buf_size, 1], [max_buf_size, H] with H and E taken from the
+    encoder and the embedding table (the reference hard-codes 256 and 128)."""
+
+    def __init__(self, path, state_encoder, batch_size=25, device=torch.device("cuda"), layout=None, max_buf_size=1000,
+                 num_workers=1, embed_batch=utils.batch_tensor_embeddings, *args, **kwargs):
+        super().__init__(path, min_seq_size=10, embed_batch=embed_batch, *args, **kwargs)
+        self.state_encoder = state_encoder
+        self.batch_size = batch_size
+        self.num_workers = num_workers          # kept for API compatibility; there are no worker processes
+        self.device = torch.device(device)
+        self.max_buf_size = max_buf_size
+        self.buffer_layout = layout
+        if path is not None:
+            self._make_loaders()
+
+    @classmethod
+    def from_user_dict(cls, embeddings: torch.Tensor, user_dict, train_users, test_users=(), state_encoder=None, **kwargs):
+        """Build an env from in-memory data (the output contract of `prepare_dataset`) without csv / pickle files."""
+        self = cls(None, state_encoder, **kwargs)
+        self._fill_from_user_dict(embeddings, user_dict, train_users, test_users)
+        return self
+
+    @classmethod
+    def from_store(cls, embeddings: torch.Tensor, items, ratings, user_off, state_encoder=None, test_fraction=0.05, **kwargs):
+        """Build an env straight from CSR arrays (see FrameEnv.from_store)."""
+        self = cls(None, state_encoder, **kwargs)
+        self._fill_from_csr(embeddings, items, ratings, user_off, test_fraction)
+        return self
+
+    def _make_loaders(self):
+        if self.buffer_layout is None:
+            h, e = self.state_encoder.hidden_size, self.base.embeddings.shape[1]
+            n = self.max_buf_size
+            self.buffer_layout = [torch.Size([n, h]), torch.Size([n, e]), torch.Size([n, 1]), torch.Size([n, h])]
+        self._check_layout()
+        self.train_dataloader = SeqLoader(self, self.base.train_user_dataset, self.batch_size)
+        self.test_dataloader = SeqLoader(self, self.base.test_user_dataset, self.batch_size)
+        self.train_buffer = utils.ReplayBuffer(self.max_buf_size, layout=self.buffer_layout, device=self.device)
+        self.test_buffer = utils.ReplayBuffer(self.max_buf_size, layout=self.buffer_layout, device=self.device)
+
+    def _check_layout(self):
+        """The collect launch writes rows of H, E, 1 and H floats: a layout of other widths (the reference's hard-coded 256 / 128
+        over another encoder, say) or of unequal row counts is refused here, not discovered by the kernel."""
+        h, e = self.state_encoder.hidden_size, self.base.embeddings.shape[1]
+        lay = [tuple(int(v) for v in i) for i in self.buffer_layout]
+        ok = len(lay) == 4 and all(len(i) >= 1 for i in lay) and len({i[0] for i in lay}) == 1 and lay[0][1:] == (h,) \
+            and lay[1][1:] == (e,) and lay[2][1:] in ((), (1,)) and lay[3][1:] == (h,)
+        if not ok:
+            raise ValueError(f"SeqEnv: layout {lay} does not fit the encoder and the table: needs [n, {h}], [n, {e}], [n, 1] (or [n]), "
+                             f"[n, {h}] with one n (hidden_size = {h}, embedding width = {e})")
+
+    def collate_users(self, user_ids):
+        """The `prepare_batch_dynamic_size` dict of the given users: items float32[U, Lmax, E] (padded positions hold item 0's
+        row), ratings float32[U, Lmax], sizes float32[U], users list."""
+        st = self.store
+        slots = st.slots(user_ids)
+        _, ratings, rows = utils.gather_padded(st, self._table, slots)
+        return {"items": rows, "users": list(user_ids), "ratings": ratings, "sizes": torch.from_numpy(st.lengths[slots].copy()).float()}
+
+    def prepare_batch_wrapper(self, x):
+        """collate_fn-compatible entry: x = list of UserDataset items."""
+        return utils.prepare_batch_dynamic_size(utils.padder(x), self.table)
+
+    def _hand_out(self, buffer):
+        out = buffer.get()
+        out["meta"] = dict(buffer.meta, step=list(buffer.meta["step"]), rows=buffer.len())
+        out["done"] = torch.zeros(out["state"].shape[0], device=out["state"].device)
+        buffer.flush()
+        return out
+
+    def _generate(self, loader, buffer):
+        from ..nn import functional as F_hip
+        if len(loader.dataset) == 0:
+            raise ValueError("SeqEnv: the dataset is empty, there is nothing to generate batches from")
+        st = self.store
+        # a step is kept only at t >= 1 of T = min(sizes) - 1 steps: some user batch must have histories of at least 3 elements
+        if not any(int(st.lengths[st.slots(ids)].min()) >= 3 for ids in loader.user_batches()):
+            raise ValueError("SeqEnv: no user batch has histories of at least 3 elements, no step can ever be kept")
+        while True:
+            for ids in loader.user_batches():
+                slots = st.slots(ids)
+                sizes = st.lengths[slots]
+                n_users = len(ids)
+                if n_users > buffer.capacity:
+                    raise ValueError(f"SeqEnv: a batch of {n_users} users does not fit a buffer of {self.max_buf_size} rows")
+                buffer.meta.update({"sizes": torch.from_numpy(sizes.copy()).float().to(self.device), "users": ids})
+                n_steps = int(sizes.min()) - 1
+                draws = np.random.random(n_steps) if n_steps > 0 else np.zeros(0)     # the stream of one draw per step
+                kept = [t for t in range(1, n_steps) if draws[t] > 0.95]
+                if not kept:
+                    continue
+                # one encode for every step up to the last kept one (the later steps would not be looked at)
+                h, _ = F_hip.lstm_encode(self.state_encoder, st, self._table, slots, kept[-1] + 1)
+                while kept:
+                    if not buffer.room(n_users):
+                        yield self._hand_out(buffer)
+                    fit = (buffer.capacity - buffer.len()) // n_users
+                    now, kept = kept[:fit], kept[fit:]
+                    F_hip.seq_collect(h, now, st, self._table, slots, buffer.reserve(n_users * len(now)))
+                    buffer.meta["step"].extend(now)
+                    if buffer.len() >= self.max_buf_size:
+                        yield self._hand_out(buffer)
+
+    def train_batch(self):
+        return self._generate(self.train_dataloader, self.train_buffer)
+
+    def test_batch(self):
+        return self._generate(self.test_dataloader, self.test_buffer)

@@ -48,5 +48,20 @@ class ReplayStore:
             return np.asarray(user_ids, dtype=np.int32)
         return np.fromiter((self.slot_of[u] for u in user_ids), dtype=np.int32, count=len(user_ids))
 
+    def checked_slots(self, slots, what: str, device=None) -> np.ndarray:
+        """`slots` as the int32 array the kernels read, after the host checks no launch can make: every slot in [0, len(self)),
+        the store's arrays of the types the kernels assume and, when `device` is given, on that device.  ValueError otherwise."""
+        a = np.asarray(slots)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{what}: slots must be a 1-D integer sequence (got shape {a.shape}, dtype {a.dtype})")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= len(self)):
+            raise ValueError(f"{what}: slots must lie in 0 .. {len(self) - 1} (got {int(a.min())} .. {int(a.max())})")
+        if (self.items.dtype, self.ratings.dtype, self.user_off.dtype) != (torch.int32, torch.float32, torch.int64):
+            raise ValueError(f"{what}: the store must hold int32 items, float32 ratings and int64 offsets (got {self.items.dtype}, "
+                             f"{self.ratings.dtype}, {self.user_off.dtype})")
+        if device is not None and any(t.device != torch.device(device) for t in (self.items, self.ratings, self.user_off)):
+            raise ValueError(f"{what}: the store lives on {self.items.device}, the other operands on {device}")
+        return a.astype(np.int32)
+
     def __len__(self):
         return len(self.lengths)

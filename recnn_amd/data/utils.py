@@ -12,7 +12,7 @@ from .. import _lib as L
 from .pandas_backend import pd
 
 __all__ = ["rolling_window", "get_irsu", "batch_tensor_embeddings", "batch_contstate_discaction", "batch_no_embeddings", "prepare_batch_static_size", "make_items_tensor",
-           "sort_users_itemwise", "get_base_batch", "packed_ld", "FrameBatch"]
+           "sort_users_itemwise", "get_base_batch", "packed_ld", "FrameBatch", "padder", "prepare_batch_dynamic_size", "ReplayBuffer"]
 
 
 def rolling_window(a, window):
@@ -179,6 +179,120 @@ def prepare_batch_static_size(batch, item_embeddings_tensor, frame_size=10, embe
     ratings_t = np.concatenate([rolling_window(np.asarray(b["rates"]), frame_size + 1) for b in batch], 0)
     win = {"items": torch.tensor(item_t), "users": users_t, "ratings": torch.tensor(ratings_t).float(), "sizes": sizes_t}
     return embed_batch(batch=win, item_embeddings_tensor=item_embeddings_tensor, frame_size=frame_size)
+
+
+def padder(x):
+    """Pad a list of `UserDataset` items to one length (utils.py:124-137): {"items": int64[U, Lmax], "ratings": float32[U, Lmax],
+    "sizes": float32[U], "users": list}, zero-padded at the end as `pad_sequence(batch_first=True)` does.  Host index work, CPU
+    tensors -- as in the reference; the embedding rows are gathered on the GPU by `prepare_batch_dynamic_size`."""
+    sizes = [len(b["items"]) for b in x]
+    lmax = max(sizes) if sizes else 0
+    items = np.zeros((len(x), lmax), dtype=np.int64)
+    ratings = np.zeros((len(x), lmax), dtype=np.float32)
+    for i, b in enumerate(x):
+        items[i, :sizes[i]] = np.asarray(b["items"])
+        ratings[i, :sizes[i]] = np.asarray(b["rates"])
+    return {"items": torch.from_numpy(items), "ratings": torch.from_numpy(ratings),
+            "sizes": torch.tensor([b["sizes"] for b in x]).float(), "users": [b["users"] for b in x]}
+
+
+def gather_padded_rows(item_idx, table):
+    """float32[..., E] = table[item_idx] for an int64 id tensor of any shape, one HIP launch (`recnn_seq_gather_idx`)."""
+    _require_cuda(table, "prepare_batch_dynamic_size(item_embeddings_tensor)")
+    table = table.float().contiguous()
+    idx = torch.as_tensor(item_idx).to(table.device, torch.int64).contiguous()
+    out = torch.empty(*idx.shape, table.shape[1], dtype=torch.float32, device=table.device)
+    L.call("recnn_seq_gather_idx", L.ptr(idx), idx.numel(), L.ptr(table), table.shape[0], table.shape[1], L.ptr(out), L.current_stream())
+    return out
+
+
+def gather_padded(store, table, slots, l_max=None, embeddings=True):
+    """The padded batch of the users in `slots` straight from the CSR replay store, one HIP launch (`recnn_seq_gather`):
+    (items int64[U, Lmax], ratings float32[U, Lmax], rows float32[U, Lmax, E] or None).  Lmax defaults to the longest history."""
+    _require_cuda(table, "gather_padded(table)")
+    slots = store.checked_slots(slots, "gather_padded", table.device)
+    u = len(slots)
+    if l_max is None:
+        l_max = int(store.lengths[slots].max()) if u else 0
+    dev = table.device
+    items = torch.empty(u, l_max, dtype=torch.int64, device=dev)
+    ratings = torch.empty(u, l_max, dtype=torch.float32, device=dev)
+    rows = torch.empty(u, l_max, table.shape[1], dtype=torch.float32, device=dev) if embeddings else None
+    slots_d = torch.from_numpy(slots).to(dev)
+    L.call("recnn_seq_gather", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), u, l_max,
+           L.ptr(table), table.shape[0], table.shape[1], L.ptr(items), L.ptr(ratings), L.ptr(rows), L.current_stream())
+    return items, ratings, rows
+
+
+def prepare_batch_dynamic_size(batch, item_embeddings_tensor, embed_batch=None):
+    """The dynamic-length collate (utils.py:149-153): the `padder` dict with "items" replaced by the embedding rows
+    table[item_idx], float32[U, Lmax, E] on the table's device.  The reference's quirk is kept: a padded position holds index 0,
+    so it receives item 0's row, not zeros.  `embed_batch` is accepted and unused, as in the reference."""
+    item_idx, ratings_t, sizes_t, users_t = get_irsu(batch)
+    return {"items": gather_padded_rows(item_idx, item_embeddings_tensor), "users": users_t, "ratings": ratings_t, "sizes": sizes_t}
+
+
+class ReplayBuffer:
+    """Fixed-size SARS' storage that SeqEnv fills (utils.py:217-262): `layout` is the four shapes of state, action, reward,
+    next_state; `append` writes a batch's rows behind the ones already held and records batch["step"] in meta["step"]; `get`
+    returns the FULL buffers (zeros beyond `len()`) with the meta dict; `flush` starts over with fresh zero tensors, so a batch
+    handed out by `get` stays valid.
+
+    Extension: `device` -- where the buffers live (default: the device of the first appended batch; "cpu" is allowed, the buffer
+    is plain storage).  An append that does not fit raises ValueError (the reference dies inside a slice assignment)."""
+
+    def __init__(self, buffer_size, layout, device=None):
+        self.buffer = None
+        self.idx = 0
+        self.size = buffer_size
+        self.layout = layout
+        self.device = None if device is None else torch.device(device)
+        self.meta = {"step": []}
+        self.flush()
+
+    def flush(self):
+        self.buffer = None          # fresh zero tensors, made when they are first needed
+        self.idx = 0
+        self.meta["step"] = []
+
+    def _ensure(self, like=None):
+        if self.buffer is None:
+            if self.device is None:
+                self.device = torch.device("cpu") if like is None else like.device
+            self.buffer = [torch.zeros(tuple(i), device=self.device) for i in self.layout]
+
+    @property
+    def capacity(self):
+        """Rows the buffer can hold: `buffer_size`, or the shortest of the four tensors of `layout` if that is less."""
+        return min(self.size, *(int(i[0]) for i in self.layout))
+
+    def room(self, rows):
+        """Whether `rows` more rows fit."""
+        return self.idx + rows <= self.capacity
+
+    def reserve(self, rows):
+        """Views of the next `rows` rows of the four buffers, for a writer that fills them in place (SeqEnv's collect launch)."""
+        if not self.room(rows):
+            raise ValueError(f"ReplayBuffer: {rows} rows do not fit, {self.idx} of {self.capacity} are taken")
+        self._ensure()
+        lower, self.idx = self.idx, self.idx + rows
+        return [b[lower:self.idx] for b in self.buffer]
+
+    def append(self, batch):
+        state = batch["state"]
+        self._ensure(state)
+        views = self.reserve(state.size(0))
+        self.meta["step"].append(batch["step"])
+        for v, k in zip(views, ("state", "action", "reward", "next_state")):
+            v.copy_(batch[k])
+
+    def get(self):
+        self._ensure()
+        state, action, reward, next_state = self.buffer
+        return {"state": state, "action": action, "reward": reward, "next_state": next_state, "meta": self.meta}
+
+    def len(self):
+        return self.idx
 
 
 def make_items_tensor(items_embeddings_key_dict):

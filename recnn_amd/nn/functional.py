@@ -10,6 +10,8 @@ Replaces recnn/nn/models.py:66-73 and :207-213 (addmm, relu, dropout) and their 
 import ctypes as C
 import itertools
 
+import numpy as np
+
 import torch
 
 from .. import _lib as L
@@ -1255,3 +1257,123 @@ class DuelDQNFunction(torch.autograd.Function):
 def duel_dqn_forward(x, net):
     """DuelDQN(x) on the kernels, differentiable in x and in every parameter of `net`."""
     return DuelDQNFunction.apply(x, net, *net.parameters())
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# LSTM state encoder over whole user histories (csrc/seq.hip, DESIGN.md 14): what SeqEnv turns a user batch into states with.
+LSTM_VARIANTS = {"fused": 0, "chunked": 1}
+_lstm_variant = "chunked"
+
+
+def set_lstm_variant(name: str):
+    """How `lstm_encode` schedules the input projection: "fused" into every step, or "chunked" (projected per chunk of steps by a
+    grid-wide launch, the chain launch starts from it).  Both compute the same bits; DESIGN.md 14 has the timings."""
+    global _lstm_variant
+    if name not in LSTM_VARIANTS:
+        raise ValueError(f"unknown LSTM variant {name!r}; choose from {sorted(LSTM_VARIANTS)}")
+    _lstm_variant = name
+
+
+def _check_lstm(lstm):
+    """The one recurrent layer the encode kernel implements; anything else is refused by name, never approximated."""
+    for attr, want in (("num_layers", 1), ("bidirectional", False), ("proj_size", 0), ("dropout", 0), ("bias", True)):
+        got = getattr(lstm, attr, want)
+        if got != want:
+            raise L.RecnnHipError(f"lstm_encode: {attr}={got!r} is not supported (needs {attr}={want!r}): the HIP encoder is a "
+                                  "single-layer, unidirectional torch.nn.LSTM with biases, without projection or dropout")
+    w = lstm.weight_ih_l0
+    if not w.is_cuda:
+        raise L.RecnnHipError(f"lstm_encode: the module lives on {w.device} (weight_ih_l0.device); it needs a GPU module "
+                              "(recnn_amd has no CPU fallback)")
+    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+        p = getattr(lstm, name)
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise L.RecnnHipError(f"lstm_encode: {name} must be a contiguous float32 tensor (got {p.dtype})")
+
+
+@torch.no_grad()
+def lstm_encode(lstm, store, table, slots, T, h0c0=None, *, t0=0):
+    """States of the users `slots` (store slots) after each of the steps t0 .. t0 + T - 1 of their histories, one HIP launch
+    chain: the input of step t is [table[item_t] | rating_t] (width E + 1 == lstm.input_size), read through the replay `store`.
+    Returns (h float32[U, T, H], (h_T, c_T) float32[U, H] each).  `h0c0` = (h0, c0), each [U, H] or [1, U, H]; default zeros.
+    Carrying (h_T, c_T) into a call with t0 moved on gives bit for bit what one longer call gives.
+
+    Runs under no_grad; the weights are read live from the module on every call (weight_ih_l0, weight_hh_l0, bias_ih_l0,
+    bias_hh_l0, gate order i, f, g, o), state and accumulation are fp32.  Refused with RecnnHipError naming the attribute:
+    num_layers != 1, bidirectional, proj_size != 0, dropout != 0, bias=False, a CPU module.
+
+    `batch_first` is ignored: the users are always the batch and time always runs along a user's own history.  (The
+    reference's commented-out SeqEnv feeds [1, U, E + 1] to its encoder, which a batch_first=True LSTM reads as ONE sequence
+    running across the users -- the bug that makes its notebook "not work yet".  It is not reproduced.)"""
+    _check_lstm(lstm)
+    dev = lstm.weight_ih_l0.device
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()):
+        raise L.RecnnHipError("lstm_encode: table must be a contiguous float32 GPU tensor")
+    E, H = table.shape[1], lstm.hidden_size
+    if lstm.input_size != E + 1:
+        raise L.RecnnHipError(f"lstm_encode: input_size={lstm.input_size} but the table has {E} columns (needs E + 1: the rating)")
+    slots = store.checked_slots(slots, "lstm_encode", dev)
+    U, T, t0 = len(slots), int(T), int(t0)
+    if table.device != dev:
+        raise ValueError(f"lstm_encode: the table lives on {table.device}, the module on {dev}")
+    if T < 1 or t0 < 0:
+        raise ValueError(f"lstm_encode: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
+    if U and int(store.lengths[slots].min()) < t0 + T:
+        raise ValueError(f"lstm_encode: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
+    h0 = c0 = None
+    if h0c0 is not None:
+        h0, c0 = (t.to(dev, torch.float32).reshape(U, H).contiguous() for t in h0c0)
+    h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+    hT = torch.empty(U, H, dtype=torch.float32, device=dev)
+    cT = torch.empty(U, H, dtype=torch.float32, device=dev)
+    variant = LSTM_VARIANTS[_lstm_variant]
+    ws = L.workspace("recnn_lstm_workspace_bytes", U, T, H, variant, device=dev)
+    slots_d = torch.from_numpy(slots).to(dev)
+    L.call("recnn_lstm_encode", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
+           L.ptr(table), table.shape[0], E, H, L.ptr(lstm.weight_ih_l0), L.ptr(lstm.weight_hh_l0), L.ptr(lstm.bias_ih_l0),
+           L.ptr(lstm.bias_hh_l0), L.ptr(h0), L.ptr(c0), L.ptr(h), L.ptr(hT), L.ptr(cT), variant, L.ptr(ws), L.current_stream())
+    return h, (hT, cT)
+
+
+def seq_collect(h, steps, store, table, slots, views):
+    """Fill `views` = (state, action, reward, next_state) rows [len(steps) * U, ...] for the kept `steps` of one user batch from
+    the encode output h [U, T, H]: one launch (`recnn_seq_collect`).
+
+    The kernel writes rows of H, E, 1 and H floats and cannot see the destinations' sizes, so they are checked here, before
+    anything else: each view float32, contiguous, on h's device and shaped [rows, H], [rows, E], [rows] or [rows, 1], [rows, H]
+    with rows == len(steps) * U.  ValueError naming the sizes otherwise."""
+    if not (isinstance(h, torch.Tensor) and h.dim() == 3 and h.dtype == torch.float32 and h.is_contiguous()):
+        raise ValueError("seq_collect: h must be a contiguous float32 [U, T, H] tensor")
+    U, T, H = h.shape
+    E = table.shape[1]
+    steps = np.asarray(steps, dtype=np.int32).reshape(-1)
+    if len(steps) and (steps.min() < 1 or steps.max() >= T):
+        raise ValueError(f"seq_collect: steps must lie in 1 .. {T - 1}")
+    if len(slots) != U:
+        raise ValueError(f"seq_collect: {len(slots)} slots for the {U} users of h")
+    rows = len(steps) * U
+    if len(views) != 4:
+        raise ValueError(f"seq_collect: views must be (state, action, reward, next_state), got {len(views)} tensors")
+    want = {"state": [(rows, H)], "action": [(rows, E)], "reward": [(rows,), (rows, 1)], "next_state": [(rows, H)]}
+    for (name, shapes), v in zip(want.items(), views):
+        if not isinstance(v, torch.Tensor) or tuple(v.shape) not in shapes or v.dtype != torch.float32 or not v.is_contiguous() \
+                or v.device != h.device:
+            got = (tuple(v.shape), v.dtype, str(v.device), "contiguous" if v.is_contiguous() else "strided") \
+                if isinstance(v, torch.Tensor) else type(v)
+            raise ValueError(f"seq_collect: {name} must be a contiguous float32 tensor of shape {' or '.join(map(str, shapes))} on "
+                             f"{h.device} ({len(steps)} steps x {U} users, H = {H}, E = {E}); got {got}")
+    if not h.is_cuda:
+        raise L.RecnnHipError(f"seq_collect: needs GPU tensors (recnn_amd has no CPU fallback); got {h.device}")
+    if not (table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.device == h.device):
+        raise L.RecnnHipError("seq_collect: table must be a contiguous float32 tensor on h's device")
+    slots = store.checked_slots(slots, "seq_collect", h.device)
+    if len(steps) and int(store.lengths[slots].min()) <= int(steps.max()):
+        raise ValueError(f"seq_collect: step {int(steps.max())} asked of a history of {int(store.lengths[slots].min())} elements")
+    state, action, reward, next_state = views
+    # (both index tensors stay referenced until the launch is queued: a temporary freed inside the argument list hands its block
+    # to the next one)
+    steps_d = torch.from_numpy(steps).to(h.device)
+    slots_d = torch.from_numpy(slots).to(h.device)
+    L.call("recnn_seq_collect", L.ptr(h), U, T, H, L.ptr(steps_d), len(steps), L.ptr(store.items),
+           L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), L.ptr(table), table.shape[0],
+           E, L.ptr(state), L.ptr(action), L.ptr(reward), L.ptr(next_state), L.current_stream())

@@ -812,6 +812,35 @@ int recnn_seq_collect(const float* h, int n_users, int T, int hidden, const int3
                       const float* ratings, const int64_t* user_off, const int32_t* slots, const float* table, int n_items,
                       int emb_dim, float* state, float* action, float* reward, float* next_state, void* stream);
 
+/* Training the encoder (csrc/seq_bwd.hip).  recnn_lstm_encode_train is recnn_lstm_encode -- the same h_out, h_T, c_T bit for bit,
+ * either variant -- that also records, per (user, step, hidden unit), the gate activations i, f, g, o and the cell state c_t into
+ * `saved` (saved_bytes of recnn_lstm_train_workspace_bytes: 5 * 16 ceil(n_users / 16) * T * hidden floats; 16-byte aligned; its
+ * layout is private to the library).  `workspace` is that of recnn_lstm_workspace_bytes, as for recnn_lstm_encode.
+ *
+ * recnn_lstm_backward is backward through time over the steps of ONE such call (same store, slots, t0, T, table, w_hh, h0 / c0;
+ * `saved` and `h_out` as that call wrote them).  Upstream gradients, each may be NULL (zeros): g_h float[n_users, T, hidden],
+ * g_hT / g_cT float[n_users, hidden].  Outputs, each may be NULL (not wanted): d_w_ih float[4 hidden, emb_dim + 1], d_w_hh
+ * float[4 hidden, hidden], d_b float[4 hidden] (the gradient of b_ih and of b_hh), d_h0 / d_c0 float[n_users, hidden]; they are
+ * written, not added to.  With d_w_ih, d_w_hh and d_b all NULL the weight-gradient launches are skipped.  `workspace`: bwd_bytes of
+ * recnn_lstm_train_workspace_bytes, 16-byte aligned.  Fixed summation orders, no atomics: equal calls give equal bits.  T >= 1. */
+int recnn_lstm_train_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int variant, int64_t* saved_bytes,
+                                     int64_t* bwd_bytes);
+int recnn_lstm_encode_train(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                            int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
+                            const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, const float* c0, float* h_out,
+                            float* h_T, float* c_T, int variant, void* workspace, void* saved, void* stream);
+int recnn_lstm_backward(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                        int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_hh,
+                        const void* saved, const float* h_out, const float* h0, const float* c0, const float* g_h,
+                        const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b, float* d_h0, float* d_c0,
+                        void* workspace, void* stream);
+/* Backward of recnn_seq_collect with respect to h: g_h float[n_users, T, hidden] (every element written) from the gradients of the
+ * state and next_state rows (each float[n_steps * n_users, hidden] or NULL: zeros): g_h[u, t] = g_next_state[k n_users + u] where
+ * steps[k] == t, plus g_state[k' n_users + u] where steps[k'] == t + 1.  steps int32[n_steps] (device) must be strictly increasing
+ * (the caller checks). */
+int recnn_seq_collect_bwd(const float* g_state, const float* g_next_state, int n_users, int T, int hidden, const int32_t* steps,
+                          int n_steps, float* g_h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

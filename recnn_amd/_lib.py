@@ -234,6 +234,10 @@ SIGNATURES = {
     "recnn_lstm_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
     "recnn_lstm_encode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "recnn_seq_collect": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "recnn_lstm_train_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L), C.POINTER(_L)]),
+    "recnn_lstm_encode_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "recnn_lstm_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "recnn_seq_collect_bwd": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

@@ -331,8 +331,10 @@ class SeqEnv(StoreEnv):
     (`seq_collect`); the padded [U, Lmax, E] tensor is not built on this path.  `state_encoder` must be a single-layer
     unidirectional `torch.nn.LSTM(E + 1, H)` on the GPU; its `batch_first` is ignored (users are always the batch).
 
-    The encoder is a FROZEN feature extractor here: the states in the buffer carry no autograd graph, and the encoder's weights
-    are read live, so a caller may change them between batches, but training the encoder through the buffer is a follow-up.
+    The encoder is a FROZEN feature extractor for the replay buffer: the states in the buffer carry no autograd graph, and the
+    encoder's weights are read live, so a caller may change them between batches.  `user_batch(user_ids, steps)` is the way to
+    TRAIN it: the same rows for one user batch, on policy, with `state` / `next_state` attached to the encoder's graph
+    (`recnn_amd.nn.functional.lstm_encode_train`, backward through time in HIP).
 
     Default layout: [max_buf_size, H], [max_buf_size, E], [max_buf_size, 1], [max_buf_size, H] with H and E taken from the
     encoder and the embedding table (the reference hard-codes 256 and 128)."""
@@ -436,6 +438,32 @@ class SeqEnv(StoreEnv):
                     buffer.meta["step"].extend(now)
                     if buffer.len() >= self.max_buf_size:
                         yield self._hand_out(buffer)
+
+    def user_batch(self, user_ids, steps):
+        """{"state", "action", "reward", "next_state", "done", "meta"} for the users `user_ids` and the kept `steps` (strictly
+        increasing, 1 <= step < min(sizes) - 1): exactly the rows the generator would put into the buffer for them, U per step in
+        the order k * U + u, without going through the buffer.  When grad mode is on and a parameter of the encoder requires
+        grad, `state` and `next_state` are attached to the encoder's graph (`lstm_encode_train` + `seq_collect_rows`): a loss on
+        them back-propagates through time into the encoder's weights.  Otherwise they are the detached rows of `lstm_encode`."""
+        from ..nn import functional as F_hip
+        st = self.store
+        ids = list(user_ids)
+        slots = st.slots(ids)
+        sizes = st.lengths[slots]
+        steps = [int(t) for t in np.asarray(steps).reshape(-1)]
+        if not ids or not steps:
+            raise ValueError("SeqEnv.user_batch: needs at least one user and one step")
+        n_steps = int(sizes.min()) - 1
+        if any(b <= a for a, b in zip(steps, steps[1:])):
+            raise ValueError(f"SeqEnv.user_batch: steps must be strictly increasing (got {steps})")
+        if steps[0] < 1 or steps[-1] >= n_steps:
+            raise ValueError(f"SeqEnv.user_batch: steps must lie in 1 .. {n_steps - 1} (the shortest history has "
+                             f"{int(sizes.min())} elements)")
+        h, _ = F_hip.lstm_encode_train(self.state_encoder, st, self._table, slots, steps[-1] + 1)
+        state, action, reward, next_state = F_hip.seq_collect_rows(h, steps, st, self._table, slots)
+        meta = {"sizes": torch.from_numpy(sizes.copy()).float().to(self.device), "users": ids, "step": steps, "rows": state.shape[0]}
+        return {"state": state, "action": action, "reward": reward, "next_state": next_state,
+                "done": torch.zeros(state.shape[0], device=state.device), "meta": meta}
 
     def train_batch(self):
         return self._generate(self.train_dataloader, self.train_buffer)

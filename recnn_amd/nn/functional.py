@@ -1298,7 +1298,7 @@ def lstm_encode(lstm, store, table, slots, T, h0c0=None, *, t0=0):
     Returns (h float32[U, T, H], (h_T, c_T) float32[U, H] each).  `h0c0` = (h0, c0), each [U, H] or [1, U, H]; default zeros.
     Carrying (h_T, c_T) into a call with t0 moved on gives bit for bit what one longer call gives.
 
-    Runs under no_grad; the weights are read live from the module on every call (weight_ih_l0, weight_hh_l0, bias_ih_l0,
+    Runs under no_grad (`lstm_encode_train` is the same call with a graph); the weights are read live from the module on every call (weight_ih_l0, weight_hh_l0, bias_ih_l0,
     bias_hh_l0, gate order i, f, g, o), state and accumulation are fp32.  Refused with RecnnHipError naming the attribute:
     num_layers != 1, bidirectional, proj_size != 0, dropout != 0, bias=False, a CPU module.
 
@@ -1377,3 +1377,147 @@ def seq_collect(h, steps, store, table, slots, views):
     L.call("recnn_seq_collect", L.ptr(h), U, T, H, L.ptr(steps_d), len(steps), L.ptr(store.items),
            L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), L.ptr(table), table.shape[0],
            E, L.ptr(state), L.ptr(action), L.ptr(reward), L.ptr(next_state), L.current_stream())
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Training the encoder (csrc/seq_bwd.hip): backward through time for the encode chain, a differentiable collect.
+def _lstm_call_args(name, lstm, store, table, slots, T, h0c0, t0):
+    """The checks of `lstm_encode`, for both encode entry points: (dev, E, H, U, T, t0, slots, h0, c0)."""
+    _check_lstm(lstm)
+    dev = lstm.weight_ih_l0.device
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()):
+        raise L.RecnnHipError(f"{name}: table must be a contiguous float32 GPU tensor")
+    E, H = table.shape[1], lstm.hidden_size
+    if lstm.input_size != E + 1:
+        raise L.RecnnHipError(f"{name}: input_size={lstm.input_size} but the table has {E} columns (needs E + 1: the rating)")
+    slots = store.checked_slots(slots, name, dev)
+    U, T, t0 = len(slots), int(T), int(t0)
+    if table.device != dev:
+        raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
+    if T < 1 or t0 < 0:
+        raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
+    if U and int(store.lengths[slots].min()) < t0 + T:
+        raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
+    h0 = c0 = None
+    if h0c0 is not None:
+        h0, c0 = (t.to(dev, torch.float32).reshape(U, H).contiguous() for t in h0c0)
+    return dev, E, H, U, T, t0, slots, h0, c0
+
+
+class LSTMEncodeFunction(torch.autograd.Function):
+    """(h, h_T, c_T) of the encode chain with the gates and cell states recorded, and backward through time for them
+    (`recnn_lstm_encode_train` / `recnn_lstm_backward`).  Differentiable in the four weights and in h0 / c0; once."""
+
+    @staticmethod
+    def forward(ctx, w_ih, w_hh, b_ih, b_hh, h0, c0, store, table, slots_d, T, t0):
+        dev = w_ih.device
+        U, E, H = slots_d.shape[0], table.shape[1], w_hh.shape[1]
+        variant = LSTM_VARIANTS[_lstm_variant]
+        nsaved, nbwd = C.c_int64(), C.c_int64()
+        L.call("recnn_lstm_train_workspace_bytes", U, T, H, E, variant, C.byref(nsaved), C.byref(nbwd))
+        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+        ws = L.workspace("recnn_lstm_workspace_bytes", U, T, H, variant, device=dev)
+        h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+        hT = torch.empty(U, H, dtype=torch.float32, device=dev)
+        cT = torch.empty(U, H, dtype=torch.float32, device=dev)
+        L.call("recnn_lstm_encode_train", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
+               L.ptr(table), table.shape[0], E, H, L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), L.ptr(h0), L.ptr(c0),
+               L.ptr(h), L.ptr(hT), L.ptr(cT), variant, L.ptr(ws), L.ptr(saved), L.current_stream())
+        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
+        ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None and is passed as NULL
+        ctx.has_h0 = h0 is not None
+        ctx.save_for_backward(w_hh, table, slots_d, saved, h, *((h0, c0) if h0 is not None else ()))
+        return h, hT, cT
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h, g_hT, g_cT):
+        w_hh, table, slots_d, saved, h = ctx.saved_tensors[:5]
+        h0, c0 = ctx.saved_tensors[5:] if ctx.has_h0 else (None, None)
+        U, T, t0, E, H = ctx.dims
+        store, dev = ctx.store, h.device
+        need = ctx.needs_input_grad
+        if g_h is None and g_hT is None and g_cT is None:
+            return (None,) * 11
+        g_h, g_hT, g_cT = (None if g is None else g.to(torch.float32).contiguous() for g in (g_h, g_hT, g_cT))
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        d_w_ih = new(4 * H, E + 1) if need[0] else None
+        d_w_hh = new(4 * H, H) if need[1] else None
+        d_b = new(4 * H) if need[2] or need[3] else None
+        d_h0 = new(U, H) if need[4] else None
+        d_c0 = new(U, H) if need[5] else None
+        ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
+        L.call("recnn_lstm_backward", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
+               L.ptr(table), table.shape[0], E, H, L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(c0), L.ptr(g_h),
+               L.ptr(g_hT), L.ptr(g_cT), L.ptr(d_w_ih), L.ptr(d_w_hh), L.ptr(d_b), L.ptr(d_h0), L.ptr(d_c0), L.ptr(ws),
+               L.current_stream())
+        return (d_w_ih, d_w_hh, d_b if need[2] else None, (d_b.clone() if need[2] else d_b) if need[3] else None, d_h0, d_c0,
+                None, None, None, None, None)
+
+
+def lstm_encode_train(lstm, store, table, slots, T, h0c0=None, *, t0=0):
+    """`lstm_encode` with a graph: the same arguments, checks and return value (h, (h_T, c_T)) -- bit for bit the same numbers
+    under either variant -- differentiable with respect to weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, and to h0 / c0 when
+    they require grad, so truncated BPTT over calls with `t0` moved on works: carry (h_T, c_T) into the next call.
+
+    The forward also records the gate activations and cell states (5 U T H floats, U rounded up to 16); the backward is one HIP
+    launch chain backward through time plus the weight-gradient launches per chunk of steps (csrc/seq_bwd.hip), in fixed
+    summation orders: equal calls give equal gradients bit for bit.  It is once differentiable.  Gradients with respect to the
+    embedding table are not computed: a `table` that requires grad is refused with RecnnHipError.  Under `torch.no_grad()`, or
+    when nothing requires grad, this IS `lstm_encode`: nothing is recorded."""
+    if isinstance(table, torch.Tensor) and table.requires_grad:
+        raise L.RecnnHipError("lstm_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
+                              "not computed; pass table.detach()")
+    dev, E, H, U, T, t0, slots, h0, c0 = _lstm_call_args("lstm_encode_train", lstm, store, table, slots, T, h0c0, t0)
+    params = (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
+    live = [p for p in params if p.requires_grad] + [t for t in (h0, c0) if t is not None and t.requires_grad]
+    if not torch.is_grad_enabled() or not live:
+        return lstm_encode(lstm, store, table, slots, T, None if h0 is None else (h0, c0), t0=t0)
+    slots_d = torch.from_numpy(slots).to(dev)
+    h, hT, cT = LSTMEncodeFunction.apply(*params, h0, c0, store, table, slots_d, T, t0)
+    return h, (hT, cT)
+
+
+class SeqCollectFunction(torch.autograd.Function):
+    """The rows of `seq_collect`, and the gather that returns the gradients of the state / next_state rows to h."""
+
+    @staticmethod
+    def forward(ctx, h, steps, store, table, slots):
+        U, T, H = h.shape
+        rows, E = len(steps) * U, table.shape[1]
+        views = (h.new_empty(rows, H), h.new_empty(rows, E), h.new_empty(rows, 1), h.new_empty(rows, H))
+        seq_collect(h, steps, store, table, slots, views)
+        ctx.steps, ctx.shape = np.asarray(steps, dtype=np.int32).reshape(-1), (U, T, H)
+        ctx.mark_non_differentiable(views[1], views[2])
+        ctx.set_materialize_grads(False)
+        return views
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_state, _ga, _gr, g_next):
+        U, T, H = ctx.shape
+        if g_state is None and g_next is None:
+            return None, None, None, None, None
+        g_state, g_next = (None if g is None else g.to(torch.float32).contiguous() for g in (g_state, g_next))
+        dev = (g_state if g_state is not None else g_next).device
+        g_h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+        steps_d = torch.from_numpy(ctx.steps).to(dev)
+        L.call("recnn_seq_collect_bwd", L.ptr(g_state), L.ptr(g_next), U, T, H, L.ptr(steps_d), len(ctx.steps), L.ptr(g_h),
+               L.current_stream())
+        return g_h, None, None, None, None
+
+
+def seq_collect_rows(h, steps, store, table, slots):
+    """`seq_collect` with a graph: allocates and returns (state, action, reward, next_state) for the kept `steps` (strictly
+    increasing) of one user batch, rows in the order k * U + u, bit for bit what `seq_collect` writes.  The gradients of the
+    state and next_state rows reach `h` (one gather launch, `recnn_seq_collect_bwd`); action and reward carry none."""
+    if not (isinstance(h, torch.Tensor) and h.is_cuda):
+        raise L.RecnnHipError(f"seq_collect_rows: needs GPU tensors (recnn_amd has no CPU fallback); got "
+                              f"{h.device if isinstance(h, torch.Tensor) else type(h)}")
+    st = np.asarray(steps, dtype=np.int64).reshape(-1)
+    if len(st) > 1 and (np.diff(st) <= 0).any():
+        raise ValueError(f"seq_collect_rows: steps must be strictly increasing (got {st.tolist()})")
+    if h.dim() == 3 and h.dtype == torch.float32 and not h.is_contiguous():
+        h = h.contiguous()
+    return SeqCollectFunction.apply(h, [int(t) for t in st], store, table, slots)
+

@@ -8,7 +8,10 @@ on the same GPU, at the reference SeqEnv's defaults (U = 25 users, H = 256, E = 
 Device-event times around the whole Python call, median of `--repeats` calls after one warm-up call: the HIP figures include the call's
 host work (a pageable upload of the slots, the workspace and the three output allocations), microseconds against tens of milliseconds.
 Also reports max |hip - torch| over h.  Prints one JSON line.
-usage: python tools/seq_bench.py [--quick] [--repeats 5] [--out profiles/seq_bench.json]"""
+  --backward   training instead (csrc/seq_bwd.hip): `lstm_encode_train` forward + backward of the loss h.sum() (every
+               step live) against torch.nn.LSTM forward + backward of the same loss, the training forward alone against the inference
+               encode, and max |hip - torch| relative to max |torch| per weight gradient.  Same shapes, same timing method.
+usage: python tools/seq_bench.py [--quick] [--repeats 5] [--backward] [--out profiles/seq_bench.json]"""
 import argparse
 import json
 import os
@@ -34,7 +37,7 @@ def median_ms(fn, repeats):
     return float(np.median(times))
 
 
-def case(U, T, E, H, repeats, dev):
+def case(U, T, E, H, repeats, dev, backward=False):
     from recnn_amd.data.store import ReplayStore
     from recnn_amd.nn import functional as F
     rng = np.random.default_rng(U)
@@ -54,6 +57,8 @@ def case(U, T, E, H, repeats, dev):
     x = torch.cat([table[idx], rts[..., None]], 2).contiguous()
     res = {"U": U, "T": T, "E": E, "H": H}
     out = {}
+    if backward:
+        return backward_case(res, lstm, store, table, slots, x, T, repeats)
     for variant in ("fused", "chunked"):
         F.set_lstm_variant(variant)
         res[f"hip_{variant}_ms"] = median_ms(lambda: out.__setitem__(variant, F.lstm_encode(lstm, store, table, slots, T)[0]), repeats)
@@ -68,17 +73,47 @@ def case(U, T, E, H, repeats, dev):
     return res
 
 
+def backward_case(res, lstm, store, table, slots, x, T, repeats):
+    from recnn_amd.nn import functional as F
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+    grads = {}
+
+    def hip_step():
+        lstm.zero_grad(set_to_none=True)
+        F.lstm_encode_train(lstm, store, table, slots, T)[0].sum().backward()
+        grads["hip"] = [getattr(lstm, n).grad for n in names]
+
+    def torch_step():
+        lstm.zero_grad(set_to_none=True)
+        lstm(x)[0].sum().backward()
+        grads["torch"] = [getattr(lstm, n).grad for n in names]
+
+    res["hip_train_fwd_bwd_ms"] = median_ms(hip_step, repeats)
+    res["torch_fwd_bwd_ms"] = median_ms(torch_step, repeats)
+    res["hip_train_fwd_ms"] = median_ms(lambda: F.lstm_encode_train(lstm, store, table, slots, T), repeats)
+    res["hip_infer_fwd_ms"] = median_ms(lambda: F.lstm_encode(lstm, store, table, slots, T), repeats)
+    with torch.no_grad():
+        res["torch_fwd_ms"] = median_ms(lambda: lstm(x), repeats)
+    res["hip_bwd_ms"] = res["hip_train_fwd_bwd_ms"] - res["hip_train_fwd_ms"]       # a difference of two medians
+    res["torch_over_hip_fwd_bwd"] = res["torch_fwd_bwd_ms"] / res["hip_train_fwd_bwd_ms"]
+    res["train_fwd_over_infer_fwd"] = res["hip_train_fwd_ms"] / res["hip_infer_fwd_ms"]
+    res["hip_bwd_us_per_step"] = 1e3 * res["hip_bwd_ms"] / T
+    res["grad_rel_diff_vs_torch"] = {n: float((a - b).abs().max() / b.abs().max()) for n, a, b in zip(names, grads["hip"], grads["torch"])}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="T = 100 instead of 1000")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--backward", action="store_true", help="time the training forward + backward (DESIGN.md 15)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda")
     T = 100 if a.quick else 1000
-    res = {"tool": "seq_bench", "device": torch.cuda.get_device_name(0),
+    res = {"tool": "seq_bench --backward" if a.backward else "seq_bench", "device": torch.cuda.get_device_name(0),
            "arch": torch.cuda.get_device_properties(0).gcnArchName,      # (the marketing name may read generic; the arch does not)
-           "lib": os.environ.get("RECNN_HIP_LIB", "in-tree"), "cases": [case(U, T, 128, 256, a.repeats, dev) for U in (25, 256)]}
+           "lib": os.environ.get("RECNN_HIP_LIB", "in-tree"), "cases": [case(U, T, 128, 256, a.repeats, dev, a.backward) for U in (25, 256)]}
     line = json.dumps(res)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

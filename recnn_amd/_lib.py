@@ -180,6 +180,7 @@ SIGNATURES = {
     "recnn_engine_value_grads": (_I, [_P, _I, _I, _P]),
     "recnn_engine_value_apply": (_I, [_P, _I, _F, _P]),
     "recnn_engine_policy_grads": (_I, [_P, _I, _I, _P]),
+    "recnn_engine_state_grads": (_I, [_P, _I, _I, _P, _L, _P]),
     "recnn_engine_policy_apply": (_I, [_P, _I, _F, _P]),
     "recnn_engine_clip_policy_grads": (_I, [_P, _F, _P]),
     "recnn_engine_soft_update": (_I, [_P, _I, _I, _F, _P]),

@@ -423,8 +423,11 @@ extern "C" int recnn_engine_value_grads(recnn_engine* e, int rows, int learn, vo
   rc = stage_batch(e, rows, (hipStream_t)stream);
   e->use_sampler = false;
   if (rc) return rc;
+  e->sg_ok = 0;
   if ((rc = ph_forward(e, rows, true, false, learn != 0, (hipStream_t)stream))) return rc;
-  if (learn) return ph_value_backward(e, rows, true, (hipStream_t)stream);
+  if (!learn) return 0;
+  if ((rc = ph_value_backward(e, rows, true, (hipStream_t)stream))) return rc;
+  e->sg_ok = 1;
   return 0;
 }
 
@@ -436,8 +439,28 @@ extern "C" int recnn_engine_value_apply(recnn_engine* e, int soft, float grad_sc
 extern "C" int recnn_engine_policy_grads(recnn_engine* e, int rows, int backward, void* stream) {
   int rc = check_ready(e, rows);
   if (rc) return rc;
+  e->sg_ok = 0;
   if ((rc = ph_forward(e, rows, false, true, false, (hipStream_t)stream))) return rc;
-  return ph_policy(e, rows, backward != 0, false, (hipStream_t)stream, false);
+  if ((rc = ph_policy(e, rows, backward != 0, false, (hipStream_t)stream, false))) return rc;
+  if (backward) e->sg_ok = 2;
+  return 0;
+}
+
+// d loss / d state of the phase that just ran, into the caller's fp32 [rows, ld_out] (include/recnn_hip.h).
+extern "C" int recnn_engine_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_out, void* stream) {
+  RECNN_REQUIRE(e, "state_grads: null engine");
+  RECNN_REQUIRE(out, "state_grads: null output");
+  RECNN_REQUIRE(which == 0 || which == 1, "state_grads: which must be 0 (value loss) or 1 (policy loss)");
+  RECNN_REQUIRE(rows > 0 && rows <= e->cfg.max_rows, "state_grads: rows=%d outside [1, %d]", rows, e->cfg.max_rows);
+  RECNN_REQUIRE(ld_out >= e->S, "state_grads: ld_out=%lld is smaller than state_dim=%d", (long long)ld_out, e->S);
+  if (e->td3) { recnn_set_error("state_grads: DDPG only -- this is a TD3 engine (its update takes no gradient into the state)"); return RECNN_E_UNSUPPORTED; }
+  if (e->x3) { recnn_set_error("state_grads: the split-bf16 compute type (bf16x3) is not supported; use fp32 or bf16"); return RECNN_E_UNSUPPORTED; }
+  if (!(e->sg_ok & (1 << which))) {
+    recnn_set_error(which ? "state_grads: which=1 needs recnn_engine_policy_grads(backward=1) right before it (no optimizer apply / refresh in between)"
+                          : "state_grads: which=0 needs recnn_engine_value_grads(learn=1) right before it, before the value optimizer is applied or refreshed");
+    return RECNN_E_STATE;
+  }
+  return ph_state_grads(e, rows, which, out, ld_out, (hipStream_t)stream);
 }
 
 extern "C" int recnn_engine_policy_apply(recnn_engine* e, int soft, float grad_scale, void* stream) {

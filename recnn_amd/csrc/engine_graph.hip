@@ -227,6 +227,7 @@ extern "C" int recnn_engine_graph_run(recnn_engine* e, int first_step, int n_ste
   RECNN_REQUIRE(e && e->gexec[0] && e->gexec[1], "graph_run: graphs not built");
   const int pe = e->hy.policy_every;
   hipStream_t s = (hipStream_t)stream;
+  e->sg_ok = 0;   // a replay overwrites what recnn_engine_state_grads reads
   for (int c = 0; c < recnn_engine::CUSTOM_MAX; ++c)
     if (e->grun_custom[c] && e->grun_custom_len[c] == n_steps && e->grun_custom_phase[c] == first_step % pe) {
       RECNN_HIP(hipGraphLaunch(e->grun_custom[c], s));
@@ -384,6 +385,7 @@ extern "C" int recnn_engine_dp_sets(recnn_engine* e) { return e ? e->dp_sets : 1
 extern "C" int recnn_engine_dp_graph_launch(recnn_engine* e, int which, void* stream) {
   const int kind = which & 7, set = which >> 3;
   RECNN_REQUIRE(e && which >= 0 && kind < 7 && set < 2 && e->gdp[kind][set], "dp_graph_launch: graph %d not built", which);
+  e->sg_ok = 0;
   RECNN_HIP(hipGraphLaunch(e->gdp[kind][set], (hipStream_t)stream));
   // where the debug views find the batch afterwards: merged graphs (kinds 5, 6) end in the other set's head
   use_set(e, (kind >= 5 && e->dp_sets == 2) ? (set ^ 1) : set);

@@ -20,6 +20,7 @@
 #include "split.h"
 #include "x3.h"
 #include "x3tail.h"
+#include "state_grad.h"
 
 constexpr int LOSS_RING = 1024;   // loss history ring entries (power of two)
 
@@ -141,6 +142,12 @@ struct recnn_engine {
   bool half_panels = false;                // this step's tail launch ran 16-row panels: the small tensors' panel sums and the value-loss
                                            // partials are HALF-panel sums, consumed in pairs (TensorSeg.pair, LossFinalizeArgs.pair)
   bool hist_half[LOSS_HIST_MAX] = {};      // ... per step of the run being captured (loss history)
+  // recnn_engine_state_grads: what the backward buffers and weight shadows still hold.  Bit 0: the value loss's dz_c1 next to the critic the
+  // value backward used (set by recnn_engine_value_grads with learn); bit 1: the policy loss's dz_e1 / dz_p1 next to the critic and actor
+  // ph_policy used (set by recnn_engine_policy_grads with backward).  Cleared by whatever overwrites either: a step, a graph replay, an
+  // optimizer apply or a shadow refresh of the network.
+  int sg_ok = 0;
+  bool dze1_ok = false;                    // the last ph_policy backward left dz_e1 in memory (the row-panel chain keeps it on chip)
   float* pl_part;                          // policy loss: per-wave partial dots of the policy-critic's layer-2 GEMM
   int pl_cap = 0, pl_dot_parts = 0;        // capacity / number written by this step (0: the head kernel produced the loss)                           // ... their outputs, fp32 [Bc]
   float *loss_part[3];                     // value1, value2, policy  (per head block): the CURRENT step's slot of ...
@@ -254,6 +261,7 @@ int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool
 int ph_value_backward(recnn_engine* e, int rows, bool reduce, hipStream_t s, bool dx_only = false);
 int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_t s, bool need_rows = true);
 int ph_policy_l1(recnn_engine* e, hipStream_t s);
+int ph_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_out, hipStream_t s);
 int ph_finish(recnn_engine* e, int rows, bool ticked_value, bool ticked_policy, hipStream_t s);
 int value_apply(recnn_engine* e, bool soft, float grad_scale, hipStream_t s, int rows = 0);
 bool dwadam_ok(const recnn_engine* e, int rows);

@@ -120,6 +120,9 @@ int fill_apply_args(recnn_engine* e, int ni, const NetLayout& L, bool do_adam, i
 int apply_net(recnn_engine* e, int ni, int rows, bool do_adam, int opt_idx, float grad_scale, bool clip, int target_ni,
               float tau, hipStream_t s, bool from_slabs) {
   Net& n = e->net[ni];
+  // (recnn_engine_state_grads: this launch rewrites the shadow of `ni` -- the critic's serves both gradients, the actor's the policy loss's)
+  if (ni == RECNN_NET_VALUE1) e->sg_ok = 0;
+  else if (ni == RECNN_NET_POLICY) e->sg_ok &= ~2;
   NetLayout L = make_layout(e, ni, rows);
   ApplyArgs a;
   int rc = fill_apply_args(e, ni, L, do_adam, opt_idx, grad_scale, clip, target_ni, tau, &a);
@@ -1163,6 +1166,7 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
       const double fl = 2.0 * rows * ((double)H * H + (double)H * A + (double)A * H + (double)H * H);
       if ((rc = slot(e, "bwd_chain_policy", fl, s, [&] { return bwd_chain_launch(c, s); }))) return rc;
       chain_done = true;
+      e->dze1_ok = false;   // dz_e2 / dz_e1 stayed on chip (ph_state_grads makes them when it is asked for the policy loss's gradient)
     } else {
     // backward seed d = -1/B for every row: dz_e2 and dz_e1 in one row-panel launch, no critic parameter gradients
     BwdPanelBatch bb;
@@ -1195,6 +1199,7 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
     if ((rc = slot(e, "head_policy_loss", 0, s, [&] { return head_launch(h, s); }))) return rc;
   }
   if (!backward) return 0;
+  if (!chain_done) e->dze1_ok = true;
   Net& pn = e->net[POL];
   RECNN_REQUIRE(pn.g, "policy backward: the actor has no gradient arena bound");
   auto dx1 = [&](const char* nm, const void* Ain, int64_t lda, int Kc, int ni, int which, int N, void* C, int64_t ldc, const void* yref,
@@ -1223,6 +1228,46 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
   return slot(e, "grad_reduce_actor", 0, s, [&] { return grad_reduce_launch(L, g_produce(e, RECNN_NET_POLICY), with_l1 ? pn.l1part : nullptr, s); });
 }
 
+// The input gradient of the step (state_grad.hip; recnn_engine_state_grads): d loss / d state through layer 1.
+//   which 0: gV = dz_c1 * W1c[:, state columns]                                   (value loss; the critic the value backward used)
+//   which 1: gP = dz_e1 * W1c[:, state columns] + dz_p1 * W1a                     (policy loss; the updated critic, then the actor)
+// W comes from the compute-type SHADOWS: they hold exactly the numbers the forward and the backward multiplied with (bf16: the master
+// rounded to nearest even by the optimizer / refresh launch), they keep the pre-step critic until the refresh that follows the value
+// optimizer, and their rows are 16-byte aligned and zero padded whatever S is -- the master's rows (stride S + A floats) are not.
+int ph_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_out, hipStream_t s) {
+  const int A = e->A, H = e->H, S = e->S, V1 = RECNN_NET_VALUE1, POL = RECNN_NET_POLICY;
+  const Net& v = e->net[V1];
+  const Net& p = e->net[POL];
+  const int vec = 16 / e->esz;
+  RECNN_REQUIRE(A + ru(S, vec) <= v.ld_w1 && ru(S, vec) <= p.ld_w1, "state_grads: shadow rows shorter than the state columns");
+  int rc;
+  StateGradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = rows; a.S = S; a.K = H; a.out = out; a.ld_out = ld_out;
+  const char* w1c = sh_ptr(e, V1, W1) + tc_off(e, A);   // the shadow is rotated to [action | state]
+  if (which == 0) {
+    a.nseg = 1;
+    a.seg[0] = StateGradSeg{e->dzc1[0], e->Hp, w1c, v.ld_w1};
+    if (e->unit_bwd) a.row_scale = e->delta[0];         // the fused forward left UNIT tensors: the per-row seed d is applied here, as the dW launch does
+  } else {
+    if (!e->dze1_ok) {
+      // the row-panel chain kept the critic's dz on chip: the same two tensors from the same activations and weights, one row-panel launch
+      BwdPanelBatch bb;
+      memset(&bb, 0, sizeof(bb));
+      BwdPanelProb& b = bb.p[0];
+      b.rows = rows; b.H = H; b.mode = 1; b.delta_const = -1.0f / (float)rows;
+      b.h2 = e->pc.h2; b.ldh = e->Hp; b.w3 = v.p + v.off[W3]; b.scale = e->cfg.mask_mode != RECNN_MASK_NONE ? 2.0f : 1.0f;
+      b.dz2 = e->dze2; b.W2 = sh_ptr(e, V1, W2); b.ldw2 = v.ld_w2; b.h1 = e->pc.h1; b.dz1 = e->dze1;
+      if ((rc = slot(e, "head_dx_pcritic", 2.0 * rows * (double)H * H, s, [&] { return bwd_panel_launch(bb, 1, s); }))) return rc;
+      e->dze1_ok = true;
+    }
+    a.nseg = 2;
+    a.seg[0] = StateGradSeg{e->dze1, e->Hp, w1c, v.ld_w1};
+    a.seg[1] = StateGradSeg{e->dzp1, e->Hp, sh_ptr(e, POL, W1), p.ld_w1};
+  }
+  return slot(e, which ? "state_grad_policy" : "state_grad_value", 2.0 * rows * (double)S * H * a.nseg, s,
+              [&] { return state_grad_launch(a, e->cfg.dtype, s); });
+}
 
 int ph_finish(recnn_engine* e, int rows, bool ticked_value, bool ticked_policy, hipStream_t s) {
   if (e->run_off >= 0 && e->run_off < LOSS_HIST_MAX) e->hist_half[e->run_off] = e->half_panels;
@@ -1688,6 +1733,7 @@ int net_allreduce(recnn_engine* e, int ni, const char* name, hipStream_t s) {
 int step_impl(recnn_engine* e, int rows, bool learn, bool policy_step, hipStream_t s, bool pregathered, bool gather_next,
               bool defer_policy_fwd, bool frozen_done) {
   int rc;
+  e->sg_ok = 0;   // (recnn_engine_state_grads belongs to the phase API: a whole step leaves nothing it may read)
   if (!pregathered && (rc = stage_batch(e, rows, s))) return rc;
   // Split bf16 with the fused dW + optimizer launch: that launch (147 KB of LDS per workgroup) cannot carry the look-ahead gather the
   // way apply_gather_kernel does, so the critic HEAD launch does -- armed here, consumed inside ph_forward (if no head launch takes it,

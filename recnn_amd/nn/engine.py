@@ -321,6 +321,16 @@ class StepEngine:
     def policy_apply(self, soft: bool, grad_scale: float = 1.0):
         L.call("recnn_engine_policy_apply", self.handle, int(soft), float(grad_scale), self._stream())
 
+    def state_grads(self, rows: int, which: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """d loss / d state of the phase that just ran (`recnn_engine_state_grads`): which = 0 the value loss's (right after
+        `value_grads(learn=True)`, before the critic is stepped or refreshed), 1 the policy loss's (right after
+        `policy_grads(backward=True)`).  Returns fp32 [rows, S]; `out` (fp32, last stride 1) is written in place."""
+        if out is None:
+            out = torch.empty(rows, self.S, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.stride(-1) == 1 and out.shape[0] >= rows
+        L.call("recnn_engine_state_grads", self.handle, rows, int(which), L.ptr(out), out.stride(0), self._stream())
+        return out
+
     def finish(self, rows: int, value_stepped: bool, policy_stepped: bool):
         L.call("recnn_engine_finish", self.handle, rows, int(value_stepped), int(policy_stepped), self._stream())
 

@@ -182,6 +182,14 @@ class FusedContext:
                 self.versions[ni] = cur
                 self.dirty.discard(id(m))
 
+    def refresh_stepped(self, ni):
+        """An optimizer outside the engine just stepped network `ni` in place: re-derive its shadow now (the next phase reads it)
+        and take the new version counters as seen, so that `_sync_versions` does not refresh it a second time."""
+        self.engine.refresh(ni)
+        m = self.modules[ni]
+        self.versions[ni] = [p._version for p in _module_params(m)]
+        self.dirty.discard(id(m))
+
     def mark_stepped(self, nis):
         """The engine just wrote the parameters of networks `nis` from its kernels (optimizer step / soft update): tell the
         module-level forward path, whose derived weight layouts (`functional._derived_of`) are keyed on version counters the

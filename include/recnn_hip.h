@@ -449,23 +449,28 @@ int recnn_engine_value_grads(recnn_engine* e, int rows, int learn, void* stream)
 int recnn_engine_value_apply(recnn_engine* e, int soft, float grad_scale, void* stream);
 int recnn_engine_policy_grads(recnn_engine* e, int rows, int backward, void* stream);
 int recnn_engine_policy_apply(recnn_engine* e, int soft, float grad_scale, void* stream);
-/* The input gradient of a DDPG step: d loss / d state, what value_loss.backward() and policy_loss.backward() send into `state` when it
- * is attached to a graph (an LSTM state encoder in front: recnn/nn/update/ddpg.py:58-104, misc.py:25-44).  One launch
- * (csrc/state_grad.hip) writes out[rows, state_dim] (fp32, row stride ld_out >= state_dim; columns past state_dim are not touched):
- *   which 0 (value loss) : gV = dz_c1 * W1c[:, state columns]
- *                          valid after recnn_engine_value_grads(.., learn = 1) and BEFORE the value optimizer is applied or the critic
- *                          refreshed: W1c is the critic the value backward used.
- *   which 1 (policy loss): gP = dz_e1 * W1c[:, state columns] + dz_p1 * W1a    (the raw gradient: neither clipped nor sign-flipped)
+/* The input gradient of a DDPG / TD3 step: d loss / d state, what the value losses' and the policy loss's backward() send into `state`
+ * when it is attached to a graph (an LSTM state encoder in front: recnn/nn/update/ddpg.py:58-104, td3.py:95-132, misc.py:25-44).  One
+ * launch (csrc/state_grad.hip) writes out[rows, state_dim] (fp32, row stride ld_out >= state_dim; columns past state_dim are not touched):
+ *   which 0 (value loss [1]): gV1 = dz_c1[0] * W1c1[:, state columns]
+ *                          valid after recnn_engine_value_grads(.., learn = 1) and BEFORE a value optimizer is applied or a critic
+ *                          refreshed: W1c1 is the critic the value backward used.
+ *   which 1 (policy loss): gP = dz_e1 * W1c1[:, state columns] + dz_p1 * W1a   (the raw gradient: neither clipped nor sign-flipped)
  *                          valid after recnn_engine_policy_grads(.., backward = 1) and before either network is applied or refreshed:
- *                          W1c is the UPDATED critic the policy loss went through.
+ *                          W1c1 is the UPDATED critic (TD3: critic 1) the policy loss went through.
+ *   which 2 (TD3, value loss 2): gV2 = dz_c1[1] * W1c2[:, state columns]        valid as which 0, critic 2 as the value backward used it
+ *   which 3 (TD3, value losses 1 + 2): gV1 + gV2 in ONE launch, two contraction segments, critic 1 first -- what a single backward
+ *                          through the encoder needs (the encoder's backward is linear in the gradient it is handed).  Valid as which 0.
  * The dz are the layer-1 pre-activation gradients of the phase (dropout's mask and scale folded in), the weights the compute-type
  * values the phase multiplied with (bf16 engines: the master rounded to nearest even); fp32 engines multiply on the exact-fp32 MFMA,
- * bf16 engines on the bf16 MFMA with fp32 accumulation.  The contraction runs in a fixed order inside one workgroup per output tile
- * (no atomics, no split-K): two calls give the same bits.  Anything else in between (a step, a graph replay, another phase) makes the
- * call return RECNN_E_STATE.  DDPG engines of type RECNN_F32 / RECNN_BF16 only: a TD3 or RECNN_BF16X3 engine gets RECNN_E_UNSUPPORTED.
- * Not part of recnn_engine_step or of any graph. */
-int recnn_engine_state_grads(recnn_engine* e, int rows, int which /* 0 value loss, 1 policy loss */, float* out, int64_t ld_out,
-                             void* stream);
+ * bf16 engines on the bf16 MFMA with fp32 accumulation; where the fused bf16 forward left unit backward tensors, each critic's per-row
+ * seed multiplies its segment's fp32 accumulator.  The contraction runs in a fixed order inside one workgroup per output tile
+ * (no atomics, no split-K): two calls give the same bits.  Anything else in between (a step, a graph replay, another phase, an apply
+ * or refresh of EITHER critic for which 0 / 2 / 3) makes the call return RECNN_E_STATE.  RECNN_F32 / RECNN_BF16 engines only: a
+ * RECNN_BF16X3 engine, and which 2 / 3 on a DDPG engine, get RECNN_E_UNSUPPORTED.  Not part of recnn_engine_step or of any graph.
+ * recnn_engine_buffer names "critic2_dz2" / "critic2_dz1" are critic 2's backward tensors (TD3 engines). */
+int recnn_engine_state_grads(recnn_engine* e, int rows, int which /* 0 value loss, 1 policy loss; TD3: 2 value loss 2, 3 both */,
+                             float* out, int64_t ld_out, void* stream);
 /* the same pieces for callers that run their own optimizer: */
 int recnn_engine_clip_policy_grads(recnn_engine* e, float grad_scale, void* stream);  /* g *= coef */
 int recnn_engine_soft_update(recnn_engine* e, int net, int target_net, float tau, void* stream);

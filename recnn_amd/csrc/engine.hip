@@ -450,14 +450,28 @@ extern "C" int recnn_engine_policy_grads(recnn_engine* e, int rows, int backward
 extern "C" int recnn_engine_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_out, void* stream) {
   RECNN_REQUIRE(e, "state_grads: null engine");
   RECNN_REQUIRE(out, "state_grads: null output");
-  RECNN_REQUIRE(which == 0 || which == 1, "state_grads: which must be 0 (value loss) or 1 (policy loss)");
+  RECNN_REQUIRE(which >= 0 && which <= 3, "state_grads: which must be 0 (value loss), 1 (policy loss) or, on a TD3 engine, 2 (value loss 2) or "
+                                          "3 (value losses 1 + 2); got %d", which);
   RECNN_REQUIRE(rows > 0 && rows <= e->cfg.max_rows, "state_grads: rows=%d outside [1, %d]", rows, e->cfg.max_rows);
   RECNN_REQUIRE(ld_out >= e->S, "state_grads: ld_out=%lld is smaller than state_dim=%d", (long long)ld_out, e->S);
-  if (e->td3) { recnn_set_error("state_grads: DDPG only -- this is a TD3 engine (its update takes no gradient into the state)"); return RECNN_E_UNSUPPORTED; }
+  if (!e->td3 && which >= 2) {
+    recnn_set_error("state_grads: which=%d (value loss 2 / value losses 1 + 2) is TD3 only -- this is a DDPG engine, it has one critic", which);
+    return RECNN_E_UNSUPPORTED;
+  }
   if (e->x3) { recnn_set_error("state_grads: the split-bf16 compute type (bf16x3) is not supported; use fp32 or bf16"); return RECNN_E_UNSUPPORTED; }
-  if (!(e->sg_ok & (1 << which))) {
-    recnn_set_error(which ? "state_grads: which=1 needs recnn_engine_policy_grads(backward=1) right before it (no optimizer apply / refresh in between)"
-                          : "state_grads: which=0 needs recnn_engine_value_grads(learn=1) right before it, before the value optimizer is applied or refreshed");
+  const int bit = which == 1 ? 2 : 1;   // bit 0: the value losses' dz_c1 next to the pre-step critic(s); bit 1: the policy phase
+  if (!(e->sg_ok & bit)) {
+    if (e->td3) {
+      if (which == 1)
+        recnn_set_error("state_grads (TD3 engine): which=1 needs recnn_engine_policy_grads(backward=1) right before it (no optimizer apply / "
+                        "refresh in between)");
+      else
+        recnn_set_error("state_grads (TD3 engine): which=%d needs recnn_engine_value_grads(learn=1) right before it, before either value "
+                        "optimizer is applied or refreshed", which);
+    } else {
+      recnn_set_error(which ? "state_grads: which=1 needs recnn_engine_policy_grads(backward=1) right before it (no optimizer apply / refresh in between)"
+                            : "state_grads: which=0 needs recnn_engine_value_grads(learn=1) right before it, before the value optimizer is applied or refreshed");
+    }
     return RECNN_E_STATE;
   }
   return ph_state_grads(e, rows, which, out, ld_out, (hipStream_t)stream);
@@ -541,6 +555,7 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
       {"critic1_h1", e->cv[0].h1, e->H, Hp, 0},    {"critic1_h2", e->cv[0].h2, e->H, Hp, 0},
       {"actor_h1", e->pa.h1, e->H, Hp, 0},         {"actor_h2", e->pa.h2, e->H, Hp, 0},
       {"critic1_dz2", e->dzc2[0], e->H, Hp, 0},    {"critic1_dz1", e->dzc1[0], e->H, Hp, 0},
+      {"critic2_dz2", e->dzc2[1], e->H, Hp, 0},    {"critic2_dz1", e->dzc1[1], e->H, Hp, 0},   // (TD3; NULL on a DDPG engine)
       {"dact", e->dag, e->A, e->Ap, 0},
       {"pc_h1", e->pc.h1, e->H, Hp, 0},            {"pc_h2", e->pc.h2, e->H, Hp, 0},
       {"dze2", e->dze2, e->H, Hp, 0},              {"dze1", e->dze1, e->H, Hp, 0},

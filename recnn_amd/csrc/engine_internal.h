@@ -143,9 +143,9 @@ struct recnn_engine {
                                            // partials are HALF-panel sums, consumed in pairs (TensorSeg.pair, LossFinalizeArgs.pair)
   bool hist_half[LOSS_HIST_MAX] = {};      // ... per step of the run being captured (loss history)
   // recnn_engine_state_grads: what the backward buffers and weight shadows still hold.  Bit 0: the value loss's dz_c1 next to the critic the
-  // value backward used (set by recnn_engine_value_grads with learn); bit 1: the policy loss's dz_e1 / dz_p1 next to the critic and actor
-  // ph_policy used (set by recnn_engine_policy_grads with backward).  Cleared by whatever overwrites either: a step, a graph replay, an
-  // optimizer apply or a shadow refresh of the network.
+  // value backward used -- TD3: both critics' (which 0, 2, 3) -- (set by recnn_engine_value_grads with learn); bit 1: the policy loss's
+  // dz_e1 / dz_p1 next to the critic and actor ph_policy used (set by recnn_engine_policy_grads with backward).  Cleared by whatever
+  // overwrites either: a step, a graph replay, an optimizer apply or a shadow refresh of the network (bit 0: of either critic).
   int sg_ok = 0;
   bool dze1_ok = false;                    // the last ph_policy backward left dz_e1 in memory (the row-panel chain keeps it on chip)
   float* pl_part;                          // policy loss: per-wave partial dots of the policy-critic's layer-2 GEMM

@@ -122,6 +122,7 @@ int apply_net(recnn_engine* e, int ni, int rows, bool do_adam, int opt_idx, floa
   Net& n = e->net[ni];
   // (recnn_engine_state_grads: this launch rewrites the shadow of `ni` -- the critic's serves both gradients, the actor's the policy loss's)
   if (ni == RECNN_NET_VALUE1) e->sg_ok = 0;
+  else if (ni == RECNN_NET_VALUE2) e->sg_ok &= ~1;   // (TD3: critic 2 serves the value losses' gradient only)
   else if (ni == RECNN_NET_POLICY) e->sg_ok &= ~2;
   NetLayout L = make_layout(e, ni, rows);
   ApplyArgs a;
@@ -1229,26 +1230,42 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
 }
 
 // The input gradient of the step (state_grad.hip; recnn_engine_state_grads): d loss / d state through layer 1.
-//   which 0: gV = dz_c1 * W1c[:, state columns]                                   (value loss; the critic the value backward used)
-//   which 1: gP = dz_e1 * W1c[:, state columns] + dz_p1 * W1a                     (policy loss; the updated critic, then the actor)
+//   which 0: gV1 = dz_c1[0] * W1c1[:, state columns]                              (value loss 1; the critic the value backward used)
+//   which 1: gP  = dz_e1 * W1c1[:, state columns] + dz_p1 * W1a                   (policy loss; the updated critic 1, then the actor)
+//   which 2: gV2 = dz_c1[1] * W1c2[:, state columns]                              (TD3: value loss 2, critic 2 likewise)
+//   which 3: gV1 + gV2 in one launch, two segments, critic 1 first                (TD3: what one backward through the encoder needs)
 // W comes from the compute-type SHADOWS: they hold exactly the numbers the forward and the backward multiplied with (bf16: the master
 // rounded to nearest even by the optimizer / refresh launch), they keep the pre-step critic until the refresh that follows the value
 // optimizer, and their rows are 16-byte aligned and zero padded whatever S is -- the master's rows (stride S + A floats) are not.
+// Where the fused forward left UNIT tensors, each critic's segment carries its own per-row seed (delta[c]), as its dW launch does.
 int ph_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_out, hipStream_t s) {
   const int A = e->A, H = e->H, S = e->S, V1 = RECNN_NET_VALUE1, POL = RECNN_NET_POLICY;
+  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2};
   const Net& v = e->net[V1];
   const Net& p = e->net[POL];
   const int vec = 16 / e->esz;
   RECNN_REQUIRE(A + ru(S, vec) <= v.ld_w1 && ru(S, vec) <= p.ld_w1, "state_grads: shadow rows shorter than the state columns");
+  RECNN_REQUIRE(which == 0 || which == 1 || e->n_critic == 2, "state_grads: which=%d needs the second critic", which);
   int rc;
   StateGradArgs a;
   memset(&a, 0, sizeof(a));
   a.rows = rows; a.S = S; a.K = H; a.out = out; a.ld_out = ld_out;
   const char* w1c = sh_ptr(e, V1, W1) + tc_off(e, A);   // the shadow is rotated to [action | state]
-  if (which == 0) {
+  // critic c's value-loss segment; the fused forward left UNIT tensors: the per-row seed d is applied in the launch, as the dW launch does
+  auto value_seg = [&](int c) {
+    const Net& vc = e->net[VAL[c]];
+    return StateGradSeg{e->dzc1[c], e->Hp, sh_ptr(e, VAL[c], W1) + tc_off(e, A), vc.ld_w1, e->unit_bwd ? e->delta[c] : nullptr};
+  };
+  const char* name = "state_grad_value";
+  if (which == 0 || which == 2) {
     a.nseg = 1;
-    a.seg[0] = StateGradSeg{e->dzc1[0], e->Hp, w1c, v.ld_w1};
-    if (e->unit_bwd) a.row_scale = e->delta[0];         // the fused forward left UNIT tensors: the per-row seed d is applied here, as the dW launch does
+    a.seg[0] = value_seg(which / 2);
+  } else if (which == 3) {
+    RECNN_REQUIRE(A + ru(S, vec) <= e->net[VAL[1]].ld_w1, "state_grads: shadow rows shorter than the state columns");
+    a.nseg = 2;
+    a.seg[0] = value_seg(0);
+    a.seg[1] = value_seg(1);
+    name = "state_grad_value12";
   } else {
     if (!e->dze1_ok) {
       // the row-panel chain kept the critic's dz on chip: the same two tensors from the same activations and weights, one row-panel launch
@@ -1262,11 +1279,11 @@ int ph_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_
       e->dze1_ok = true;
     }
     a.nseg = 2;
-    a.seg[0] = StateGradSeg{e->dze1, e->Hp, w1c, v.ld_w1};
-    a.seg[1] = StateGradSeg{e->dzp1, e->Hp, sh_ptr(e, POL, W1), p.ld_w1};
+    a.seg[0] = StateGradSeg{e->dze1, e->Hp, w1c, v.ld_w1, nullptr};
+    a.seg[1] = StateGradSeg{e->dzp1, e->Hp, sh_ptr(e, POL, W1), p.ld_w1, nullptr};
+    name = "state_grad_policy";
   }
-  return slot(e, which ? "state_grad_policy" : "state_grad_value", 2.0 * rows * (double)S * H * a.nseg, s,
-              [&] { return state_grad_launch(a, e->cfg.dtype, s); });
+  return slot(e, name, 2.0 * rows * (double)S * H * a.nseg, s, [&] { return state_grad_launch(a, e->cfg.dtype, s); });
 }
 
 int ph_finish(recnn_engine* e, int rows, bool ticked_value, bool ticked_policy, hipStream_t s) {

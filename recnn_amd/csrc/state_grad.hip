@@ -1,5 +1,5 @@
-// state_grad.hip -- the input gradient of the DDPG step: d loss / d state through layer 1 of the critic and the actor
-// (recnn/nn/update/ddpg.py:58-104: value_loss.backward() and policy_loss.backward() both reach `state`).
+// state_grad.hip -- the input gradient of the DDPG / TD3 step: d loss / d state through layer 1 of the critic(s) and the actor
+// (recnn/nn/update/ddpg.py:58-104, td3.py:95-132: the value losses' and the policy loss's backward reach `state`).
 //
 //   out[rows, S] (fp32) = sum_seg dz_seg[rows, K] * W_seg[K, S]
 //
@@ -11,6 +11,13 @@
 // [action | state], row stride a multiple of 128 elements, zero padded): every 16-byte chunk of either operand is aligned and lies
 // inside its row's allocation, also the last chunk of an S that is no multiple of the chunk (S = 1290, S = 27); what such a chunk
 // holds past column S only reaches output columns >= S, which are never stored.  Rows >= rows and k >= K are predicated off (zeros).
+//
+// Seeds.  A segment may carry an fp32 [rows] seed d (the fused bf16 path leaves UNIT backward tensors u = dz / d): its part of the
+// sum is d[r] * (u[r, :] * W).  One segment: the seed multiplies the accumulator in the epilogue.  Two segments of which any carries a
+// seed (FOLD; TD3's merged twin-critic gradient d1 (u1 W1c1) + d2 (u2 W1c2)): the accumulator tile is folded into a second tile at
+// each segment's last stage -- total = acc * d for segment 0 (assigned), total = fma(acc, d, total) for segment 1 -- and cleared.
+// Either way the seed meets the fp32 accumulator, never the bf16 operand (d u rounded to bf16 would cost 2^-9 per term).  The
+// launches without a fold are a separate instantiation: their instruction sequence does not know about the second tile.
 //
 // The weights go in as the MFMA's first operand, so a lane ends up with four neighbouring columns of one output row:
 //   fp32  v_mfma_f32_16x16x4_f32  : lane (fr, fg) supplies W[k = 4 fg + e][n = fr] and dz[m = fr][k = 4 fg + e], e = 0..3 per 16 k
@@ -39,7 +46,7 @@ template <> struct SgTraits<bf16_t> {
   static constexpr int PB = SG_BN * 2 + 16;      // (the pitch of x3.hip's transpose-read image)
 };
 
-template <class T>
+template <class T, bool FOLD>
 __global__ __launch_bounds__(256) void state_grad_kernel(const StateGradArgs a) {
   using TR = SgTraits<T>;
   constexpr int VEC = TR::VEC, PA = TR::PA, PB = TR::PB;
@@ -89,6 +96,7 @@ __global__ __launch_bounds__(256) void state_grad_kernel(const StateGradArgs a) 
 
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 acc[2][2] = {{zero4, zero4}, {zero4, zero4}};
+  [[maybe_unused]] f32x4 total[2][2] = {{zero4, zero4}, {zero4, zero4}};   // FOLD only: the sum of the folded segments
   if (nt > 0) {
     fetch(0);
     put(0);
@@ -129,23 +137,42 @@ __global__ __launch_bounds__(256) void state_grad_kernel(const StateGradArgs a) 
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bv[tn], av[tm], acc[tm][tn], 0, 0, 0);
     }
+    if constexpr (FOLD) {
+      const int sg = t / nk;
+      if (t + 1 == (sg + 1) * nk) {   // the segment's last stage (uniform over the workgroup): fold its tile, seeded per row
+        const float* d = a.seg[sg].scale;
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+          const int m = m0 + wm0 + tm * 16 + fr;
+          const float sc = (d && m < a.rows) ? d[m] : 1.0f;
+#pragma unroll
+          for (int tn = 0; tn < 2; ++tn) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) total[tm][tn][i] = sg == 0 ? acc[tm][tn][i] * sc : __builtin_fmaf(acc[tm][tn][i], sc, total[tm][tn][i]);
+            acc[tm][tn] = zero4;
+          }
+        }
+      }
+    }
     if (t + 1 < nt) put(buf ^ 1);
     __syncthreads();
   }
 
-  // ---- epilogue: optional per-row seed, masked fp32 store (16 bytes per lane where the row allows it)
+  // ---- epilogue: optional per-row seed (one segment; a fold has applied its seeds already), masked fp32 store (16 bytes per lane
+  // where the row allows it)
+  const float* row_scale = FOLD ? nullptr : a.seg[0].scale;
   const bool vec_ok = (a.ld_out & 3) == 0 && (((uintptr_t)a.out) & 15) == 0;
 #pragma unroll
   for (int tm = 0; tm < 2; ++tm) {
     const int m = m0 + wm0 + tm * 16 + fr;
     if (m >= a.rows) continue;
-    const float sc = a.row_scale ? a.row_scale[m] : 1.0f;
+    const float sc = row_scale ? row_scale[m] : 1.0f;
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
       const int n = n0 + wn0 + tn * 16 + 4 * fg;
       if (n >= a.S) continue;
-      f32x4 v = acc[tm][tn];
-      if (a.row_scale) v *= sc;
+      f32x4 v = FOLD ? total[tm][tn] : acc[tm][tn];
+      if (row_scale) v *= sc;
       float* o = a.out + (int64_t)m * a.ld_out + n;
       if (vec_ok && n + 3 < a.S) {
         *(f32x4*)o = v;
@@ -164,7 +191,6 @@ int state_grad_launch(const StateGradArgs& a, int dtype, hipStream_t s) {
   RECNN_REQUIRE(dtype == RECNN_F32 || dtype == RECNN_BF16, "state_grad: compute type %d is not supported (fp32 and bf16 are)", dtype);
   RECNN_REQUIRE(a.rows > 0 && a.S > 0 && a.K > 0 && a.K % 8 == 0, "state_grad: need rows > 0, S > 0, K a positive multiple of 8");
   RECNN_REQUIRE(a.nseg == 1 || a.nseg == 2, "state_grad: 1 or 2 segments");
-  RECNN_REQUIRE(!a.row_scale || a.nseg == 1, "state_grad: a per-row seed goes with one segment");
   RECNN_REQUIRE(a.out && a.ld_out >= a.S, "state_grad: bad output");
   const int vec = dtype == RECNN_F32 ? 4 : 8;
   for (int i = 0; i < a.nseg; ++i) {
@@ -176,7 +202,14 @@ int state_grad_launch(const StateGradArgs& a, int dtype, hipStream_t s) {
   }
   const int64_t tiles = (int64_t)((a.rows + SG_BM - 1) / SG_BM) * ((a.S + SG_BN - 1) / SG_BN);
   RECNN_REQUIRE(tiles < (1 << 30), "state_grad: too many tiles");
-  if (dtype == RECNN_F32) hipLaunchKernelGGL(state_grad_kernel<float>, dim3((unsigned)tiles), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(state_grad_kernel<bf16_t>, dim3((unsigned)tiles), dim3(256), 0, s, a);
+  // (a seed on a segment the launch does not have is ignored; one segment never folds: its seed is the epilogue's)
+  const bool fold = a.nseg == 2 && (a.seg[0].scale || a.seg[1].scale);
+  if (dtype == RECNN_F32) {
+    if (fold) hipLaunchKernelGGL((state_grad_kernel<float, true>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((state_grad_kernel<float, false>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+  } else {
+    if (fold) hipLaunchKernelGGL((state_grad_kernel<bf16_t, true>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((state_grad_kernel<bf16_t, false>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+  }
   return recnn_check_hip(hipGetLastError(), "state_grad launch");
 }

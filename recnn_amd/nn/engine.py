@@ -322,9 +322,10 @@ class StepEngine:
         L.call("recnn_engine_policy_apply", self.handle, int(soft), float(grad_scale), self._stream())
 
     def state_grads(self, rows: int, which: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """d loss / d state of the phase that just ran (`recnn_engine_state_grads`): which = 0 the value loss's (right after
-        `value_grads(learn=True)`, before the critic is stepped or refreshed), 1 the policy loss's (right after
-        `policy_grads(backward=True)`).  Returns fp32 [rows, S]; `out` (fp32, last stride 1) is written in place."""
+        """d loss / d state of the phase that just ran (`recnn_engine_state_grads`): which = 0 the value loss's (TD3: value loss 1's;
+        right after `value_grads(learn=True)`, before a critic is stepped or refreshed), 1 the policy loss's (right after
+        `policy_grads(backward=True)`; through the updated critic 1 and the actor), and on a TD3 engine 2 value loss 2's and 3 the sum
+        of both value losses' in one launch (valid as 0).  Returns fp32 [rows, S]; `out` (fp32, last stride 1) is written in place."""
         if out is None:
             out = torch.empty(rows, self.S, dtype=torch.float32, device=self.device)
         assert out.dtype == torch.float32 and out.stride(-1) == 1 and out.shape[0] >= rows
@@ -419,7 +420,7 @@ class StepEngine:
             t = t[:, col].float() + t[:, col + 32].float()
         else:
             t = t[:, :c.value].float().clone()
-        if name in ("critic1_dz2", "critic1_dz1") and self.lib.recnn_engine_unit_backward(self.handle):
+        if name in ("critic1_dz2", "critic1_dz1", "critic2_dz2", "critic2_dz1") and self.lib.recnn_engine_unit_backward(self.handle):
             # the fused bf16 path stores dz / d (unit backward tensors); the per-row seed d is applied inside the dW launch
-            t *= self.buffer("delta1", rows).reshape(rows, 1)
+            t *= self.buffer("delta" + name[6], rows).reshape(rows, 1)
         return t

@@ -480,7 +480,7 @@ int recnn_engine_finish(recnn_engine* e, int rows, int value_stepped, int policy
 
 /* Capture `recnn_engine_step` for a fixed row count into hipGraphs -- one ordinary step, one policy step, and a family
  * of RUN graphs (k ordinary steps; a policy step + k ordinary steps, k < policy_every; whole policy cycles up to 64
- * steps, see tuning.graph_run) -- and replay `n_steps` consecutive steps starting at `first_step`: ANY
+ * steps, see tuning.graph_run; with tuning.run_align also whole cycles that start right AFTER a policy step) -- and replay `n_steps` consecutive steps starting at `first_step`: ANY
  * (first_step, n_steps) is covered with at most n_steps / policy_every + 2 graph launches (policy_every <= 17; longer
  * cycles compose power-of-two stretches).  Inside a run graph the device counters are ticked once at its end, the sampler + gather of step t+1 and the policy-loss forward of step t ride on
  * other launches (tuning.pregather, tuning.defer_policy_fwd), and every step's losses land in the history ring
@@ -491,6 +491,35 @@ int recnn_engine_graph_run(recnn_engine* e, int first_step, int n_steps, void* s
  * to first_step modulo policy_every; recnn_engine_graph_run then serves such requests with ONE graph launch instead of
  * composing them from the family.  Up to 4 are kept (oldest replaced); dropped with the other graphs. */
 int recnn_engine_graph_prepare(recnn_engine* e, int first_step, int n_steps, void* stream);
+
+/* How recnn_engine_graph_run composes a request from the run-graph family (host arithmetic only: no GPU, no engine).
+ * recnn_run_family_init describes the family recnn_engine_graph_build captures for (policy_every, tuning.graph_run, tuning.run_align);
+ * recnn_run_plan cuts [first_step, first_step + n_steps) into pieces (kind, length) of that family, in order:
+ *   align = 0  [ordinary stretch up to the next policy step] [multi-cycle graphs] [policy step + the rest of its cycle] ... [policy step + tail]
+ *   align = 1  when the largest aligned graph fits behind the next policy step: [ordinary stretch] [that policy step alone]
+ *              [aligned multi-cycle graphs] [aligned single cycles], then the pieces of align = 0 for what is left
+ * Returns the number of pieces; at most `cap` of them are written (a caller with a short buffer plans again from where they end: the
+ * composition of a remainder depends on nothing before it).  < 0: bad arguments. */
+#define RECNN_RUN_MAX 64
+enum {
+  RECNN_RUN_STEP = 0,           /* one ordinary step */
+  RECNN_RUN_POLICY_STEP = 1,    /* one policy step */
+  RECNN_RUN_ORDINARY = 2,       /* len ordinary steps (len >= 2) */
+  RECNN_RUN_POLICY_HEAD = 3,    /* a policy step + len - 1 ordinary steps */
+  RECNN_RUN_MULTI = 4,          /* whole cycles, starts ON a policy step */
+  RECNN_RUN_ALIGNED_MULTI = 5,  /* whole cycles, starts right AFTER a policy step and ends on one */
+  RECNN_RUN_ALIGNED_CYCLE = 6   /* one such cycle */
+};
+typedef struct recnn_run_family {
+  unsigned char has_o[RECNN_RUN_MAX + 1];   /* has_o[k]: the graph of k ordinary steps exists (k >= 2) */
+  unsigned char has_p[RECNN_RUN_MAX + 1];   /* has_p[k]: the graph of a policy step + k ordinary steps exists (k >= 1) */
+  int multi_len;                            /* steps of the multi-cycle graph (0: none) */
+  int aligned_multi_len;                    /* steps of the aligned multi-cycle graph (0: none) */
+  int aligned_cycle_len;                    /* policy_every when the aligned single cycle exists, else 0 */
+} recnn_run_family;
+int recnn_run_family_init(int policy_every, int graph_run, int align, recnn_run_family* h_out);
+int recnn_run_plan(int policy_every, const recnn_run_family* h_family, int first_step, int n_steps, int align, int* h_kinds, int* h_lens,
+                   int cap);
 
 /* Runs n_steps eager steps with a hipEvent pair around every kernel launch and returns, per
  * launch slot, the average device time in milliseconds (h_ms[i]), its name (h_names[i], static
@@ -612,7 +641,14 @@ typedef struct recnn_engine_tuning {
                                cycle gather writes state rows, action rows and the ten next ratings only, and the target networks' layer 1 reads s'
                                as shifted windows of those (csrc/mlpf.hip: up to four contraction segments); the packed next rows of the cycle are
                                then not allocated.  0: the gather also writes a next_state row per transition.  Bit-identical */
-  int reserved[3];
+  int run_align;            /* 1 (default): recnn_engine_graph_build also captures run graphs that START right after a policy step and END on
+                               one (whole cycles: every cycle segment ends on its policy step, none is a lone step), and
+                               recnn_engine_graph_run composes long requests from them (recnn_run_plan); 0: the family that starts on a
+                               policy step only.  Bit-identical */
+  int frozen_acts_policy_only;  /* 1 (default): the cycle-batched actor launch (csrc/mlpf.hip) stores its hidden activations only for the
+                               batch that reads them -- the policy step's, a segment's last -- and for none in a segment without a policy
+                               step; 0: for every batch of the segment.  Bit-identical */
+  int reserved[1];
 } recnn_engine_tuning;
 void recnn_engine_tuning_init(recnn_engine_tuning* h_t);
 int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* h_t);
@@ -632,7 +668,8 @@ int recnn_engine_read_losses(recnn_engine* e, float* h_out, void* stream);
 int recnn_engine_unit_backward(recnn_engine* e);
 /* Debug / test access to intermediate device buffers by name
  * ("next_action", "expected", "q1", "gen_action", ...).  Returns NULL if unknown.  Cycle mode's arrays (MSET_MAX x max_rows rows each):
- * "cycle_gen_action", "cycle_target_q1" / "2", "cycle_next_action0" / "1" (the target actor's output of window mode, per copy) and
+ * "cycle_gen_action", "cycle_actor_h1" / "cycle_actor_h2" (the actor's hidden activations: with tuning.frozen_acts_policy_only only the
+ * policy step's batch of a batched segment is written), "cycle_target_q1" / "2", "cycle_next_action0" / "1" (the target actor's output of window mode, per copy) and
  * "cycle_xn0" / "1" (the packed next rows whose action slot holds it otherwise: the engine's own allocation, NULL while it has none). */
 const void* recnn_engine_buffer(recnn_engine* e, const char* name, int64_t* h_rows, int64_t* h_cols,
                                 int64_t* h_ld, int* h_is_f32);

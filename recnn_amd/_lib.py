@@ -104,12 +104,22 @@ class Sampler(C.Structure):
 TUNING_FIELDS = ("fused_mlp", "chain_target_critic", "bwd_panel", "policy_chain", "split_fwd", "cycle_min_len", "cycle_min_seg",
                  "frozen_fused", "frozen_gemm", "graph_run", "pregather", "defer_policy_fwd", "sampler_f32_rows", "dw_splits", "comm_fused",
                  "l1_big", "gemm_variant", "gemm_v0_threshold", "gemm_dma", "gemm_dma_depth", "gemm_dma_waves", "gemm_waves", "dw_dma", "x3_tail", "x3_fwd", "dw_fuse", "tail_half", "l1_ws", "frozen_half",
-                 "frozen_window")
+                 "frozen_window", "run_align", "frozen_acts_policy_only")
+
+
+RUN_MAX = 64
+RUN_STEP, RUN_POLICY_STEP, RUN_ORDINARY, RUN_POLICY_HEAD, RUN_MULTI, RUN_ALIGNED_MULTI, RUN_ALIGNED_CYCLE = range(7)
+
+
+class RunFamily(C.Structure):
+    """include/recnn_hip.h recnn_run_family: which run graphs recnn_engine_graph_build captures."""
+    _fields_ = [("has_o", C.c_ubyte * (RUN_MAX + 1)), ("has_p", C.c_ubyte * (RUN_MAX + 1)), ("multi_len", C.c_int),
+                ("aligned_multi_len", C.c_int), ("aligned_cycle_len", C.c_int)]
 
 
 class EngineTuning(C.Structure):
     """include/recnn_hip.h recnn_engine_tuning: schedule / tile choices of ONE engine (all compute the same numbers)."""
-    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS] + [("reserved", C.c_int * 3)]
+    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS] + [("reserved", C.c_int * 1)]
 
 
 _P = C.c_void_p
@@ -188,6 +198,8 @@ SIGNATURES = {
     "recnn_engine_graph_build": (_I, [_P, _I, _P]),
     "recnn_engine_graph_run": (_I, [_P, _I, _I, _P]),
     "recnn_engine_graph_prepare": (_I, [_P, _I, _I, _P]),
+    "recnn_run_family_init": (_I, [_I, _I, _I, _P]),
+    "recnn_run_plan": (_I, [_I, _P, _I, _I, _I, _P, _P, _I]),
     "recnn_engine_dp_graph_build": (_I, [_P, _I, _F, _I, _P]),
     "recnn_engine_dp_graph_launch": (_I, [_P, _I, _P]),
     "recnn_comm_create": (_I, [_I, _I, _L, C.POINTER(_P)]),

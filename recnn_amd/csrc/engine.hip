@@ -272,6 +272,9 @@ void drop_graphs(recnn_engine* e) {
   }
   if (e->grun_multi) { (void)hipGraphExecDestroy(e->grun_multi); e->grun_multi = nullptr; }
   e->grun_multi_len = 0;
+  if (e->grun_amulti) { (void)hipGraphExecDestroy(e->grun_amulti); e->grun_amulti = nullptr; }
+  if (e->grun_acycle) { (void)hipGraphExecDestroy(e->grun_acycle); e->grun_acycle = nullptr; }
+  e->grun_amulti_len = 0;
   for (int i = 0; i < recnn_engine::CUSTOM_MAX; ++i) {
     if (e->grun_custom[i]) { (void)hipGraphExecDestroy(e->grun_custom[i]); e->grun_custom[i] = nullptr; }
     e->grun_custom_len[i] = 0;
@@ -569,6 +572,7 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
       {"cycle_next_action0", e->m_na_b[0], e->A, e->Ap, 0},        {"cycle_next_action1", e->m_na_b[1], e->A, e->Ap, 0},
       {"cycle_target_q1", e->m_tq[0], 1, 1, 1},                    {"cycle_target_q2", e->m_tq[1], 1, 1, 1},
       {"cycle_gen_action", e->m_ga, e->A, e->Ap, 0},
+      {"cycle_actor_h1", e->m_pa_h1, e->H, Hp, 0},                 {"cycle_actor_h2", e->m_pa_h2, e->H, Hp, 0},
   };
   for (const Ent& t : cyc)
     if (!strcmp(t.n, name)) {

@@ -73,6 +73,13 @@ extern "C" int recnn_engine_profile(recnn_engine* e, int rows, int policy_steps,
 //   grun_p[k]   a policy step + k ordinary steps  -- k = policy_every-1 is a whole cycle, smaller k the request's tail
 //   grun_multi  as many whole cycles as fit 64 steps
 // (policy_every <= 17: every k; larger: k in {1, 2, 4, 8, 16, 32} and greedy composition.)
+// A graph that starts ON a policy step has that step as a cycle segment of its own at its head (the frozen networks change right
+// after it): one step on the fused forward with a gather of its own.  tuning.run_align adds members cut the other way round,
+//   grun_amulti as many whole cycles as fit 64 steps, from the step AFTER a policy step up to and including the next ones
+//   grun_acycle one such cycle (the stretch where fewer than grun_amulti's cycles are left)
+// whose segments all end on their policy step; a long request reaches them through [ordinary stretch][the policy step alone].
+// Which members exist is recnn_run_family_init's decision and how a request is cut into them recnn_run_plan's: both are host
+// arithmetic, exported so that they can be checked without a GPU.
 namespace recnn_eng {
 // One run of `len` steps captured into *out.  phase = (number of the run's first step) mod policy_every: step i of the run is
 // a policy step when (phase + i) is a multiple of policy_every; phase < 0: no policy step in the run.
@@ -110,7 +117,7 @@ int capture_run(recnn_engine* e, int rows, hipStream_t s, int phase, int len, hi
       //  Round 5, after the kernel-argument prefetches: the same command 67.6-68.2 in cycle mode against 69.3-69.4 fused, A/B inside one
       //  call -- cycle_min_len is 20 now.)
       const bool batched = seg_batched(k);
-      if (batched) rc = ph_frozen_batched(e, rows, n, i0, s);
+      if (batched) rc = ph_frozen_batched(e, rows, n, i0, s, is_pol(i1));
       for (int i = i0; i <= i1 && !rc; ++i) {
         const bool pol = is_pol(i);
         use_mset(e, i - i0, rows);
@@ -177,23 +184,27 @@ extern "C" int recnn_engine_graph_build(recnn_engine* e, int rows, void* stream)
   RECNN_REQUIRE(s != nullptr, "graph_build: capture needs a non-null stream");
   drop_graphs(e);
   const int pe = e->hy.policy_every;
-  int cap = e->tune.graph_run < 0 ? recnn_engine::RUN_MAX : e->tune.graph_run;   // longest run graph wanted
-  if (cap > recnn_engine::RUN_MAX) cap = recnn_engine::RUN_MAX;
+  // the aligned members pay where a run graph is cut into cycle segments: the single-GPU bf16 cycle schedule (the data-parallel path,
+  // split bf16 and fp32 keep the family that starts on a policy step)
+  const bool align = e->tune.run_align && !e->comm && e->bf16 && cycle_ok(e, rows);
+  recnn_run_family fam;
+  if ((rc = recnn_run_family_init(pe, e->tune.graph_run, align, &fam))) return rc;
   if ((rc = capture_run(e, rows, s, -1, 1, &e->gexec[0]))) return rc;
   if ((rc = capture_run(e, rows, s, 0, 1, &e->gexec[1]))) return rc;
-  if (cap >= 2) {
-    const int o_max = pe - 1 < cap ? pe - 1 : cap;            // ordinary stretch: never across a policy step
-    for (int k = 2; k <= o_max; ++k)
-      if (run_len_kept(k, o_max) && (rc = capture_run(e, rows, s, -1, k, &e->grun_o[k]))) return rc;
-    const int p_max = pe - 1 < cap - 1 ? pe - 1 : cap - 1;    // policy step + k ordinary ones
-    for (int k = 1; k <= p_max; ++k)
-      if (run_len_kept(k, p_max) && (rc = capture_run(e, rows, s, 0, k + 1, &e->grun_p[k]))) return rc;
-    const int cycles = cap / pe;
-    if (cycles >= 2) {
-      if ((rc = capture_run(e, rows, s, 0, cycles * pe, &e->grun_multi))) return rc;
-      e->grun_multi_len = cycles * pe;
-    }
+  for (int k = 2; k <= recnn_engine::RUN_MAX; ++k)
+    if (fam.has_o[k] && (rc = capture_run(e, rows, s, -1, k, &e->grun_o[k]))) return rc;
+  for (int k = 1; k <= recnn_engine::RUN_MAX; ++k)
+    if (fam.has_p[k] && (rc = capture_run(e, rows, s, 0, k + 1, &e->grun_p[k]))) return rc;
+  if (fam.multi_len) {
+    if ((rc = capture_run(e, rows, s, 0, fam.multi_len, &e->grun_multi))) return rc;
+    e->grun_multi_len = fam.multi_len;
   }
+  // the aligned members start at phase 1: the step after a policy step
+  if (fam.aligned_multi_len) {
+    if ((rc = capture_run(e, rows, s, 1 % pe, fam.aligned_multi_len, &e->grun_amulti))) return rc;
+    e->grun_amulti_len = fam.aligned_multi_len;
+  }
+  if (fam.aligned_cycle_len && (rc = capture_run(e, rows, s, 1 % pe, fam.aligned_cycle_len, &e->grun_acycle))) return rc;
   e->grun_look = lookahead_ok(e);
   e->graph_rows = rows;
   return 0;
@@ -221,8 +232,66 @@ extern "C" int recnn_engine_graph_prepare(recnn_engine* e, int first_step, int n
   return 0;
 }
 
-// Replays n_steps consecutive steps starting at step number first_step with as few graph launches as the family allows:
-// [ordinary stretch up to the next policy step] [multi-cycle graphs] [whole cycles] [policy step + tail].
+// ---- the composition of a request, host arithmetic only (include/recnn_hip.h)
+static_assert(RECNN_RUN_MAX == recnn_engine::RUN_MAX, "recnn_run_family covers every run length");
+
+extern "C" int recnn_run_family_init(int pe, int graph_run, int align, recnn_run_family* f) {
+  RECNN_REQUIRE(f && pe > 0, "run_family_init: bad arguments");
+  memset(f, 0, sizeof(*f));
+  int cap = graph_run < 0 ? recnn_engine::RUN_MAX : graph_run;   // longest run graph wanted
+  if (cap > recnn_engine::RUN_MAX) cap = recnn_engine::RUN_MAX;
+  if (cap < 2) return 0;
+  const int o_max = pe - 1 < cap ? pe - 1 : cap;            // ordinary stretch: never across a policy step
+  for (int k = 2; k <= o_max; ++k) f->has_o[k] = run_len_kept(k, o_max);
+  const int p_max = pe - 1 < cap - 1 ? pe - 1 : cap - 1;    // policy step + k ordinary ones
+  for (int k = 1; k <= p_max; ++k) f->has_p[k] = run_len_kept(k, p_max);
+  const int cycles = cap / pe;
+  if (cycles >= 2) f->multi_len = cycles * pe;
+  if (align && pe >= 2 && pe <= cap) {                      // (policy_every 1: every step is a policy step, nothing to align)
+    if (cycles >= 2) f->aligned_multi_len = cycles * pe;
+    f->aligned_cycle_len = pe;
+  }
+  return 0;
+}
+
+// [ordinary stretch up to the next policy step] [multi-cycle graphs] [whole cycles] [policy step + tail]; with align, where the largest
+// aligned graph fits behind a policy step: [that policy step alone] [aligned multi-cycle graphs] [aligned cycles], then as before.
+extern "C" int recnn_run_plan(int pe, const recnn_run_family* f, int first_step, int n_steps, int align, int* kinds, int* lens, int cap) {
+  RECNN_REQUIRE(f && pe > 0 && first_step >= 0 && n_steps >= 0 && cap >= 0 && (cap == 0 || (kinds && lens)), "run_plan: bad arguments");
+  const int a_big = !align ? 0 : (f->aligned_multi_len ? f->aligned_multi_len : f->aligned_cycle_len);
+  int n = 0;
+  for (int i = 0; i < n_steps;) {
+    const int phase = (int)(((int64_t)first_step + i) % pe), rem = n_steps - i;
+    int kind, len = 1;
+    if (phase == 0) {
+      if (a_big && rem - 1 >= a_big) kind = RECNN_RUN_POLICY_STEP;                 // on to phase 1
+      else if (f->multi_len && rem >= f->multi_len) { kind = RECNN_RUN_MULTI; len = f->multi_len; }
+      else {
+        int k = (rem < pe ? rem : pe) - 1;                    // ordinary steps that may follow inside this cycle
+        if (k > recnn_engine::RUN_MAX) k = recnn_engine::RUN_MAX;
+        while (k >= 1 && !f->has_p[k]) --k;
+        if (k >= 1) { kind = RECNN_RUN_POLICY_HEAD; len = k + 1; } else kind = RECNN_RUN_POLICY_STEP;
+      }
+    } else if (a_big && phase == 1 && f->aligned_multi_len && rem >= f->aligned_multi_len) {
+      kind = RECNN_RUN_ALIGNED_MULTI; len = f->aligned_multi_len;
+    } else if (a_big && phase == 1 && f->aligned_cycle_len && rem >= f->aligned_cycle_len) {
+      kind = RECNN_RUN_ALIGNED_CYCLE; len = f->aligned_cycle_len;
+    } else {
+      int k = pe - phase;                                     // ordinary steps before the next policy step
+      if (k > rem) k = rem;
+      if (k > recnn_engine::RUN_MAX) k = recnn_engine::RUN_MAX;
+      while (k >= 2 && !f->has_o[k]) --k;
+      if (k >= 2) { kind = RECNN_RUN_ORDINARY; len = k; } else kind = RECNN_RUN_STEP;
+    }
+    if (n < cap) { kinds[n] = kind; lens[n] = len; }
+    ++n;
+    i += len;
+  }
+  return n;
+}
+
+// Replays n_steps consecutive steps starting at step number first_step with as few graph launches as the family allows: a graph made to
+// order for the request if there is one, else the pieces recnn_run_plan cuts it into.
 extern "C" int recnn_engine_graph_run(recnn_engine* e, int first_step, int n_steps, void* stream) {
   RECNN_REQUIRE(e && e->gexec[0] && e->gexec[1], "graph_run: graphs not built");
   const int pe = e->hy.policy_every;
@@ -234,30 +303,35 @@ extern "C" int recnn_engine_graph_run(recnn_engine* e, int first_step, int n_ste
       use_set(e, e->grun_look ? ((n_steps - 1) & 1) : 0);
       return 0;
     }
-  int i = 0;
-  while (i < n_steps) {
-    const int step = first_step + i, rem = n_steps - i;
-    const bool pol = (step % pe) == 0;
-    hipGraphExec_t g = nullptr;
-    int len = 1;
-    if (pol) {
-      if (e->grun_multi && rem >= e->grun_multi_len) { g = e->grun_multi; len = e->grun_multi_len; }
-      else {
-        int k = (rem < pe ? rem : pe) - 1;                    // ordinary steps that may follow inside this cycle
-        if (k > recnn_engine::RUN_MAX) k = recnn_engine::RUN_MAX;
-        while (k >= 1 && !e->grun_p[k]) --k;
-        if (k >= 1) { g = e->grun_p[k]; len = k + 1; } else g = e->gexec[1];
+  recnn_run_family fam;                                       // what exists (graph_build captured recnn_run_family_init's choice)
+  memset(&fam, 0, sizeof(fam));
+  for (int k = 0; k <= recnn_engine::RUN_MAX; ++k) { fam.has_o[k] = e->grun_o[k] != nullptr; fam.has_p[k] = e->grun_p[k] != nullptr; }
+  fam.multi_len = e->grun_multi ? e->grun_multi_len : 0;
+  fam.aligned_multi_len = e->grun_amulti ? e->grun_amulti_len : 0;
+  fam.aligned_cycle_len = e->grun_acycle ? pe : 0;
+  constexpr int PIECES = 64;
+  int kinds[PIECES], lens[PIECES];
+  for (int i = 0; i < n_steps;) {
+    int np = recnn_run_plan(pe, &fam, first_step + i, n_steps - i, e->tune.run_align, kinds, lens, PIECES);
+    if (np < 0) return np;
+    if (np > PIECES) np = PIECES;                             // (the rest is planned from where these end)
+    for (int k = 0; k < np; ++k) {
+      const int len = lens[k];
+      hipGraphExec_t g = nullptr;
+      switch (kinds[k]) {
+        case RECNN_RUN_STEP: g = e->gexec[0]; break;
+        case RECNN_RUN_POLICY_STEP: g = e->gexec[1]; break;
+        case RECNN_RUN_ORDINARY: g = e->grun_o[len]; break;
+        case RECNN_RUN_POLICY_HEAD: g = e->grun_p[len - 1]; break;
+        case RECNN_RUN_MULTI: g = e->grun_multi; break;
+        case RECNN_RUN_ALIGNED_MULTI: g = e->grun_amulti; break;
+        case RECNN_RUN_ALIGNED_CYCLE: g = e->grun_acycle; break;
       }
-    } else {
-      int k = pe - (step % pe);                               // ordinary steps before the next policy step
-      if (k > rem) k = rem;
-      if (k > recnn_engine::RUN_MAX) k = recnn_engine::RUN_MAX;
-      while (k >= 2 && !e->grun_o[k]) --k;
-      if (k >= 2) { g = e->grun_o[k]; len = k; } else g = e->gexec[0];
+      RECNN_REQUIRE(g, "graph_run: the plan names a run graph that was not built (kind %d, %d steps)", kinds[k], len);
+      RECNN_HIP(hipGraphLaunch(g, s));
+      use_set(e, (e->grun_look && len > 1) ? ((len - 1) & 1) : 0);   // where the debug views find the last batch
+      i += len;
     }
-    RECNN_HIP(hipGraphLaunch(g, s));
-    use_set(e, (e->grun_look && len > 1) ? ((len - 1) & 1) : 0);   // where the debug views find the last batch
-    i += len;
   }
   return 0;
 }

@@ -186,13 +186,18 @@ struct recnn_engine {
   //   grun_o[k]  k ordinary steps                      (k >= 2; k = 1 is gexec[0])
   //   grun_p[k]  a policy step + k ordinary steps      (k >= 1; k = 0 is gexec[1]); k = policy_every-1 is a whole cycle
   //   grun_multi whole policy cycles, grun_multi_len steps (starts on a policy step)
-  // graph_run() covers any (first_step, n_steps) with them: see recnn_engine_graph_run
+  // tuning.run_align adds the ALIGNED members, which start right after a policy step and end on one (every cycle segment of theirs
+  // ends on its policy step; none is the lone policy step a graph that starts on one has at its head):
+  //   grun_amulti  whole cycles, grun_amulti_len steps    grun_acycle  one cycle, policy_every steps
+  // graph_run() covers any (first_step, n_steps) with them: the composition is recnn_run_plan's (include/recnn_hip.h)
   hipGraphExec_t gexec[2] = {nullptr, nullptr};
   static constexpr int RUN_MAX = 64;       // = LOSS_HIST_MAX: steps per run graph
   hipGraphExec_t grun_o[RUN_MAX + 1] = {};
   hipGraphExec_t grun_p[RUN_MAX + 1] = {};
   hipGraphExec_t grun_multi = nullptr;
   int grun_multi_len = 0;
+  hipGraphExec_t grun_amulti = nullptr, grun_acycle = nullptr;
+  int grun_amulti_len = 0;
   // run graphs made to order (recnn_engine_graph_prepare): one launch for a whole request (phase, n_steps)
   static constexpr int CUSTOM_MAX = 8;
   hipGraphExec_t grun_custom[CUSTOM_MAX] = {};
@@ -256,7 +261,8 @@ int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipSt
 bool window_ok(const recnn_engine* e, int rows);
 // decides e->win for the capture / profile about to be issued and makes sure the next rows it will write exist; NOT inside a capture
 int begin_cycle_mode(recnn_engine* e, int rows);
-int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s);
+// ends_on_policy: the segment's last step is a policy step (its batch's actor activations feed the backward; nobody reads another batch's)
+int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s, bool ends_on_policy = true);
 int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool value_bwd, hipStream_t s);
 int ph_value_backward(recnn_engine* e, int rows, bool reduce, hipStream_t s, bool dx_only = false);
 int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_t s, bool need_rows = true);

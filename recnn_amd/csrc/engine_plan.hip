@@ -274,6 +274,7 @@ extern "C" void recnn_engine_tuning_init(recnn_engine_tuning* t) {
   t->gemm_variant = -1; t->gemm_v0_threshold = 512; t->gemm_dma = 1; t->gemm_dma_depth = 1; t->gemm_dma_waves = 8;
   t->gemm_waves = 8; t->dw_dma = 2; t->x3_tail = 1; t->x3_fwd = 2; t->dw_fuse = 1; t->tail_half = 1; t->l1_ws = 1; t->frozen_half = 1;
   t->frozen_window = 1;
+  t->run_align = 1; t->frozen_acts_policy_only = 1;
 }
 extern "C" int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* t) {
   RECNN_REQUIRE(e && t, "set_tuning: null pointer");
@@ -1551,7 +1552,7 @@ int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipSt
   return slot(e, "frame_gather_cycle", 0, s, [&] { return frame_gather_multi_launch(g, n, s); });
 }
 
-int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s) {
+int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s, bool ends_on_policy) {
   const int A = e->A, nc = e->n_critic;
   const int POL = RECNN_NET_POLICY, TPOL = RECNN_NET_TARGET_POLICY;
   const int TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
@@ -1609,6 +1610,12 @@ int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_
       p->rows = nsets * rows;
       p->step_add = run_off0 + set0;
       p->h1 = e->m_pa_h1 + r0 * e->Hp * 2; p->h2 = e->m_pa_h2 + r0 * e->Hp * 2;
+      if (e->tune.frozen_acts_policy_only) {
+        // h1 / h2 have one reader: the backward of the policy step (bwd_chain / the actor's dW), on the segment's LAST batch
+        const int pol_set = n - 1 - set0;                            // ... as a batch of this part
+        if (!ends_on_policy || pol_set < 0 || pol_set >= nsets) p->h1 = p->h2 = nullptr;
+        else p->store_row0 = pol_set * rows;
+      }
       p->out = e->m_ga + r0 * e->Ap * 2; p->ldo = e->Ap;
     };
     // Window mode (tuning.frozen_window): no next rows exist.  s' = [e1..eF | r1..rF | 0] of a transition is, column for column,

@@ -78,14 +78,15 @@ __device__ __forceinline__ void hidden_epilogue(f32x4 (&acc)[2][TNH], const f32x
   if (gbits) *gbits = bits;
 }
 
-// the finished 32 x 256 panel -> global [rows, ldg] bf16: whole 512-byte rows, one 16-byte chunk per thread and pass
+// the finished 32 x 256 panel -> global [rows, ldg] bf16: whole 512-byte rows, one 16-byte chunk per thread and pass; of the panel's
+// rows m0 .. m0 + 31 those in [row_lo, rows) are stored
 template <int NW>
-__device__ __forceinline__ void panel_to_global(const unsigned char* panel, bf16_t* gout, int64_t ldg, int m0, int rows, int tid) {
+__device__ __forceinline__ void panel_to_global(const unsigned char* panel, bf16_t* gout, int64_t ldg, int m0, int rows, int tid, int row_lo = 0) {
 #pragma unroll
   for (int j = 0; j < (BM * 32) / (NW * 64); ++j) {
     const int idx = tid + j * NW * 64, row = idx >> 5, cc = idx & 31;
     const uint4 v = *(const uint4*)(panel + (cc >> 4) * PANEL_HALF + row * 256 + (((cc & 15) ^ (row & 15)) << 4));
-    if (m0 + row < rows) *(uint4*)(gout + (int64_t)(m0 + row) * ldg + cc * 8) = v;
+    if (m0 + row < rows && m0 + row >= row_lo) *(uint4*)(gout + (int64_t)(m0 + row) * ldg + cc * 8) = v;
   }
 }
 }  // namespace

@@ -236,9 +236,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
     for (int j = 0; j < TNH; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int q = 0; q < 4; ++q) {
     const unsigned char* st = next_post();        // (its barrier also completes the h1 panel for q = 0)
-    if (q == 0 && P.h1) {
+    if (q == 0 && P.h1 && m0 + FR > P.store_row0) {   // (a workgroup wholly below the first stored row skips the pass)
 #pragma unroll
-      for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h1, P.ldh, m0 + sp * 32, P.rows, tid);
+      for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h1, P.ldh, m0 + sp * 32, P.rows, tid, P.store_row0);
     }
     const unsigned char* sa = spanel + (q >> 1) * PANEL_HALF;
 #pragma unroll
@@ -272,9 +272,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
       for (int j = 0; j < TN3; ++j) o[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < 2; ++p) {
       const unsigned char* st = next_post();      // (completes the h2 panel for p = 0)
-      if (p == 0 && P.h2) {
+      if (p == 0 && P.h2 && m0 + FR > P.store_row0) {
 #pragma unroll
-        for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h2, P.ldh, m0 + sp * 32, P.rows, tid);
+        for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h2, P.ldh, m0 + sp * 32, P.rows, tid, P.store_row0);
       }
 #pragma unroll
       for (int hq = 0; hq < 2; ++hq) {            // k quarter q = 2 p + hq of the panel against image rows hq * 128 + output column
@@ -340,9 +340,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   // ------------------------------------------------------------------ critic head: q[m] = h2[m, :] . w3 + b3, 8 rows per wave
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b3s) : : "memory");
   __builtin_amdgcn_s_barrier();                   // h2 panel complete
-  if (P.h2) {
+  if (P.h2 && m0 + FR > P.store_row0) {
 #pragma unroll
-    for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h2, P.ldh, m0 + sp * 32, P.rows, tid);
+    for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h2, P.ldh, m0 + sp * 32, P.rows, tid, P.store_row0);
   }
   for (int i = 0; i < FR / NW; ++i) {
     const int prow = wave * (FR / NW) + i;        // row of the 128-row panel
@@ -387,6 +387,7 @@ int mlpf_launch(const FrozenBatch& b, int nprob, hipStream_t s, int panel_rows) 
     RECNN_REQUIRE(k64 >= 2, "mlp_frozen: layer 1 needs at least 128 k");
     RECNN_REQUIRE(p.ldw1 % 8 == 0 && p.ldw2 % 8 == 0 && (((uintptr_t)p.W1 | (uintptr_t)p.W2) & 15) == 0, "mlp_frozen: bad weight pitches");
     RECNN_REQUIRE(p.mask_mode == RECNN_MASK_NONE || p.mask_mode == RECNN_MASK_HASH, "mlp_frozen: hash dropout masks only");
+    RECNN_REQUIRE(p.store_row0 >= 0 && p.store_row0 <= p.rows, "mlp_frozen: the first stored activation row lies outside the problem");
     RECNN_REQUIRE(p.rows_per_set == 0 || p.rows_per_set % 32 == 0, "mlp_frozen: batches must be multiples of 32 rows");
     if (p.W3) RECNN_REQUIRE(p.out && p.ldw3 == p.ldw2 && (((uintptr_t)p.W3) & 15) == 0 && p.ldo % 4 == 0, "mlp_frozen: actor needs W3 (same pitch as W2) and an output");
     else RECNN_REQUIRE(p.w3row && p.q, "mlp_frozen: critic needs its last layer's row and a Q output");

@@ -130,6 +130,7 @@ struct FrozenProb {
   int step_add;
   int rows_per_set;               // batches of this many rows (a multiple of 32): batch j uses mask step + j
   void* h1; void* h2; int64_t ldh;   // optional bf16 [rows, ldh] (the actor's activations, for the policy step's backward)
+  int store_row0;                 // ... of which rows store_row0 .. rows - 1 are stored (the policy step's batch is a cycle segment's last)
   void* out; int64_t ldo;         // actor output, bf16
   const float* addend; int64_t ld_add; float add_clip;
   float* q;                       // critic output, fp32 [rows] (b3 included)

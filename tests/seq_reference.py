@@ -4,6 +4,12 @@ import numpy as np
 import torch
 
 
+# The shape sweep between the two ends (8, 16) and (128, 256) (tests/test_gpu_seq_shapes.py has what each one reaches; the host-side
+# tests check the workspace sizes at the same shapes): (E, H), and (U, T, h0 / c0 set).
+SWEEP_SHAPES = ((24, 48), (16, 128), (40, 96), (72, 144), (120, 240))
+SWEEP_CASES = ((33, 70, True), (16, 32, False), (17, 65, False))
+
+
 def padder_ref(x):
     items = torch.nn.utils.rnn.pad_sequence([torch.as_tensor(np.asarray(b["items"])) for b in x], batch_first=True).long()
     ratings = torch.nn.utils.rnn.pad_sequence([torch.as_tensor(np.asarray(b["rates"])) for b in x], batch_first=True).float()

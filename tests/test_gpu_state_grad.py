@@ -52,8 +52,36 @@ def _check_product(tag, got, terms, n):
     return ratio, ref, bound
 
 
+# (rows, S, A, H).  The two ends of the range, then what lies between them:
+#   (65, 27, 8, 16)       a second row tile with one live row: tile_m and the m0 offset into dz, the seeds and out are non-zero
+#   (130, 1290, 128, 256) the notebook's state width: 21 column tiles, the last 10 wide, three row tiles, the scalar tail store at n = 1288
+#   (100, 70, 8, 40)      K = 40 ends 8 into the second 32-wide stage; S = 70 leaves a second column tile 6 wide, and the bf16 16-byte W
+#                         chunk at columns 64 .. 71 crosses S.  No seeds here: the engine leaves unit backward tensors only on its
+#                         fused bf16 path (A = 128, H in 136 .. 256), so TD3's which = 3 is the plain two-segment launch at this shape
+#   (70, 70, 128, 232)    the fused bf16 path with K % 32 != 0: seeded rows (the epilogue's seed here, TD3's FOLD at which = 3) whose
+#                         segments end 8 into their eighth stage, in a second row tile (m0 = 64) and a second column tile 6 wide
+KERNEL_SHAPES = [(37, 27, 8, 16), (50, 256, 128, 256), (65, 27, 8, 16), (130, 1290, 128, 256), (100, 70, 8, 40), (70, 70, 128, 232)]
+
+
+def seeded(shape, dtype):
+    """Whether the engine leaves unit backward tensors (dz / d, the per-row seed applied by the launch) at this shape: its fused bf16
+    path, which needs A = 128 and H rounded up to 128 equal to 256."""
+    return dtype == "bf16" and shape[2] == 128 and 128 < shape[3] <= 256
+
+
+def check_vector_store_tail(cuda, eng, rows, which, plain):
+    """A second `out=` whose rows take the 16-byte store path (row stride a multiple of 4 floats on a 16-byte-aligned base), so the
+    vectorised store meets the n + 3 >= S tail in whichever column tile S ends in: bit for bit the plain result, sentinels untouched."""
+    S = plain.shape[1]
+    ld = (S + 3) // 4 * 4 + 4
+    out = torch.full((rows, ld), 7.0, device=cuda)
+    assert out.data_ptr() % 16 == 0 and out.stride(0) % 4 == 0
+    eng.state_grads(rows, which, out=out)
+    return torch.equal(out[:, :S], plain) and bool((out[:, S:] == 7.0).all())
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape", [(37, 27, 8, 16), (50, 256, 128, 256)])
+@pytest.mark.parametrize("shape", KERNEL_SHAPES)
 def test_kernel_against_its_own_buffers(cuda, shape, dtype):
     from recnn_amd import _lib as L
     from recnn_amd.nn.engine import StepEngine
@@ -63,7 +91,7 @@ def test_kernel_against_its_own_buffers(cuda, shape, dtype):
     batch = [torch.randn(rows, S, generator=gen), torch.randn(rows, A, generator=gen), torch.randn(rows, generator=gen),
              torch.randn(rows, S, generator=gen), (torch.rand(rows, generator=gen) < 0.1).float()]
     masks = [(torch.rand(rows, H, generator=gen) < 0.5).to(torch.uint8) for _ in range(6)]
-    eng = StepEngine("ddpg", S, A, H, 64, dtype=dtype, mask_mode="external", device=cuda)
+    eng = StepEngine("ddpg", S, A, H, max(rows, 64), dtype=dtype, mask_mode="external", device=cuda)
     for ni, p in ((L.NET_POLICY, actor), (L.NET_TARGET_POLICY, actor), (L.NET_VALUE1, critic), (L.NET_TARGET_VALUE1, critic)):
         eng.load_params(ni, p)
     eng.set_hyper(policy_every=1, policy_opt=dict(lr=1e-3), value_opt=dict(lr=0.1))
@@ -75,12 +103,16 @@ def test_kernel_against_its_own_buffers(cuda, shape, dtype):
 
     # ---- which = 0, against the critic as it is BEFORE its step
     eng.value_grads(rows, True)
+    unit = int(eng.lib.recnn_engine_unit_backward(eng.handle))
+    print(f"{shape} {dtype}: unit backward tensors (the per-row seed in the launch's epilogue): {unit}")
+    assert unit == int(seeded(shape, dtype))                              # the seeded cases are really seeded
     w1c_old = _w_seen(eng.param_views(L.NET_VALUE1)["w1"][:, :S].clone(), dtype)
     gv = eng.state_grads(rows, 0)
     assert torch.equal(gv, eng.state_grads(rows, 0))                      # two launches, the same bits
     wide = torch.full((rows, S + 5), 7.0, device=cuda)
     eng.state_grads(rows, 0, out=wide)
     assert torch.equal(wide[:, :S], gv) and bool((wide[:, S:] == 7.0).all())
+    assert check_vector_store_tail(cuda, eng, rows, 0, gv)
     dzc1 = eng.buffer("critic1_dz1", rows)
     assert float(dzc1.abs().max()) > 0
     rv, _, _ = _check_product(f"gV {shape} {dtype}", gv, [(dzc1, w1c_old)], H)
@@ -94,6 +126,7 @@ def test_kernel_against_its_own_buffers(cuda, shape, dtype):
     eng.policy_grads(rows, True)
     gp = eng.state_grads(rows, 1)
     assert torch.equal(gp, eng.state_grads(rows, 1))
+    assert check_vector_store_tail(cuda, eng, rows, 1, gp)
     w1c_new = _w_seen(eng.param_views(L.NET_VALUE1)["w1"][:, :S].clone(), dtype)
     w1a = _w_seen(eng.param_views(L.NET_POLICY)["w1"].clone(), dtype)
     assert float((w1c_new - w1c_old).abs().mean()) > 0.05

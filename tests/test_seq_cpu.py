@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from seq_reference import padder_ref
+from seq_reference import SWEEP_CASES, SWEEP_SHAPES, padder_ref
 
 
 def _users(lengths, seed=0):
@@ -97,6 +97,23 @@ def test_seq_abi_error_paths_launch_nothing():
     assert lib.recnn_lstm_workspace_bytes(25, 1000, 256, 0, C.byref(n)) == 0 and n.value == 0
     assert lib.recnn_lstm_workspace_bytes(25, 1000, 256, 1, C.byref(n)) == 0 and n.value == 2 * 32 * 1024 * 16 * 4
     assert lib.recnn_lstm_workspace_bytes(25, 1000, 24, 1, C.byref(n)) != 0
+
+
+def test_encode_workspace_at_the_in_between_shapes():
+    """The projection workspace against the layout seq_lstm.h documents for `pre`, written out: [user tile][min(T, 32) steps][H / 16
+    hidden tiles][4 gates][64 lanes] 16-byte vectors.  An undersized workspace would be an out-of-bounds write on the GPU."""
+    from recnn_amd import _lib as L
+    lib = L.load()
+    n = C.c_int64(-1)
+    for _, H in SWEEP_SHAPES:
+        for U, T, _ in SWEEP_CASES:
+            tiles = (U + 15) // 16
+            assert lib.recnn_lstm_workspace_bytes(U, T, H, 1, C.byref(n)) == 0
+            assert n.value == tiles * min(T, 32) * (H // 16) * 4 * 64 * 16, (U, T, H, n.value)
+            assert lib.recnn_lstm_workspace_bytes(U, T, H, 0, C.byref(n)) == 0 and n.value == 0
+    for H in (8, 24, 272):                     # (this query takes no embedding width: seq_bwd.hip's, which does, refuses E by name too)
+        assert lib.recnn_lstm_workspace_bytes(33, 70, H, 1, C.byref(n)) != 0
+        assert b"lstm_workspace_bytes" in lib.recnn_last_error() and b"hidden" in lib.recnn_last_error()
 
 
 def _tiny_env(**kw):

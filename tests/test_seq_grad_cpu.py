@@ -56,6 +56,33 @@ def test_train_workspace_query_is_host_only_and_validates():
     assert b"null" in lib.recnn_last_error()
 
 
+def test_train_workspaces_at_the_in_between_shapes():
+    """Both training workspaces against the layouts seq_lstm.h (`saved`) and seq_bwd.hip (`bwd_ws`) document, written out, at the
+    shapes tests/test_gpu_seq_shapes.py launches.  An undersized workspace would be an out-of-bounds write on the GPU.
+      saved     [user tile][T][H / 16][i, f, g, o, c][64 lanes] 16-byte vectors
+      backward  W_hh^T (H x 4H floats), dh and dc (U x H floats each, rounded up to 16 bytes), one chunk of da
+                ([user tiles x 16 rows][min(T, 32) steps][4H] floats)"""
+    from recnn_amd import _lib as L
+    lib = L.load()
+    s, b = C.c_int64(-1), C.c_int64(-1)
+    for E, H in R.SWEEP_SHAPES:
+        for U, T, _ in R.SWEEP_CASES:
+            tiles = (U + 15) // 16
+            state = (4 * U * H + 15) // 16 * 16                       # dh or dc: U x H floats, rounded up to 16 bytes
+            for variant in (0, 1):
+                assert lib.recnn_lstm_train_workspace_bytes(U, T, H, E, variant, C.byref(s), C.byref(b)) == 0
+                assert s.value == tiles * T * (H // 16) * 5 * 64 * 16, (E, H, U, T, s.value)
+                assert b.value == 16 * H * H + 2 * state + tiles * 16 * min(T, 32) * 16 * H, (E, H, U, T, b.value)
+    for E in (4, 12, 136):
+        assert lib.recnn_lstm_train_workspace_bytes(33, 70, 144, E, 1, C.byref(s), C.byref(b)) != 0
+        err = lib.recnn_last_error()
+        assert b"lstm_train_workspace_bytes" in err and b"emb_dim" in err and str(E).encode() in err
+    for H in (8, 24, 272):
+        assert lib.recnn_lstm_train_workspace_bytes(33, 70, H, 72, 1, C.byref(s), C.byref(b)) != 0
+        err = lib.recnn_last_error()
+        assert b"lstm_train_workspace_bytes" in err and b"hidden" in err and str(H).encode() in err
+
+
 def test_new_entry_points_refuse_bad_arguments_before_any_launch():
     from recnn_amd import _lib as L
     lib = L.load()

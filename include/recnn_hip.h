@@ -893,6 +893,24 @@ int recnn_lstm_backward(const int32_t* items, const float* ratings, const int64_
                         const void* saved, const float* h_out, const float* h0, const float* c0, const float* g_h,
                         const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b, float* d_h0, float* d_c0,
                         void* workspace, void* stream);
+/* The gradient of the embedding table through the encoder (csrc/seq_bwd.hip).  recnn_lstm_backward_table is
+ * recnn_lstm_backward -- the same arguments, and the same bits in d_w_ih, d_w_hh, d_b, d_h0, d_c0 -- that also writes
+ * d_table float[n_items, emb_dim] (required, 16-byte aligned; EVERY row is written, items the call's positions do not hold get exact
+ * zeros): d_table[item] = sum of dX[u, t, 0:emb_dim] over the positions (u, t) with items_u[t0 + t] == item, where
+ * dX[u, t, n] = sum_m da[u, t, m] w_ih[m, n] and da is the gradient of the gate pre-activations.  w_ih float[4 hidden, emb_dim + 1] is
+ * read in place (its rating column is not used).  The weight-gradient outputs may all be NULL: d_table alone is computed then.
+ * `table_workspace`: recnn_lstm_table_grad_workspace_bytes (host-only; a packed transpose of w_ih[:, 0:emb_dim], dX of the whole call
+ * -- n_users * T * emb_dim floats, the one place where [n_users, T, emb_dim] is materialised --, the inverted index of the call's
+ * n_users * T positions by item id and the partial sums of its pieces), 16-byte aligned; n_users * T < 2^31.  dX runs on the exact-f32
+ * MFMA in a fixed contraction order; the sum per item runs over its positions in ascending u * T + t, cut into fixed pieces added in
+ * order: no float atomics (integer atomics build the index), equal calls give equal bits.  Item ids outside [0, n_items) contribute to
+ * no row. */
+int recnn_lstm_table_grad_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_items, int64_t* bytes);
+int recnn_lstm_backward_table(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                              int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
+                              const float* w_hh, const void* saved, const float* h_out, const float* h0, const float* c0,
+                              const float* g_h, const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b,
+                              float* d_h0, float* d_c0, float* d_table, void* workspace, void* table_workspace, void* stream);
 /* Backward of recnn_seq_collect with respect to h: g_h float[n_users, T, hidden] (every element written) from the gradients of the
  * state and next_state rows (each float[n_steps * n_users, hidden] or NULL: zeros): g_h[u, t] = g_next_state[k n_users + u] where
  * steps[k] == t, plus g_state[k' n_users + u] where steps[k'] == t + 1.  steps int32[n_steps] (device) must be strictly increasing

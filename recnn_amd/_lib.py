@@ -250,6 +250,8 @@ SIGNATURES = {
     "recnn_lstm_train_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L), C.POINTER(_L)]),
     "recnn_lstm_encode_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "recnn_lstm_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "recnn_lstm_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_lstm_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 18),
     "recnn_seq_collect_bwd": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
 }
 

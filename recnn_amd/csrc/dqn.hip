@@ -6,11 +6,12 @@
 // target's max_n runs as the only catalogue GEMM, with a row-max epilogue (dqn_head_kernel, MODE_MAX) that never stores A.
 // Every float sum has a fixed order: column sums in fixed row chunks added in chunk order, the TD reduction as a fixed tree, and the
 // scatter-sums through an inverted index built by a stable counting sort (histogram, scan, placement, per-destination rank by
-// contribution index), long lists cut into pieces of PIECE entries whose partial sums are added in piece order.  Integer atomics only
-// (counts, and the row max on the order-preserving integer image of a float, which is exact in any order).
+// contribution index: scatter_index.h), long lists cut into pieces of PIECE entries whose partial sums are added in piece order.
+// Integer atomics only (counts, and the row max on the order-preserving integer image of a float, which is exact in any order).
 #include <type_traits>
 
 #include "common.h"
+#include "scatter_index.h"
 
 namespace {
 
@@ -296,109 +297,19 @@ __global__ __launch_bounds__(256) void dqn_dh_kernel(const float* __restrict__ h
 // contribution j (j < rows * per_row): source row src + (j / per_row) ld + (j % per_row) 128, weight scale[j / per_row] (1 if NULL),
 // destination ids[(j / per_row) ld_ids + j % per_row].  Ids outside [0, n_dest) are dropped.
 struct ScatterWs {
-  int* count;     // [n_dest]
-  int* start;     // [n_dest + 1]
-  int* slot;      // [M] arrival slot of contribution j in its list (unordered)
-  int* placed;    // [M] contributions by destination, arrival order
-  int* sorted;    // [M] ... in contribution order (the inverted index)
-  float* part;    // [M][128] piece partial rows
-  float* part_s;  // [M] piece partial weights
+  ScatterIndex ix;  // count, start, slot, placed, sorted (scatter_index.h)
+  float* part;      // [M][128] piece partial rows
+  float* part_s;    // [M] piece partial weights
+};
+// the destination of contribution j: for the index build (scatter_index.h) and, through contrib_id, for the float passes
+struct MatrixId {
+  const int64_t* ids;
+  int64_t ld_ids;
+  int per_row;
+  __device__ int64_t operator()(int j) const { return ids[(int64_t)(j / per_row) * ld_ids + j % per_row]; }
 };
 __device__ inline int contrib_id(const int64_t* ids, int64_t ld_ids, int per_row, int j) {
-  return (int)ids[(int64_t)(j / per_row) * ld_ids + j % per_row];
-}
-__global__ void scatter_hist_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int per_row, int M, int n_dest, int* count, int* slot) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= M) return;
-  const int64_t id = ids[(int64_t)(j / per_row) * ld_ids + j % per_row];
-  slot[j] = (id >= 0 && id < n_dest) ? atomicAdd(count + id, 1) : -1;
-}
-// exclusive scan of count into start[0 .. n + 1): one workgroup of 1024, each thread a contiguous run
-__global__ __launch_bounds__(1024) void scatter_scan_kernel(const int* __restrict__ count, int n, int* __restrict__ start) {
-  __shared__ int sums[1024];
-  const int per = (n + 1023) / 1024;
-  const int i0 = threadIdx.x * per, i1 = min(n, i0 + per);
-  int s = 0;
-  for (int i = i0; i < i1; ++i) s += count[i];
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = threadIdx.x >= off ? sums[threadIdx.x - off] : 0;
-    __syncthreads();
-    sums[threadIdx.x] += v;
-    __syncthreads();
-  }
-  int run = sums[threadIdx.x] - s;
-  for (int i = i0; i < i1; ++i) {
-    start[i] = run;
-    run += count[i];
-  }
-  if (threadIdx.x == 1023) start[n] = sums[1023];
-}
-__global__ void scatter_place_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int per_row, int M, const int* __restrict__ start,
-                                     const int* __restrict__ slot, int* __restrict__ placed) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= M || slot[j] < 0) return;
-  placed[start[contrib_id(ids, ld_ids, per_row, j)] + slot[j]] = j;
-}
-// stable order: each destination's list sorted by contribution index j (all distinct, < M).  One workgroup per destination with two
-// or more entries.  Lists of up to 256 entries: in LDS, rank = number of smaller j in the list.  Longer lists (the popular items): a
-// bitmap of the list's j over [0, M) in LDS, rank = popcount below j -- linear in M / 32 + L instead of quadratic in L.  (M beyond the
-// bitmap: the quadratic count over LDS chunks.)
-constexpr int RANK_SMALL = 256, RANK_WORDS = 16384;
-__global__ __launch_bounds__(256) void scatter_rank_kernel(const int* __restrict__ start, int n_dest, const int* __restrict__ placed,
-                                                           int M, int* __restrict__ sorted) {
-  __shared__ uint32_t bits[RANK_WORDS];
-  __shared__ int tsum[256];
-  const int d = blockIdx.x, t = threadIdx.x;
-  if (d >= n_dest) return;
-  const int s = start[d], L = start[d + 1] - s;
-  if (L <= 1) {
-    if (L == 1 && t == 0) sorted[s] = placed[s];
-    return;
-  }
-  int* lst = (int*)bits;
-  const int words = (M + 31) / 32;
-  if (L > RANK_SMALL && words <= RANK_WORDS) {
-    for (int w = t; w < words; w += 256) bits[w] = 0u;
-    __syncthreads();
-    for (int i = t; i < L; i += 256) {
-      const int j = placed[s + i];
-      atomicOr(&bits[j >> 5], 1u << (j & 31));
-    }
-    __syncthreads();
-    const int per = (words + 255) / 256, w0 = t * per, w1 = min(words, w0 + per);
-    int c = 0;
-    for (int w = w0; w < w1; ++w) c += __popc(bits[w]);
-    tsum[t] = c;
-    __syncthreads();
-    if (t == 0) {
-      int run = 0;
-      for (int k = 0; k < 256; ++k) { const int v = tsum[k]; tsum[k] = run; run += v; }
-    }
-    __syncthreads();
-    for (int i = t; i < L; i += 256) {
-      const int j = placed[s + i], w = j >> 5, owner = w / per;
-      int r = tsum[owner];
-      for (int k = owner * per; k < w; ++k) r += __popc(bits[k]);
-      r += __popc(bits[w] & ((1u << (j & 31)) - 1u));
-      sorted[s + r] = j;
-    }
-    return;
-  }
-  for (int g0 = 0; g0 < L; g0 += 256) {
-    const int i = g0 + t;
-    const int mine = i < L ? placed[s + i] : 0x7FFFFFFF;
-    int rank = 0;
-    for (int c0 = 0; c0 < L; c0 += RANK_WORDS) {
-      const int n = min(RANK_WORDS, L - c0);
-      __syncthreads();
-      for (int k = t; k < n; k += 256) lst[k] = placed[s + c0 + k];
-      __syncthreads();
-      for (int k = 0; k < n; ++k) rank += lst[k] < mine;
-    }
-    if (i < L) sorted[s + rank] = mine;
-  }
+  return (int)MatrixId{ids, ld_ids, per_row}(j);
 }
 // pass 1: one wave per PIECE sorted entries; the run of each destination inside the piece is summed in list order and written at the
 // run's first sorted position.  Lanes own columns lane and lane + 64.
@@ -536,11 +447,7 @@ ScatterWs scatter_ws(void* ws, int M, int n_dest) {
   char* p = (char*)ws;
   auto take = [&](int64_t bytes) { char* r = p; p += (bytes + 255) / 256 * 256; return r; };
   ScatterWs w;
-  w.count = (int*)take(4LL * n_dest);
-  w.start = (int*)take(4LL * (n_dest + 1));
-  w.slot = (int*)take(4LL * M);
-  w.placed = (int*)take(4LL * M);
-  w.sorted = (int*)take(4LL * M);
+  w.ix = scatter_index_carve(p, M, n_dest);
   w.part = (float*)take(4LL * M * HK);
   w.part_s = (float*)take(4LL * M);
   return w;
@@ -565,18 +472,14 @@ extern "C" int recnn_dqn_scatter_sum(const float* src, int64_t ld_src, int rows,
   hipStream_t s = (hipStream_t)stream;
   const int M = rows * per_row;
   ScatterWs w = scatter_ws(workspace, M, n_dest);
-  RECNN_HIP(hipMemsetAsync(w.count, 0, 4LL * n_dest, s));
-  if (M) hipLaunchKernelGGL(scatter_hist_kernel, dim3((M + 255) / 256), dim3(256), 0, s, ids, ld_ids, per_row, M, n_dest, w.count, w.slot);
-  hipLaunchKernelGGL(scatter_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, n_dest, w.start);
+  RECNN_HIP(scatter_index_build(w.ix, MatrixId{ids, ld_ids, per_row}, M, n_dest, s));
   if (M) {
-    hipLaunchKernelGGL(scatter_place_kernel, dim3((M + 255) / 256), dim3(256), 0, s, ids, ld_ids, per_row, M, w.start, w.slot, w.placed);
-    hipLaunchKernelGGL(scatter_rank_kernel, dim3(n_dest), dim3(256), 0, s, w.start, n_dest, w.placed, M, w.sorted);
     // (dropped ids are not in the lists: the pieces cover the first start[n_dest] sorted entries)
     const int pieces = (M + PIECE - 1) / PIECE;
-    hipLaunchKernelGGL(scatter_piece_kernel, dim3((pieces + 3) / 4), dim3(256), 0, s, src, ld_src, per_row, ids, ld_ids, scale, w.sorted,
-                       w.start + n_dest, w.part, w.part_s);
+    hipLaunchKernelGGL(scatter_piece_kernel, dim3((pieces + 3) / 4), dim3(256), 0, s, src, ld_src, per_row, ids, ld_ids, scale, w.ix.sorted,
+                       w.ix.start + n_dest, w.part, w.part_s);
   }
-  hipLaunchKernelGGL(scatter_merge_kernel, dim3((n_dest + 3) / 4), dim3(256), 0, s, w.start, n_dest, w.part, w.part_s, out, out_s, rank1,
+  hipLaunchKernelGGL(scatter_merge_kernel, dim3((n_dest + 3) / 4), dim3(256), 0, s, w.ix.start, n_dest, w.part, w.part_s, out, out_s, rank1,
                      coef);
   return recnn_check_hip(hipGetLastError(), "dqn_scatter_sum");
 }

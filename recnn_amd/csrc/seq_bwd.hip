@@ -20,8 +20,23 @@
 //                     of the same stage.  Chunks are added into dW in launch order (last chunk first).  No atomics anywhere.
 //                     Only the rows of real users are walked: the clamped rows of a partly filled tile give nothing.
 //                     (dw_tile.h / gemm.h are bf16 tiles; the gradients here are exact f32, so they are not reused.)
+//   table gradient   (recnn_lstm_backward_table only) d_table[item] = sum of dX[u, t, 0:E] over the call's positions (u, t) that hold
+//                     `item`, dX[u, t, n] = sum_m da[u, t, m] W_ih[m, n].  dX: one launch per chunk after its chain launch, a grid
+//                     over tiles of 16 samples (real users only), wave w of a workgroup owning column tiles w and w + 4, on the
+//                     exact-f32 MFMA.  One accumulator per element, from zero; the contraction walks m in blocks of 16 upwards,
+//                     four MFMAs e = 0 .. 3 per block, MFMA e adding the products m = m0 + e, m0 + 4 + e, m0 + 8 + e, m0 + 12 + e.
+//                     W_ih[:, 0:E] (row stride E + 1: 4-byte aligned only) is read from a packed transposed copy [E][4H] made
+//                     once per call, so the contraction index is contiguous and a lane loads 16 bytes of either operand.  dX is
+//                     written to a [U, T, E] buffer for the WHOLE call -- the one place where [U, T, E] is materialised -- so that
+//                     the scatter's order does not depend on the chunk cut.  The scatter-sum runs once per call over the inverted
+//                     index of scatter_index.h (stable counting sort by item id, per item its contributions in ascending
+//                     j = u T + t; built before the chain starts, it does not depend on da): the sorted entries are cut into
+//                     pieces of 16, a wave sums the run of each item inside its piece in list order from zero, and one wave per
+//                     item adds the piece partials of its list in piece order from zero.  Every row of d_table is written
+//                     (untouched items: exact zeros).  No float atomics.  Ids outside the table are in no list.
 //   collect backward  g_h[u, t] = g_next_state[k U + u] where steps[k] == t, plus g_state[k' U + u] where steps[k'] == t + 1: a
 //                     gather over 16-byte chunks of g_h (flat_walk.h), each chunk summing its two or fewer sources.
+#include "scatter_index.h"
 #include "seq_lstm.h"
 
 namespace {
@@ -369,6 +384,162 @@ __global__ __launch_bounds__(256) void lstm_dw_kernel(const DwArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ table gradient
+// wp[n][m] = w_ih[m][n], n < E: W_ih without its rating column, transposed and packed
+__global__ __launch_bounds__(256) void lstm_wih_pack_kernel(const float* __restrict__ w, int E, int G, float* __restrict__ wp) {
+  flat_walk<1>((int64_t)E * G, [&](int64_t i, Width<1>) {
+    const int n = (int)(i / G), m = (int)(i - (int64_t)n * G);
+    wp[i] = w[(int64_t)m * (E + 1) + n];
+  });
+}
+
+constexpr int DX_S = 16;            // samples per workgroup
+constexpr int DX_WV = 4;            // waves per workgroup
+
+struct DxArgs {
+  int U, T, H, E, tb, Tc, da_T;
+  const float* da;                  // the chunk's [..][da_T][4H]
+  const float* wp;                  // [E][4H]
+  float* dx;                        // [U][T][E]
+};
+
+// grid ceil(U Tc / 16), min(4, ceil(E / 16)) waves: sample s = u Tc + tl of the chunk (u < U: real users only); wave w owns columns 16 w .. 16 w + 15
+// and 16 (w + 4) .. of the 16 samples.  Both operands come straight from global memory, 16 bytes per lane, the next block's loads
+// issued ahead of this block's products (the four waves read the same da rows: they meet in the cache).
+__global__ __launch_bounds__(64 * DX_WV) void lstm_dx_kernel(const DxArgs a) {
+  const int G = 4 * a.H, E = a.E;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int S = a.U * a.Tc, s0 = blockIdx.x * DX_S;
+  const int ntiles = (E + 15) >> 4;
+  if (wave >= ntiles) return;                          // (wave-uniform; the kernel has no barrier)
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const bool alive = s0 + r < S;
+  const int ua = alive ? (s0 + r) / a.Tc : 0, tla = alive ? s0 + r - ua * a.Tc : 0;
+  const float* arow = a.da + ((int64_t)ua * a.da_T + tla) * G + 4 * g;
+  bool on[2], bl[2];
+  const float* brow[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = (wave + DX_WV * j) * 16 + r;
+    on[j] = wave + DX_WV * j < ntiles;
+    bl[j] = on[j] && n < E;                            // E is a multiple of 8: the last column tile may be half empty
+    brow[j] = a.wp + (int64_t)(bl[j] ? n : 0) * G + 4 * g;
+  }
+  f32x4 acc[2] = {zero4, zero4};
+  f32x4 an = alive ? *(const f32x4*)arow : zero4, bn[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) bn[j] = bl[j] ? *(const f32x4*)brow[j] : zero4;
+  for (int k0 = 0; k0 < G; k0 += 16) {
+    const f32x4 av = an;
+    f32x4 bv[2];
+    const int kn = k0 + 16 < G ? k0 + 16 : k0;
+    an = alive ? *(const f32x4*)(arow + kn) : zero4;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      bv[j] = bn[j];
+      bn[j] = bl[j] ? *(const f32x4*)(brow[j] + kn) : zero4;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[0][e], acc[0], 0, 0, 0);
+      if (on[1]) acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[1][e], acc[1], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (!bl[j]) continue;
+    const int n = (wave + DX_WV * j) * 16 + r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = s0 + 4 * g + i;
+      if (s >= S) continue;
+      const int u = s / a.Tc, tl = s - u * a.Tc;
+      a.dx[((int64_t)u * a.T + a.tb + tl) * E + n] = acc[j][i];
+    }
+  }
+}
+
+// contribution j = u T + t of a call: the item at position t0 + t of user u's history (the encode's clamp; the host refuses steps
+// past a history's end)
+struct StoreId {
+  const int32_t* items;
+  const int64_t* user_off;
+  const int32_t* slots;
+  int T, t0;
+  __device__ int64_t operator()(int j) const {
+    const int u = j / T, t = j - u * T;
+    const int slot = slots[u];
+    const int64_t off = user_off[slot];
+    const int len = (int)(user_off[slot + 1] - off);
+    return len > 0 ? (int64_t)items[off + max(min(t0 + t, len - 1), 0)] : -1;
+  }
+};
+
+constexpr int TG_PIECE = 16;        // scatter-sum: sorted entries per wave in the first pass
+// pass 1: one wave per TG_PIECE sorted entries; the run of each item inside the piece is summed in list order and written at the
+// run's first sorted position.  Lanes own columns lane and lane + 64 (E <= 128).
+__global__ __launch_bounds__(256) void table_piece_kernel(const float* __restrict__ dx, int E, const StoreId id_of,
+                                                          const int* __restrict__ sorted, const int* __restrict__ total_ptr,
+                                                          float* __restrict__ part) {
+  const int total = *total_ptr;
+  const int piece = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int p0 = piece * TG_PIECE;
+  if (p0 >= total) return;
+  const int p1 = min(total, p0 + TG_PIECE);
+  const bool c0 = lane < E, c1 = lane + 64 < E;
+  float a0 = 0.f, a1 = 0.f;
+  int first = p0;
+  int cur = (int)id_of(sorted[p0]);
+  for (int p = p0; p < p1; ++p) {
+    const float* s = dx + (int64_t)sorted[p] * E;
+    if (c0) a0 += s[lane];
+    if (c1) a1 += s[lane + 64];
+    const int nxt = p + 1 < p1 ? (int)id_of(sorted[p + 1]) : -1;
+    if (nxt != cur) {
+      if (c0) part[(int64_t)first * E + lane] = a0;
+      if (c1) part[(int64_t)first * E + lane + 64] = a1;
+      a0 = a1 = 0.f;
+      first = p + 1;
+      cur = nxt;
+    }
+  }
+}
+// pass 2: one wave per item, the pieces of its list in order; an item nothing reached gets zeros
+__global__ __launch_bounds__(256) void table_merge_kernel(const int* __restrict__ start, int n_items, int E, const float* __restrict__ part,
+                                                          float* __restrict__ out) {
+  const int d = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (d >= n_items) return;
+  const int s = start[d], e = start[d + 1];
+  const bool c0 = lane < E, c1 = lane + 64 < E;
+  float a0 = 0.f, a1 = 0.f;
+  if (e > s) {
+    for (int k = s / TG_PIECE; k <= (e - 1) / TG_PIECE; ++k) {
+      const int at = max(s, k * TG_PIECE);
+      if (c0) a0 += part[(int64_t)at * E + lane];
+      if (c1) a1 += part[(int64_t)at * E + lane + 64];
+    }
+  }
+  if (c0) out[(int64_t)d * E + lane] = a0;
+  if (c1) out[(int64_t)d * E + lane + 64] = a1;
+}
+
+// workspace of the table gradient: packed W_ih^T, dX of the whole call, the inverted index, the piece partials (each rounded up to
+// 256 bytes)
+struct TableWs {
+  int64_t wp, dx, index, part, total;    // byte offsets
+};
+inline TableWs table_ws(int n_users, int T, int H, int E, int n_items) {
+  const int64_t M = (int64_t)n_users * T;
+  TableWs w;
+  w.wp = 0;
+  w.dx = scatter_index_round((int64_t)E * 4 * H * 4);
+  w.index = w.dx + scatter_index_round(M * E * 4);
+  w.part = w.index + scatter_index_bytes(M, n_items);
+  w.total = w.part + scatter_index_round(M * E * 4);
+  return w;
+}
+
 // workspace of a backward call: W_hh^T, the dh / dc hand-over buffers, one chunk of da
 struct BwdWs {
   int64_t wt, dh, dc, da, total;    // byte offsets
@@ -423,19 +594,37 @@ extern "C" int recnn_lstm_encode_train(const int32_t* items, const float* rating
   return recnn_check_hip(hipGetLastError(), "lstm_encode_train");
 }
 
-extern "C" int recnn_lstm_backward(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
-                                   int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_hh,
-                                   const void* saved, const float* h_out, const float* h0, const float* c0, const float* g_h,
-                                   const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b, float* d_h0,
-                                   float* d_c0, void* workspace, void* stream) {
+extern "C" int recnn_lstm_table_grad_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_items, int64_t* bytes) {
+  RECNN_REQUIRE(bytes, "lstm_table_grad_workspace_bytes: null pointer");
+  RECNN_LSTM_DIMS_OK("lstm_table_grad_workspace_bytes", emb_dim, hidden);
+  RECNN_REQUIRE(n_users >= 0 && T >= 0 && n_items >= 1 && (int64_t)n_users * T < (1LL << 31),
+                "lstm_table_grad_workspace_bytes: need n_users >= 0, T >= 0, n_items >= 1 and n_users * T < 2^31");
+  *bytes = table_ws(n_users, T, hidden, emb_dim, n_items).total;
+  return 0;
+}
+
+// recnn_lstm_backward (d_table == NULL: w_ih and table_workspace are not looked at) and recnn_lstm_backward_table
+static int lstm_backward_impl(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                              int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
+                              const float* w_hh, const void* saved, const float* h_out, const float* h0, const float* c0,
+                              const float* g_h, const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b,
+                              float* d_h0, float* d_c0, float* d_table, void* workspace, void* table_workspace, void* stream) {
   RECNN_REQUIRE(store_ok(items, ratings, user_off, slots, table) && w_hh && saved && h_out && workspace, "lstm_backward: null pointer");
   RECNN_REQUIRE((h0 == nullptr) == (c0 == nullptr), "lstm_backward: h0 and c0 come together");
   RECNN_LSTM_DIMS_OK("lstm_backward", emb_dim, hidden);
   RECNN_REQUIRE(n_users >= 0 && t0 >= 0 && T >= 1 && n_items > 0, "lstm_backward: need n_users, t0 >= 0, T >= 1 and n_items > 0");
   RECNN_REQUIRE(aligned16(table, w_hh, saved, h_out, h0, workspace),
                 "lstm_backward: table, w_hh, saved, h_out, h0 and workspace must be 16-byte aligned");
-  if (n_users == 0) return 0;
+  if (d_table) {
+    RECNN_REQUIRE(w_ih && table_workspace, "lstm_backward_table: null pointer (w_ih, table_workspace)");
+    RECNN_REQUIRE(aligned16(d_table, table_workspace), "lstm_backward_table: d_table and table_workspace must be 16-byte aligned");
+    RECNN_REQUIRE((int64_t)n_users * T < (1LL << 31), "lstm_backward_table: n_users * T must stay below 2^31");
+  }
   const hipStream_t s = (hipStream_t)stream;
+  if (n_users == 0) {
+    if (d_table) RECNN_HIP(hipMemsetAsync(d_table, 0, (size_t)n_items * emb_dim * sizeof(float), s));
+    return 0;
+  }
   const int H = hidden, G = 4 * H;
   const BwdWs w = bwd_ws(n_users, T, H);
   char* ws = (char*)workspace;
@@ -455,13 +644,34 @@ extern "C" int recnn_lstm_backward(const int32_t* items, const float* ratings, c
   a.saved = (const float*)saved;
   a.w_hhT = wt;
   a.c0 = c0; a.g_h = g_h; a.g_hT = g_hT; a.g_cT = g_cT;
-  a.da = want_w ? (float*)(ws + w.da) : nullptr;
+  a.da = want_w || d_table ? (float*)(ws + w.da) : nullptr;
   a.da_T = T < LSTM_CHUNK ? T : LSTM_CHUNK;
   DwArgs d{};
   d.s = SeqStore{items, ratings, user_off, slots, n_users, table, n_items, emb_dim};
   d.t0 = t0;
   d.U = n_users; d.T = T; d.H = H; d.da_T = a.da_T;
   d.da = a.da;
+  // the table gradient's operands that do not depend on da: the packed W_ih^T and the inverted index of the call's positions
+  const StoreId id_of{items, user_off, slots, T, t0};
+  DxArgs dx{};
+  ScatterIndex ix{};
+  float* part = nullptr;
+  int M = 0;                                           // positions of the call (d_table only: checked below 2^31 above)
+  if (d_table) {
+    M = n_users * T;
+    const TableWs tw = table_ws(n_users, T, H, emb_dim, n_items);
+    char* tp = (char*)table_workspace;
+    dx.U = n_users; dx.T = T; dx.H = H; dx.E = emb_dim; dx.da_T = a.da_T;
+    dx.da = a.da;
+    dx.wp = (const float*)(tp + tw.wp);
+    dx.dx = (float*)(tp + tw.dx);
+    part = (float*)(tp + tw.part);
+    char* ip = tp + tw.index;
+    ix = scatter_index_carve(ip, M, n_items);
+    hipLaunchKernelGGL(lstm_wih_pack_kernel, dim3(grid_for((int64_t)emb_dim * G, 256, 2048)), dim3(256), 0, s, w_ih, emb_dim, G,
+                       (float*)(tp + tw.wp));
+    RECNN_HIP(scatter_index_build(ix, id_of, M, n_items, s));
+  }
   const int nchunks = (T + LSTM_CHUNK - 1) / LSTM_CHUNK;
   for (int ci = nchunks - 1; ci >= 0; --ci) {
     a.tb = ci * LSTM_CHUNK;
@@ -473,6 +683,11 @@ extern "C" int recnn_lstm_backward(const int32_t* items, const float* ratings, c
     const dim3 grid(user_tiles(n_users));
     if (two) hipLaunchKernelGGL((lstm_bwd_chain_kernel<2>), grid, dim3(NT), lds, s, a);
     else hipLaunchKernelGGL((lstm_bwd_chain_kernel<1>), grid, dim3(NT), lds, s, a);
+    if (d_table) {
+      dx.tb = a.tb; dx.Tc = a.Tc;
+      const int dx_waves = (emb_dim + 15) / 16 < DX_WV ? (emb_dim + 15) / 16 : DX_WV;      // E <= 48: no wave without a column tile
+      hipLaunchKernelGGL(lstm_dx_kernel, dim3((n_users * a.Tc + DX_S - 1) / DX_S), dim3(64 * dx_waves), 0, s, dx);
+    }
     if (!want_w) continue;
     d.tb = a.tb; d.Tc = a.Tc;
     d.accumulate = ci != nchunks - 1;
@@ -490,7 +705,34 @@ extern "C" int recnn_lstm_backward(const int32_t* items, const float* ratings, c
       hipLaunchKernelGGL((lstm_dw_kernel<true>), dim3(G / DW_T, d_w_ih ? (emb_dim + DW_T - 1) / DW_T : 1), dim3(256), 0, s, x);
     }
   }
-  return recnn_check_hip(hipGetLastError(), "lstm_backward");
+  if (d_table) {
+    // (dropped ids are not in the lists: the pieces cover the first start[n_items] sorted entries)
+    const int pieces = (M + TG_PIECE - 1) / TG_PIECE;
+    hipLaunchKernelGGL(table_piece_kernel, dim3((pieces + 3) / 4), dim3(256), 0, s, dx.dx, emb_dim, id_of, ix.sorted, ix.start + n_items,
+                       part);
+    hipLaunchKernelGGL(table_merge_kernel, dim3((n_items + 3) / 4), dim3(256), 0, s, ix.start, n_items, emb_dim, part, d_table);
+  }
+  return recnn_check_hip(hipGetLastError(), d_table ? "lstm_backward_table" : "lstm_backward");
+}
+
+extern "C" int recnn_lstm_backward(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                                   int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_hh,
+                                   const void* saved, const float* h_out, const float* h0, const float* c0, const float* g_h,
+                                   const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b, float* d_h0,
+                                   float* d_c0, void* workspace, void* stream) {
+  return lstm_backward_impl(items, ratings, user_off, slots, n_users, t0, T, table, n_items, emb_dim, hidden, nullptr, w_hh, saved,
+                            h_out, h0, c0, g_h, g_hT, g_cT, d_w_ih, d_w_hh, d_b, d_h0, d_c0, nullptr, workspace, nullptr, stream);
+}
+
+extern "C" int recnn_lstm_backward_table(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots,
+                                         int n_users, int t0, int T, const float* table, int n_items, int emb_dim, int hidden,
+                                         const float* w_ih, const float* w_hh, const void* saved, const float* h_out, const float* h0,
+                                         const float* c0, const float* g_h, const float* g_hT, const float* g_cT, float* d_w_ih,
+                                         float* d_w_hh, float* d_b, float* d_h0, float* d_c0, float* d_table, void* workspace,
+                                         void* table_workspace, void* stream) {
+  RECNN_REQUIRE(d_table, "lstm_backward_table: null pointer (d_table; recnn_lstm_backward is the call without it)");
+  return lstm_backward_impl(items, ratings, user_off, slots, n_users, t0, T, table, n_items, emb_dim, hidden, w_ih, w_hh, saved, h_out,
+                            h0, c0, g_h, g_hT, g_cT, d_w_ih, d_w_hh, d_b, d_h0, d_c0, d_table, workspace, table_workspace, stream);
 }
 
 extern "C" int recnn_seq_collect_bwd(const float* g_state, const float* g_next_state, int n_users, int T, int hidden,

@@ -439,12 +439,18 @@ class SeqEnv(StoreEnv):
                     if buffer.len() >= self.max_buf_size:
                         yield self._hand_out(buffer)
 
-    def user_batch(self, user_ids, steps):
+    def user_batch(self, user_ids, steps, table=None):
         """{"state", "action", "reward", "next_state", "done", "meta"} for the users `user_ids` and the kept `steps` (strictly
         increasing, 1 <= step < min(sizes) - 1): exactly the rows the generator would put into the buffer for them, U per step in
         the order k * U + u, without going through the buffer.  When grad mode is on and a parameter of the encoder requires
         grad, `state` and `next_state` are attached to the encoder's graph (`lstm_encode_train` + `seq_collect_rows`): a loss on
-        them back-propagates through time into the encoder's weights.  Otherwise they are the detached rows of `lstm_encode`."""
+        them back-propagates through time into the encoder's weights.  Otherwise they are the detached rows of `lstm_encode`.
+
+        `table` (default: the env's own embedding table, frozen) is a contiguous float32 GPU tensor of the env table's shape that
+        is read INSTEAD of it -- a trainable copy of the embeddings, say.  When it requires grad, `state` / `next_state` are
+        attached to it as well (`lstm_encode_train(..., train_table=True)`): their gradients reach `table.grad` through the
+        encoder, also with every encoder parameter frozen.  The `action` rows are gathered from it and stay non-differentiable:
+        a value loss's gradient with respect to `action` is not sent back (the update steps return state gradients only)."""
         from ..nn import functional as F_hip
         st = self.store
         ids = list(user_ids)
@@ -459,8 +465,15 @@ class SeqEnv(StoreEnv):
         if steps[0] < 1 or steps[-1] >= n_steps:
             raise ValueError(f"SeqEnv.user_batch: steps must lie in 1 .. {n_steps - 1} (the shortest history has "
                              f"{int(sizes.min())} elements)")
-        h, _ = F_hip.lstm_encode_train(self.state_encoder, st, self._table, slots, steps[-1] + 1)
-        state, action, reward, next_state = F_hip.seq_collect_rows(h, steps, st, self._table, slots)
+        tbl = self._table
+        if table is not None:
+            if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
+                    and table.shape == tbl.shape and table.device == tbl.device):
+                raise ValueError(f"SeqEnv.user_batch: table must be a contiguous float32 tensor of shape {tuple(tbl.shape)} on "
+                                 f"{tbl.device}")
+            tbl = table
+        h, _ = F_hip.lstm_encode_train(self.state_encoder, st, tbl, slots, steps[-1] + 1, train_table=tbl.requires_grad)
+        state, action, reward, next_state = F_hip.seq_collect_rows(h, steps, st, tbl.detach(), slots)
         meta = {"sizes": torch.from_numpy(sizes.copy()).float().to(self.device), "users": ids, "step": steps, "rows": state.shape[0]}
         return {"state": state, "action": action, "reward": reward, "next_state": next_state,
                 "done": torch.zeros(state.shape[0], device=state.device), "meta": meta}

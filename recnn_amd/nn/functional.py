@@ -1406,7 +1406,8 @@ def _lstm_call_args(name, lstm, store, table, slots, T, h0c0, t0):
 
 class LSTMEncodeFunction(torch.autograd.Function):
     """(h, h_T, c_T) of the encode chain with the gates and cell states recorded, and backward through time for them
-    (`recnn_lstm_encode_train` / `recnn_lstm_backward`).  Differentiable in the four weights and in h0 / c0; once."""
+    (`recnn_lstm_encode_train` / `recnn_lstm_backward`).  Differentiable in the four weights, in h0 / c0 and in the embedding
+    `table` (`recnn_lstm_backward_table`: the dense [n_items, E] gradient, allocated only when `needs_input_grad` asks for it); once."""
 
     @staticmethod
     def forward(ctx, w_ih, w_hh, b_ih, b_hh, h0, c0, store, table, slots_d, T, t0):
@@ -1426,14 +1427,14 @@ class LSTMEncodeFunction(torch.autograd.Function):
         ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
         ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None and is passed as NULL
         ctx.has_h0 = h0 is not None
-        ctx.save_for_backward(w_hh, table, slots_d, saved, h, *((h0, c0) if h0 is not None else ()))
+        ctx.save_for_backward(w_hh, table, slots_d, saved, h, w_ih, *((h0, c0) if h0 is not None else ()))
         return h, hT, cT
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_h, g_hT, g_cT):
-        w_hh, table, slots_d, saved, h = ctx.saved_tensors[:5]
-        h0, c0 = ctx.saved_tensors[5:] if ctx.has_h0 else (None, None)
+        w_hh, table, slots_d, saved, h, w_ih = ctx.saved_tensors[:6]
+        h0, c0 = ctx.saved_tensors[6:] if ctx.has_h0 else (None, None)
         U, T, t0, E, H = ctx.dims
         store, dev = ctx.store, h.device
         need = ctx.needs_input_grad
@@ -1446,33 +1447,47 @@ class LSTMEncodeFunction(torch.autograd.Function):
         d_b = new(4 * H) if need[2] or need[3] else None
         d_h0 = new(U, H) if need[4] else None
         d_c0 = new(U, H) if need[5] else None
+        d_table = new(table.shape[0], E) if need[7] else None
         ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
-        L.call("recnn_lstm_backward", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
-               L.ptr(table), table.shape[0], E, H, L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(c0), L.ptr(g_h),
-               L.ptr(g_hT), L.ptr(g_cT), L.ptr(d_w_ih), L.ptr(d_w_hh), L.ptr(d_b), L.ptr(d_h0), L.ptr(d_c0), L.ptr(ws),
-               L.current_stream())
+        head = (L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T, L.ptr(table),
+                table.shape[0], E, H)
+        mid = (L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(c0), L.ptr(g_h), L.ptr(g_hT), L.ptr(g_cT), L.ptr(d_w_ih),
+               L.ptr(d_w_hh), L.ptr(d_b), L.ptr(d_h0), L.ptr(d_c0))
+        if d_table is None:
+            L.call("recnn_lstm_backward", *head, *mid, L.ptr(ws), L.current_stream())
+        else:
+            tws = L.workspace("recnn_lstm_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
+            L.call("recnn_lstm_backward_table", *head, L.ptr(w_ih), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
         return (d_w_ih, d_w_hh, d_b if need[2] else None, (d_b.clone() if need[2] else d_b) if need[3] else None, d_h0, d_c0,
-                None, None, None, None, None)
+                None, d_table, None, None, None)
 
 
-def lstm_encode_train(lstm, store, table, slots, T, h0c0=None, *, t0=0):
+def lstm_encode_train(lstm, store, table, slots, T, h0c0=None, *, t0=0, train_table=False):
     """`lstm_encode` with a graph: the same arguments, checks and return value (h, (h_T, c_T)) -- bit for bit the same numbers
     under either variant -- differentiable with respect to weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, and to h0 / c0 when
     they require grad, so truncated BPTT over calls with `t0` moved on works: carry (h_T, c_T) into the next call.
 
     The forward also records the gate activations and cell states (5 U T H floats, U rounded up to 16); the backward is one HIP
     launch chain backward through time plus the weight-gradient launches per chunk of steps (csrc/seq_bwd.hip), in fixed
-    summation orders: equal calls give equal gradients bit for bit.  It is once differentiable.  Gradients with respect to the
-    embedding table are not computed: a `table` that requires grad is refused with RecnnHipError.  Under `torch.no_grad()`, or
-    when nothing requires grad, this IS `lstm_encode`: nothing is recorded."""
-    if isinstance(table, torch.Tensor) and table.requires_grad:
+    summation orders: equal calls give equal gradients bit for bit.  It is once differentiable.
+
+    The embedding table: by default a `table` that requires grad is refused with RecnnHipError (pass `table.detach()` to keep the
+    embeddings frozen).  With `train_table=True` the call is differentiable in `table` as well when it requires grad -- even with
+    every encoder parameter frozen --: the backward adds one contraction launch per chunk of steps and one deterministic
+    scatter-sum over the item ids, and `table.grad` receives the dense [n_items, E] gradient, exact zeros in the
+    rows of items the batch's steps do not hold.  The weight gradients, dh0 and dc0 keep their bits.
+
+    Under `torch.no_grad()`, or when nothing requires grad, this IS `lstm_encode`: nothing is recorded."""
+    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
         raise L.RecnnHipError("lstm_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
-                              "not computed; pass table.detach()")
+                              "computed only on request; pass train_table=True to train it, or table.detach()")
     dev, E, H, U, T, t0, slots, h0, c0 = _lstm_call_args("lstm_encode_train", lstm, store, table, slots, T, h0c0, t0)
     params = (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
     live = [p for p in params if p.requires_grad] + [t for t in (h0, c0) if t is not None and t.requires_grad]
+    if table.requires_grad:                               # (only with train_table)
+        live.append(table)
     if not torch.is_grad_enabled() or not live:
-        return lstm_encode(lstm, store, table, slots, T, None if h0 is None else (h0, c0), t0=t0)
+        return lstm_encode(lstm, store, table.detach(), slots, T, None if h0 is None else (h0, c0), t0=t0)
     slots_d = torch.from_numpy(slots).to(dev)
     h, hT, cT = LSTMEncodeFunction.apply(*params, h0, c0, store, table, slots_d, T, t0)
     return h, (hT, cT)

@@ -11,7 +11,12 @@ Also reports max |hip - torch| over h.  Prints one JSON line.
   --backward   training instead (csrc/seq_bwd.hip): `lstm_encode_train` forward + backward of the loss h.sum() (every
                step live) against torch.nn.LSTM forward + backward of the same loss, the training forward alone against the inference
                encode, and max |hip - torch| relative to max |torch| per weight gradient.  Same shapes, same timing method.
-usage: python tools/seq_bench.py [--quick] [--repeats 5] [--backward] [--out profiles/seq_bench.json]"""
+  --backward --table-grad   the embedding table trained as well: `lstm_encode_train(..., train_table=True)` forward +
+               backward with `table.requires_grad` against the same call with the table frozen, and against eager torch.nn.LSTM
+               over `table[idx]` with `table.requires_grad` on the same GPU (here the gather IS timed: it is part of the graph);
+               max |hip - torch| of the table gradient relative to max |torch|, and how many table rows the batch touches.
+               Default --out: profiles/seq_table_grad_bench.json.
+usage: python tools/seq_bench.py [--quick] [--repeats 5] [--backward [--table-grad]] [--out profiles/seq_bench.json]"""
 import argparse
 import json
 import os
@@ -37,7 +42,7 @@ def median_ms(fn, repeats):
     return float(np.median(times))
 
 
-def case(U, T, E, H, repeats, dev, backward=False):
+def case(U, T, E, H, repeats, dev, backward=False, table_grad=False):
     from recnn_amd.data.store import ReplayStore
     from recnn_amd.nn import functional as F
     rng = np.random.default_rng(U)
@@ -57,6 +62,8 @@ def case(U, T, E, H, repeats, dev, backward=False):
     x = torch.cat([table[idx], rts[..., None]], 2).contiguous()
     res = {"U": U, "T": T, "E": E, "H": H}
     out = {}
+    if table_grad:
+        return table_grad_case(res, lstm, store, table, slots, idx, rts, T, repeats)
     if backward:
         return backward_case(res, lstm, store, table, slots, x, T, repeats)
     for variant in ("fused", "chunked"):
@@ -102,18 +109,54 @@ def backward_case(res, lstm, store, table, slots, x, T, repeats):
     return res
 
 
+def table_grad_case(res, lstm, store, table, slots, idx, rts, T, repeats):
+    from recnn_amd.nn import functional as F
+    P = table.clone().requires_grad_(True)
+    grads = {}
+
+    def hip_step(tbl):
+        lstm.zero_grad(set_to_none=True)
+        P.grad = None
+        F.lstm_encode_train(lstm, store, tbl, slots, T, train_table=tbl.requires_grad)[0].sum().backward()
+        grads["hip"] = P.grad
+
+    def torch_step():
+        lstm.zero_grad(set_to_none=True)
+        P.grad = None
+        lstm(torch.cat([P[idx], rts[..., None]], 2))[0].sum().backward()
+        grads["torch"] = P.grad
+
+    res["hip_fwd_bwd_table_frozen_ms"] = median_ms(lambda: hip_step(table), repeats)
+    res["hip_fwd_bwd_table_grad_ms"] = median_ms(lambda: hip_step(P), repeats)
+    res["torch_fwd_bwd_table_grad_ms"] = median_ms(torch_step, repeats)
+    res["table_grad_added_ms"] = res["hip_fwd_bwd_table_grad_ms"] - res["hip_fwd_bwd_table_frozen_ms"]   # a difference of two medians
+    res["table_grad_added_fraction"] = res["table_grad_added_ms"] / res["hip_fwd_bwd_table_frozen_ms"]
+    res["torch_over_hip_fwd_bwd_table_grad"] = res["torch_fwd_bwd_table_grad_ms"] / res["hip_fwd_bwd_table_grad_ms"]
+    res["table_grad_rel_diff_vs_torch"] = float((grads["hip"] - grads["torch"]).abs().max() / grads["torch"].abs().max())
+    res["table_rows_touched"] = int((grads["hip"].abs().amax(1) > 0).sum())
+    res["n_items"] = int(table.shape[0])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="T = 100 instead of 1000")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--backward", action="store_true", help="time the training forward + backward (DESIGN.md 15)")
+    ap.add_argument("--table-grad", action="store_true", help="with --backward: train the embedding table as well (DESIGN.md 18)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.table_grad and not a.backward:
+        ap.error("--table-grad goes with --backward")
+    if a.table_grad and a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "seq_table_grad_bench.json")
     dev = torch.device("cuda")
     T = 100 if a.quick else 1000
-    res = {"tool": "seq_bench --backward" if a.backward else "seq_bench", "device": torch.cuda.get_device_name(0),
+    tool = "seq_bench --backward --table-grad" if a.table_grad else "seq_bench --backward" if a.backward else "seq_bench"
+    res = {"tool": tool, "device": torch.cuda.get_device_name(0),
            "arch": torch.cuda.get_device_properties(0).gcnArchName,      # (the marketing name may read generic; the arch does not)
-           "lib": os.environ.get("RECNN_HIP_LIB", "in-tree"), "cases": [case(U, T, 128, 256, a.repeats, dev, a.backward) for U in (25, 256)]}
+           "lib": os.environ.get("RECNN_HIP_LIB", "in-tree"), "cases": [case(U, T, 128, 256, a.repeats, dev, a.backward, a.table_grad)
+                                                                       for U in (25, 256)]}
     line = json.dumps(res)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -918,6 +918,60 @@ int recnn_lstm_backward_table(const int32_t* items, const float* ratings, const 
 int recnn_seq_collect_bwd(const float* g_state, const float* g_next_state, int n_users, int T, int hidden, const int32_t* steps,
                           int n_steps, float* g_h, void* stream);
 
+/* A GRU as the state encoder (csrc/gru.hip): the recnn_lstm_* family for torch.nn.GRU(emb_dim + 1, hidden), one layer,
+ * one direction, gate order r, z, n, weights read in place: w_ih float[3 hidden, emb_dim + 1], w_hh float[3 hidden, hidden],
+ * b_ih / b_hh float[3 hidden];
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z = sigmoid(W_iz x + b_iz + W_hz h + b_hz), n = tanh(W_in x + b_in + r (W_hn h + b_hn)),
+ *   h' = (1 - z) n + z h.
+ * The store, the input of a step, t0 / T, the shape limits (emb_dim a multiple of 8 up to 128, hidden a multiple of 16 up to 256), the
+ * two variants (bit-identical), the alignment rules and the independence of a user's result from the batch and from how its steps are
+ * cut into calls are those of recnn_lstm_encode.  There is no cell state: steps run from h0 float[n_users, hidden] (NULL: zeros);
+ * h_out float[n_users, T, hidden]; h_T float[n_users, hidden] (may alias h0).  With tiles = ceil(n_users / 16) and
+ * Tc = min(T, 32):
+ *   recnn_gru_workspace_bytes        variant 1: tiles * Tc * (hidden / 16) * 3 * 64 * 16 (r, z and the input half of n per step of a
+ *                                    chunk, accumulator layout); variant 0: 0.
+ *   recnn_gru_train_workspace_bytes  saved_bytes = tiles * T * (hidden / 16) * 4 * 64 * 16 (r, z, n and hn = W_hn h + b_hn per user,
+ *                                    step and hidden unit; layout private to the library);
+ *                                    bwd_bytes = 12 hidden^2 (W_hh^T) + round16(4 n_users hidden) (the dh hand-over)
+ *                                                + tiles * 16 * Tc * 4 hidden * 4 (one chunk of [da_r | da_z | da_n | da_hn]).
+ *   recnn_gru_table_grad_workspace_bytes  round256(12 emb_dim hidden) (packed W_ih^T) + 2 round256(4 n_users T emb_dim) (dX and the
+ *                                    piece partials) + the inverted index: round256(4 n_items) + round256(4 (n_items + 1))
+ *                                    + 3 round256(4 n_users T).  n_users * T < 2^31.
+ * All three are host-only.
+ *
+ * recnn_gru_encode_train is recnn_gru_encode -- the same h_out and h_T bit for bit, either variant -- that also writes `saved`.
+ * recnn_gru_backward is backward through time over the steps of ONE such call (same store, slots, t0, T, table, w_hh, h0; `saved` and
+ * `h_out` as that call wrote them).  Upstream gradients, each may be NULL (zeros): g_h float[n_users, T, hidden], g_hT
+ * float[n_users, hidden].  Outputs, each may be NULL (not wanted), written, not added to: d_w_ih float[3 hidden, emb_dim + 1], d_w_hh
+ * float[3 hidden, hidden], d_b_ih and d_b_hh float[3 hidden] -- two tensors: they agree in their first 2 hidden entries and differ in
+ * the last hidden, because b_hn sits inside the reset product --, d_h0 float[n_users, hidden].  With all four weight outputs NULL the
+ * weight-gradient launches are skipped.  `workspace`: bwd_bytes, 16-byte aligned.  T >= 1.
+ * recnn_gru_backward_table is recnn_gru_backward -- the same bits in the outputs they share -- that also writes d_table
+ * float[n_items, emb_dim] (required; EVERY row, exact zeros for items the call's positions do not hold) as
+ * recnn_lstm_backward_table does, with da = [da_r | da_z | da_n]; w_ih is read in place (its rating column is not used).
+ * Fixed summation orders, no float atomics: equal calls give equal bits.  Errors: RECNN_E_INVALID with a message, before any launch. */
+int recnn_gru_workspace_bytes(int n_users, int T, int hidden, int variant, int64_t* bytes);
+int recnn_gru_encode(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users, int t0,
+                     int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih, const float* w_hh,
+                     const float* b_ih, const float* b_hh, const float* h0, float* h_out, float* h_T, int variant, void* workspace,
+                     void* stream);
+int recnn_gru_train_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int variant, int64_t* saved_bytes,
+                                    int64_t* bwd_bytes);
+int recnn_gru_encode_train(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                           int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
+                           const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, float* h_out, float* h_T,
+                           int variant, void* workspace, void* saved, void* stream);
+int recnn_gru_backward(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users, int t0,
+                       int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_hh, const void* saved,
+                       const float* h_out, const float* h0, const float* g_h, const float* g_hT, float* d_w_ih, float* d_w_hh,
+                       float* d_b_ih, float* d_b_hh, float* d_h0, void* workspace, void* stream);
+int recnn_gru_table_grad_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_items, int64_t* bytes);
+int recnn_gru_backward_table(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                             int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
+                             const float* w_hh, const void* saved, const float* h_out, const float* h0, const float* g_h,
+                             const float* g_hT, float* d_w_ih, float* d_w_hh, float* d_b_ih, float* d_b_hh, float* d_h0,
+                             float* d_table, void* workspace, void* table_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

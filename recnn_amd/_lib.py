@@ -253,6 +253,13 @@ SIGNATURES = {
     "recnn_lstm_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
     "recnn_lstm_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 18),
     "recnn_seq_collect_bwd": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "recnn_gru_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_gru_encode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 7 + [_I, _P, _P]),
+    "recnn_gru_train_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L), C.POINTER(_L)]),
+    "recnn_gru_encode_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 7 + [_I, _P, _P, _P]),
+    "recnn_gru_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 13),
+    "recnn_gru_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_gru_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 16),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

@@ -19,6 +19,7 @@
 //                     no partial sums between workgroups.  The rating column of dW_ih and db are rank-1 / plain sums on the VALU
 //                     of the same stage.  Chunks are added into dW in launch order (last chunk first).  No atomics anywhere.
 //                     Only the rows of real users are walked: the clamped rows of a partly filled tile give nothing.
+//                     (The kernels of this and of the table gradient live in seq_grad.h, shared with the GRU encoder of gru.hip.)
 //                     (dw_tile.h / gemm.h are bf16 tiles; the gradients here are exact f32, so they are not reused.)
 //   table gradient   (recnn_lstm_backward_table only) d_table[item] = sum of dX[u, t, 0:E] over the call's positions (u, t) that hold
 //                     `item`, dX[u, t, n] = sum_m da[u, t, m] W_ih[m, n].  dX: one launch per chunk after its chain launch, a grid
@@ -36,8 +37,7 @@
 //                     (untouched items: exact zeros).  No float atomics.  Ids outside the table are in no list.
 //   collect backward  g_h[u, t] = g_next_state[k U + u] where steps[k] == t, plus g_state[k' U + u] where steps[k'] == t + 1: a
 //                     gather over 16-byte chunks of g_h (flat_walk.h), each chunk summing its two or fewer sources.
-#include "scatter_index.h"
-#include "seq_lstm.h"
+#include "seq_grad.h"
 
 namespace {
 
@@ -272,274 +272,6 @@ __global__ __launch_bounds__(NT) void lstm_bwd_chain_kernel(const BwdArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------ weight gradients
-constexpr int DW_T = 64;            // output tile, rows (of 4H) and columns (of H or E)
-constexpr int DW_S = 16;            // samples per stage
-constexpr int DW_LD = DW_T + PAD;
-
-struct DwArgs {
-  SeqStore s;
-  int t0;                           // the call's step 0 is position t0 of a history
-  int U, T, H, tb, Tc, da_T;
-  const float* da;
-  const float *h_out, *h0;          // dW_hh: X rows are h_{t-1}: h_out[u, t - 1], h0[u] (NULL: zeros) at the call's step 0
-  float* out;                       // [4H][ldo], columns 0 .. N - 1
-  int ldo, N;
-  float *d_wr, *d_b;                // dW_ih only: the rating column (stride ldo) and db; NULL: not wanted
-  int accumulate;                   // add to out / d_wr / d_b (a later launch of the same call) or write them
-};
-
-// grid (4H / 64, ceil(N / 64)), 256 threads: wave w owns rows 16 w .. 16 w + 15 of the tile and its four 16-column tiles
-template <bool IH>
-__global__ __launch_bounds__(256) void lstm_dw_kernel(const DwArgs a) {
-  __shared__ __attribute__((aligned(16))) float As[2][DW_S][DW_LD];
-  __shared__ __attribute__((aligned(16))) float Xs[2][DW_S][DW_LD];
-  __shared__ float Rs[2][DW_S];
-  const int H = a.H, G = 4 * H, N = a.N;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * DW_T, n0 = blockIdx.y * DW_T;
-  const int S = a.U * a.Tc, nb = (S + DW_S - 1) / DW_S;
-  const int sr = tid >> 4, sc = tid & 15;     // the stager: sample row sr of a stage, 16-byte chunk sc of both operands
-  const bool xcol = n0 + 4 * sc < N;          // (N is a multiple of 4)
-  const bool extras = IH && blockIdx.y == 0 && (a.d_wr || a.d_b);
-
-  auto fetch = [&](int b, float4& av, float4& xv, float& rv) {
-    const int s = b * DW_S + sr;
-    av = make_float4(0.f, 0.f, 0.f, 0.f);
-    xv = av;
-    rv = 0.f;
-    if (s >= S) return;
-    const int u = s / a.Tc, tl = s - u * a.Tc, t = a.tb + tl;
-    av = *(const float4*)(a.da + ((int64_t)u * a.da_T + tl) * G + m0 + 4 * sc);
-    if constexpr (IH) {
-      const int slot = a.s.slots[u];
-      const int64_t off = a.s.user_off[slot];
-      const int len = (int)(a.s.user_off[slot + 1] - off);
-      const int64_t pos = off + max(min(a.t0 + t, len - 1), 0);       // (the host refuses steps past a history's end)
-      if (xcol) xv = len > 0 ? table_chunk(a.s, a.s.items[pos], (n0 >> 2) + sc) : nan4();
-      if (sc == 0) rv = len > 0 ? a.s.ratings[pos] : __builtin_nanf("");
-    } else {
-      if (xcol) {
-        if (t >= 1) xv = *(const float4*)(a.h_out + ((int64_t)u * a.T + t - 1) * H + n0 + 4 * sc);
-        else if (a.h0) xv = *(const float4*)(a.h0 + (int64_t)u * H + n0 + 4 * sc);
-      }
-    }
-  };
-  auto put = [&](int buf, const float4& av, const float4& xv, float rv) {
-    *(float4*)&As[buf][sr][4 * sc] = av;
-    *(float4*)&Xs[buf][sr][4 * sc] = xv;
-    if (IH && sc == 0) Rs[buf][sr] = rv;
-  };
-
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[4] = {zero4, zero4, zero4, zero4};
-  float bsum = 0.f, rsum = 0.f;
-  float4 av, xv;
-  float rv;
-  if (nb > 0) {
-    fetch(0, av, xv, rv);
-    put(0, av, xv, rv);
-  }
-  __syncthreads();
-  for (int b = 0; b < nb; ++b) {
-    const int buf = b & 1;
-    if (b + 1 < nb) fetch(b + 1, av, xv, rv);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float am = As[buf][4 * g + e][16 * wave + r];
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) {
-        if (n0 + 16 * tn >= N) continue;
-        acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(am, Xs[buf][4 * g + e][16 * tn + r], acc[tn], 0, 0, 0);
-      }
-    }
-    if (extras && tid < DW_T) {       // db and the rating column of this tile's rows: plain sums in sample order
-#pragma unroll
-      for (int s = 0; s < DW_S; ++s) {
-        const float d = As[buf][s][tid];
-        bsum += d;
-        rsum = fmaf(d, Rs[buf][s], rsum);
-      }
-    }
-    if (b + 1 < nb) put(buf ^ 1, av, xv, rv);
-    __syncthreads();
-  }
-  if (a.out) {
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
-      const int n = n0 + 16 * tn + r;
-      if (n >= N) continue;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float* o = a.out + (int64_t)(m0 + 16 * wave + 4 * g + i) * a.ldo + n;
-        *o = a.accumulate ? *o + acc[tn][i] : acc[tn][i];
-      }
-    }
-  }
-  if (extras && tid < DW_T) {
-    const int m = m0 + tid;
-    if (a.d_b) a.d_b[m] = a.accumulate ? a.d_b[m] + bsum : bsum;
-    if (a.d_wr) a.d_wr[(int64_t)m * a.ldo] = a.accumulate ? a.d_wr[(int64_t)m * a.ldo] + rsum : rsum;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ table gradient
-// wp[n][m] = w_ih[m][n], n < E: W_ih without its rating column, transposed and packed
-__global__ __launch_bounds__(256) void lstm_wih_pack_kernel(const float* __restrict__ w, int E, int G, float* __restrict__ wp) {
-  flat_walk<1>((int64_t)E * G, [&](int64_t i, Width<1>) {
-    const int n = (int)(i / G), m = (int)(i - (int64_t)n * G);
-    wp[i] = w[(int64_t)m * (E + 1) + n];
-  });
-}
-
-constexpr int DX_S = 16;            // samples per workgroup
-constexpr int DX_WV = 4;            // waves per workgroup
-
-struct DxArgs {
-  int U, T, H, E, tb, Tc, da_T;
-  const float* da;                  // the chunk's [..][da_T][4H]
-  const float* wp;                  // [E][4H]
-  float* dx;                        // [U][T][E]
-};
-
-// grid ceil(U Tc / 16), min(4, ceil(E / 16)) waves: sample s = u Tc + tl of the chunk (u < U: real users only); wave w owns columns 16 w .. 16 w + 15
-// and 16 (w + 4) .. of the 16 samples.  Both operands come straight from global memory, 16 bytes per lane, the next block's loads
-// issued ahead of this block's products (the four waves read the same da rows: they meet in the cache).
-__global__ __launch_bounds__(64 * DX_WV) void lstm_dx_kernel(const DxArgs a) {
-  const int G = 4 * a.H, E = a.E;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int S = a.U * a.Tc, s0 = blockIdx.x * DX_S;
-  const int ntiles = (E + 15) >> 4;
-  if (wave >= ntiles) return;                          // (wave-uniform; the kernel has no barrier)
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  const bool alive = s0 + r < S;
-  const int ua = alive ? (s0 + r) / a.Tc : 0, tla = alive ? s0 + r - ua * a.Tc : 0;
-  const float* arow = a.da + ((int64_t)ua * a.da_T + tla) * G + 4 * g;
-  bool on[2], bl[2];
-  const float* brow[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = (wave + DX_WV * j) * 16 + r;
-    on[j] = wave + DX_WV * j < ntiles;
-    bl[j] = on[j] && n < E;                            // E is a multiple of 8: the last column tile may be half empty
-    brow[j] = a.wp + (int64_t)(bl[j] ? n : 0) * G + 4 * g;
-  }
-  f32x4 acc[2] = {zero4, zero4};
-  f32x4 an = alive ? *(const f32x4*)arow : zero4, bn[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) bn[j] = bl[j] ? *(const f32x4*)brow[j] : zero4;
-  for (int k0 = 0; k0 < G; k0 += 16) {
-    const f32x4 av = an;
-    f32x4 bv[2];
-    const int kn = k0 + 16 < G ? k0 + 16 : k0;
-    an = alive ? *(const f32x4*)(arow + kn) : zero4;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      bv[j] = bn[j];
-      bn[j] = bl[j] ? *(const f32x4*)(brow[j] + kn) : zero4;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[0][e], acc[0], 0, 0, 0);
-      if (on[1]) acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[1][e], acc[1], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if (!bl[j]) continue;
-    const int n = (wave + DX_WV * j) * 16 + r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int s = s0 + 4 * g + i;
-      if (s >= S) continue;
-      const int u = s / a.Tc, tl = s - u * a.Tc;
-      a.dx[((int64_t)u * a.T + a.tb + tl) * E + n] = acc[j][i];
-    }
-  }
-}
-
-// contribution j = u T + t of a call: the item at position t0 + t of user u's history (the encode's clamp; the host refuses steps
-// past a history's end)
-struct StoreId {
-  const int32_t* items;
-  const int64_t* user_off;
-  const int32_t* slots;
-  int T, t0;
-  __device__ int64_t operator()(int j) const {
-    const int u = j / T, t = j - u * T;
-    const int slot = slots[u];
-    const int64_t off = user_off[slot];
-    const int len = (int)(user_off[slot + 1] - off);
-    return len > 0 ? (int64_t)items[off + max(min(t0 + t, len - 1), 0)] : -1;
-  }
-};
-
-constexpr int TG_PIECE = 16;        // scatter-sum: sorted entries per wave in the first pass
-// pass 1: one wave per TG_PIECE sorted entries; the run of each item inside the piece is summed in list order and written at the
-// run's first sorted position.  Lanes own columns lane and lane + 64 (E <= 128).
-__global__ __launch_bounds__(256) void table_piece_kernel(const float* __restrict__ dx, int E, const StoreId id_of,
-                                                          const int* __restrict__ sorted, const int* __restrict__ total_ptr,
-                                                          float* __restrict__ part) {
-  const int total = *total_ptr;
-  const int piece = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int p0 = piece * TG_PIECE;
-  if (p0 >= total) return;
-  const int p1 = min(total, p0 + TG_PIECE);
-  const bool c0 = lane < E, c1 = lane + 64 < E;
-  float a0 = 0.f, a1 = 0.f;
-  int first = p0;
-  int cur = (int)id_of(sorted[p0]);
-  for (int p = p0; p < p1; ++p) {
-    const float* s = dx + (int64_t)sorted[p] * E;
-    if (c0) a0 += s[lane];
-    if (c1) a1 += s[lane + 64];
-    const int nxt = p + 1 < p1 ? (int)id_of(sorted[p + 1]) : -1;
-    if (nxt != cur) {
-      if (c0) part[(int64_t)first * E + lane] = a0;
-      if (c1) part[(int64_t)first * E + lane + 64] = a1;
-      a0 = a1 = 0.f;
-      first = p + 1;
-      cur = nxt;
-    }
-  }
-}
-// pass 2: one wave per item, the pieces of its list in order; an item nothing reached gets zeros
-__global__ __launch_bounds__(256) void table_merge_kernel(const int* __restrict__ start, int n_items, int E, const float* __restrict__ part,
-                                                          float* __restrict__ out) {
-  const int d = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (d >= n_items) return;
-  const int s = start[d], e = start[d + 1];
-  const bool c0 = lane < E, c1 = lane + 64 < E;
-  float a0 = 0.f, a1 = 0.f;
-  if (e > s) {
-    for (int k = s / TG_PIECE; k <= (e - 1) / TG_PIECE; ++k) {
-      const int at = max(s, k * TG_PIECE);
-      if (c0) a0 += part[(int64_t)at * E + lane];
-      if (c1) a1 += part[(int64_t)at * E + lane + 64];
-    }
-  }
-  if (c0) out[(int64_t)d * E + lane] = a0;
-  if (c1) out[(int64_t)d * E + lane + 64] = a1;
-}
-
-// workspace of the table gradient: packed W_ih^T, dX of the whole call, the inverted index, the piece partials (each rounded up to
-// 256 bytes)
-struct TableWs {
-  int64_t wp, dx, index, part, total;    // byte offsets
-};
-inline TableWs table_ws(int n_users, int T, int H, int E, int n_items) {
-  const int64_t M = (int64_t)n_users * T;
-  TableWs w;
-  w.wp = 0;
-  w.dx = scatter_index_round((int64_t)E * 4 * H * 4);
-  w.index = w.dx + scatter_index_round(M * E * 4);
-  w.part = w.index + scatter_index_bytes(M, n_items);
-  w.total = w.part + scatter_index_round(M * E * 4);
-  return w;
-}
-
 // workspace of a backward call: W_hh^T, the dh / dc hand-over buffers, one chunk of da
 struct BwdWs {
   int64_t wt, dh, dc, da, total;    // byte offsets
@@ -599,7 +331,7 @@ extern "C" int recnn_lstm_table_grad_workspace_bytes(int n_users, int T, int hid
   RECNN_LSTM_DIMS_OK("lstm_table_grad_workspace_bytes", emb_dim, hidden);
   RECNN_REQUIRE(n_users >= 0 && T >= 0 && n_items >= 1 && (int64_t)n_users * T < (1LL << 31),
                 "lstm_table_grad_workspace_bytes: need n_users >= 0, T >= 0, n_items >= 1 and n_users * T < 2^31");
-  *bytes = table_ws(n_users, T, hidden, emb_dim, n_items).total;
+  *bytes = table_ws(n_users, T, 4 * hidden, emb_dim, n_items).total;
   return 0;
 }
 
@@ -650,28 +382,11 @@ static int lstm_backward_impl(const int32_t* items, const float* ratings, const 
   d.s = SeqStore{items, ratings, user_off, slots, n_users, table, n_items, emb_dim};
   d.t0 = t0;
   d.U = n_users; d.T = T; d.H = H; d.da_T = a.da_T;
+  d.G = G; d.lda = G; d.msplit = G; d.mshift = 0;
   d.da = a.da;
   // the table gradient's operands that do not depend on da: the packed W_ih^T and the inverted index of the call's positions
-  const StoreId id_of{items, user_off, slots, T, t0};
-  DxArgs dx{};
-  ScatterIndex ix{};
-  float* part = nullptr;
-  int M = 0;                                           // positions of the call (d_table only: checked below 2^31 above)
-  if (d_table) {
-    M = n_users * T;
-    const TableWs tw = table_ws(n_users, T, H, emb_dim, n_items);
-    char* tp = (char*)table_workspace;
-    dx.U = n_users; dx.T = T; dx.H = H; dx.E = emb_dim; dx.da_T = a.da_T;
-    dx.da = a.da;
-    dx.wp = (const float*)(tp + tw.wp);
-    dx.dx = (float*)(tp + tw.dx);
-    part = (float*)(tp + tw.part);
-    char* ip = tp + tw.index;
-    ix = scatter_index_carve(ip, M, n_items);
-    hipLaunchKernelGGL(lstm_wih_pack_kernel, dim3(grid_for((int64_t)emb_dim * G, 256, 2048)), dim3(256), 0, s, w_ih, emb_dim, G,
-                       (float*)(tp + tw.wp));
-    RECNN_HIP(scatter_index_build(ix, id_of, M, n_items, s));
-  }
+  TableGrad tg{};
+  if (d_table) RECNN_HIP(table_grad_prepare(tg, d.s, t0, T, G, G, a.da_T, a.da, w_ih, table_workspace, s));
   const int nchunks = (T + LSTM_CHUNK - 1) / LSTM_CHUNK;
   for (int ci = nchunks - 1; ci >= 0; --ci) {
     a.tb = ci * LSTM_CHUNK;
@@ -683,11 +398,7 @@ static int lstm_backward_impl(const int32_t* items, const float* ratings, const 
     const dim3 grid(user_tiles(n_users));
     if (two) hipLaunchKernelGGL((lstm_bwd_chain_kernel<2>), grid, dim3(NT), lds, s, a);
     else hipLaunchKernelGGL((lstm_bwd_chain_kernel<1>), grid, dim3(NT), lds, s, a);
-    if (d_table) {
-      dx.tb = a.tb; dx.Tc = a.Tc;
-      const int dx_waves = (emb_dim + 15) / 16 < DX_WV ? (emb_dim + 15) / 16 : DX_WV;      // E <= 48: no wave without a column tile
-      hipLaunchKernelGGL(lstm_dx_kernel, dim3((n_users * a.Tc + DX_S - 1) / DX_S), dim3(64 * dx_waves), 0, s, dx);
-    }
+    if (d_table) table_grad_chunk(tg, a.tb, a.Tc, s);
     if (!want_w) continue;
     d.tb = a.tb; d.Tc = a.Tc;
     d.accumulate = ci != nchunks - 1;
@@ -695,23 +406,17 @@ static int lstm_backward_impl(const int32_t* items, const float* ratings, const 
       DwArgs x = d;
       x.h_out = h_out; x.h0 = h0;
       x.out = d_w_hh; x.ldo = H; x.N = H;
-      hipLaunchKernelGGL((lstm_dw_kernel<false>), dim3(G / DW_T, (H + DW_T - 1) / DW_T), dim3(256), 0, s, x);
+      hipLaunchKernelGGL((seq_dw_kernel<false, false>), dim3(G / DW_T, (H + DW_T - 1) / DW_T), dim3(256), 0, s, x);
     }
     if (d_w_ih || d_b) {
       DwArgs x = d;
       x.out = d_w_ih; x.ldo = emb_dim + 1; x.N = emb_dim;
       x.d_wr = d_w_ih ? d_w_ih + emb_dim : nullptr;
       x.d_b = d_b;
-      hipLaunchKernelGGL((lstm_dw_kernel<true>), dim3(G / DW_T, d_w_ih ? (emb_dim + DW_T - 1) / DW_T : 1), dim3(256), 0, s, x);
+      hipLaunchKernelGGL((seq_dw_kernel<true, false>), dim3(G / DW_T, d_w_ih ? (emb_dim + DW_T - 1) / DW_T : 1), dim3(256), 0, s, x);
     }
   }
-  if (d_table) {
-    // (dropped ids are not in the lists: the pieces cover the first start[n_items] sorted entries)
-    const int pieces = (M + TG_PIECE - 1) / TG_PIECE;
-    hipLaunchKernelGGL(table_piece_kernel, dim3((pieces + 3) / 4), dim3(256), 0, s, dx.dx, emb_dim, id_of, ix.sorted, ix.start + n_items,
-                       part);
-    hipLaunchKernelGGL(table_merge_kernel, dim3((n_items + 3) / 4), dim3(256), 0, s, ix.start, n_items, emb_dim, part, d_table);
-  }
+  if (d_table) table_grad_finish(tg, d_table, s);
   return recnn_check_hip(hipGetLastError(), d_table ? "lstm_backward_table" : "lstm_backward");
 }
 

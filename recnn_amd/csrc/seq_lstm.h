@@ -1,5 +1,6 @@
 // seq_lstm.h -- what the inference encode (seq.hip) and the training encode and its backward (seq_bwd.hip) share: the replay-store
 // view, the LSTM chain kernel and its launch sequence.  seq.hip describes the chain; SAVE adds the stores the backward reads.
+// The GRU encoder (gru.hip) takes the store view, the stager, the input links and the shape checks from here.
 #pragma once
 #include "flat_walk.h"
 
@@ -64,7 +65,9 @@ struct Stager {
 
 // first E + 1 links of the chains of hidden tile jt: acc[q] = fma(rating, w_ih[row, E], b_ih[row] + b_hh[row]) + sum_k x[k] w_ih[row, k]
 // with row = q H + 16 jt + r.  xs: LDS [16][ldx] (columns E .. KX - 1 zero), rs: LDS [16].
-template <int TPW>
+// NG = 4: the LSTM's gates.  NG = 3: the GRU's r, z and the input half of n (gru.hip), whose chain starts from b_ih alone: b_hh of n
+// belongs to the h products, inside the reset product.  acc[.][3] is not touched then.
+template <int TPW, int NG = 4>
 __device__ __forceinline__ void input_links(const EncArgs& a, const float* xs, const float* rs, int ldx, const int (&jt)[TPW],
                                             const bool (&on)[TPW], f32x4 (&acc)[TPW][4], int lane) {
   const int r = lane & 15, g = lane >> 4, E = a.s.E, H = a.H, K1 = E + 1;
@@ -72,9 +75,9 @@ __device__ __forceinline__ void input_links(const EncArgs& a, const float* xs, c
   for (int j = 0; j < TPW; ++j) {
     if (!on[j]) continue;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NG; ++q) {
       const int row = q * H + jt[j] * 16 + r;
-      const float b = a.b_ih[row] + a.b_hh[row], wr = a.w_ih[(int64_t)row * K1 + E];
+      const float b = (NG == 3 && q == 2) ? a.b_ih[row] : a.b_ih[row] + a.b_hh[row], wr = a.w_ih[(int64_t)row * K1 + E];
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[j][q][i] = fmaf(rs[4 * g + i], wr, b);
     }
@@ -85,16 +88,16 @@ __device__ __forceinline__ void input_links(const EncArgs& a, const float* xs, c
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
       if (!on[j]) continue;
-      f32x4 bv[4];
+      f32x4 bv[NG];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int q = 0; q < NG; ++q) {
         const int row = q * H + jt[j] * 16 + r;
         bv[q] = kin ? (f32x4)(*(const f32x4u*)(a.w_ih + (int64_t)row * K1 + k0 + 4 * g)) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[j][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[q][e], acc[j][q], 0, 0, 0);
+        for (int q = 0; q < NG; ++q) acc[j][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[q][e], acc[j][q], 0, 0, 0);
     }
   }
 }

@@ -327,20 +327,25 @@ class SeqEnv(StoreEnv):
     {"state", "action", "reward", "next_state", "done", "meta"} (full tensors, zeros beyond meta["rows"]; `done` is all zeros, added
     so that `recnn.nn.ddpg_update` runs on the batch unchanged) and the buffer starts over.
 
-    All T steps of a user batch are ONE HIP launch chain (`recnn_amd.nn.functional.lstm_encode`), the kept rows one more
-    (`seq_collect`); the padded [U, Lmax, E] tensor is not built on this path.  `state_encoder` must be a single-layer
-    unidirectional `torch.nn.LSTM(E + 1, H)` on the GPU; its `batch_first` is ignored (users are always the batch).
+    All T steps of a user batch are ONE HIP launch chain (`recnn_amd.nn.functional.lstm_encode` or `gru_encode`), the kept rows one
+    more (`seq_collect`); the padded [U, Lmax, E] tensor is not built on this path.  `state_encoder` must be a single-layer
+    unidirectional `torch.nn.LSTM(E + 1, H)` or `torch.nn.GRU(E + 1, H)` on the GPU; its `batch_first` is ignored (users are always
+    the batch).  A module of any other type (a `torch.nn.RNN`, say) is refused at construction, naming the type.
 
     The encoder is a FROZEN feature extractor for the replay buffer: the states in the buffer carry no autograd graph, and the
     encoder's weights are read live, so a caller may change them between batches.  `user_batch(user_ids, steps)` is the way to
     TRAIN it: the same rows for one user batch, on policy, with `state` / `next_state` attached to the encoder's graph
-    (`recnn_amd.nn.functional.lstm_encode_train`, backward through time in HIP).
+    (`recnn_amd.nn.functional.lstm_encode_train` / `gru_encode_train`, backward through time in HIP).
 
     Default layout: [max_buf_size, H], [max_buf_size, E], [max_buf_size, 1], [max_buf_size, H] with H and E taken from the
     encoder and the embedding table (the reference hard-codes 256 and 128)."""
 
     def __init__(self, path, state_encoder, batch_size=25, device=torch.device("cuda"), layout=None, max_buf_size=1000,
                  num_workers=1, embed_batch=utils.batch_tensor_embeddings, *args, **kwargs):
+        if state_encoder is not None and not isinstance(state_encoder, (torch.nn.LSTM, torch.nn.GRU)):
+            t = type(state_encoder)
+            raise TypeError(f"SeqEnv: state_encoder is a {t.__module__}.{t.__qualname__}; the HIP encoders are a single-layer "
+                            "torch.nn.LSTM(E + 1, H) and a single-layer torch.nn.GRU(E + 1, H)")
         super().__init__(path, min_seq_size=10, embed_batch=embed_batch, *args, **kwargs)
         self.state_encoder = state_encoder
         self.batch_size = batch_size
@@ -428,7 +433,7 @@ class SeqEnv(StoreEnv):
                 if not kept:
                     continue
                 # one encode for every step up to the last kept one (the later steps would not be looked at)
-                h, _ = F_hip.lstm_encode(self.state_encoder, st, self._table, slots, kept[-1] + 1)
+                h = F_hip.state_encode(self.state_encoder, st, self._table, slots, kept[-1] + 1)
                 while kept:
                     if not buffer.room(n_users):
                         yield self._hand_out(buffer)
@@ -443,12 +448,13 @@ class SeqEnv(StoreEnv):
         """{"state", "action", "reward", "next_state", "done", "meta"} for the users `user_ids` and the kept `steps` (strictly
         increasing, 1 <= step < min(sizes) - 1): exactly the rows the generator would put into the buffer for them, U per step in
         the order k * U + u, without going through the buffer.  When grad mode is on and a parameter of the encoder requires
-        grad, `state` and `next_state` are attached to the encoder's graph (`lstm_encode_train` + `seq_collect_rows`): a loss on
-        them back-propagates through time into the encoder's weights.  Otherwise they are the detached rows of `lstm_encode`.
+        grad, `state` and `next_state` are attached to the encoder's graph (`lstm_encode_train` or `gru_encode_train`, whichever
+        the encoder is, + `seq_collect_rows`): a loss on them back-propagates through time into the encoder's weights.  Otherwise
+        they are the detached rows of `lstm_encode` / `gru_encode`.
 
         `table` (default: the env's own embedding table, frozen) is a contiguous float32 GPU tensor of the env table's shape that
         is read INSTEAD of it -- a trainable copy of the embeddings, say.  When it requires grad, `state` / `next_state` are
-        attached to it as well (`lstm_encode_train(..., train_table=True)`): their gradients reach `table.grad` through the
+        attached to it as well (`lstm_encode_train` / `gru_encode_train(..., train_table=True)`): their gradients reach `table.grad` through the
         encoder, also with every encoder parameter frozen.  The `action` rows are gathered from it and stay non-differentiable:
         a value loss's gradient with respect to `action` is not sent back (the update steps return state gradients only)."""
         from ..nn import functional as F_hip
@@ -472,7 +478,7 @@ class SeqEnv(StoreEnv):
                 raise ValueError(f"SeqEnv.user_batch: table must be a contiguous float32 tensor of shape {tuple(tbl.shape)} on "
                                  f"{tbl.device}")
             tbl = table
-        h, _ = F_hip.lstm_encode_train(self.state_encoder, st, tbl, slots, steps[-1] + 1, train_table=tbl.requires_grad)
+        h = F_hip.state_encode(self.state_encoder, st, tbl, slots, steps[-1] + 1, train=True, train_table=tbl.requires_grad)
         state, action, reward, next_state = F_hip.seq_collect_rows(h, steps, st, tbl.detach(), slots)
         meta = {"sizes": torch.from_numpy(sizes.copy()).float().to(self.device), "users": ids, "step": steps, "rows": state.shape[0]}
         return {"state": state, "action": action, "reward": reward, "next_state": next_state,

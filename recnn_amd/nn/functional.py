@@ -1267,28 +1267,45 @@ _lstm_variant = "chunked"
 
 def set_lstm_variant(name: str):
     """How `lstm_encode` schedules the input projection: "fused" into every step, or "chunked" (projected per chunk of steps by a
-    grid-wide launch, the chain launch starts from it).  Both compute the same bits; DESIGN.md 14 has the timings."""
+    grid-wide launch, the chain launch starts from it).  Both compute the same bits; DESIGN.md 14 has the timings.  `gru_encode` and
+    `gru_encode_train` follow the same setting."""
     global _lstm_variant
     if name not in LSTM_VARIANTS:
         raise ValueError(f"unknown LSTM variant {name!r}; choose from {sorted(LSTM_VARIANTS)}")
     _lstm_variant = name
 
 
-def _check_lstm(lstm):
-    """The one recurrent layer the encode kernel implements; anything else is refused by name, never approximated."""
-    for attr, want in (("num_layers", 1), ("bidirectional", False), ("proj_size", 0), ("dropout", 0), ("bias", True)):
-        got = getattr(lstm, attr, want)
+_CELLS = {"lstm": (torch.nn.LSTM, (("num_layers", 1), ("bidirectional", False), ("proj_size", 0), ("dropout", 0), ("bias", True)),
+                   "without projection or dropout", "a torch.nn.GRU goes to gru_encode / gru_encode_train"),
+          "gru": (torch.nn.GRU, (("num_layers", 1), ("bidirectional", False), ("dropout", 0), ("bias", True)),
+                  "without dropout", "a torch.nn.LSTM goes to lstm_encode / lstm_encode_train")}
+
+
+def _check_cell(module, cell):
+    """The one recurrent layer an encode kernel implements; anything else is refused by name, never approximated.  The type comes
+    first: the kernels read 4H (LSTM) or 3H (GRU) weight rows, and a module of the other kind has the same attribute names."""
+    cls, attrs, tail, other = _CELLS[cell]
+    if not isinstance(module, cls):
+        t = type(module)
+        raise L.RecnnHipError(f"{cell}_encode: the state encoder is a {t.__module__}.{t.__qualname__}, not a torch.nn.{cls.__name__} "
+                              f"({other})")
+    for attr, want in attrs:
+        got = getattr(module, attr, want)
         if got != want:
-            raise L.RecnnHipError(f"lstm_encode: {attr}={got!r} is not supported (needs {attr}={want!r}): the HIP encoder is a "
-                                  "single-layer, unidirectional torch.nn.LSTM with biases, without projection or dropout")
-    w = lstm.weight_ih_l0
+            raise L.RecnnHipError(f"{cell}_encode: {attr}={got!r} is not supported (needs {attr}={want!r}): the HIP encoder is a "
+                                  f"single-layer, unidirectional torch.nn.{cls.__name__} with biases, {tail}")
+    w = module.weight_ih_l0
     if not w.is_cuda:
-        raise L.RecnnHipError(f"lstm_encode: the module lives on {w.device} (weight_ih_l0.device); it needs a GPU module "
+        raise L.RecnnHipError(f"{cell}_encode: the module lives on {w.device} (weight_ih_l0.device); it needs a GPU module "
                               "(recnn_amd has no CPU fallback)")
     for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-        p = getattr(lstm, name)
+        p = getattr(module, name)
         if p.dtype != torch.float32 or not p.is_contiguous():
-            raise L.RecnnHipError(f"lstm_encode: {name} must be a contiguous float32 tensor (got {p.dtype})")
+            raise L.RecnnHipError(f"{cell}_encode: {name} must be a contiguous float32 tensor (got {p.dtype})")
+
+
+def _check_lstm(lstm):
+    _check_cell(lstm, "lstm")
 
 
 @torch.no_grad()
@@ -1300,7 +1317,8 @@ def lstm_encode(lstm, store, table, slots, T, h0c0=None, *, t0=0):
 
     Runs under no_grad (`lstm_encode_train` is the same call with a graph); the weights are read live from the module on every call (weight_ih_l0, weight_hh_l0, bias_ih_l0,
     bias_hh_l0, gate order i, f, g, o), state and accumulation are fp32.  Refused with RecnnHipError naming the attribute:
-    num_layers != 1, bidirectional, proj_size != 0, dropout != 0, bias=False, a CPU module.
+    num_layers != 1, bidirectional, proj_size != 0, dropout != 0, bias=False, a CPU module -- and, naming the type, a module that is
+    not a torch.nn.LSTM (a torch.nn.GRU has the same attribute names and 3H weight rows: it goes to `gru_encode`).
 
     `batch_first` is ignored: the users are always the batch and time always runs along a user's own history.  (The
     reference's commented-out SeqEnv feeds [1, U, E + 1] to its encoder, which a batch_first=True LSTM reads as ONE sequence
@@ -1381,15 +1399,16 @@ def seq_collect(h, steps, store, table, slots, views):
 
 # ------------------------------------------------------------------------------------------------------------------------
 # Training the encoder (csrc/seq_bwd.hip): backward through time for the encode chain, a differentiable collect.
-def _lstm_call_args(name, lstm, store, table, slots, T, h0c0, t0):
-    """The checks of `lstm_encode`, for both encode entry points: (dev, E, H, U, T, t0, slots, h0, c0)."""
-    _check_lstm(lstm)
-    dev = lstm.weight_ih_l0.device
+def _encode_call_args(name, cell, module, store, table, slots, T, states, t0):
+    """The checks of `lstm_encode` / `gru_encode`, for the encode entry points: (dev, E, H, U, T, t0, slots, states), `states` the
+    carried tensors as [U, H] each, or None."""
+    _check_cell(module, cell)
+    dev = module.weight_ih_l0.device
     if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()):
         raise L.RecnnHipError(f"{name}: table must be a contiguous float32 GPU tensor")
-    E, H = table.shape[1], lstm.hidden_size
-    if lstm.input_size != E + 1:
-        raise L.RecnnHipError(f"{name}: input_size={lstm.input_size} but the table has {E} columns (needs E + 1: the rating)")
+    E, H = table.shape[1], module.hidden_size
+    if module.input_size != E + 1:
+        raise L.RecnnHipError(f"{name}: input_size={module.input_size} but the table has {E} columns (needs E + 1: the rating)")
     slots = store.checked_slots(slots, name, dev)
     U, T, t0 = len(slots), int(T), int(t0)
     if table.device != dev:
@@ -1398,10 +1417,15 @@ def _lstm_call_args(name, lstm, store, table, slots, T, h0c0, t0):
         raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
     if U and int(store.lengths[slots].min()) < t0 + T:
         raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
-    h0 = c0 = None
-    if h0c0 is not None:
-        h0, c0 = (t.to(dev, torch.float32).reshape(U, H).contiguous() for t in h0c0)
-    return dev, E, H, U, T, t0, slots, h0, c0
+    if states is not None:
+        states = tuple(t.to(dev, torch.float32).reshape(U, H).contiguous() for t in states)
+    return dev, E, H, U, T, t0, slots, states
+
+
+def _lstm_call_args(name, lstm, store, table, slots, T, h0c0, t0):
+    """`_encode_call_args` for the LSTM: (dev, E, H, U, T, t0, slots, h0, c0)."""
+    *head, hc = _encode_call_args(name, "lstm", lstm, store, table, slots, T, h0c0, t0)
+    return (*head, *(hc if hc is not None else (None, None)))
 
 
 class LSTMEncodeFunction(torch.autograd.Function):
@@ -1491,6 +1515,135 @@ def lstm_encode_train(lstm, store, table, slots, T, h0c0=None, *, t0=0, train_ta
     slots_d = torch.from_numpy(slots).to(dev)
     h, hT, cT = LSTMEncodeFunction.apply(*params, h0, c0, store, table, slots_d, T, t0)
     return h, (hT, cT)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# A GRU as the state encoder (csrc/gru.hip): the same path with one carried tensor and three gates.
+@torch.no_grad()
+def gru_encode(gru, store, table, slots, T, h0=None, *, t0=0):
+    """`lstm_encode` for a single-layer unidirectional `torch.nn.GRU(E + 1, H)` on the GPU: the states of the users `slots` after
+    each of the steps t0 .. t0 + T - 1 of their histories, one HIP launch chain, the input of step t being
+    [table[item_t] | rating_t].  Returns (h float32[U, T, H], h_T float32[U, H]).  `h0`: [U, H] or [1, U, H]; default zeros.
+    Carrying h_T into a call with t0 moved on gives bit for bit what one longer call gives; both schedules of `set_lstm_variant`
+    apply and give the same bits.
+
+    Runs under no_grad (`gru_encode_train` is the same call with a graph); the weights are read live from the module (gate order
+    r, z, n; b_hn inside the reset product, as torch.nn.GRU has it), state and accumulation are fp32.  Refused with RecnnHipError
+    naming what is wrong: a module that is not a torch.nn.GRU (an LSTM goes to `lstm_encode`), num_layers != 1, bidirectional,
+    dropout != 0, bias=False, a CPU module, a non-contiguous or non-float32 weight, input_size != E + 1.  `batch_first` is ignored."""
+    dev, E, H, U, T, t0, slots, h0 = _encode_call_args("gru_encode", "gru", gru, store, table, slots, T, None if h0 is None else (h0,), t0)
+    h0 = None if h0 is None else h0[0]
+    h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+    hT = torch.empty(U, H, dtype=torch.float32, device=dev)
+    variant = LSTM_VARIANTS[_lstm_variant]
+    ws = L.workspace("recnn_gru_workspace_bytes", U, T, H, variant, device=dev)
+    slots_d = torch.from_numpy(slots).to(dev)
+    L.call("recnn_gru_encode", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
+           L.ptr(table), table.shape[0], E, H, L.ptr(gru.weight_ih_l0), L.ptr(gru.weight_hh_l0), L.ptr(gru.bias_ih_l0),
+           L.ptr(gru.bias_hh_l0), L.ptr(h0), L.ptr(h), L.ptr(hT), variant, L.ptr(ws), L.current_stream())
+    return h, hT
+
+
+class GRUEncodeFunction(torch.autograd.Function):
+    """(h, h_T) of the GRU encode chain with r, z, n and hn recorded, and backward through time for them (`recnn_gru_encode_train` /
+    `recnn_gru_backward`).  Differentiable in the four weights, in h0 and in the embedding `table` (`recnn_gru_backward_table`: the
+    dense [n_items, E] gradient, allocated only when `needs_input_grad` asks for it); once."""
+
+    @staticmethod
+    def forward(ctx, w_ih, w_hh, b_ih, b_hh, h0, store, table, slots_d, T, t0):
+        dev = w_ih.device
+        U, E, H = slots_d.shape[0], table.shape[1], w_hh.shape[1]
+        variant = LSTM_VARIANTS[_lstm_variant]
+        nsaved, nbwd = C.c_int64(), C.c_int64()
+        L.call("recnn_gru_train_workspace_bytes", U, T, H, E, variant, C.byref(nsaved), C.byref(nbwd))
+        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+        ws = L.workspace("recnn_gru_workspace_bytes", U, T, H, variant, device=dev)
+        h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+        hT = torch.empty(U, H, dtype=torch.float32, device=dev)
+        L.call("recnn_gru_encode_train", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
+               L.ptr(table), table.shape[0], E, H, L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), L.ptr(h0), L.ptr(h), L.ptr(hT),
+               variant, L.ptr(ws), L.ptr(saved), L.current_stream())
+        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
+        ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None and is passed as NULL
+        ctx.has_h0 = h0 is not None
+        ctx.save_for_backward(w_hh, table, slots_d, saved, h, w_ih, *((h0,) if h0 is not None else ()))
+        return h, hT
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h, g_hT):
+        w_hh, table, slots_d, saved, h, w_ih = ctx.saved_tensors[:6]
+        h0 = ctx.saved_tensors[6] if ctx.has_h0 else None
+        U, T, t0, E, H = ctx.dims
+        store, dev = ctx.store, h.device
+        need = ctx.needs_input_grad
+        if g_h is None and g_hT is None:
+            return (None,) * 10
+        g_h, g_hT = (None if g is None else g.to(torch.float32).contiguous() for g in (g_h, g_hT))
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        d_w_ih = new(3 * H, E + 1) if need[0] else None
+        d_w_hh = new(3 * H, H) if need[1] else None
+        d_b_ih = new(3 * H) if need[2] else None
+        d_b_hh = new(3 * H) if need[3] else None
+        d_h0 = new(U, H) if need[4] else None
+        d_table = new(table.shape[0], E) if need[6] else None
+        ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
+        head = (L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T, L.ptr(table),
+                table.shape[0], E, H)
+        mid = (L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(g_h), L.ptr(g_hT), L.ptr(d_w_ih), L.ptr(d_w_hh), L.ptr(d_b_ih),
+               L.ptr(d_b_hh), L.ptr(d_h0))
+        if d_table is None:
+            L.call("recnn_gru_backward", *head, *mid, L.ptr(ws), L.current_stream())
+        else:
+            tws = L.workspace("recnn_gru_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
+            L.call("recnn_gru_backward_table", *head, L.ptr(w_ih), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
+        return d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_h0, None, d_table, None, None, None
+
+
+def gru_encode_train(gru, store, table, slots, T, h0=None, *, t0=0, train_table=False):
+    """`gru_encode` with a graph: the same arguments, checks and return value (h, h_T) -- bit for bit the same numbers under either
+    variant -- differentiable with respect to weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0 (the two bias gradients differ in
+    their last H entries: b_hn sits inside the reset product), and to h0 when it requires grad, so truncated BPTT over calls with
+    `t0` moved on works: carry h_T into the next call.
+
+    The forward also records r, z, n and W_hn h + b_hn (4 U T H floats, U rounded up to 16); the backward is one HIP launch chain
+    backward through time plus the weight-gradient launches per chunk of steps (csrc/gru.hip), in fixed summation orders: equal
+    calls give equal gradients bit for bit.  It is once differentiable.
+
+    The embedding table is handled as in `lstm_encode_train`: a `table` that requires grad is refused with RecnnHipError unless
+    `train_table=True`, and then `table.grad` receives the dense [n_items, E] gradient, exact zeros in the rows of items the batch's
+    steps do not hold -- also with every encoder parameter frozen.  The weight gradients and dh0 keep their bits.
+
+    Under `torch.no_grad()`, or when nothing requires grad, this IS `gru_encode`: nothing is recorded."""
+    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
+        raise L.RecnnHipError("gru_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
+                              "computed only on request; pass train_table=True to train it, or table.detach()")
+    dev, E, H, U, T, t0, slots, h0 = _encode_call_args("gru_encode_train", "gru", gru, store, table, slots, T,
+                                                       None if h0 is None else (h0,), t0)
+    h0 = None if h0 is None else h0[0]
+    params = (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)
+    live = [p for p in params if p.requires_grad] + [t for t in (h0,) if t is not None and t.requires_grad]
+    if table.requires_grad:                               # (only with train_table)
+        live.append(table)
+    if not torch.is_grad_enabled() or not live:
+        return gru_encode(gru, store, table.detach(), slots, T, h0, t0=t0)
+    slots_d = torch.from_numpy(slots).to(dev)
+    return GRUEncodeFunction.apply(*params, h0, store, table, slots_d, T, t0)
+
+
+def state_encode(encoder, store, table, slots, T, *, train=False, train_table=False):
+    """h float32[U, T, H] of whichever state encoder `encoder` is -- the one place that dispatches on the module's type (SeqEnv goes
+    through it): a torch.nn.LSTM runs `lstm_encode` / `lstm_encode_train`, a torch.nn.GRU `gru_encode` / `gru_encode_train`, from a
+    zero state at step 0.  Any other module is refused by name."""
+    if isinstance(encoder, torch.nn.LSTM):
+        fn = lstm_encode_train if train else lstm_encode
+    elif isinstance(encoder, torch.nn.GRU):
+        fn = gru_encode_train if train else gru_encode
+    else:
+        t = type(encoder)
+        raise L.RecnnHipError(f"state encoder: a {t.__module__}.{t.__qualname__} is not supported; the HIP encoders are a single-layer "
+                              "torch.nn.LSTM(E + 1, H) and a single-layer torch.nn.GRU(E + 1, H)")
+    return fn(encoder, store, table, slots, T, **(dict(train_table=train_table) if train else {}))[0]
 
 
 class SeqCollectFunction(torch.autograd.Function):

@@ -16,7 +16,10 @@ Also reports max |hip - torch| over h.  Prints one JSON line.
                over `table[idx]` with `table.requires_grad` on the same GPU (here the gather IS timed: it is part of the graph);
                max |hip - torch| of the table gradient relative to max |torch|, and how many table rows the batch touches.
                Default --out: profiles/seq_table_grad_bench.json.
-usage: python tools/seq_bench.py [--quick] [--repeats 5] [--backward [--table-grad]] [--out profiles/seq_bench.json]"""
+  --cell gru   the same columns for the GRU encoder (csrc/gru.hip): `gru_encode` / `gru_encode_train` against
+               torch.nn.GRU on the same GPU.  --cell both runs the LSTM and the GRU in one invocation and also prints, per case, the
+               GRU's times beside the LSTM's ("gru_beside_lstm": every *_ms column as [gru, lstm, gru / lstm]).
+usage: python tools/seq_bench.py [--quick] [--repeats 5] [--cell lstm|gru|both] [--backward [--table-grad]] [--out profiles/seq_bench.json]"""
 import argparse
 import json
 import os
@@ -42,9 +45,16 @@ def median_ms(fn, repeats):
     return float(np.median(times))
 
 
-def case(U, T, E, H, repeats, dev, backward=False, table_grad=False):
+def cell_of(name):
+    """(torch module class, inference encode, training encode) of the cell `name`."""
+    from recnn_amd.nn import functional as F
+    return {"lstm": (torch.nn.LSTM, F.lstm_encode, F.lstm_encode_train), "gru": (torch.nn.GRU, F.gru_encode, F.gru_encode_train)}[name]
+
+
+def case(U, T, E, H, repeats, dev, backward=False, table_grad=False, cell="lstm"):
     from recnn_amd.data.store import ReplayStore
     from recnn_amd.nn import functional as F
+    module, encode, encode_train = cell_of(cell)
     rng = np.random.default_rng(U)
     n_items = 26744
     lens = rng.integers(T + 1, T + 50, size=U)
@@ -55,7 +65,7 @@ def case(U, T, E, H, repeats, dev, backward=False, table_grad=False):
     store = ReplayStore.from_arrays(items, ratings, off, dev)
     table = torch.from_numpy(rng.standard_normal((n_items, E)).astype(np.float32)).to(dev)
     torch.manual_seed(0)
-    lstm = torch.nn.LSTM(E + 1, H, batch_first=True).to(dev)
+    lstm = module(E + 1, H, batch_first=True).to(dev)
     slots = np.arange(U, dtype=np.int32)
     idx = torch.from_numpy(np.stack([items[off[u]:off[u] + T] for u in range(U)]).astype(np.int64)).to(dev)
     rts = torch.from_numpy(np.stack([ratings[off[u]:off[u] + T] for u in range(U)])).to(dev)
@@ -63,12 +73,12 @@ def case(U, T, E, H, repeats, dev, backward=False, table_grad=False):
     res = {"U": U, "T": T, "E": E, "H": H}
     out = {}
     if table_grad:
-        return table_grad_case(res, lstm, store, table, slots, idx, rts, T, repeats)
+        return table_grad_case(res, lstm, store, table, slots, idx, rts, T, repeats, encode_train)
     if backward:
-        return backward_case(res, lstm, store, table, slots, x, T, repeats)
+        return backward_case(res, lstm, store, table, slots, x, T, repeats, encode, encode_train)
     for variant in ("fused", "chunked"):
         F.set_lstm_variant(variant)
-        res[f"hip_{variant}_ms"] = median_ms(lambda: out.__setitem__(variant, F.lstm_encode(lstm, store, table, slots, T)[0]), repeats)
+        res[f"hip_{variant}_ms"] = median_ms(lambda: out.__setitem__(variant, encode(lstm, store, table, slots, T)[0]), repeats)
     F.set_lstm_variant("chunked")
     with torch.no_grad():
         res["torch_ms"] = median_ms(lambda: out.__setitem__("torch", lstm(x)[0]), repeats)
@@ -80,14 +90,13 @@ def case(U, T, E, H, repeats, dev, backward=False, table_grad=False):
     return res
 
 
-def backward_case(res, lstm, store, table, slots, x, T, repeats):
-    from recnn_amd.nn import functional as F
+def backward_case(res, lstm, store, table, slots, x, T, repeats, encode, encode_train):
     names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
     grads = {}
 
     def hip_step():
         lstm.zero_grad(set_to_none=True)
-        F.lstm_encode_train(lstm, store, table, slots, T)[0].sum().backward()
+        encode_train(lstm, store, table, slots, T)[0].sum().backward()
         grads["hip"] = [getattr(lstm, n).grad for n in names]
 
     def torch_step():
@@ -97,8 +106,8 @@ def backward_case(res, lstm, store, table, slots, x, T, repeats):
 
     res["hip_train_fwd_bwd_ms"] = median_ms(hip_step, repeats)
     res["torch_fwd_bwd_ms"] = median_ms(torch_step, repeats)
-    res["hip_train_fwd_ms"] = median_ms(lambda: F.lstm_encode_train(lstm, store, table, slots, T), repeats)
-    res["hip_infer_fwd_ms"] = median_ms(lambda: F.lstm_encode(lstm, store, table, slots, T), repeats)
+    res["hip_train_fwd_ms"] = median_ms(lambda: encode_train(lstm, store, table, slots, T), repeats)
+    res["hip_infer_fwd_ms"] = median_ms(lambda: encode(lstm, store, table, slots, T), repeats)
     with torch.no_grad():
         res["torch_fwd_ms"] = median_ms(lambda: lstm(x), repeats)
     res["hip_bwd_ms"] = res["hip_train_fwd_bwd_ms"] - res["hip_train_fwd_ms"]       # a difference of two medians
@@ -109,15 +118,14 @@ def backward_case(res, lstm, store, table, slots, x, T, repeats):
     return res
 
 
-def table_grad_case(res, lstm, store, table, slots, idx, rts, T, repeats):
-    from recnn_amd.nn import functional as F
+def table_grad_case(res, lstm, store, table, slots, idx, rts, T, repeats, encode_train):
     P = table.clone().requires_grad_(True)
     grads = {}
 
     def hip_step(tbl):
         lstm.zero_grad(set_to_none=True)
         P.grad = None
-        F.lstm_encode_train(lstm, store, tbl, slots, T, train_table=tbl.requires_grad)[0].sum().backward()
+        encode_train(lstm, store, tbl, slots, T, train_table=tbl.requires_grad)[0].sum().backward()
         grads["hip"] = P.grad
 
     def torch_step():
@@ -144,6 +152,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--backward", action="store_true", help="time the training forward + backward (DESIGN.md 15)")
     ap.add_argument("--table-grad", action="store_true", help="with --backward: train the embedding table as well (DESIGN.md 18)")
+    ap.add_argument("--cell", choices=("lstm", "gru", "both"), default="lstm", help="the encoder's cell (DESIGN.md 19)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.table_grad and not a.backward:
@@ -153,10 +162,17 @@ def main():
     dev = torch.device("cuda")
     T = 100 if a.quick else 1000
     tool = "seq_bench --backward --table-grad" if a.table_grad else "seq_bench --backward" if a.backward else "seq_bench"
+    if a.cell != "lstm":
+        tool += f" --cell {a.cell}"
+    run = lambda cell: [case(U, T, 128, 256, a.repeats, dev, a.backward, a.table_grad, cell) for U in (25, 256)]
     res = {"tool": tool, "device": torch.cuda.get_device_name(0),
            "arch": torch.cuda.get_device_properties(0).gcnArchName,      # (the marketing name may read generic; the arch does not)
-           "lib": os.environ.get("RECNN_HIP_LIB", "in-tree"), "cases": [case(U, T, 128, 256, a.repeats, dev, a.backward, a.table_grad)
-                                                                       for U in (25, 256)]}
+           "lib": os.environ.get("RECNN_HIP_LIB", "in-tree"), "cases": run("gru" if a.cell == "gru" else "lstm")}
+    if a.cell == "both":
+        res["gru_cases"] = run("gru")
+        res["gru_beside_lstm"] = [dict({k: g[k] for k in ("U", "T", "E", "H")},
+                                       **{k: [g[k], l[k], g[k] / l[k]] for k in g if k.endswith("_ms")})
+                                  for g, l in zip(res["gru_cases"], res["cases"])]
     line = json.dumps(res)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

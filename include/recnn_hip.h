@@ -972,6 +972,46 @@ int recnn_gru_backward_table(const int32_t* items, const float* ratings, const i
                              const float* g_hT, float* d_w_ih, float* d_w_hh, float* d_b_ih, float* d_b_hh, float* d_h0,
                              float* d_table, void* workspace, void* table_workspace, void* stream);
 
+/* =====================================================================================
+ * 11. Offline ranking evaluation (csrc/rank.hip, csrc/topk.hip, csrc/evalrank.hip): where the item the user took
+ *    next lands in the ranking a generated action induces over the catalogue, and the hit rate / NDCG / MRR of a batch of such ranks.
+ *    rank[b] = the number of items i != targets[b] that come before item targets[b] in the order of the search of section 7
+ *    (recnn_dist_target_rank: distance ascending, -0 as +0, every NaN as one value after +inf, ties to the smaller id) or of
+ *    section 5 (recnn_topk_target_rank: the internal key q.t, 2 q.t - |t|^2 or q.t / |t| descending, ties to the smaller id; an
+ *    item whose key is NaN comes after every number, NaN keys order by id), in [0, n_items - 1].  The target's own key has the
+ *    bits the scoring loop produces for that pair, so the result agrees with recnn_dist_matrix / recnn_dist_topk /
+ *    recnn_topk_search entry for entry, and does not depend on the batch, the tile or the split.  A target id outside
+ *    [0, n_items) gives rank -1; nothing is read out of bounds.  No limit on the rank: the whole table is counted.
+ *    Per-split integer counts are summed afterwards (no atomics on global memory): equal calls give equal results.
+ *    Limits: emb_dim == 128, ld_q % 4 == 0, queries / table / aux / workspace 16-byte aligned; item_aux as in sections 5 and 7.
+ *    Errors: RECNN_E_INVALID, before any HIP call, for an unknown metric, p < 1 or NaN for minkowski, a null pointer, a misaligned
+ *    operand, a missing aux and the limits above.  n_queries == 0 launches nothing.
+ * ===================================================================================== */
+int recnn_dist_target_rank_workspace_bytes(int n_queries, int n_items, int metric, int64_t* h_bytes);
+/* targets int64[n_queries] (table row ids), out_rank int32[n_queries]; the metrics and p of section 7 */
+int recnn_dist_target_rank(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                           int metric, double p, const float* item_aux, const int64_t* targets, int32_t* out_rank, void* workspace,
+                           void* stream);
+int recnn_topk_target_rank_workspace_bytes(int n_queries, int n_items, int64_t* h_bytes);
+/* the same for RECNN_METRIC_IP / L2 / COS of section 5 */
+int recnn_topk_target_rank(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                           int metric, const float* item_aux, const int64_t* targets, int32_t* out_rank, void* workspace,
+                           void* stream);
+/* Metrics of ranks int32[n], one relevant item per row.  mask uint8[n] (may be NULL): a zero byte skips the row.  h_ks: n_ks
+ * cutoffs on the HOST, 1 <= n_ks <= 8, each >= 1, strictly ascending, of any size.  Both accumulators are device arrays that are
+ * ACCUMULATED into (the caller zeroes them once):
+ *   acc_f double[n_ks + 1]: per cutoff K the sum of 1 / log2(rank + 2) over the rows with 0 <= rank < K (NDCG@K, IDCG = 1), then the
+ *                           sum of 1 / (rank + 1) (MRR);
+ *   acc_i int64[n_ks + 3]:  per cutoff K the rows with 0 <= rank < K (hits), then the sum of ranks, the rows counted, and the rows with
+ *                           rank < 0 that were not masked out (invalid: they count in nothing else).
+ * Integers are exact; the float64 sums run in a fixed order that depends on n alone (per-workgroup trees, then one workgroup in
+ * workgroup order): equal call sequences give equal bits.  workspace: recnn_rank_metrics_workspace_bytes(n) bytes, 8-byte aligned.
+ * Errors: RECNN_E_INVALID, before any HIP call, for a null pointer, n < 0, n_ks outside 1..8 and cutoffs that are < 1 or not
+ * strictly ascending.  n == 0 launches nothing. */
+int recnn_rank_metrics_workspace_bytes(int n, int64_t* h_bytes);
+int recnn_rank_metrics(const int32_t* ranks, const uint8_t* mask, int n, const int32_t* h_ks, int n_ks, double* acc_f,
+                       int64_t* acc_i, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,12 @@ SIGNATURES = {
     "recnn_gru_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 13),
     "recnn_gru_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
     "recnn_gru_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 16),
+    "recnn_dist_target_rank_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
+    "recnn_dist_target_rank": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P]),
+    "recnn_topk_target_rank_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_topk_target_rank": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "recnn_rank_metrics_workspace_bytes": (_I, [_I, C.POINTER(_L)]),
+    "recnn_rank_metrics": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

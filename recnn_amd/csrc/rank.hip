@@ -25,10 +25,12 @@
 // Epilogues: MATRIX stores the tile; TOPK lets each wave keep the sorted K-best list of each of its rows in registers (entry e in
 // lane e; one ballot per row and 64 items against the row's current K-th, survivors inserted) and writes it as one partial list per (row, split); a
 // merge kernel then takes the K best of a row's sorted partial lists.  Order: distance ascending, NaN after every number, ties
-// to the smaller item id.
+// to the smaller item id.  A third kernel, dist_rank_kernel, streams the table the same way and only counts, per row, the items that
+// come before one target item in that order.
 #include <algorithm>
 
 #include "common.h"
+#include "target_rank.h"
 
 #pragma clang fp contract(off)
 
@@ -217,6 +219,111 @@ __global__ __launch_bounds__(256) void dist_kernel(const DistArgs a) {
   }
 }
 
+// The rank of a target item: row b counts the items of its split whose rank_key is below that of (d(b, g_b), g_b), g_b = targets[b].
+// The target's distance is computed first, by the chain every streamed pair goes through (combine over k = 0..127 in order, then
+// finish), so it has the bits the stream produces for item g_b: the target itself compares equal and is not counted, and a twin
+// row ties and is decided by its id.  Rows and items are tiled as in dist_kernel.  A wave's count of a row is a ballot's popcount:
+// it lives in scalar registers and goes out as one partial per (row, split).  A target outside [0, N) reads row 0; its count is
+// ignored by the finishing kernel, which reports -1.
+template <int LOOP, int TQ, int TI>
+__global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgs a, const int64_t* __restrict__ targets,
+                                                        int32_t* __restrict__ part) {   // part: [B][splits]
+  constexpr int QT = 4 * TQ, IT = 64 * TI;
+  constexpr int STAGE = IT * (E / 4) / 256;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* Ts = (float*)smem;                     // [IT][PITCH]
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q0 = blockIdx.x * QT;
+  const int n_begin = blockIdx.y * a.per, n_end = min(a.N, n_begin + a.per);
+
+  const float* qrow[TQ];
+#pragma unroll
+  for (int i = 0; i < TQ; ++i) qrow[i] = a.q + (int64_t)min(q0 + wave * TQ + i, a.B - 1) * a.ldq;
+  float4 stage[STAGE];
+  auto load_chunk = [&](int n0) {
+#pragma unroll
+    for (int s = 0; s < STAGE; ++s) {
+      const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
+      stage[s] = n0 + r < n_end ? *(const float4*)(a.t + (int64_t)(n0 + r) * E + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  if (n_begin < n_end) load_chunk(n_begin);
+  const bool wave_live = q0 + wave * TQ < a.B;
+
+  // the rows' target keys (wave-uniform)
+  uint64_t tkey[TQ];
+  int cnt[TQ];
+#pragma unroll
+  for (int i = 0; i < TQ; ++i) {
+    const int64_t g64 = targets[min(q0 + wave * TQ + i, a.B - 1)];
+    const int g = (uint64_t)g64 < (uint64_t)a.N ? (int)g64 : 0;
+    const float* trow = a.t + (int64_t)g * E;
+    float t0 = 0.f, t1 = 0.f;
+    for (int k = 0; k < E; k += 4) {
+      const float4 qv = *(const float4*)(qrow[i] + k);
+      const float4 tv = *(const float4*)(trow + k);
+      combine<LOOP>(t0, t1, qv.x, tv.x, a.p);
+      combine<LOOP>(t0, t1, qv.y, tv.y, a.p);
+      combine<LOOP>(t0, t1, qv.z, tv.z, a.p);
+      combine<LOOP>(t0, t1, qv.w, tv.w, a.p);
+    }
+    const uint64_t key = rank_key(finish<LOOP>(t0, t1, a.metric, a.invp), g);
+    tkey[i] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(key >> 32)) << 32) |
+              (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
+    cnt[i] = 0;
+  }
+
+  for (int n0 = n_begin; n0 < n_end; n0 += IT) {
+    __syncthreads();                              // the previous chunk's readers are done
+#pragma unroll
+    for (int s = 0; s < STAGE; ++s) {
+      const int c = tid + s * 256;
+      *(float4*)&Ts[(c >> 5) * PITCH + (c & 31) * 4] = stage[s];
+    }
+    __syncthreads();
+    if (n0 + IT < n_end) load_chunk(n0 + IT);     // in flight while this chunk is scored
+    if (!wave_live) continue;
+
+    float a0[TQ][TI], a1[TQ][TI];
+#pragma unroll
+    for (int i = 0; i < TQ; ++i)
+#pragma unroll
+      for (int j = 0; j < TI; ++j) { a0[i][j] = 0.f; a1[i][j] = 0.f; }
+#pragma unroll 2
+    for (int k = 0; k < E; k += 4) {
+      float4 tv[TI];
+#pragma unroll
+      for (int j = 0; j < TI; ++j) tv[j] = *(const float4*)&Ts[(j * 64 + lane) * PITCH + k];
+#pragma unroll
+      for (int i = 0; i < TQ; ++i) {
+        const float4 qv = *(const float4*)(qrow[i] + k);
+#pragma unroll
+        for (int j = 0; j < TI; ++j) {
+          combine<LOOP>(a0[i][j], a1[i][j], qv.x, tv[j].x, a.p);
+          combine<LOOP>(a0[i][j], a1[i][j], qv.y, tv[j].y, a.p);
+          combine<LOOP>(a0[i][j], a1[i][j], qv.z, tv[j].z, a.p);
+          combine<LOOP>(a0[i][j], a1[i][j], qv.w, tv[j].w, a.p);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < TQ; ++i)
+#pragma unroll
+      for (int j = 0; j < TI; ++j) {
+        const int id = n0 + j * 64 + lane;
+        const float d = finish<LOOP>(a0[i][j], a1[i][j], a.metric, a.invp);
+        cnt[i] += __popcll(__ballot(id < n_end && rank_key(d, id) < tkey[i]));
+      }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) {
+      const int row = q0 + wave * TQ + i;
+      if (row < a.B) part[(int64_t)row * a.splits + blockIdx.y] = cnt[i];
+    }
+  }
+}
+
 // K best of a row's S sorted partial lists (S <= 256, S*K <= MERGE_CAND): one 64-lane workgroup per row, the lists in LDS,
 // lane l holding the heads of lists l, l+64, l+128, l+192
 __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict__ pd, const int32_t* __restrict__ pi, int S, int K,
@@ -348,6 +455,34 @@ template <bool TOPK> int launch(const DistArgs& a, const Plan& pl, hipStream_t s
   }
 }
 
+template <int LOOP, int TQ, int TI> int launch_rank_one(const DistArgs& a, const Plan& pl, const int64_t* targets, int32_t* part,
+                                                        hipStream_t st) {
+  const size_t lds = lds_bytes(TQ == 8);
+  static bool attr = false;
+  if (!attr) {
+    RECNN_HIP(hipFuncSetAttribute((const void*)dist_rank_kernel<LOOP, TQ, TI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  hipLaunchKernelGGL((dist_rank_kernel<LOOP, TQ, TI>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a, targets, part);
+  return 0;
+}
+
+template <int LOOP> int launch_rank_loop(const DistArgs& a, const Plan& pl, const int64_t* targets, int32_t* part, hipStream_t st) {
+  return pl.big ? launch_rank_one<LOOP, 8, 2>(a, pl, targets, part, st) : launch_rank_one<LOOP, 1, 1>(a, pl, targets, part, st);
+}
+
+int launch_rank(const DistArgs& a, const Plan& pl, const int64_t* targets, int32_t* part, hipStream_t st) {
+  switch (a.metric) {
+    case SQEUCLIDEAN: case EUCLIDEAN: return launch_rank_loop<L_SQ>(a, pl, targets, part, st);
+    case CITYBLOCK: return launch_rank_loop<L_ABS>(a, pl, targets, part, st);
+    case CHEBYSHEV: return launch_rank_loop<L_MAX>(a, pl, targets, part, st);
+    case MINKOWSKI: return launch_rank_loop<L_POW>(a, pl, targets, part, st);
+    case CANBERRA: return launch_rank_loop<L_CANB>(a, pl, targets, part, st);
+    case BRAYCURTIS: return launch_rank_loop<L_BRAY>(a, pl, targets, part, st);
+    default: return launch_rank_loop<L_DOT>(a, pl, targets, part, st);
+  }
+}
+
 int64_t query_prep_bytes(int B, int metric) { return needs_aux(metric) ? ((int64_t)B * E * 4 + 255) / 256 * 256 : 0; }
 
 // argument checks shared by matrix and top-K (before any HIP call)
@@ -440,4 +575,32 @@ extern "C" int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries
   if (int rc = launch<true>(a, pl, st)) return rc;
   hipLaunchKernelGGL(dist_merge_kernel, dim3(n_queries), dim3(64), 0, st, a.part_d, a.part_i, pl.splits, k, out_dist, out_ids);
   return recnn_check_hip(hipGetLastError(), "dist_topk");
+}
+
+extern "C" int recnn_dist_target_rank_workspace_bytes(int n_queries, int n_items, int metric, int64_t* h_bytes) {
+  RECNN_REQUIRE(h_bytes && n_queries >= 0 && n_items > 0 && metric >= SQEUCLIDEAN && metric <= CORRELATION,
+                "dist_target_rank_workspace_bytes: bad arguments");
+  int64_t b = query_prep_bytes(n_queries, metric);
+  if (n_queries > 0) b += (int64_t)n_queries * make_plan(n_queries, n_items, 0).splits * 4;
+  *h_bytes = b;
+  return 0;
+}
+
+extern "C" int recnn_dist_target_rank(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                                      int metric, double p, const float* item_aux, const int64_t* targets, int32_t* out_rank,
+                                      void* workspace, void* stream) {
+  if (int rc = check_common("dist_target_rank", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
+  RECNN_REQUIRE((targets && out_rank && workspace) || n_queries == 0, "dist_target_rank: null pointer");
+  RECNN_REQUIRE(aligned16(workspace), "dist_target_rank: 16-byte alignment (workspace)");
+  if (n_queries == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  DistArgs a;
+  prepare(a, queries, ld_q, n_queries, table, n_items, metric, p, item_aux, workspace, st);
+  const Plan pl = make_plan(n_queries, n_items, 0);
+  a.per = pl.per; a.splits = pl.splits;
+  int32_t* part = (int32_t*)((char*)workspace + query_prep_bytes(n_queries, metric));
+  if (int rc = launch_rank(a, pl, targets, part, st)) return rc;
+  hipLaunchKernelGGL(target_rank_finish_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, st, part, pl.splits, targets, n_queries,
+                     n_items, out_rank);
+  return recnn_check_hip(hipGetLastError(), "dist_target_rank");
 }

@@ -16,7 +16,13 @@
 // top-K lists of 16 query rows: a chunk's scores are compared against the row's current K-th best with one ballot per
 // 64 items, and only the (rare) survivors are inserted.  Ties are broken towards the smaller item id.  Partial lists
 // [B][S][K] are merged by a second tiny kernel.
+//
+// topk_rank_kernel scores the same way and, instead of selecting, counts per query row the items that come before one target
+// item: no lists, no limit on K.
+#include <algorithm>
+
 #include "common.h"
+#include "target_rank.h"
 
 namespace {
 constexpr int QT = 64;     // query rows per workgroup
@@ -207,6 +213,183 @@ __global__ __launch_bounds__(256) void topk_aux_kernel(const float* __restrict__
   s = wave_sum(s);
   if (lane == 0) aux[n] = metric == M_L2 ? s : (s > 0.f ? 1.0f / sqrtf(s) : 0.f);
 }
+
+// ---------------------------------------------------------------- the rank of a target item
+struct TopkRankArgs {
+  const float* q; int64_t ldq; int B;
+  const float* table; int N;
+  const float* aux;
+  int metric, splits, per;   // per: items per split, a multiple of IT
+  const int64_t* targets;    // [B]
+  int32_t* part;             // [B][splits]
+};
+
+// the total order the counting uses: better() wherever both keys are numbers; an item whose key is NaN comes after every number, and
+// NaN keys order by id
+__device__ inline bool comes_before(float s, int id, float s2, int id2) {
+  if (s != s) return s2 != s2 && id < id2;
+  return s2 != s2 || better(s, id, s2, id2);
+}
+
+__device__ __forceinline__ float rank_score(float s, float ax, int metric) {   // the internal key of topk_scores_kernel
+  if (metric == M_L2) s = 2.f * s - ax;
+  else if (metric == M_COS) s = s * ax;
+  return s;
+}
+
+// 64 x 64 scores of the query tile against the 64 rows in Ts: the k order of topk_scores_kernel, which is the same for every element
+// of the tile
+__device__ __forceinline__ void score_tile(const float* Qs, const float* Ts, int wm0, int wn0, int fr, int fg, f32x4 (&acc)[2][2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int ks = 0; ks < 128 / 16; ++ks) {
+    float4 qa[2], tb[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) qa[i] = *(const float4*)&Qs[(wm0 + i * 16 + fr) * PITCH + ks * 16 + fg * 4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) tb[j] = *(const float4*)&Ts[(wn0 + j * 16 + fr) * PITCH + ks * 16 + fg * 4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(((const float*)&qa[i])[e], ((const float*)&tb[j])[e], acc[i][j], 0, 0, 0);
+  }
+}
+
+// Row b counts the items of its split that come before item g_b = targets[b].  The workgroup first gathers the target rows of its
+// 64 queries into the chunk buffer and runs the scoring tile on them: the diagonal holds each row's target key, with the bits the
+// stream produces for that pair (an element's k order does not depend on its place in the tile).  Then it streams its split
+// (register-staged) and compares every score, still in the MFMA accumulators, against its row's target key; the target itself is
+// skipped by id.  Counts: per lane, summed over each 16-lane row, then over the two waves of a row with LDS integer atomics.  A
+// target outside [0, N) scores a zero row; the finishing kernel reports -1 for it.
+__global__ __launch_bounds__(256) void topk_rank_kernel(const TopkRankArgs a) {
+  constexpr int E_ = 128;
+  constexpr int STAGE = IT * (E_ / 4) / 256;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* Qs = (float*)smem;                  // [QT][PITCH]
+  float* Ts = Qs + QT * PITCH;               // [IT][PITCH]
+  float* Tk = Ts + IT * PITCH;               // [QT] target keys
+  int* Tg = (int*)(Tk + QT);                 // [QT] target ids, -1: none
+  int* Cn = Tg + QT;                         // [QT] counts
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q0 = blockIdx.x * QT;
+  const int n_begin = blockIdx.y * a.per, n_end = min(a.N, n_begin + a.per);
+
+  if (tid < QT) {
+    const int64_t g = q0 + tid < a.B ? a.targets[q0 + tid] : -1;
+    Tg[tid] = (uint64_t)g < (uint64_t)a.N ? (int)g : -1;
+    Cn[tid] = 0;
+  }
+  for (int c = tid; c < QT * (E_ / 4); c += 256) {
+    const int r = c / (E_ / 4), k4 = c % (E_ / 4);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q0 + r < a.B) v = *(const float4*)(a.q + (int64_t)(q0 + r) * a.ldq + k4 * 4);
+    *(float4*)&Qs[r * PITCH + k4 * 4] = v;
+  }
+  float4 stage[STAGE];
+  auto load_chunk = [&](int n0) {
+#pragma unroll
+    for (int s = 0; s < STAGE; ++s) {
+      const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
+      stage[s] = n0 + r < n_end ? *(const float4*)(a.table + (int64_t)(n0 + r) * E_ + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  if (n_begin < n_end) load_chunk(n_begin);
+  const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;   // wave tile: 32 queries x 32 items
+  const int fr = lane & 15, fg = lane >> 4;
+  __syncthreads();
+  // ---- target rows -> Ts, scored like a chunk; the diagonal is each row's target key
+  for (int c = tid; c < QT * (E_ / 4); c += 256) {
+    const int r = c / (E_ / 4), k4 = c % (E_ / 4);
+    const int g = Tg[r];
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g >= 0) v = *(const float4*)(a.table + (int64_t)g * E_ + k4 * 4);
+    *(float4*)&Ts[r * PITCH + k4 * 4] = v;
+  }
+  __syncthreads();
+  f32x4 acc[2][2];
+  score_tile(Qs, Ts, wm0, wn0, fr, fg, acc);
+  if (wm0 == wn0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int col = wn0 + i * 16 + fr;
+      const int g = Tg[col];
+      const float ax = a.metric != M_IP && g >= 0 ? a.aux[g] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (wm0 + i * 16 + fg * 4 + r == col) Tk[col] = rank_score(acc[i][i][r], ax, a.metric);
+    }
+  }
+  __syncthreads();
+  float tk[2][4];
+  int tg[2][4], cnt[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = wm0 + i * 16 + fg * 4 + r;
+      tk[i][r] = Tk[row];
+      tg[i][r] = Tg[row];
+      cnt[i][r] = 0;
+    }
+
+  for (int n0 = n_begin; n0 < n_end; n0 += IT) {
+    __syncthreads();                              // the previous tile's readers are done
+#pragma unroll
+    for (int s = 0; s < STAGE; ++s) {
+      const int c = tid + s * 256;
+      *(float4*)&Ts[(c >> 5) * PITCH + (c & 31) * 4] = stage[s];
+    }
+    __syncthreads();
+    if (n0 + IT < n_end) load_chunk(n0 + IT);     // in flight while this chunk is scored
+    score_tile(Qs, Ts, wm0, wn0, fr, fg, acc);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wn0 + j * 16 + fr;
+      const bool live = n < n_end;
+      const float ax = a.metric != M_IP && live ? a.aux[n] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float s = rank_score(acc[i][j][r], ax, a.metric);
+          cnt[i][r] += live && n != tg[i][r] && comes_before(s, n, tk[i][r], tg[i][r]);
+        }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int c = cnt[i][r];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);      // over the 16 lanes that share fg
+      if (fr == 0) atomicAdd(&Cn[wm0 + i * 16 + fg * 4 + r], c);
+    }
+  __syncthreads();
+  if (tid < QT && q0 + tid < a.B) a.part[(int64_t)(q0 + tid) * a.splits + blockIdx.y] = Cn[tid];
+}
+
+constexpr int RANK_TARGET_WG = 512;   // workgroups to aim for: two per CU, which is what the LDS tile lets a CU hold
+constexpr int RANK_MIN_CHUNKS = 4;    // per split: the target tile costs one chunk's work
+
+struct RankPlan { int tiles, splits, per; };
+
+RankPlan make_rank_plan(int B, int N) {
+  RankPlan pl;
+  pl.tiles = (B + QT - 1) / QT;
+  const int chunks = (N + IT - 1) / IT;
+  int s = std::min(RANK_TARGET_WG / pl.tiles, (chunks + RANK_MIN_CHUNKS - 1) / RANK_MIN_CHUNKS);
+  s = std::max(s, 1);
+  pl.per = (chunks + s - 1) / s * IT;
+  pl.splits = (N + pl.per - 1) / pl.per;     // no empty split
+  return pl;
+}
 }  // namespace
 
 extern "C" int recnn_topk_workspace_bytes(int n_queries, int k, int64_t* h_bytes) {
@@ -251,4 +434,36 @@ extern "C" int recnn_topk_search(const float* queries, int64_t ld_q, int n_queri
   hipLaunchKernelGGL(topk_merge_kernel, dim3((n_queries + 3) / 4), dim3(256), 0, (hipStream_t)stream, a.part_score, a.part_id, n_queries,
                      splits, k, metric, queries, ld_q, emb_dim, out_dist, out_ids);
   return recnn_check_hip(hipGetLastError(), "topk_search");
+}
+
+extern "C" int recnn_topk_target_rank_workspace_bytes(int n_queries, int n_items, int64_t* h_bytes) {
+  RECNN_REQUIRE(h_bytes && n_queries >= 0 && n_items > 0, "topk_target_rank_workspace_bytes: bad arguments");
+  *h_bytes = n_queries > 0 ? (int64_t)n_queries * make_rank_plan(n_queries, n_items).splits * 4 : 0;
+  return 0;
+}
+
+extern "C" int recnn_topk_target_rank(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                                      int metric, const float* item_aux, const int64_t* targets, int32_t* out_rank, void* workspace,
+                                      void* stream) {
+  RECNN_REQUIRE(table && ((queries && targets && out_rank && workspace) || n_queries == 0), "topk_target_rank: null pointer");
+  RECNN_REQUIRE(n_queries >= 0 && n_items > 0, "topk_target_rank: need n_queries >= 0 and n_items > 0");
+  RECNN_REQUIRE(emb_dim == 128, "topk_target_rank: emb_dim must be 128 (the reference's embedding width)");
+  RECNN_REQUIRE(metric == M_IP || ((metric == M_L2 || metric == M_COS) && item_aux), "topk_target_rank: metric must be IP, or L2 / COS with the item aux array");
+  RECNN_REQUIRE(aligned16(queries, table) && ld_q % 4 == 0 && ld_q >= 128, "topk_target_rank: 16-byte alignment (rows and ld_q)");
+  if (n_queries == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const RankPlan pl = make_rank_plan(n_queries, n_items);
+  TopkRankArgs a;
+  a.q = queries; a.ldq = ld_q; a.B = n_queries; a.table = table; a.N = n_items; a.aux = item_aux;
+  a.metric = metric; a.splits = pl.splits; a.per = pl.per; a.targets = targets; a.part = (int32_t*)workspace;
+  const size_t lds = (size_t)(QT * PITCH + IT * PITCH + 3 * QT) * 4;
+  static bool attr = false;
+  if (!attr) {
+    RECNN_HIP(hipFuncSetAttribute((const void*)topk_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  hipLaunchKernelGGL(topk_rank_kernel, dim3(pl.tiles, pl.splits), dim3(256), lds, st, a);
+  hipLaunchKernelGGL(target_rank_finish_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, st, a.part, pl.splits, targets, n_queries,
+                     n_items, out_rank);
+  return recnn_check_hip(hipGetLastError(), "topk_target_rank");
 }

@@ -204,6 +204,7 @@ class FrameEnv(StoreEnv):
         self.device = torch.device("cuda" if device is None else device)
         self._store = None
         self._table = None
+        self._host_off = None                   # host copy of the store's user offsets (target_items)
         if path is not None:
             self._make_loaders()
 
@@ -278,6 +279,37 @@ class FrameEnv(StoreEnv):
         whole = self.collate_slots(seq[i0:i1 + 1].astype(np.int32), rows_per_batch=None)
         out = {k: (v[a:a + rows] if isinstance(v, torch.Tensor) else v) for k, v in whole.items()}
         return out
+
+    def target_items(self, batch, slots=None):
+        """int64 [rows] on the env's device: the table row id of each row's action, the item at the end of its window -- what
+        `FlatIndex.rank_of(policy(batch["state"]), env.target_items(batch))` ranks.  Built from `batch["meta"]` and the batch's
+        row count through the replay store: for each user of `meta["users"]` in order, the items at positions `frame_size ..` of
+        its history, concatenated and cut to the batch's rows.  Covers the batches of `collate_users`, `collate_slots` and the
+        two loaders, with or without `rows_per_batch`.  A `collate_slots` batch made without `user_ids` records the slots as its
+        users; where those differ from the user ids (`from_user_dict`), give the slots here.  `collate_rows` batches start
+        inside a user and are not covered."""
+        st = self.store
+        meta = batch["meta"]
+        if slots is None:
+            try:
+                slots = st.slots(meta["users"].tolist())
+            except KeyError as e:
+                raise ValueError(f"target_items: user {e} of the batch is not in the replay store (a collate_slots batch made "
+                                 "without user_ids names slots: pass them as `slots`)") from None
+        slots = np.asarray(slots, dtype=np.int32)
+        sizes = meta["sizes"].numpy().astype(np.int64)
+        if len(slots) != len(sizes) or not np.array_equal(st.lengths[slots], sizes):
+            raise ValueError("target_items: the batch's users and sizes do not match the replay store")
+        rows = batch["action"].shape[0]
+        wins = np.maximum(sizes - self.frame_size, 0)
+        if rows > int(wins.sum()):
+            raise ValueError(f"target_items: the batch has {rows} rows but its users have {int(wins.sum())} windows")
+        if self._host_off is None:
+            self._host_off = np.concatenate([[0], np.cumsum(st.lengths)]).astype(np.int64)
+        first = self._host_off[slots] + self.frame_size           # position of each user's first action in the store
+        before = np.cumsum(wins) - wins                            # rows of the users before it
+        pos = (np.repeat(first - before, wins) + np.arange(int(wins.sum())))[:rows]
+        return st.items[torch.from_numpy(pos).to(self.device)].long()
 
     def prepare_batch_wrapper(self, x):
         """collate_fn-compatible entry (env.py:241-248): x = list of UserDataset items."""

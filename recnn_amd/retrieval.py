@@ -120,6 +120,36 @@ class FlatIndex:
                L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream())
         return dist, ids
 
+    def rank_of(self, queries: torch.Tensor, targets: torch.Tensor):
+        """int32 [B]: for each query row, how many items come before item `targets[b]` in the order `search` uses (0 = the
+        target is the best item); -1 for a target id outside [0, n_items).  The whole table is counted: no limit of 64."""
+        if self.metric in DIST_METRICS:
+            _on_gpu(queries, "FlatIndex.rank_of: the queries")
+        q = _queries(queries, self.table.device)
+        B = q.shape[0]
+        t = _targets(targets, B, q.device, "FlatIndex.rank_of")
+        rank = torch.empty(B, dtype=torch.int32, device=q.device)
+        if B == 0:                                                       # an empty batch has no storage to point at
+            return rank
+        if self.metric in DIST_METRICS:
+            ws = L.workspace("recnn_dist_target_rank_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], device=q.device)
+            L.call("recnn_dist_target_rank", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
+                   DIST_METRICS[self.metric], self.p, L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream())
+            return rank
+        ws = L.workspace("recnn_topk_target_rank_workspace_bytes", B, self.n_items, device=q.device)
+        L.call("recnn_topk_target_rank", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim, METRICS[self.metric],
+               L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream())
+        return rank
+
+
+def _targets(targets, B, device, what):
+    t = torch.as_tensor(targets)
+    if t.dtype.is_floating_point or t.dtype == torch.bool or t.dim() != 1:
+        raise ValueError(f"{what}: targets must be a 1-D integer tensor, got {t.dtype} {tuple(t.shape)}")
+    if t.shape[0] != B:
+        raise ValueError(f"{what}: {B} queries but {t.shape[0]} targets")
+    return t.detach().to(device, torch.int64).contiguous()
+
 
 def cdist(queries: torch.Tensor, table: torch.Tensor, metric="euclidean", p=None):
     """float32 [B, N] matrix of scipy's `cdist(queries, table, metric)` on the GPU (table: [N, 128]; metric: a name of
@@ -250,3 +280,102 @@ class DiversityMeter:
 
 
 __all__ += ["topk_stats", "DiversityMeter"]
+
+
+# ---- offline ranking evaluation (csrc/rank.hip, csrc/topk.hip, csrc/evalrank.hip): the rank of the item the
+# user took next under the generated action, and hit rate / NDCG / MRR accumulated over the test loader's batches.
+
+def target_ranks(queries, table, targets, metric="L2", p=None):
+    """`FlatIndex(table, metric, p).rank_of(queries, targets)` in one call, as `cdist` is for the matrix."""
+    return FlatIndex(table, metric, p).rank_of(queries, targets)
+
+
+MAX_CUTOFFS = 8
+
+
+class RankingMeter:
+    """Accumulates the ranking metrics of `update(ranks)` calls (one per batch of the test loader), one relevant item per row.
+
+    `ranks` is what `FlatIndex.rank_of` returns (int32 [B] on the GPU); `mask` (optional, [B]) keeps the rows where it is
+    non-zero.  `hit_rate()[K]` is the share of rows with rank < K, `ndcg()[K]` the mean of 1 / log2(rank + 2) over rows with
+    rank < K counted against all rows (IDCG = 1), `mrr` the mean of 1 / (rank + 1), `mean_rank` the mean rank.  Cutoffs: up to 8,
+    ascending, of any size.  Reading synchronises once; it raises ValueError if a rank was negative (a target outside the table)
+    and not masked out, or if no row was counted."""
+
+    def __init__(self, ks=(1, 5, 10), device="cuda"):
+        ks = tuple(ks)
+        if not 1 <= len(ks) <= MAX_CUTOFFS:
+            raise ValueError(f"RankingMeter: need 1 to {MAX_CUTOFFS} cutoffs, got {len(ks)}")
+        if any(int(k) != k or k < 1 or k >= 2 ** 31 for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+            raise ValueError(f"RankingMeter: cutoffs must be integers >= 1 in strictly ascending order, got {ks}")
+        self.ks = tuple(int(k) for k in ks)
+        device = torch.device(device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise L.RecnnHipError("RankingMeter: the accumulators live on the GPU (no CPU fallback)")
+        self._ks = (C.c_int32 * len(self.ks))(*self.ks)
+        self.sums = torch.zeros(len(self.ks) + 1, dtype=torch.float64, device=device)     # ndcg per cutoff, mrr
+        self.counts = torch.zeros(len(self.ks) + 3, dtype=torch.int64, device=device)     # hits per cutoff, rank sum, rows, invalid
+
+    def update(self, ranks, mask=None):
+        """Adds one batch of ranks (int32 [B] on the GPU)."""
+        _on_gpu(ranks, "RankingMeter.update: ranks")
+        if ranks.dtype != torch.int32 or ranks.dim() != 1:
+            raise ValueError(f"RankingMeter.update: ranks must be int32 [B], got {ranks.dtype} {tuple(ranks.shape)}")
+        ranks = ranks.detach().contiguous()
+        n = ranks.shape[0]
+        if mask is not None:
+            _on_gpu(mask, "RankingMeter.update: mask")
+            if mask.shape != ranks.shape:
+                raise ValueError(f"RankingMeter.update: {n} ranks but a mask of shape {tuple(mask.shape)}")
+            mask = (mask.detach() != 0).to(torch.uint8).contiguous()
+        if n == 0:
+            return
+        ws = L.workspace("recnn_rank_metrics_workspace_bytes", n, device=ranks.device)
+        L.call("recnn_rank_metrics", L.ptr(ranks), L.ptr(mask), n, self._ks, len(self.ks), L.ptr(self.sums), L.ptr(self.counts),
+               L.ptr(ws), L.current_stream())
+
+    def reset(self):
+        self.sums.zero_()
+        self.counts.zero_()
+
+    def _read(self, need_rows=True):
+        c = self.counts.tolist()                          # the one synchronisation; sums follow on the same stream
+        if c[-1] != 0:
+            raise ValueError(f"RankingMeter: {c[-1]} rows had a negative rank (a target outside the table) and were not counted")
+        if need_rows and c[-2] == 0:
+            raise ValueError("RankingMeter: no rows counted yet")
+        return c, self.sums.tolist()
+
+    @property
+    def rows(self):
+        return self._read(need_rows=False)[0][-2]
+
+    @property
+    def invalid(self):
+        return int(self.counts[-1])
+
+    def hits(self):
+        """{K: rows with rank < K} as Python ints."""
+        c, _ = self._read(need_rows=False)
+        return dict(zip(self.ks, c))
+
+    def hit_rate(self):
+        c, _ = self._read()
+        return {k: h / c[-2] for k, h in zip(self.ks, c)}
+
+    def ndcg(self):
+        c, f = self._read()
+        return {k: v / c[-2] for k, v in zip(self.ks, f)}
+
+    @property
+    def mrr(self):
+        c, f = self._read()
+        return f[-1] / c[-2]
+
+    @property
+    def mean_rank(self):
+        c, _ = self._read()
+        return c[-3] / c[-2]
+
+
+__all__ += ["target_ranks", "RankingMeter"]

@@ -1012,6 +1012,40 @@ int recnn_rank_metrics_workspace_bytes(int n, int64_t* h_bytes);
 int recnn_rank_metrics(const int32_t* ranks, const uint8_t* mask, int n, const int32_t* h_ks, int n_ks, double* acc_f,
                        int64_t* acc_i, void* workspace, void* stream);
 
+/* =====================================================================================
+ * 12. Per-row exclusion for the searches of sections 5 and 7 and the ranks of section 11 (csrc/seen.hip): leave the
+ *    items a user has already consumed out of the candidate set, as the usual offline protocol does before hit@K / NDCG / MRR.
+ *    mask: uint64[n_rows][W], W = ceil(n_items / 64); bit (i & 63) of word (i >> 6) of row b set = item i does not exist for query
+ *    row b; the bits above n_items are zero.  recnn_seen_mask_build fills it from slices of one device id array: row b's list is
+ *    ids[starts[b] : starts[b] + lengths[b]], unordered, duplicates allowed.  An id outside [0, n_items) and a position outside
+ *    [0, n_ids) (a negative start or length, a list running past the end) are ignored: nothing is read out of bounds.  keep (may be
+ *    NULL): bit keep[b] of row b is cleared after the row is built; a keep[b] outside [0, n_items) is a no-op.  A row is built in
+ *    one workgroup's LDS with integer atomics and stored once (no global atomics, no memset): equal calls give equal words.
+ *    Limit: n_items <= 1,048,576 (one row's words in LDS).  recnn_seen_mask_words is host-only.
+ *    The *_excluding entry points take (mask, words_per_row = W) after the arguments of the call they extend, use that call's
+ *    workspace query, and report its results over the items whose bit is clear:
+ *      search  an excluded item is never reported, whatever its key.  A row with fewer than k items left ends in id -1 with distance
+ *              +inf where distances ascend (L2, section 7) and -inf where scores descend (IP, COS).  k <= min(64, n_items) as before.
+ *      rank    the number of items i != targets[b] that are not excluded in row b and come before the target.  The target's own bit is
+ *              not consulted; its key has the bits of the plain call.  A target outside [0, n_items) gives -1.
+ *    Errors: those of the extended call, and RECNN_E_INVALID for a null or misaligned mask, words_per_row != W, n_items above the limit.
+ * ===================================================================================== */
+int recnn_seen_mask_words(int n_items, int64_t* h_words);
+int recnn_seen_mask_build(const int32_t* ids, int64_t n_ids, const int64_t* starts, const int64_t* lengths, const int64_t* keep,
+                          int n_rows, int n_items, uint64_t* out_words, void* stream);
+int recnn_topk_search_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                                int metric, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
+                                void* stream, const uint64_t* mask, int64_t words_per_row);
+int recnn_dist_topk_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                              int metric, double p, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
+                              void* stream, const uint64_t* mask, int64_t words_per_row);
+int recnn_topk_target_rank_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                                     int metric, const float* item_aux, const int64_t* targets, int32_t* out_rank, void* workspace,
+                                     void* stream, const uint64_t* mask, int64_t words_per_row);
+int recnn_dist_target_rank_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                                     int metric, double p, const float* item_aux, const int64_t* targets, int32_t* out_rank,
+                                     void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row);
+
 #ifdef __cplusplus
 }
 #endif

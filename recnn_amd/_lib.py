@@ -266,6 +266,12 @@ SIGNATURES = {
     "recnn_topk_target_rank": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "recnn_rank_metrics_workspace_bytes": (_I, [_I, C.POINTER(_L)]),
     "recnn_rank_metrics": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "recnn_seen_mask_words": (_I, [_I, C.POINTER(_L)]),
+    "recnn_seen_mask_build": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _P]),
+    "recnn_topk_search_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _L]),
+    "recnn_dist_topk_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _L]),
+    "recnn_topk_target_rank_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L]),
+    "recnn_dist_target_rank_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P, _L]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

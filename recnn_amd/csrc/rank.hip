@@ -29,7 +29,10 @@
 // come before one target item in that order.
 #include <algorithm>
 
+#include <type_traits>
+
 #include "common.h"
+#include "seen.h"
 #include "target_rank.h"
 
 #pragma clang fp contract(off)
@@ -56,6 +59,9 @@ struct DistArgs {
   float* out; int64_t ldo;              // MATRIX epilogue
   int K, splits; float* part_d; int32_t* part_i;  // TOPK epilogue: [B][splits][K]
 };
+// the excluding kernels take the mask of seen.h behind the same arguments; the plain ones keep their argument block
+struct DistArgsX : DistArgs { const uint64_t* mask; int64_t W; };
+template <bool EXCL> using DistArgsOf = std::conditional_t<EXCL, DistArgsX, DistArgs>;
 
 // the same order as one 64-bit key: distance bits (distances are >= +0: -0 counts as +0, every NaN as one value above +inf),
 // then the id
@@ -108,8 +114,9 @@ template <int LOOP> __device__ __forceinline__ float finish(float a0, float a1, 
   } else return a0;
 }
 
-template <int LOOP, int TQ, int TI, bool TOPK>
-__global__ __launch_bounds__(256) void dist_kernel(const DistArgs a) {
+template <int LOOP, int TQ, int TI, bool TOPK, bool EXCL = false>
+__global__ __launch_bounds__(256) void dist_kernel(const DistArgsOf<EXCL> a) {
+  static_assert(TOPK || !EXCL, "a matrix has no notion of absence");
   constexpr int QT = 4 * TQ, IT = 64 * TI;
   constexpr int STAGE = IT * (E / 4) / 256;     // float4 per thread per chunk
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -189,6 +196,11 @@ __global__ __launch_bounds__(256) void dist_kernel(const DistArgs a) {
           const uint64_t key = id < n_end ? rank_key(d, id) : ~0ull;
           uint64_t thr = rank_key(readlane_f(ld[i], K - 1), __builtin_amdgcn_readlane(li[i], K - 1));
           unsigned long long m = __ballot(key < thr);
+          if constexpr (EXCL) {
+            // per and n0 are multiples of 64: the block's 64 exclusion bits are one aligned word at a wave-uniform address; an
+            // excluded item is never a candidate, and the re-ballots below only clear bits of m
+            if (n0 + j * 64 < n_end) m &= ~seen_word(a.mask, a.W, q0 + row, n0 + j * 64);
+          }
           while (m) {
             const int src = __ffsll((long long)m) - 1;
             const float cd = readlane_f(d, src);
@@ -225,8 +237,8 @@ __global__ __launch_bounds__(256) void dist_kernel(const DistArgs a) {
 // row ties and is decided by its id.  Rows and items are tiled as in dist_kernel.  A wave's count of a row is a ballot's popcount:
 // it lives in scalar registers and goes out as one partial per (row, split).  A target outside [0, N) reads row 0; its count is
 // ignored by the finishing kernel, which reports -1.
-template <int LOOP, int TQ, int TI>
-__global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgs a, const int64_t* __restrict__ targets,
+template <int LOOP, int TQ, int TI, bool EXCL = false>
+__global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgsOf<EXCL> a, const int64_t* __restrict__ targets,
                                                         int32_t* __restrict__ part) {   // part: [B][splits]
   constexpr int QT = 4 * TQ, IT = 64 * TI;
   constexpr int STAGE = IT * (E / 4) / 256;
@@ -312,7 +324,13 @@ __global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgs a, const 
       for (int j = 0; j < TI; ++j) {
         const int id = n0 + j * 64 + lane;
         const float d = finish<LOOP>(a0[i][j], a1[i][j], a.metric, a.invp);
-        cnt[i] += __popcll(__ballot(id < n_end && rank_key(d, id) < tkey[i]));
+        unsigned long long m = __ballot(id < n_end && rank_key(d, id) < tkey[i]);
+        if constexpr (EXCL) {
+          // one aligned word at a wave-uniform address (rows past B repeat row B-1, as their queries do); the target's own bit is
+          // never consulted: its key is not below itself
+          if (n0 + j * 64 < n_end) m &= ~seen_word(a.mask, a.W, min(q0 + wave * TQ + i, a.B - 1), n0 + j * 64);
+        }
+        cnt[i] += __popcll(m);
       }
   }
   if (lane == 0) {
@@ -326,6 +344,7 @@ __global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgs a, const 
 
 // K best of a row's S sorted partial lists (S <= 256, S*K <= MERGE_CAND): one 64-lane workgroup per row, the lists in LDS,
 // lane l holding the heads of lists l, l+64, l+128, l+192
+template <bool EXCL = false>
 __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict__ pd, const int32_t* __restrict__ pi, int S, int K,
                                                         float* __restrict__ out_d, int64_t* __restrict__ out_i) {
   __shared__ float cd[MERGE_CAND];
@@ -356,7 +375,11 @@ __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict_
       const int oi = __shfl_xor(bi, o, 64);
       if (rank_key(od, oi) < rank_key(bd, bi)) { bd = od; bi = oi; }
     }
-    // k <= n_items, so the best head is a real item; its id is unique across the lists
+    // k <= n_items, so the best head is a real item; its id is unique across the lists.  EXCL: a row may have fewer than K items
+    // left; then every head is the sentinel, nothing advances, and the slot reads (+inf, -1)
+    if constexpr (EXCL) {
+      if (bi == 0x7FFFFFFF) { bd = INFINITY; bi = -1; }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (hi[j] == bi) {
@@ -428,58 +451,59 @@ Plan make_plan(int B, int N, int K) {
 
 size_t lds_bytes(bool big) { return (size_t)(big ? 128 : 64) * PITCH * 4; }
 
-template <int LOOP, int TQ, int TI, bool TOPK> int launch_one(const DistArgs& a, const Plan& pl, hipStream_t st) {
+template <int LOOP, int TQ, int TI, bool TOPK, bool EXCL> int launch_one(const DistArgsOf<EXCL>& a, const Plan& pl, hipStream_t st) {
   const size_t lds = lds_bytes(TQ == 8);
   static bool attr = false;
   if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)dist_kernel<LOOP, TQ, TI, TOPK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RECNN_HIP(hipFuncSetAttribute((const void*)dist_kernel<LOOP, TQ, TI, TOPK, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL((dist_kernel<LOOP, TQ, TI, TOPK>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((dist_kernel<LOOP, TQ, TI, TOPK, EXCL>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a);
   return 0;
 }
 
-template <int LOOP, bool TOPK> int launch_loop(const DistArgs& a, const Plan& pl, hipStream_t st) {
-  return pl.big ? launch_one<LOOP, 8, 2, TOPK>(a, pl, st) : launch_one<LOOP, 1, 1, TOPK>(a, pl, st);
+template <int LOOP, bool TOPK, bool EXCL> int launch_loop(const DistArgsOf<EXCL>& a, const Plan& pl, hipStream_t st) {
+  return pl.big ? launch_one<LOOP, 8, 2, TOPK, EXCL>(a, pl, st) : launch_one<LOOP, 1, 1, TOPK, EXCL>(a, pl, st);
 }
 
-template <bool TOPK> int launch(const DistArgs& a, const Plan& pl, hipStream_t st) {
+template <bool TOPK, bool EXCL = false> int launch(const DistArgsOf<EXCL>& a, const Plan& pl, hipStream_t st) {
   switch (a.metric) {
-    case SQEUCLIDEAN: case EUCLIDEAN: return launch_loop<L_SQ, TOPK>(a, pl, st);
-    case CITYBLOCK: return launch_loop<L_ABS, TOPK>(a, pl, st);
-    case CHEBYSHEV: return launch_loop<L_MAX, TOPK>(a, pl, st);
-    case MINKOWSKI: return launch_loop<L_POW, TOPK>(a, pl, st);
-    case CANBERRA: return launch_loop<L_CANB, TOPK>(a, pl, st);
-    case BRAYCURTIS: return launch_loop<L_BRAY, TOPK>(a, pl, st);
-    default: return launch_loop<L_DOT, TOPK>(a, pl, st);
+    case SQEUCLIDEAN: case EUCLIDEAN: return launch_loop<L_SQ, TOPK, EXCL>(a, pl, st);
+    case CITYBLOCK: return launch_loop<L_ABS, TOPK, EXCL>(a, pl, st);
+    case CHEBYSHEV: return launch_loop<L_MAX, TOPK, EXCL>(a, pl, st);
+    case MINKOWSKI: return launch_loop<L_POW, TOPK, EXCL>(a, pl, st);
+    case CANBERRA: return launch_loop<L_CANB, TOPK, EXCL>(a, pl, st);
+    case BRAYCURTIS: return launch_loop<L_BRAY, TOPK, EXCL>(a, pl, st);
+    default: return launch_loop<L_DOT, TOPK, EXCL>(a, pl, st);
   }
 }
 
-template <int LOOP, int TQ, int TI> int launch_rank_one(const DistArgs& a, const Plan& pl, const int64_t* targets, int32_t* part,
+template <int LOOP, int TQ, int TI, bool EXCL> int launch_rank_one(const DistArgsOf<EXCL>& a, const Plan& pl, const int64_t* targets, int32_t* part,
                                                         hipStream_t st) {
   const size_t lds = lds_bytes(TQ == 8);
   static bool attr = false;
   if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)dist_rank_kernel<LOOP, TQ, TI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RECNN_HIP(hipFuncSetAttribute((const void*)dist_rank_kernel<LOOP, TQ, TI, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL((dist_rank_kernel<LOOP, TQ, TI>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a, targets, part);
+  hipLaunchKernelGGL((dist_rank_kernel<LOOP, TQ, TI, EXCL>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a, targets, part);
   return 0;
 }
 
-template <int LOOP> int launch_rank_loop(const DistArgs& a, const Plan& pl, const int64_t* targets, int32_t* part, hipStream_t st) {
-  return pl.big ? launch_rank_one<LOOP, 8, 2>(a, pl, targets, part, st) : launch_rank_one<LOOP, 1, 1>(a, pl, targets, part, st);
+template <int LOOP, bool EXCL> int launch_rank_loop(const DistArgsOf<EXCL>& a, const Plan& pl, const int64_t* targets, int32_t* part,
+                                                    hipStream_t st) {
+  return pl.big ? launch_rank_one<LOOP, 8, 2, EXCL>(a, pl, targets, part, st) : launch_rank_one<LOOP, 1, 1, EXCL>(a, pl, targets, part, st);
 }
 
-int launch_rank(const DistArgs& a, const Plan& pl, const int64_t* targets, int32_t* part, hipStream_t st) {
+template <bool EXCL = false> int launch_rank(const DistArgsOf<EXCL>& a, const Plan& pl, const int64_t* targets, int32_t* part, hipStream_t st) {
   switch (a.metric) {
-    case SQEUCLIDEAN: case EUCLIDEAN: return launch_rank_loop<L_SQ>(a, pl, targets, part, st);
-    case CITYBLOCK: return launch_rank_loop<L_ABS>(a, pl, targets, part, st);
-    case CHEBYSHEV: return launch_rank_loop<L_MAX>(a, pl, targets, part, st);
-    case MINKOWSKI: return launch_rank_loop<L_POW>(a, pl, targets, part, st);
-    case CANBERRA: return launch_rank_loop<L_CANB>(a, pl, targets, part, st);
-    case BRAYCURTIS: return launch_rank_loop<L_BRAY>(a, pl, targets, part, st);
-    default: return launch_rank_loop<L_DOT>(a, pl, targets, part, st);
+    case SQEUCLIDEAN: case EUCLIDEAN: return launch_rank_loop<L_SQ, EXCL>(a, pl, targets, part, st);
+    case CITYBLOCK: return launch_rank_loop<L_ABS, EXCL>(a, pl, targets, part, st);
+    case CHEBYSHEV: return launch_rank_loop<L_MAX, EXCL>(a, pl, targets, part, st);
+    case MINKOWSKI: return launch_rank_loop<L_POW, EXCL>(a, pl, targets, part, st);
+    case CANBERRA: return launch_rank_loop<L_CANB, EXCL>(a, pl, targets, part, st);
+    case BRAYCURTIS: return launch_rank_loop<L_BRAY, EXCL>(a, pl, targets, part, st);
+    default: return launch_rank_loop<L_DOT, EXCL>(a, pl, targets, part, st);
   }
 }
 
@@ -557,24 +581,71 @@ extern "C" int recnn_dist_matrix(const float* queries, int64_t ld_q, int n_queri
   return recnn_check_hip(hipGetLastError(), "dist_matrix");
 }
 
-extern "C" int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
-                               int metric, double p, const float* item_aux, int k, float* out_dist, int64_t* out_ids,
-                               void* workspace, void* stream) {
-  if (int rc = check_common("dist_topk", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
-  RECNN_REQUIRE((out_dist && out_ids && workspace) || n_queries == 0, "dist_topk: null pointer");
-  RECNN_REQUIRE(k > 0 && k <= KMAX && k <= n_items, "dist_topk: need 0 < k <= min(64, n_items)");
-  RECNN_REQUIRE(aligned16(workspace), "dist_topk: 16-byte alignment (workspace)");
+namespace {
+template <bool EXCL>
+int dist_topk_impl(const char* fn, const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                   int metric, double p, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
+                   void* stream, const uint64_t* mask, int64_t words_per_row) {
+  if (int rc = check_common(fn, queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
+  RECNN_REQUIRE((out_dist && out_ids && workspace) || n_queries == 0, "%s: null pointer", fn);
+  RECNN_REQUIRE(k > 0 && k <= KMAX && k <= n_items, "%s: need 0 < k <= min(64, n_items)", fn);
+  RECNN_REQUIRE(aligned16(workspace), "%s: 16-byte alignment (workspace)", fn);
+  if constexpr (EXCL) {
+    if (int rc = seen_check(fn, mask, words_per_row, n_queries, n_items)) return rc;
+  }
   if (n_queries == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  DistArgs a;
+  DistArgsOf<EXCL> a;
   prepare(a, queries, ld_q, n_queries, table, n_items, metric, p, item_aux, workspace, st);
   const Plan pl = make_plan(n_queries, n_items, k);
   a.per = pl.per; a.K = k; a.splits = pl.splits;
   a.part_d = (float*)((char*)workspace + query_prep_bytes(n_queries, metric));
   a.part_i = (int32_t*)(a.part_d + (int64_t)n_queries * pl.splits * k);
-  if (int rc = launch<true>(a, pl, st)) return rc;
-  hipLaunchKernelGGL(dist_merge_kernel, dim3(n_queries), dim3(64), 0, st, a.part_d, a.part_i, pl.splits, k, out_dist, out_ids);
-  return recnn_check_hip(hipGetLastError(), "dist_topk");
+  if constexpr (EXCL) { a.mask = mask; a.W = words_per_row; }
+  if (int rc = launch<true, EXCL>(a, pl, st)) return rc;
+  hipLaunchKernelGGL(dist_merge_kernel<EXCL>, dim3(n_queries), dim3(64), 0, st, a.part_d, a.part_i, pl.splits, k, out_dist, out_ids);
+  return recnn_check_hip(hipGetLastError(), fn);
+}
+
+template <bool EXCL>
+int dist_target_rank_impl(const char* fn, const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items,
+                          int emb_dim, int metric, double p, const float* item_aux, const int64_t* targets, int32_t* out_rank,
+                          void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row) {
+  if (int rc = check_common(fn, queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
+  RECNN_REQUIRE((targets && out_rank && workspace) || n_queries == 0, "%s: null pointer", fn);
+  RECNN_REQUIRE(aligned16(workspace), "%s: 16-byte alignment (workspace)", fn);
+  if constexpr (EXCL) {
+    if (int rc = seen_check(fn, mask, words_per_row, n_queries, n_items)) return rc;
+  }
+  if (n_queries == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  DistArgsOf<EXCL> a;
+  prepare(a, queries, ld_q, n_queries, table, n_items, metric, p, item_aux, workspace, st);
+  const Plan pl = make_plan(n_queries, n_items, 0);
+  a.per = pl.per; a.splits = pl.splits;
+  if constexpr (EXCL) { a.mask = mask; a.W = words_per_row; }
+  int32_t* part = (int32_t*)((char*)workspace + query_prep_bytes(n_queries, metric));
+  if (int rc = launch_rank<EXCL>(a, pl, targets, part, st)) return rc;
+  hipLaunchKernelGGL(target_rank_finish_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, st, part, pl.splits, targets, n_queries,
+                     n_items, out_rank);
+  return recnn_check_hip(hipGetLastError(), fn);
+}
+}  // namespace
+
+extern "C" int recnn_dist_topk(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                               int metric, double p, const float* item_aux, int k, float* out_dist, int64_t* out_ids,
+                               void* workspace, void* stream) {
+  return dist_topk_impl<false>("dist_topk", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux, k, out_dist,
+                               out_ids, workspace, stream, nullptr, 0);
+}
+
+// the same search over the items whose bit in `mask` (seen.h) is clear; short rows end in (+inf, -1)
+extern "C" int recnn_dist_topk_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items,
+                                         int emb_dim, int metric, double p, const float* item_aux, int k, float* out_dist,
+                                         int64_t* out_ids, void* workspace, void* stream, const uint64_t* mask,
+                                         int64_t words_per_row) {
+  return dist_topk_impl<true>("dist_topk_excluding", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux, k,
+                              out_dist, out_ids, workspace, stream, mask, words_per_row);
 }
 
 extern "C" int recnn_dist_target_rank_workspace_bytes(int n_queries, int n_items, int metric, int64_t* h_bytes) {
@@ -589,18 +660,15 @@ extern "C" int recnn_dist_target_rank_workspace_bytes(int n_queries, int n_items
 extern "C" int recnn_dist_target_rank(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
                                       int metric, double p, const float* item_aux, const int64_t* targets, int32_t* out_rank,
                                       void* workspace, void* stream) {
-  if (int rc = check_common("dist_target_rank", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux)) return rc;
-  RECNN_REQUIRE((targets && out_rank && workspace) || n_queries == 0, "dist_target_rank: null pointer");
-  RECNN_REQUIRE(aligned16(workspace), "dist_target_rank: 16-byte alignment (workspace)");
-  if (n_queries == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  DistArgs a;
-  prepare(a, queries, ld_q, n_queries, table, n_items, metric, p, item_aux, workspace, st);
-  const Plan pl = make_plan(n_queries, n_items, 0);
-  a.per = pl.per; a.splits = pl.splits;
-  int32_t* part = (int32_t*)((char*)workspace + query_prep_bytes(n_queries, metric));
-  if (int rc = launch_rank(a, pl, targets, part, st)) return rc;
-  hipLaunchKernelGGL(target_rank_finish_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, st, part, pl.splits, targets, n_queries,
-                     n_items, out_rank);
-  return recnn_check_hip(hipGetLastError(), "dist_target_rank");
+  return dist_target_rank_impl<false>("dist_target_rank", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p, item_aux,
+                                      targets, out_rank, workspace, stream, nullptr, 0);
+}
+
+// the same count over the items whose bit in `mask` (seen.h) is clear
+extern "C" int recnn_dist_target_rank_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items,
+                                                int emb_dim, int metric, double p, const float* item_aux, const int64_t* targets,
+                                                int32_t* out_rank, void* workspace, void* stream, const uint64_t* mask,
+                                                int64_t words_per_row) {
+  return dist_target_rank_impl<true>("dist_target_rank_excluding", queries, ld_q, n_queries, table, n_items, emb_dim, metric, p,
+                                     item_aux, targets, out_rank, workspace, stream, mask, words_per_row);
 }

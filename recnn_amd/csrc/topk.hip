@@ -20,8 +20,10 @@
 // topk_rank_kernel scores the same way and, instead of selecting, counts per query row the items that come before one target
 // item: no lists, no limit on K.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
+#include "seen.h"
 #include "target_rank.h"
 
 namespace {
@@ -39,20 +41,26 @@ struct TopkArgs {
   float* part_score;       // [B][S][K]  internal key (larger = better)
   int32_t* part_id;        // [B][S][K]
 };
+// the excluding kernel takes the mask of seen.h behind the same arguments, and a split that is a multiple of IT so that a chunk's 64
+// exclusion bits are one word (results do not depend on the split); the plain kernel keeps its argument block and its split
+struct TopkArgsX : TopkArgs { const uint64_t* mask; int64_t W; int per; };
 
 __device__ inline bool better(float s, int id, float s2, int id2) { return s > s2 || (s == s2 && id < id2); }
 
-template <int E_>
-__global__ __launch_bounds__(256) void topk_scores_kernel(const TopkArgs a) {
+template <int E_, bool EXCL = false>
+__global__ __launch_bounds__(256) void topk_scores_kernel(const std::conditional_t<EXCL, TopkArgsX, TopkArgs> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Qs = (float*)smem;                  // [QT][PITCH]
   float* Ts = Qs + QT * PITCH;               // [IT][PITCH]
   float* Ss = Ts + IT * PITCH;               // [QT][IT + 4]
   float* Ls = Ss + QT * (IT + 4);            // [QT][KMAX] keys
   int* Li = (int*)(Ls + QT * KMAX);          // [QT][KMAX] ids
+  uint64_t* Xw = (uint64_t*)(Li + QT * KMAX);   // EXCL: [QT] the chunk's exclusion word of each query row
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q0 = blockIdx.x * QT;
-  const int per = (a.N + a.splits - 1) / a.splits;
+  int per;
+  if constexpr (EXCL) per = a.per;
+  else per = (a.N + a.splits - 1) / a.splits;
   const int n_begin = blockIdx.y * per, n_end = min(a.N, n_begin + per);
   const int K = a.K;
 
@@ -75,6 +83,9 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(const TopkArgs a) {
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (n0 + r < n_end) v = *(const float4*)(a.table + (int64_t)(n0 + r) * E_ + k4 * 4);
       *(float4*)&Ts[r * PITCH + k4 * 4] = v;
+    }
+    if constexpr (EXCL) {
+      if (tid < QT) Xw[tid] = q0 + tid < a.B ? seen_word(a.mask, a.W, q0 + tid, n0) : 0ull;   // n0 is a multiple of 64
     }
     __syncthreads();
     // ---- scores = Q T^T (exact fp32 MFMA)
@@ -129,6 +140,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(const TopkArgs a) {
       float thr = ls[K - 1];
       int thr_id = li[K - 1];
       unsigned long long m = __ballot(id < n_end && better(s, id, thr, thr_id));
+      if constexpr (EXCL) m &= ~Xw[row];                // an excluded item is never a candidate
       while (m) {                                       // rare after the first chunks
         const int src = __ffsll((long long)m) - 1;
         m &= m - 1;
@@ -223,6 +235,7 @@ struct TopkRankArgs {
   const int64_t* targets;    // [B]
   int32_t* part;             // [B][splits]
 };
+struct TopkRankArgsX : TopkRankArgs { const uint64_t* mask; int64_t W; };
 
 // the total order the counting uses: better() wherever both keys are numbers; an item whose key is NaN comes after every number, and
 // NaN keys order by id
@@ -267,7 +280,10 @@ __device__ __forceinline__ void score_tile(const float* Qs, const float* Ts, int
 // (register-staged) and compares every score, still in the MFMA accumulators, against its row's target key; the target itself is
 // skipped by id.  Counts: per lane, summed over each 16-lane row, then over the two waves of a row with LDS integer atomics.  A
 // target outside [0, N) scores a zero row; the finishing kernel reports -1 for it.
-__global__ __launch_bounds__(256) void topk_rank_kernel(const TopkRankArgs a) {
+// EXCL: an item whose bit is set in its row's mask (seen.h) is not counted.  The chunk's 64 words, one per query row, travel with the
+// register-staged table chunk into LDS; the target's own bit is never consulted (the target is skipped by id).
+template <bool EXCL = false>
+__global__ __launch_bounds__(256) void topk_rank_kernel(const std::conditional_t<EXCL, TopkRankArgsX, TopkRankArgs> a) {
   constexpr int E_ = 128;
   constexpr int STAGE = IT * (E_ / 4) / 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -276,6 +292,7 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const TopkRankArgs a) {
   float* Tk = Ts + IT * PITCH;               // [QT] target keys
   int* Tg = (int*)(Tk + QT);                 // [QT] target ids, -1: none
   int* Cn = Tg + QT;                         // [QT] counts
+  uint64_t* Xw = (uint64_t*)(Cn + QT);       // EXCL: [QT] the chunk's exclusion word of each query row (8-byte aligned: 3 QT ints)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q0 = blockIdx.x * QT;
   const int n_begin = blockIdx.y * a.per, n_end = min(a.N, n_begin + a.per);
@@ -292,11 +309,15 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const TopkRankArgs a) {
     *(float4*)&Qs[r * PITCH + k4 * 4] = v;
   }
   float4 stage[STAGE];
+  uint64_t xstage = 0ull;
   auto load_chunk = [&](int n0) {
 #pragma unroll
     for (int s = 0; s < STAGE; ++s) {
       const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
       stage[s] = n0 + r < n_end ? *(const float4*)(a.table + (int64_t)(n0 + r) * E_ + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if constexpr (EXCL) {
+      if (tid < QT && q0 + tid < a.B) xstage = seen_word(a.mask, a.W, q0 + tid, n0);   // per and n0 are multiples of 64
     }
   };
   if (n_begin < n_end) load_chunk(n_begin);
@@ -345,9 +366,19 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const TopkRankArgs a) {
       const int c = tid + s * 256;
       *(float4*)&Ts[(c >> 5) * PITCH + (c & 31) * 4] = stage[s];
     }
+    if constexpr (EXCL) {
+      if (tid < QT) Xw[tid] = xstage;
+    }
     __syncthreads();
     if (n0 + IT < n_end) load_chunk(n0 + IT);     // in flight while this chunk is scored
     score_tile(Qs, Ts, wm0, wn0, fr, fg, acc);
+    uint64_t xw[2][4];
+    if constexpr (EXCL) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xw[i][r] = Xw[wm0 + i * 16 + fg * 4 + r];
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int n = n0 + wn0 + j * 16 + fr;
@@ -358,7 +389,9 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const TopkRankArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float s = rank_score(acc[i][j][r], ax, a.metric);
-          cnt[i][r] += live && n != tg[i][r] && comes_before(s, n, tk[i][r], tg[i][r]);
+          bool counts = live && n != tg[i][r];
+          if constexpr (EXCL) counts = counts && !((xw[i][r] >> (n & 63)) & 1);
+          cnt[i][r] += counts && comes_before(s, n, tk[i][r], tg[i][r]);
         }
     }
   }
@@ -404,16 +437,21 @@ extern "C" int recnn_topk_item_aux(const float* table, int n_items, int emb_dim,
   return recnn_check_hip(hipGetLastError(), "topk_aux_kernel");
 }
 
-extern "C" int recnn_topk_search(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
-                                 int metric, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
-                                 void* stream) {
-  RECNN_REQUIRE(queries && table && out_dist && out_ids && workspace, "topk_search: null pointer");
-  RECNN_REQUIRE(n_queries >= 0 && n_items > 0 && k > 0 && k <= KMAX && k <= n_items, "topk_search: need 0 < k <= min(64, n_items)");
-  RECNN_REQUIRE(emb_dim == 128, "topk_search: emb_dim must be 128 (the reference's embedding width)");
-  RECNN_REQUIRE(metric == M_IP || ((metric == M_L2 || metric == M_COS) && item_aux), "topk_search: L2 / COS need the item aux array");
-  RECNN_REQUIRE((((uintptr_t)queries | (uintptr_t)table) & 15) == 0 && (ld_q % 4) == 0, "topk_search: 16-byte alignment");
+namespace {
+template <bool EXCL>
+int topk_search_impl(const char* fn, const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                     int metric, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace, void* stream,
+                     const uint64_t* mask, int64_t words_per_row) {
+  RECNN_REQUIRE(queries && table && out_dist && out_ids && workspace, "%s: null pointer", fn);
+  RECNN_REQUIRE(n_queries >= 0 && n_items > 0 && k > 0 && k <= KMAX && k <= n_items, "%s: need 0 < k <= min(64, n_items)", fn);
+  RECNN_REQUIRE(emb_dim == 128, "%s: emb_dim must be 128 (the reference's embedding width)", fn);
+  RECNN_REQUIRE(metric == M_IP || ((metric == M_L2 || metric == M_COS) && item_aux), "%s: L2 / COS need the item aux array", fn);
+  RECNN_REQUIRE((((uintptr_t)queries | (uintptr_t)table) & 15) == 0 && (ld_q % 4) == 0, "%s: 16-byte alignment", fn);
+  if constexpr (EXCL) {
+    if (int rc = seen_check(fn, mask, words_per_row, n_queries, n_items)) return rc;
+  }
   if (n_queries == 0) return 0;
-  TopkArgs a;
+  std::conditional_t<EXCL, TopkArgsX, TopkArgs> a;
   a.q = queries; a.ldq = ld_q; a.B = n_queries; a.table = table; a.N = n_items; a.E = emb_dim; a.aux = item_aux;
   a.metric = metric; a.K = k;
   const int tiles = (n_queries + QT - 1) / QT;
@@ -421,19 +459,72 @@ extern "C" int recnn_topk_search(const float* queries, int64_t ld_q, int n_queri
   if (splits < 1) splits = 1;
   if (splits > 8) splits = 8;
   while (splits > 1 && (n_items + splits - 1) / splits < 4 * IT) --splits;
+  if constexpr (EXCL) {                   // whole chunks per split, no empty split (never more splits than the plain launch)
+    a.per = ((n_items + splits - 1) / splits + IT - 1) / IT * IT;
+    splits = (n_items + a.per - 1) / a.per;
+    a.mask = mask; a.W = words_per_row;
+  }
   a.splits = splits;
   a.part_score = (float*)workspace;
   a.part_id = (int32_t*)((char*)workspace + (int64_t)n_queries * 8 * k * 4);
-  const size_t lds = (size_t)(QT * PITCH + IT * PITCH + QT * (IT + 4) + QT * KMAX) * 4 + (size_t)QT * KMAX * 4;
+  const size_t lds = (size_t)(QT * PITCH + IT * PITCH + QT * (IT + 4) + QT * KMAX) * 4 + (size_t)QT * KMAX * 4 + (EXCL ? QT * 8 : 0);
   static bool attr = false;
   if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)topk_scores_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RECNN_HIP(hipFuncSetAttribute((const void*)topk_scores_kernel<128, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL(topk_scores_kernel<128>, dim3(tiles, splits), dim3(256), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((topk_scores_kernel<128, EXCL>), dim3(tiles, splits), dim3(256), lds, (hipStream_t)stream, a);
+  // a short row's trailing slots hold the lists' sentinel, which the merge reports as id -1 at -inf (L2: +inf)
   hipLaunchKernelGGL(topk_merge_kernel, dim3((n_queries + 3) / 4), dim3(256), 0, (hipStream_t)stream, a.part_score, a.part_id, n_queries,
                      splits, k, metric, queries, ld_q, emb_dim, out_dist, out_ids);
-  return recnn_check_hip(hipGetLastError(), "topk_search");
+  return recnn_check_hip(hipGetLastError(), fn);
+}
+
+template <bool EXCL>
+int topk_target_rank_impl(const char* fn, const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items,
+                          int emb_dim, int metric, const float* item_aux, const int64_t* targets, int32_t* out_rank, void* workspace,
+                          void* stream, const uint64_t* mask, int64_t words_per_row) {
+  RECNN_REQUIRE(table && ((queries && targets && out_rank && workspace) || n_queries == 0), "%s: null pointer", fn);
+  RECNN_REQUIRE(n_queries >= 0 && n_items > 0, "%s: need n_queries >= 0 and n_items > 0", fn);
+  RECNN_REQUIRE(emb_dim == 128, "%s: emb_dim must be 128 (the reference's embedding width)", fn);
+  RECNN_REQUIRE(metric == M_IP || ((metric == M_L2 || metric == M_COS) && item_aux), "%s: metric must be IP, or L2 / COS with the item aux array", fn);
+  RECNN_REQUIRE(aligned16(queries, table) && ld_q % 4 == 0 && ld_q >= 128, "%s: 16-byte alignment (rows and ld_q)", fn);
+  if constexpr (EXCL) {
+    if (int rc = seen_check(fn, mask, words_per_row, n_queries, n_items)) return rc;
+  }
+  if (n_queries == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const RankPlan pl = make_rank_plan(n_queries, n_items);
+  std::conditional_t<EXCL, TopkRankArgsX, TopkRankArgs> a;
+  a.q = queries; a.ldq = ld_q; a.B = n_queries; a.table = table; a.N = n_items; a.aux = item_aux;
+  a.metric = metric; a.splits = pl.splits; a.per = pl.per; a.targets = targets; a.part = (int32_t*)workspace;
+  if constexpr (EXCL) { a.mask = mask; a.W = words_per_row; }
+  const size_t lds = (size_t)(QT * PITCH + IT * PITCH + 3 * QT) * 4 + (EXCL ? QT * 8 : 0);
+  static bool attr = false;
+  if (!attr) {
+    RECNN_HIP(hipFuncSetAttribute((const void*)topk_rank_kernel<EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  hipLaunchKernelGGL(topk_rank_kernel<EXCL>, dim3(pl.tiles, pl.splits), dim3(256), lds, st, a);
+  hipLaunchKernelGGL(target_rank_finish_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, st, a.part, pl.splits, targets, n_queries,
+                     n_items, out_rank);
+  return recnn_check_hip(hipGetLastError(), fn);
+}
+}  // namespace
+
+extern "C" int recnn_topk_search(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
+                                 int metric, const float* item_aux, int k, float* out_dist, int64_t* out_ids, void* workspace,
+                                 void* stream) {
+  return topk_search_impl<false>("topk_search", queries, ld_q, n_queries, table, n_items, emb_dim, metric, item_aux, k, out_dist,
+                                 out_ids, workspace, stream, nullptr, 0);
+}
+
+// the same search over the items whose bit in `mask` (seen.h) is clear; short rows end in id -1 at -inf (L2: +inf)
+extern "C" int recnn_topk_search_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items,
+                                           int emb_dim, int metric, const float* item_aux, int k, float* out_dist, int64_t* out_ids,
+                                           void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row) {
+  return topk_search_impl<true>("topk_search_excluding", queries, ld_q, n_queries, table, n_items, emb_dim, metric, item_aux, k,
+                                out_dist, out_ids, workspace, stream, mask, words_per_row);
 }
 
 extern "C" int recnn_topk_target_rank_workspace_bytes(int n_queries, int n_items, int64_t* h_bytes) {
@@ -445,25 +536,15 @@ extern "C" int recnn_topk_target_rank_workspace_bytes(int n_queries, int n_items
 extern "C" int recnn_topk_target_rank(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items, int emb_dim,
                                       int metric, const float* item_aux, const int64_t* targets, int32_t* out_rank, void* workspace,
                                       void* stream) {
-  RECNN_REQUIRE(table && ((queries && targets && out_rank && workspace) || n_queries == 0), "topk_target_rank: null pointer");
-  RECNN_REQUIRE(n_queries >= 0 && n_items > 0, "topk_target_rank: need n_queries >= 0 and n_items > 0");
-  RECNN_REQUIRE(emb_dim == 128, "topk_target_rank: emb_dim must be 128 (the reference's embedding width)");
-  RECNN_REQUIRE(metric == M_IP || ((metric == M_L2 || metric == M_COS) && item_aux), "topk_target_rank: metric must be IP, or L2 / COS with the item aux array");
-  RECNN_REQUIRE(aligned16(queries, table) && ld_q % 4 == 0 && ld_q >= 128, "topk_target_rank: 16-byte alignment (rows and ld_q)");
-  if (n_queries == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  const RankPlan pl = make_rank_plan(n_queries, n_items);
-  TopkRankArgs a;
-  a.q = queries; a.ldq = ld_q; a.B = n_queries; a.table = table; a.N = n_items; a.aux = item_aux;
-  a.metric = metric; a.splits = pl.splits; a.per = pl.per; a.targets = targets; a.part = (int32_t*)workspace;
-  const size_t lds = (size_t)(QT * PITCH + IT * PITCH + 3 * QT) * 4;
-  static bool attr = false;
-  if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)topk_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL(topk_rank_kernel, dim3(pl.tiles, pl.splits), dim3(256), lds, st, a);
-  hipLaunchKernelGGL(target_rank_finish_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, st, a.part, pl.splits, targets, n_queries,
-                     n_items, out_rank);
-  return recnn_check_hip(hipGetLastError(), "topk_target_rank");
+  return topk_target_rank_impl<false>("topk_target_rank", queries, ld_q, n_queries, table, n_items, emb_dim, metric, item_aux, targets,
+                                      out_rank, workspace, stream, nullptr, 0);
+}
+
+// the same count over the items whose bit in `mask` (seen.h) is clear
+extern "C" int recnn_topk_target_rank_excluding(const float* queries, int64_t ld_q, int n_queries, const float* table, int n_items,
+                                                int emb_dim, int metric, const float* item_aux, const int64_t* targets,
+                                                int32_t* out_rank, void* workspace, void* stream, const uint64_t* mask,
+                                                int64_t words_per_row) {
+  return topk_target_rank_impl<true>("topk_target_rank_excluding", queries, ld_q, n_queries, table, n_items, emb_dim, metric, item_aux,
+                                     targets, out_rank, workspace, stream, mask, words_per_row);
 }

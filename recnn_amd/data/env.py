@@ -280,6 +280,32 @@ class FrameEnv(StoreEnv):
         out = {k: (v[a:a + rows] if isinstance(v, torch.Tensor) else v) for k, v in whole.items()}
         return out
 
+    def _target_positions(self, batch, slots, what):
+        """(pos, start): per row of the batch, the store position of its action (the item at the end of its window) and the store
+        position where its user's history begins; host int64 arrays.  Shared by `target_items` and `seen_items`."""
+        st = self.store
+        meta = batch["meta"]
+        if slots is None:
+            try:
+                slots = st.slots(meta["users"].tolist())
+            except KeyError as e:
+                raise ValueError(f"{what}: user {e} of the batch is not in the replay store (a collate_slots batch made "
+                                 "without user_ids names slots: pass them as `slots`)") from None
+        slots = np.asarray(slots, dtype=np.int32)
+        sizes = meta["sizes"].numpy().astype(np.int64)
+        if len(slots) != len(sizes) or not np.array_equal(st.lengths[slots], sizes):
+            raise ValueError(f"{what}: the batch's users and sizes do not match the replay store")
+        rows = batch["action"].shape[0]
+        wins = np.maximum(sizes - self.frame_size, 0)
+        if rows > int(wins.sum()):
+            raise ValueError(f"{what}: the batch has {rows} rows but its users have {int(wins.sum())} windows")
+        if self._host_off is None:
+            self._host_off = np.concatenate([[0], np.cumsum(st.lengths)]).astype(np.int64)
+        first = self._host_off[slots] + self.frame_size           # position of each user's first action in the store
+        before = np.cumsum(wins) - wins                            # rows of the users before it
+        pos = (np.repeat(first - before, wins) + np.arange(int(wins.sum())))[:rows]
+        return pos, np.repeat(self._host_off[slots], wins)[:rows]
+
     def target_items(self, batch, slots=None):
         """int64 [rows] on the env's device: the table row id of each row's action, the item at the end of its window -- what
         `FlatIndex.rank_of(policy(batch["state"]), env.target_items(batch))` ranks.  Built from `batch["meta"]` and the batch's
@@ -288,28 +314,21 @@ class FrameEnv(StoreEnv):
         two loaders, with or without `rows_per_batch`.  A `collate_slots` batch made without `user_ids` records the slots as its
         users; where those differ from the user ids (`from_user_dict`), give the slots here.  `collate_rows` batches start
         inside a user and are not covered."""
-        st = self.store
-        meta = batch["meta"]
-        if slots is None:
-            try:
-                slots = st.slots(meta["users"].tolist())
-            except KeyError as e:
-                raise ValueError(f"target_items: user {e} of the batch is not in the replay store (a collate_slots batch made "
-                                 "without user_ids names slots: pass them as `slots`)") from None
-        slots = np.asarray(slots, dtype=np.int32)
-        sizes = meta["sizes"].numpy().astype(np.int64)
-        if len(slots) != len(sizes) or not np.array_equal(st.lengths[slots], sizes):
-            raise ValueError("target_items: the batch's users and sizes do not match the replay store")
-        rows = batch["action"].shape[0]
-        wins = np.maximum(sizes - self.frame_size, 0)
-        if rows > int(wins.sum()):
-            raise ValueError(f"target_items: the batch has {rows} rows but its users have {int(wins.sum())} windows")
-        if self._host_off is None:
-            self._host_off = np.concatenate([[0], np.cumsum(st.lengths)]).astype(np.int64)
-        first = self._host_off[slots] + self.frame_size           # position of each user's first action in the store
-        before = np.cumsum(wins) - wins                            # rows of the users before it
-        pos = (np.repeat(first - before, wins) + np.arange(int(wins.sum())))[:rows]
-        return st.items[torch.from_numpy(pos).to(self.device)].long()
+        pos, _ = self._target_positions(batch, slots, "target_items")
+        return self.store.items[torch.from_numpy(pos).to(self.device)].long()
+
+    def seen_items(self, batch, slots=None, keep_targets=True):
+        """`retrieval.SeenItems` of the batch's rows: for each row, everything its user did before the row's target -- the window
+        that forms the state included -- as a slice of the replay store's `items` (no ids are copied): `starts` is the user's
+        offset in the store, `lengths` the target's store position minus that offset.  With `keep_targets` the row's own target
+        (`target_items(batch)`) is taken out of its list again, so a user who consumed the target earlier can still be recommended
+        it and `search` and `rank_of` stay consistent with each other.  Pass it as `exclude` to `FlatIndex.search` / `rank_of`.
+        Covers the batches `target_items` covers, takes `slots` as it does and raises its errors."""
+        from ..retrieval import SeenItems
+        pos, start = self._target_positions(batch, slots, "seen_items")
+        items = self.store.items
+        keep = items[torch.from_numpy(pos).to(self.device)].long() if keep_targets else None
+        return SeenItems(items, torch.from_numpy(start), torch.from_numpy(pos - start), keep)
 
     def prepare_batch_wrapper(self, x):
         """collate_fn-compatible entry (env.py:241-248): x = list of UserDataset items."""

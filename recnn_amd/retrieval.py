@@ -101,15 +101,33 @@ class FlatIndex:
     def ntotal(self):
         return self.n_items
 
-    def search(self, queries: torch.Tensor, k: int = 10):
+    def search(self, queries: torch.Tensor, k: int = 10, exclude=None):
         """(distances float32[B, k], ids int64[B, k]); L2 -> squared distances ascending, IP / COS -> scores descending,
-        scipy metrics -> distances ascending."""
+        scipy metrics -> distances ascending.
+
+        `exclude` (a `SeenItems` or `SeenMask` of B rows): the items excluded in a row do not exist for it.  A row with fewer
+        than k items left ends in id -1 with distance +inf (L2, scipy metrics) or -inf (IP, COS), faiss's convention."""
         if self.metric in DIST_METRICS:
             _on_gpu(queries, "FlatIndex.search: the queries")
         q = _queries(queries, self.table.device)
         B = q.shape[0]
         dist = torch.empty(B, k, dtype=torch.float32, device=q.device)
         ids = torch.empty(B, k, dtype=torch.int64, device=q.device)
+        if exclude is not None:
+            m = self._exclusion(exclude, B, "FlatIndex.search")
+            if B == 0:
+                return dist, ids
+            if self.metric in DIST_METRICS:
+                ws = L.workspace("recnn_dist_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], k, device=q.device)
+                L.call("recnn_dist_topk_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
+                       DIST_METRICS[self.metric], self.p, L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws),
+                       L.current_stream(), L.ptr(m.words), m.words.shape[1])
+            else:
+                ws = L.workspace("recnn_topk_workspace_bytes", B, k, device=q.device)
+                L.call("recnn_topk_search_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
+                       METRICS[self.metric], L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream(),
+                       L.ptr(m.words), m.words.shape[1])
+            return dist, ids
         if self.metric in DIST_METRICS:
             ws = L.workspace("recnn_dist_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], k, device=q.device)
             L.call("recnn_dist_topk", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
@@ -120,15 +138,47 @@ class FlatIndex:
                L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream())
         return dist, ids
 
-    def rank_of(self, queries: torch.Tensor, targets: torch.Tensor):
+    def _exclusion(self, exclude, B, what):
+        """The `SeenMask` of an `exclude` argument, checked against this index and a batch of B rows."""
+        if not isinstance(exclude, (SeenItems, SeenMask)):
+            raise TypeError(f"{what}: exclude must be a SeenItems or a SeenMask, got {type(exclude).__name__}")
+        if exclude.rows != B:
+            raise ValueError(f"{what}: {B} queries but an exclusion of {exclude.rows} rows")
+        m = exclude.mask(self.n_items) if isinstance(exclude, SeenItems) else exclude
+        if m.n_items != self.n_items:
+            raise ValueError(f"{what}: the exclusion mask was built for n_items = {m.n_items}, the index holds {self.n_items}")
+        if m.words.device != self.table.device:
+            raise ValueError(f"{what}: the exclusion mask lives on {m.words.device}, the index on {self.table.device}")
+        return m
+
+    def rank_of(self, queries: torch.Tensor, targets: torch.Tensor, exclude=None):
         """int32 [B]: for each query row, how many items come before item `targets[b]` in the order `search` uses (0 = the
-        target is the best item); -1 for a target id outside [0, n_items).  The whole table is counted: no limit of 64."""
+        target is the best item); -1 for a target id outside [0, n_items).  The whole table is counted: no limit of 64.
+
+        `exclude` (a `SeenItems` or `SeenMask` of B rows): the items excluded in a row are not counted.  The target's own bit is
+        not consulted: an excluded target is still ranked among the rest."""
         if self.metric in DIST_METRICS:
             _on_gpu(queries, "FlatIndex.rank_of: the queries")
         q = _queries(queries, self.table.device)
         B = q.shape[0]
         t = _targets(targets, B, q.device, "FlatIndex.rank_of")
         rank = torch.empty(B, dtype=torch.int32, device=q.device)
+        if exclude is not None:
+            m = self._exclusion(exclude, B, "FlatIndex.rank_of")
+            if B == 0:
+                return rank
+            if self.metric in DIST_METRICS:
+                ws = L.workspace("recnn_dist_target_rank_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric],
+                                 device=q.device)
+                L.call("recnn_dist_target_rank_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
+                       DIST_METRICS[self.metric], self.p, L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream(),
+                       L.ptr(m.words), m.words.shape[1])
+            else:
+                ws = L.workspace("recnn_topk_target_rank_workspace_bytes", B, self.n_items, device=q.device)
+                L.call("recnn_topk_target_rank_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
+                       METRICS[self.metric], L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream(),
+                       L.ptr(m.words), m.words.shape[1])
+            return rank
         if B == 0:                                                       # an empty batch has no storage to point at
             return rank
         if self.metric in DIST_METRICS:
@@ -228,7 +278,9 @@ class DiversityMeter:
 
     `mean` / `std` are the notebooks' `D.mean(axis=1).mean()` / `D.std(axis=1).mean()` over all rows seen, `recommended()`
     what `np.unique(ids, return_counts=True)` gives, `counts_of_counts()` what `pd.Series(counts).value_counts()` holds.
-    Reading any of them synchronises once and raises ValueError if an id was outside [0, n_items)."""
+    Reading any of them synchronises once and raises ValueError if an id was outside [0, n_items).  That includes the id -1 a
+    `search(..., exclude=...)` reports for a row with fewer than k items left: such a row has no k recommendations to take
+    statistics of, and raising is the right answer for it."""
 
     def __init__(self, n_items, sqrt=False, device="cuda"):
         self.n_items, self.sqrt = int(n_items), bool(sqrt)
@@ -285,9 +337,10 @@ __all__ += ["topk_stats", "DiversityMeter"]
 # ---- offline ranking evaluation (csrc/rank.hip, csrc/topk.hip, csrc/evalrank.hip): the rank of the item the
 # user took next under the generated action, and hit rate / NDCG / MRR accumulated over the test loader's batches.
 
-def target_ranks(queries, table, targets, metric="L2", p=None):
-    """`FlatIndex(table, metric, p).rank_of(queries, targets)` in one call, as `cdist` is for the matrix."""
-    return FlatIndex(table, metric, p).rank_of(queries, targets)
+def target_ranks(queries, table, targets, metric="L2", p=None, exclude=None):
+    """`FlatIndex(table, metric, p).rank_of(queries, targets, exclude)` in one call, as `cdist` is for the matrix."""
+    index = FlatIndex(table, metric, p)
+    return index.rank_of(queries, targets) if exclude is None else index.rank_of(queries, targets, exclude)
 
 
 MAX_CUTOFFS = 8
@@ -379,3 +432,89 @@ class RankingMeter:
 
 
 __all__ += ["target_ranks", "RankingMeter"]
+
+
+# ---- per-row exclusion (csrc/seen.hip): what a user has already consumed is left out of `search` and
+# `rank_of`, as the usual offline protocol does before hit@K / NDCG / MRR.
+
+class SeenMask:
+    """One bit per (query row, item): `words` int64 [rows, ceil(n_items / 64)] on the GPU, bit (i & 63) of word (i >> 6) of row b
+    set when item i is excluded for row b (the int64 holds the uint64 bit pattern).  Made by `SeenItems.mask`."""
+    __slots__ = ("words", "n_items", "rows")
+
+    def __init__(self, words, n_items):
+        self.words, self.n_items, self.rows = words, int(n_items), words.shape[0]
+
+
+def _row_ints(t, B, what, name):
+    t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.dim() != 1:
+        raise ValueError(f"{what}: {name} must be a 1-D integer tensor, got {t.dtype} {tuple(t.shape)}")
+    if B is not None and t.shape[0] != B:
+        raise ValueError(f"{what}: {B} starts but {t.shape[0]} {name}")
+    return t
+
+
+class SeenItems:
+    """Per query row, a list of item ids that do not exist for that row: row b's list is `ids[starts[b] : starts[b] + lengths[b]]`.
+
+    `ids` is one integer tensor on the GPU that the rows' lists are slices of (a replay store's `items`, used as it is when it is
+    int32; another integer dtype is converted once, values that do not fit int32 become -1).  `starts`, `lengths` and the optional
+    `keep` are 1-D integer tensors of one length B.  Lists are unordered and may repeat ids; ids outside the catalogue and
+    positions outside `ids` are ignored by the kernel, so nothing here synchronises to validate device data.  `keep[b]` (a row
+    id, typically the row's target) is taken out of row b's list again.  `FrameEnv.seen_items` builds one from a batch."""
+
+    def __init__(self, ids, starts, lengths, keep=None):
+        what = "SeenItems"
+        ids = torch.as_tensor(ids)
+        if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool or ids.dim() != 1:
+            raise ValueError(f"{what}: ids must be a 1-D integer tensor, got {ids.dtype} {tuple(ids.shape)}")
+        starts = _row_ints(starts, None, what, "starts")
+        B = starts.shape[0]
+        lengths = _row_ints(lengths, B, what, "lengths")
+        if keep is not None:
+            keep = _row_ints(keep, B, what, "keep")
+        _on_gpu(ids, "SeenItems: ids")
+        ids = ids.detach()
+        if ids.dtype != torch.int32:
+            if ids.dtype not in (torch.int8, torch.uint8, torch.int16):      # the rest can hold values int32 cannot
+                wide = ids.to(torch.int64)
+                ids = torch.where((wide >= -2 ** 31) & (wide < 2 ** 31), wide, -1)
+            ids = ids.to(torch.int32)
+        ids = ids.contiguous()
+        self.ids = ids.clone() if ids.data_ptr() % 4 else ids
+        dev = ids.device
+        self.starts = starts.detach().to(dev, torch.int64).contiguous()
+        self.lengths = lengths.detach().to(dev, torch.int64).contiguous()
+        self.keep = None if keep is None else keep.detach().to(dev, torch.int64).contiguous()
+        self.rows = B
+        self._masks = {}
+
+    @classmethod
+    def from_lists(cls, lists, device="cuda", keep=None):
+        """From one Python sequence of ids per row (for callers without a CSR)."""
+        rows = [[int(i) for i in row] for row in lists]
+        lengths = torch.tensor([len(r) for r in rows], dtype=torch.int64)
+        starts = torch.cumsum(lengths, 0) - lengths
+        flat = [i if -2 ** 63 <= i < 2 ** 63 else -1 for r in rows for i in r]
+        ids = torch.tensor(flat, dtype=torch.int64).to(device)
+        return cls(ids, starts, lengths, keep)
+
+    def mask(self, n_items):
+        """The `SeenMask` of these rows over a catalogue of `n_items` items: one launch, cached per `n_items`."""
+        n_items = int(n_items)
+        m = self._masks.get(n_items)
+        if m is None:
+            if not 0 < n_items < 2 ** 31:
+                raise ValueError(f"SeenItems.mask: n_items must be positive and below 2^31, got {n_items}")
+            nw = C.c_int64()
+            L.call("recnn_seen_mask_words", n_items, C.byref(nw))          # refuses a catalogue above the LDS limit, by name
+            words = torch.empty(self.rows, nw.value, dtype=torch.int64, device=self.ids.device)
+            if self.rows:
+                L.call("recnn_seen_mask_build", L.ptr(self.ids), self.ids.shape[0], L.ptr(self.starts), L.ptr(self.lengths),
+                       L.ptr(self.keep), self.rows, n_items, L.ptr(words), L.current_stream())
+            m = self._masks[n_items] = SeenMask(words, n_items)
+        return m
+
+
+__all__ += ["SeenItems", "SeenMask"]

@@ -11,7 +11,13 @@ Every figure is the median of 5 device-event windows of back-to-back calls after
 torch.matmul rounds differently, so near-ties may swap).  Kernel times: a separate
 `rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --quick` run.
 Prints one JSON object and writes it to profiles/eval_bench.json.
-usage: python tools/eval_bench.py [--quick] [--out profiles/eval_bench.json]"""
+`--seen` adds to each row the same `rank_of` and `search(k=10)` calls with a per-row exclusion mask: one list
+per query row, its length drawn like the synthetic store's histories (clip(round(lognormal(4.22, 1.22)), 20, 9254)),
+its ids uniform over the catalogue, all lists slices of one id array.  `mask_build_us` is `SeenItems.mask` alone (the cache
+emptied before each call), `*_excl_us` the call with the mask already built (what a second call on the same batch costs),
+`rank_of_excl_first_us` the first call (build + rank).  Every ratio is against the plain call of the same row in the same run.
+With `--seen` the default output is profiles/eval_bench_seen.json.
+usage: python tools/eval_bench.py [--quick] [--seen] [--out profiles/eval_bench.json]"""
 import argparse
 import json
 import os
@@ -57,12 +63,15 @@ def rank_from_matrix(key, targets, larger_is_better):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="B = 2048 only, short windows (for a profiler run)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench.json"))
+    ap.add_argument("--seen", action="store_true", help="also time rank_of / search with a per-row exclusion mask")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "eval_bench_seen.json" if a.seen else "eval_bench.json")
     if not torch.cuda.is_available():
         sys.exit("eval_bench.py measures on the GPU and none is visible")
     import recnn_amd
-    from recnn_amd.retrieval import FlatIndex, RankingMeter, cdist
+    from recnn_amd.retrieval import FlatIndex, RankingMeter, SeenItems, cdist
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
     table = torch.randn(N, E, generator=gen).to(dev)
@@ -83,6 +92,23 @@ def main():
     for B in ((2048,) if a.quick else (2048, 25)):
         q = (torch.randn(B, E, generator=gen) * 0.7).to(dev)
         targets = torch.randint(0, N, (B,), generator=gen).to(dev)
+        if a.seen:
+            import numpy as np
+            rng = np.random.default_rng(0)
+            lens = np.clip(np.round(rng.lognormal(4.22, 1.22, size=B)), 20, 9254).astype(np.int64)
+            starts = np.cumsum(lens) - lens
+            seen = SeenItems(torch.from_numpy(rng.integers(0, N, size=int(lens.sum())).astype(np.int32)).to(dev),
+                             torch.from_numpy(starts), torch.from_numpy(lens), keep=targets)
+
+            def build_mask():
+                seen._masks.clear()
+                return seen.mask(N)
+
+            mask_us, n_b = device_us(build_mask, window)
+            excluded = int(sum(bin(w & (2 ** 64 - 1)).count("1") for w in seen.mask(N).words.flatten().tolist()))
+            out.setdefault("seen", []).append({"B": B, "ids": int(lens.sum()), "longest": int(lens.max()),
+                                               "excluded_bits": excluded, "mask_bytes": 8 * seen.mask(N).words.numel(),
+                                               "mask_build_us": round(mask_us, 2), "iters": n_b})
         for metric in ("L2", "IP", "cityblock"):
             idx = index[metric]
             rank_us, n_r = device_us(lambda: idx.rank_of(q, targets), window)
@@ -96,6 +122,24 @@ def main():
                                  "rank_over_search": round(rank_us / search_us, 3),
                                  "materialise_over_rank": round(mat_us / rank_us, 2), "agree": round(agree, 5),
                                  "matrix_bytes": 4 * B * N})
+            if a.seen:
+                def first_call():
+                    seen._masks.clear()
+                    return idx.rank_of(q, targets, exclude=seen)
+
+                first_us, n_f = device_us(first_call, window)
+                rank_x_us, n_rx = device_us(lambda: idx.rank_of(q, targets, exclude=seen), window)
+                search_x_us, n_sx = device_us(lambda: idx.search(q, 10, exclude=seen), window)
+                # the plain calls again, after the excluding ones: the spread of the baseline within this run
+                rank2_us, _ = device_us(lambda: idx.rank_of(q, targets), window)
+                search2_us, _ = device_us(lambda: idx.search(q, 10), window)
+                assert (idx.rank_of(q, targets, exclude=seen) <= idx.rank_of(q, targets)).all()
+                out["cases"][-1].update({"rank_of_excl_us": round(rank_x_us, 2), "rank_of_excl_first_us": round(first_us, 2),
+                                         "search_k10_excl_us": round(search_x_us, 2), "rank_of_again_us": round(rank2_us, 2),
+                                         "search_k10_again_us": round(search2_us, 2),
+                                         "rank_excl_over_rank": round(rank_x_us / rank_us, 3),
+                                         "search_excl_over_search": round(search_x_us / search_us, 3),
+                                         "iters_excl": [n_f, n_rx, n_sx]})
         state = torch.randn(B, FRAME * (E + 1), generator=gen).to(dev)
         meter = RankingMeter(ks=(1, 10, 100), device=dev)
 

@@ -1046,6 +1046,42 @@ int recnn_dist_target_rank_excluding(const float* queries, int64_t ld_q, int n_q
                                      int metric, double p, const float* item_aux, const int64_t* targets, int32_t* out_rank,
                                      void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row);
 
+/* =====================================================================================
+ * 13. The catalogue ranked by the critic's Q-value (csrc/qrank.hip, csrc/scoresel.hip).
+ *    For a critic  Q(s, a) = w3 . relu(W2 . relu(W1 [s | a] + b1) + b2) + b3  and an item table [n_items][128], layer 1 splits along
+ *    its input:  S1 = state . W1[:, :S]^T + b1  per state row,  E1 = table . W1[:, S:]^T  per item (both recnn_qrank_layer1), and
+ *    recnn_qrank_scores writes  Q[b][n] = w3 . relu(W2 . relu(S1[b] + E1[n]) + b2) + b3  for every pair, float32, exact-fp32 MFMA;
+ *    no per-pair activation reaches memory.  The bits of Q[b][n] depend on the operands of that pair alone: not on n_states, n_items,
+ *    the pair's place in a tile or how the caller blocks the state rows.
+ *    hidden_padded: the hidden width zero-padded to a multiple of 64 (recnn_qrank_hidden_padded; hidden <= 256).  All operands are
+ *    padded to it with zeros by the caller: w [hidden_padded][ld_w], bias / b2 / w3 [hidden_padded], w2 [hidden_padded][hidden_padded]
+ *    (row j = output unit j), S1 / E1 rows of hidden_padded floats.  recnn_qrank_layer1: k % 16 == 0 (zero-pad the input columns),
+ *    bias may be NULL.  16-byte aligned x, w, s1, e1, w2; strides multiples of 4 floats.
+ *    recnn_qrank_block_rows (host-only): how many state rows of Q fit max_bytes, in whole 16-row tiles, at least one tile.
+ *
+ *    recnn_scores_topk / recnn_scores_rank select from float32 scores [n_rows][n_items] with row stride ld (floats) that already exist:
+ *    larger score first, ties to the smaller id (-0 == +0), NaN after every number in id order.  mask (may be NULL, then
+ *    words_per_row = 0): the exclusion words of section 12; an excluded item does not exist for its row.
+ *      topk  0 < k <= 64, k may exceed n_items; a row with fewer than k items left ends in id -1 with score -inf.
+ *      rank  int32: the items i != targets[b], not excluded, that come before the target; the target's own bit is not consulted; a target
+ *            outside [0, n_items) gives -1 and reads nothing.
+ *    Per-(row, split) results go through the workspace to a finishing kernel (no atomics): results do not depend on the split.
+ *    Errors: RECNN_E_INVALID before any HIP call for null pointers, k outside 1..64, ld < n_items, misalignment, hidden above 256, and
+ *    the mask errors of section 12.  Zero rows launch nothing.
+ * ===================================================================================== */
+int recnn_qrank_hidden_padded(int hidden, int* h_padded);
+int recnn_qrank_block_rows(int n_items, int64_t max_bytes, int64_t* h_rows);
+int recnn_qrank_layer1(const float* x, int64_t ld_x, int n_rows, int k, const float* w, int64_t ld_w, const float* bias,
+                       int hidden_padded, float* out, int64_t ld_out, void* stream);
+int recnn_qrank_scores(const float* s1, int64_t ld_s1, int n_states, const float* e1, int64_t ld_e1, int n_items, int hidden_padded,
+                       const float* w2, const float* b2, const float* w3, float b3, float* out, int64_t ld_out, void* stream);
+int recnn_scores_topk_workspace_bytes(int n_rows, int k, int64_t* h_bytes);
+int recnn_scores_topk(const float* scores, int64_t ld, int n_rows, int n_items, int k, float* out_scores, int64_t* out_ids,
+                      void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row);
+int recnn_scores_rank_workspace_bytes(int n_rows, int n_items, int64_t* h_bytes);
+int recnn_scores_rank(const float* scores, int64_t ld, int n_rows, int n_items, const int64_t* targets, int32_t* out_rank,
+                      void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row);
+
 #ifdef __cplusplus
 }
 #endif

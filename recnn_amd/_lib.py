@@ -272,6 +272,14 @@ SIGNATURES = {
     "recnn_dist_topk_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _L]),
     "recnn_topk_target_rank_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L]),
     "recnn_dist_target_rank_excluding": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P, _L]),
+    "recnn_qrank_hidden_padded": (_I, [_I, C.POINTER(_I)]),
+    "recnn_qrank_block_rows": (_I, [_I, _L, C.POINTER(_L)]),
+    "recnn_qrank_layer1": (_I, [_P, _L, _I, _I, _P, _L, _P, _I, _P, _L, _P]),
+    "recnn_qrank_scores": (_I, [_P, _L, _I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _P]),
+    "recnn_scores_topk_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_scores_topk": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _L]),
+    "recnn_scores_rank_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_scores_rank": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _L]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

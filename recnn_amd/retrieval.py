@@ -140,16 +140,7 @@ class FlatIndex:
 
     def _exclusion(self, exclude, B, what):
         """The `SeenMask` of an `exclude` argument, checked against this index and a batch of B rows."""
-        if not isinstance(exclude, (SeenItems, SeenMask)):
-            raise TypeError(f"{what}: exclude must be a SeenItems or a SeenMask, got {type(exclude).__name__}")
-        if exclude.rows != B:
-            raise ValueError(f"{what}: {B} queries but an exclusion of {exclude.rows} rows")
-        m = exclude.mask(self.n_items) if isinstance(exclude, SeenItems) else exclude
-        if m.n_items != self.n_items:
-            raise ValueError(f"{what}: the exclusion mask was built for n_items = {m.n_items}, the index holds {self.n_items}")
-        if m.words.device != self.table.device:
-            raise ValueError(f"{what}: the exclusion mask lives on {m.words.device}, the index on {self.table.device}")
-        return m
+        return _exclusion(exclude, B, self.n_items, self.table.device, what)
 
     def rank_of(self, queries: torch.Tensor, targets: torch.Tensor, exclude=None):
         """int32 [B]: for each query row, how many items come before item `targets[b]` in the order `search` uses (0 = the
@@ -190,6 +181,20 @@ class FlatIndex:
         L.call("recnn_topk_target_rank", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim, METRICS[self.metric],
                L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream())
         return rank
+
+
+def _exclusion(exclude, B, n_items, device, what):
+    """The `SeenMask` of an `exclude` argument, checked against a catalogue of `n_items` on `device` and a batch of B rows."""
+    if not isinstance(exclude, (SeenItems, SeenMask)):
+        raise TypeError(f"{what}: exclude must be a SeenItems or a SeenMask, got {type(exclude).__name__}")
+    if exclude.rows != B:
+        raise ValueError(f"{what}: {B} queries but an exclusion of {exclude.rows} rows")
+    m = exclude.mask(n_items) if isinstance(exclude, SeenItems) else exclude
+    if m.n_items != n_items:
+        raise ValueError(f"{what}: the exclusion mask was built for n_items = {m.n_items}, the index holds {n_items}")
+    if m.words.device != device:
+        raise ValueError(f"{what}: the exclusion mask lives on {m.words.device}, the index on {device}")
+    return m
 
 
 def _targets(targets, B, device, what):
@@ -518,3 +523,242 @@ class SeenItems:
 
 
 __all__ += ["SeenItems", "SeenMask"]
+
+
+# ---- the catalogue ranked by value (csrc/qrank.hip, csrc/scoresel.hip): selection from a score matrix that
+# already exists, and the critic's Q-value of every (state, item) pair as that matrix.
+
+MAX_K = 64
+
+
+def _scores(scores, what):
+    _on_gpu(scores, f"{what}: scores")
+    if scores.dim() != 2 or scores.shape[1] < 1:
+        raise ValueError(f"{what}: scores must be [B, N] with N >= 1, got {tuple(scores.shape)}")
+    s = scores.detach()
+    if s.dtype != torch.float32:
+        s = s.to(torch.float32)
+    if s.stride(1) != 1 or (s.shape[0] > 1 and s.stride(0) < s.shape[1]) or s.data_ptr() % 4:
+        s = s.contiguous()
+    return s
+
+
+def _ld(s):
+    return s.stride(0) if s.shape[0] > 1 else s.shape[1]
+
+
+def _mask_rows(m, r0, r1):
+    """(pointer, words per row) of rows [r0, r1) of a `SeenMask`, or (NULL, 0)."""
+    if m is None:
+        return None, 0
+    return C.c_void_p(m.words.data_ptr() + r0 * m.words.stride(0) * 8), m.words.shape[1]
+
+
+def _check_k(k, what):
+    if int(k) != k or not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k must be an integer from 1 to {MAX_K}, got {k}")
+    return int(k)
+
+
+def _select_topk(s, ld, B, N, k, out_s, out_i, m, r0):
+    ws = L.workspace("recnn_scores_topk_workspace_bytes", B, k, device=out_s.device)
+    mp, W = _mask_rows(m, r0, r0 + B)
+    L.call("recnn_scores_topk", s, ld, B, N, k, L.ptr(out_s), L.ptr(out_i), L.ptr(ws), L.current_stream(), mp, W)
+
+
+def _select_rank(s, ld, B, N, t, out_r, m, r0):
+    ws = L.workspace("recnn_scores_rank_workspace_bytes", B, N, device=out_r.device)
+    mp, W = _mask_rows(m, r0, r0 + B)
+    L.call("recnn_scores_rank", s, ld, B, N, L.ptr(t), L.ptr(out_r), L.ptr(ws), L.current_stream(), mp, W)
+
+
+def topk_of_scores(scores, k, exclude=None):
+    """(values float32[B, k], ids int64[B, k]) of a float32 score matrix [B, N] on the GPU (any row stride): larger score first,
+    ties to the smaller id (-0 == +0), NaN after every number in id order.  `exclude` (a `SeenItems` or `SeenMask` of B rows): the
+    items excluded in a row do not exist for it.  k <= 64 and may exceed N; a row with fewer than k items left ends in id -1 with
+    score -inf.  N is not limited by k or by 16-bit ids: `DiscreteActor`'s probabilities over a whole catalogue are such a matrix."""
+    what = "topk_of_scores"
+    s = _scores(scores, what)
+    k = _check_k(k, what)
+    B, N = s.shape
+    m = None if exclude is None else _exclusion(exclude, B, N, s.device, what)
+    out_s = torch.empty(B, k, dtype=torch.float32, device=s.device)
+    out_i = torch.empty(B, k, dtype=torch.int64, device=s.device)
+    if B:
+        _select_topk(L.ptr(s), _ld(s), B, N, k, out_s, out_i, m, 0)
+    return out_s, out_i
+
+
+def rank_in_scores(scores, targets, exclude=None):
+    """int32 [B]: per row of a float32 score matrix [B, N] on the GPU, how many items come before item `targets[b]` in the order of
+    `topk_of_scores` (0 = the target has the best score); -1 for a target outside [0, N).  Excluded items are not counted; the
+    target's own bit is not consulted.  Feeds `RankingMeter.update` as `FlatIndex.rank_of` does."""
+    what = "rank_in_scores"
+    s = _scores(scores, what)
+    B, N = s.shape
+    t = _targets(targets, B, s.device, what)
+    m = None if exclude is None else _exclusion(exclude, B, N, s.device, what)
+    rank = torch.empty(B, dtype=torch.int32, device=s.device)
+    if B:
+        _select_rank(L.ptr(s), _ld(s), B, N, t, rank, m, 0)
+    return rank
+
+
+ITEM_DIM = 128            # the embedding width of every index of this module
+MAX_HIDDEN = 256          # the pair kernel keeps all hidden columns of its pair rows in accumulators
+# One block of Q is [rows, N] float32.  256 MiB holds the 2048-row evaluation batch of the reference's catalogue (2048 x 26,744 x 4 =
+# 209 MiB) in one block, so a batch is one pair launch and one selection; more buys nothing (the pair kernel's grid is full from a
+# few hundred rows on) and less only adds launches.  Results do not depend on it.
+DEFAULT_WORKSPACE_BYTES = 256 << 20
+
+
+class CriticIndex:
+    """The catalogue ranked by a critic's Q-value: `Q[b, n] = critic(state[b], table[n])` for every item, eval semantics (no
+    dropout, whatever `critic.training` says), without the [B N, H] activations ever reaching memory (csrc/qrank.hip).
+
+    `critic` is a `recnn_amd.nn.Critic` (three linear layers, one output) with hidden size <= 256 whose `linear1` takes
+    S + 128 inputs; `table` float32 [N, 128] on the GPU.  The constructor snapshots the weights and computes the items' share of
+    layer 1, as `FlatIndex` snapshots its table; call `refresh()` after training steps.  fp32 only.
+
+    `search` and `rank_of` compute Q for a block of state rows at a time into a workspace of at most `max_workspace_bytes`
+    (default 256 MiB: the reference's 2048 x 26,744 evaluation batch in one block; never less than 16 rows) and select from it
+    (csrc/scoresel.hip).  The bits of `Q[b, n]` depend on that pair alone, so no result depends on the batch or the block size."""
+
+    def __init__(self, critic, table, max_workspace_bytes=None):
+        from .nn.models import Critic
+        lin = [getattr(critic, n, None) for n in ("linear1", "linear2", "linear3")]
+        if not isinstance(critic, Critic) or any(not isinstance(l, torch.nn.Linear) for l in lin):
+            raise TypeError(f"CriticIndex: critic must be a three-layer recnn_amd.nn.Critic, got {type(critic).__name__}")
+        if table.dim() != 2 or table.shape[1] != ITEM_DIM or table.shape[0] < 1:
+            raise ValueError(f"CriticIndex: the item table must be [N, {ITEM_DIM}] (the embedding width is {ITEM_DIM}), got "
+                             f"{tuple(table.shape)}")
+        l1, l2, l3 = lin
+        H = l1.out_features
+        if H > MAX_HIDDEN:
+            raise ValueError(f"CriticIndex: hidden size {H} is above the pair kernel's limit of {MAX_HIDDEN}")
+        if l1.in_features <= ITEM_DIM or l2.in_features != H or l2.out_features != H or l3.in_features != H or l3.out_features != 1:
+            raise ValueError(f"CriticIndex: Critic.linear1 must take S + {ITEM_DIM} inputs (S >= 1) and the layers must be "
+                             f"[H, S + {ITEM_DIM}], [H, H], [1, H]; got linear1 {tuple(l1.weight.shape)}, linear2 "
+                             f"{tuple(l2.weight.shape)}, linear3 {tuple(l3.weight.shape)}")
+        if max_workspace_bytes is None:
+            max_workspace_bytes = DEFAULT_WORKSPACE_BYTES
+        if int(max_workspace_bytes) != max_workspace_bytes or max_workspace_bytes < 1:
+            raise ValueError(f"CriticIndex: max_workspace_bytes must be a positive integer, got {max_workspace_bytes}")
+        _on_gpu(table, "CriticIndex: the item table")
+        self.critic = critic
+        self.table = table.detach().to(torch.float32).contiguous()
+        self.n_items, self.dim = self.table.shape
+        self.state_dim, self.hidden = l1.in_features - ITEM_DIM, H
+        hp = C.c_int()
+        L.call("recnn_qrank_hidden_padded", H, C.byref(hp))
+        self._hp = hp.value
+        rows = C.c_int64()
+        L.call("recnn_qrank_block_rows", self.n_items, int(max_workspace_bytes), C.byref(rows))
+        self.block_rows = rows.value
+        self.refresh()
+
+    @property
+    def ntotal(self):
+        return self.n_items
+
+    def refresh(self):
+        """Re-reads the critic's weights (after training steps) and recomputes the items' share of layer 1."""
+        c, dev, hp, S = self.critic, self.table.device, self._hp, self.state_dim
+        sp = (S + 15) // 16 * 16
+
+        def pad(t, rows, cols):
+            out = torch.zeros(rows, cols, dtype=torch.float32, device=dev)
+            out[: t.shape[0], : t.shape[1]] = t.detach().to(dev, torch.float32)
+            return out
+        w1 = c.linear1.weight
+        self._w1s = pad(w1[:, :S], hp, sp)
+        self._w1a = pad(w1[:, S:], hp, ITEM_DIM)
+        self._b1 = pad(c.linear1.bias[None], 1, hp)[0]
+        self._w2 = pad(c.linear2.weight, hp, hp)
+        self._b2 = pad(c.linear2.bias[None], 1, hp)[0]
+        self._w3 = pad(c.linear3.weight, 1, hp)[0]
+        self._b3 = float(c.linear3.bias.detach().to(torch.float32).item())
+        self._e1 = torch.empty(self.n_items, hp, dtype=torch.float32, device=dev)
+        L.call("recnn_qrank_layer1", L.ptr(self.table), ITEM_DIM, self.n_items, ITEM_DIM, L.ptr(self._w1a), ITEM_DIM, None, hp,
+               L.ptr(self._e1), hp, L.current_stream())
+
+    def _s1(self, state, what):
+        """S1 = state W1[:, :S]^T + b1 for every row, [B, hidden padded]."""
+        _on_gpu(state, f"{what}: the states")
+        st = state.detach().to(torch.float32)
+        if st.dim() == 1:
+            st = st[None]
+        if st.dim() != 2 or st.shape[1] != self.state_dim:
+            raise ValueError(f"{what}: the states must be [B, {self.state_dim}], got {tuple(st.shape)}")
+        if st.device != self.table.device:
+            raise ValueError(f"{what}: the states live on {st.device}, the index on {self.table.device}")
+        B, sp = st.shape[0], self._w1s.shape[1]
+        if sp != self.state_dim or not st.is_contiguous() or st.data_ptr() % 16:
+            x = torch.zeros(B, sp, dtype=torch.float32, device=st.device)
+            x[:, : self.state_dim] = st
+            st = x
+        s1 = torch.empty(B, self._hp, dtype=torch.float32, device=st.device)
+        if B:
+            L.call("recnn_qrank_layer1", L.ptr(st), sp, B, sp, L.ptr(self._w1s), sp, L.ptr(self._b1), self._hp, L.ptr(s1), self._hp,
+                   L.current_stream())
+        return s1
+
+    def _pairs(self, s1, r0, rows, out, ld_out):
+        L.call("recnn_qrank_scores", C.c_void_p(s1.data_ptr() + r0 * self._hp * 4), self._hp, rows, L.ptr(self._e1), self._hp,
+               self.n_items, self._hp, L.ptr(self._w2), L.ptr(self._b2), L.ptr(self._w3), self._b3, L.ptr(out), ld_out,
+               L.current_stream())
+
+    def q_values(self, state):
+        """float32 [B, N]: the critic's value of every item for every state row (the counterpart of `cdist`).  Each entry is
+        bit-identical to what `search` reports for that pair."""
+        s1 = self._s1(state, "CriticIndex.q_values")
+        B = s1.shape[0]
+        out = torch.empty(B, self.n_items, dtype=torch.float32, device=s1.device)
+        step = 65535 * 16                                  # one pair launch's rows
+        for r0 in range(0, B, step):
+            self._pairs(s1, r0, min(step, B - r0), out[r0:], self.n_items)
+        return out
+
+    def _blocks(self, B):
+        rows = min(self.block_rows, B)
+        ws = torch.empty(rows, self.n_items, dtype=torch.float32, device=self.table.device)
+        return ws, [(r0, min(rows, B - r0)) for r0 in range(0, B, rows)]
+
+    def search(self, state, k=10, exclude=None):
+        """(q float32[B, k] descending, ids int64[B, k]): the k items of highest value per state row, ties to the smaller id.
+        `exclude` as in `FlatIndex.search`; a row with fewer than k items left ends in id -1 with value -inf."""
+        what = "CriticIndex.search"
+        k = _check_k(k, what)
+        s1 = self._s1(state, what)
+        B = s1.shape[0]
+        m = None if exclude is None else _exclusion(exclude, B, self.n_items, self.table.device, what)
+        q = torch.empty(B, k, dtype=torch.float32, device=s1.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=s1.device)
+        if B == 0:
+            return q, ids
+        ws, blocks = self._blocks(B)
+        for r0, rows in blocks:
+            self._pairs(s1, r0, rows, ws, self.n_items)
+            _select_topk(L.ptr(ws), self.n_items, rows, self.n_items, k, q[r0:r0 + rows], ids[r0:r0 + rows], m, r0)
+        return q, ids
+
+    def rank_of(self, state, targets, exclude=None):
+        """int32 [B]: how many items the critic values above item `targets[b]` in state b (ties to the smaller id; 0 = the target
+        is the critic's first choice), -1 for a target outside [0, n_items).  `exclude` as in `FlatIndex.rank_of`.  Feeds
+        `RankingMeter.update` unchanged."""
+        what = "CriticIndex.rank_of"
+        s1 = self._s1(state, what)
+        B = s1.shape[0]
+        t = _targets(targets, B, s1.device, what)
+        m = None if exclude is None else _exclusion(exclude, B, self.n_items, self.table.device, what)
+        rank = torch.empty(B, dtype=torch.int32, device=s1.device)
+        if B == 0:
+            return rank
+        ws, blocks = self._blocks(B)
+        for r0, rows in blocks:
+            self._pairs(s1, r0, rows, ws, self.n_items)
+            _select_rank(L.ptr(ws), self.n_items, rows, self.n_items, t[r0:r0 + rows], rank[r0:r0 + rows], m, r0)
+        return rank
+
+
+__all__ += ["topk_of_scores", "rank_in_scores", "CriticIndex"]

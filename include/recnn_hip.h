@@ -1082,6 +1082,32 @@ int recnn_scores_rank_workspace_bytes(int n_rows, int n_items, int64_t* h_bytes)
 int recnn_scores_rank(const float* scores, int64_t ld, int n_rows, int n_items, const int64_t* targets, int32_t* out_rank,
                       void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row);
 
+/* =====================================================================================
+ * 14. The critic's Q-value over per-row candidate lists, and the list sorted by it (csrc/qcand.hip): the second stage
+ *    of a retrieve-then-rerank recommender.  s1, e1, hidden_padded, w2, b2, w3, b3 are the operands of recnn_qrank_scores (section 13).
+ *    ids: [n_states][n_candidates] table row ids with row stride ld_ids (elements), int32 (ids_are_int64 = 0) or int64 (1).
+ *      Q[b][j] = w3 . relu(W2 . relu(S1[b] + E1[ids[b][j]]) + b2) + b3,  with the bits of recnn_qrank_scores' Q[b][ids[b][j]]
+ *    whatever n_states, n_candidates or the slot j.  A slot whose id is outside [0, n_items) is empty: it reads nothing, Q = -inf.
+ *    recnn_qcand_scores: any n_candidates >= 1, out float32 [n_states][n_candidates] with row stride ld_out.
+ *    recnn_qcand_rerank: n_candidates <= 64, 1 <= k <= n_candidates; writes the first k slots of every row in the order
+ *      larger Q first, ties to the smaller id, equal ids to the smaller slot, -0 == +0, NaN after every number in id order, empty
+ *      slots last (id -1 at -inf)  into out_q float32 / out_ids int64 [n_states][k], in the launch that computes Q.
+ *      targets (int64 [n_states], may be NULL together with out_pos): out_pos[b] int32 = the non-empty slots that come before the
+ *      first slot holding targets[b], -1 if no slot holds it or it is outside [0, n_items).  fallback_rank (int32 [n_states], may
+ *      be NULL): where the target is in range but in no slot, out_pos[b] = fallback_rank[b] < 0 ? -1 : max(fallback_rank[b], the
+ *      row's non-empty slots) instead: the target's rank when every other item follows the candidates in the first stage's order.
+ *    One launch each, no workspace, no atomics.  Errors: RECNN_E_INVALID before any HIP call for null pointers, misalignment,
+ *    strides below the row length, hidden above 256, n_candidates above 64 (rerank) and k outside 1..n_candidates.  Zero rows
+ *    launch nothing.
+ * ===================================================================================== */
+int recnn_qcand_scores(const float* s1, int64_t ld_s1, int n_states, const float* e1, int64_t ld_e1, int n_items, int hidden_padded,
+                       const float* w2, const float* b2, const float* w3, float b3, const void* ids, int64_t ld_ids, int n_candidates,
+                       int ids_are_int64, float* out, int64_t ld_out, void* stream);
+int recnn_qcand_rerank(const float* s1, int64_t ld_s1, int n_states, const float* e1, int64_t ld_e1, int n_items, int hidden_padded,
+                       const float* w2, const float* b2, const float* w3, float b3, const void* ids, int64_t ld_ids, int n_candidates,
+                       int ids_are_int64, int k, float* out_q, int64_t* out_ids, const int64_t* targets, int32_t* out_pos,
+                       const int32_t* fallback_rank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -280,6 +280,8 @@ SIGNATURES = {
     "recnn_scores_topk": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _L]),
     "recnn_scores_rank_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
     "recnn_scores_rank": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _L]),
+    "recnn_qcand_scores": (_I, [_P, _L, _I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _I, _I, _P, _L, _P]),
+    "recnn_qcand_rerank": (_I, [_P, _L, _I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

@@ -3,3 +3,4 @@ from .models import *  # noqa: F401,F403
 from .algo import *  # noqa: F401,F403
 from .update import *  # noqa: F401,F403
 from .graphed import GraphedUpdate  # noqa: F401
+from .policy import WolpertingerPolicy  # noqa: F401

@@ -760,5 +760,122 @@ class CriticIndex:
             _select_rank(L.ptr(ws), self.n_items, rows, self.n_items, t[r0:r0 + rows], rank[r0:r0 + rows], m, r0)
         return rank
 
+    # ---- per-row candidate lists (csrc/qcand.hip)
+
+    def _ids(self, ids, B, what):
+        """The id matrix as the kernel takes it: int32 or int64 [B, K] with unit column stride, any row stride."""
+        if not isinstance(ids, torch.Tensor) or ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+            raise ValueError(f"{what}: ids must be an integer tensor [B, K], got "
+                             f"{ids.dtype if isinstance(ids, torch.Tensor) else type(ids).__name__}")
+        if ids.dim() != 2 or ids.shape[1] < 1:
+            raise ValueError(f"{what}: ids must be [B, K] with K >= 1, got {tuple(ids.shape)}")
+        if ids.device != self.table.device:
+            raise ValueError(f"{what}: the ids live on {ids.device}, the index on {self.table.device}")
+        if ids.shape[0] != B:
+            raise ValueError(f"{what}: {B} states but ids of {ids.shape[0]} rows")
+        t = ids.detach()
+        if t.dtype not in (torch.int32, torch.int64):
+            t = t.to(torch.int64)
+        if t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
+            t = t.contiguous()
+        return t
+
+    def _cand_args(self, s1, t):
+        B, K = t.shape
+        return (L.ptr(s1), self._hp, B, L.ptr(self._e1), self._hp, self.n_items, self._hp, L.ptr(self._w2), L.ptr(self._b2),
+                L.ptr(self._w3), self._b3, L.ptr(t), t.stride(0) if B > 1 else K, K, int(t.dtype == torch.int64))
+
+    def q_of(self, state, ids):
+        """float32 [B, K]: `Q[b, j] = critic(state[b], table[ids[b, j]])` for an integer id matrix [B, K] (int32 or int64, any row
+        stride, any K >= 1), one launch after layer 1 of the states.  Each entry has the bits of `q_values(state)[b, ids[b, j]]`;
+        a slot whose id is outside [0, n_items) (the -1 `FlatIndex.search` pads with) reads nothing and gives -inf."""
+        what = "CriticIndex.q_of"
+        s1 = self._s1(state, what)
+        B = s1.shape[0]
+        t = self._ids(ids, B, what)
+        out = torch.empty(B, t.shape[1], dtype=torch.float32, device=s1.device)
+        if B:
+            L.call("recnn_qcand_scores", *self._cand_args(s1, t), L.ptr(out), t.shape[1], L.current_stream())
+        return out
+
+    def rerank(self, state, ids, k=None, targets=None, _fallback=None):
+        """(q float32 [B, k], ids int64 [B, k]): the candidates `ids` [B, K <= 64] of every row sorted by the critic's value, the
+        first k of them (default K), in the launch that computes the values.  Order: larger Q first, ties to the smaller id, a
+        repeated id to the smaller slot, -0 == +0, NaN after every number in id order; empty slots (ids outside [0, n_items)) come
+        last as id -1 at -inf.  With `targets` (integer [B]) a third element `pos` int32 [B]: the number of non-empty slots before
+        the first slot that holds `targets[b]`, -1 if no slot holds it or it is outside [0, n_items)."""
+        what = "CriticIndex.rerank"
+        s1 = self._s1(state, what)
+        B = s1.shape[0]
+        t = self._ids(ids, B, what)
+        K = t.shape[1]
+        if K > MAX_K:
+            raise ValueError(f"{what}: the sorted form takes at most {MAX_K} candidates per row, got {K} (q_of takes any number)")
+        if k is None:
+            k = K
+        if int(k) != k or not 1 <= k <= K:
+            raise ValueError(f"{what}: k must be an integer from 1 to the {K} candidates per row, got {k}")
+        k = int(k)
+        tg = None if targets is None else _targets(targets, B, s1.device, what)
+        q = torch.empty(B, k, dtype=torch.float32, device=s1.device)
+        out = torch.empty(B, k, dtype=torch.int64, device=s1.device)
+        pos = None if tg is None else torch.empty(B, dtype=torch.int32, device=s1.device)
+        if B:
+            L.call("recnn_qcand_rerank", *self._cand_args(s1, t), k, L.ptr(q), L.ptr(out), L.ptr(tg), L.ptr(pos), L.ptr(_fallback),
+                   L.current_stream())
+        return (q, out) if tg is None else (q, out, pos)
+
 
 __all__ += ["topk_of_scores", "rank_in_scores", "CriticIndex"]
+
+
+# ---- retrieve, then rerank (csrc/qcand.hip; DESIGN.md section 23): the actor's proto-action picks the candidates by geometry, the
+# critic orders them by value -- the Wolpertinger policy of Dulac-Arnold et al. (2015).
+
+class TwoStageIndex:
+    """`flat` (a `FlatIndex`) retrieves the `n_candidates` <= 64 items nearest to an action, `critic_index` (a `CriticIndex` over
+    the same table) sorts them by Q(state, item).  `search` is the flat search's launches, layer 1 of the states and one rerank
+    launch; the whole-catalogue `CriticIndex.search` stays the offline yardstick."""
+
+    def __init__(self, flat, critic_index, n_candidates=MAX_K):
+        if not isinstance(flat, FlatIndex) or not isinstance(critic_index, CriticIndex):
+            raise TypeError(f"TwoStageIndex: need a FlatIndex and a CriticIndex, got {type(flat).__name__} and "
+                            f"{type(critic_index).__name__}")
+        if int(n_candidates) != n_candidates or not 1 <= n_candidates <= MAX_K:
+            raise ValueError(f"TwoStageIndex: n_candidates must be an integer from 1 to {MAX_K}, got {n_candidates}")
+        if flat.n_items != critic_index.n_items:
+            raise ValueError(f"TwoStageIndex: the two indexes must hold the same table; the flat index holds {flat.n_items} items, "
+                             f"the critic index {critic_index.n_items}")
+        if flat.table.device != critic_index.table.device:
+            raise ValueError(f"TwoStageIndex: the flat index lives on {flat.table.device}, the critic index on "
+                             f"{critic_index.table.device}")
+        if n_candidates > flat.n_items:
+            raise ValueError(f"TwoStageIndex: n_candidates = {n_candidates} but the table holds only {flat.n_items} items")
+        self.flat, self.critic_index, self.n_candidates = flat, critic_index, int(n_candidates)
+        self.n_items = flat.n_items
+
+    @property
+    def ntotal(self):
+        return self.n_items
+
+    def refresh(self):
+        """Re-reads the critic's weights (`CriticIndex.refresh`)."""
+        self.critic_index.refresh()
+
+    def search(self, action, state, k=10, exclude=None):
+        """(q float32 [B, k] descending, ids int64 [B, k]): the k <= n_candidates candidates of highest value among the
+        n_candidates items nearest to `action[b]`.  `exclude` as in `FlatIndex.search`; a row with fewer than k items left ends in
+        id -1 at -inf."""
+        cand = self.flat.search(action, self.n_candidates, exclude)[1]
+        return self.critic_index.rerank(state, cand, k)
+
+    def rank_of(self, action, state, targets, exclude=None):
+        """int32 [B]: the rank of item `targets[b]` in the order "the retrieved candidates by value, then every other item in the
+        flat index's order": its position among the candidates if it is one, else `max(flat.rank_of, candidates retrieved)`;
+        -1 for a target outside [0, n_items).  Feeds `RankingMeter.update` unchanged."""
+        cand = self.flat.search(action, self.n_candidates, exclude)[1]
+        behind = self.flat.rank_of(action, targets, exclude)
+        return self.critic_index.rerank(state, cand, 1, targets, _fallback=behind)[2]
+
+
+__all__ += ["TwoStageIndex"]

@@ -1108,6 +1108,40 @@ int recnn_qcand_rerank(const float* s1, int64_t ld_s1, int n_states, const float
                        int ids_are_int64, int k, float* out_q, int64_t* out_ids, const int64_t* targets, int32_t* out_pos,
                        const int32_t* fallback_rank, void* stream);
 
+/* =====================================================================================
+ * 15. IVF-Flat (csrc/ivf.hip): a k-means coarse quantiser over the item table, the items stored per nearest centroid,
+ *    a search that scores only the lists a query probes.  emb_dim is 128 throughout.  Distances to centroids -- an item's nearest
+ *    centroid while training, a query's nprobe nearest while searching -- are recnn_topk_search over the centroid table (section 5);
+ *    the entry points here take its int64 ids.
+ *    recnn_ivf_build_lists: assign int64 [n_items] (list of every item) -> out_assignment int32 [n_items] (-1 for an id outside
+ *      [0, nlist), which is then in no list), list_start int32 [nlist + 1] (CSR), list_ids int32 [n_items]: the item ids list by list,
+ *      ascending id inside a list.  A stable counting sort, integers only: a function of the ids alone.
+ *    recnn_ivf_update_centroids: centroids[c] = sum(table rows of list c) / count[c] in place, fp32.  The sum's order is fixed by the
+ *      list (rows dealt round-robin to four partial sums, added as (0 + 1) + (2 + 3)), the division is the correctly rounded one; no
+ *      float atomics.  An empty list keeps its centroid.
+ *    recnn_ivf_gather_rows: out_rows[r] = table[list_ids[r]], the table in list order.
+ *    recnn_ivf_scan: queries float32 [n_queries][128] (row stride ld_q), list_rows / list_aux the table and its |t|^2 (section 5's
+ *      item aux, L2 only) in list order, probe int64 [n_queries][nprobe] the lists of every query (distinct within a row; an id outside
+ *      [0, nlist) is an empty slot).  Reports, over the items of the probed lists, what recnn_topk_search reports over the table:
+ *      out_dist float32 / out_ids int64 [n_queries][k], L2 squared distances ascending or IP scores descending, ties to the smaller
+ *      item id, each value with the bits recnn_topk_search gives that (query, item) pair; a row with fewer than k items in reach ends
+ *      in id -1 at +inf (L2) / -inf (IP).  k may exceed the items in reach.  mask (may be NULL) / words_per_row: section 12's
+ *      exclusion bits over item ids.  metric: RECNN_TOPK IP (0) or L2 (1).
+ *    The *_workspace_bytes queries are host-only.  Limits: 1 <= nlist <= n_items, nprobe <= min(64, nlist), k <= 64,
+ *    n_queries * nprobe < 2^25.  Errors: RECNN_E_INVALID before any HIP call, with a message that names the argument.
+ * ===================================================================================== */
+int recnn_ivf_lists_workspace_bytes(int n_items, int nlist, int64_t* h_bytes);
+int recnn_ivf_build_lists(const int64_t* assign, int n_items, int nlist, int32_t* out_assignment, int32_t* list_start,
+                          int32_t* list_ids, void* workspace, void* stream);
+int recnn_ivf_update_centroids(const float* table, int n_items, const int32_t* list_start, const int32_t* list_ids, int nlist,
+                               float* centroids, void* stream);
+int recnn_ivf_gather_rows(const float* table, int n_items, const int32_t* list_ids, float* out_rows, void* stream);
+int recnn_ivf_search_workspace_bytes(int n_queries, int nprobe, int nlist, int k, int64_t* h_bytes);
+int recnn_ivf_scan(const float* queries, int64_t ld_q, int n_queries, const float* list_rows, const float* list_aux,
+                   const int32_t* list_start, const int32_t* list_ids, int nlist, int n_items, int metric, const int64_t* probe,
+                   int nprobe, int k, float* out_dist, int64_t* out_ids, void* workspace, void* stream, const uint64_t* mask,
+                   int64_t words_per_row);
+
 #ifdef __cplusplus
 }
 #endif

@@ -282,6 +282,12 @@ SIGNATURES = {
     "recnn_scores_rank": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _L]),
     "recnn_qcand_scores": (_I, [_P, _L, _I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _I, _I, _P, _L, _P]),
     "recnn_qcand_rerank": (_I, [_P, _L, _I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "recnn_ivf_lists_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_ivf_build_lists": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "recnn_ivf_update_centroids": (_I, [_P, _I, _P, _P, _I, _P, _P]),
+    "recnn_ivf_gather_rows": (_I, [_P, _I, _P, _P, _P]),
+    "recnn_ivf_search_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_ivf_scan": (_I, [_P, _L, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L]),
 }
 
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header

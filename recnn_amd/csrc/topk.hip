@@ -25,14 +25,9 @@
 #include "common.h"
 #include "seen.h"
 #include "target_rank.h"
+#include "topk_dev.h"   // tile shape, better(), score_tile(), query_sqnorm(): shared with ivf.hip
 
 namespace {
-constexpr int QT = 64;     // query rows per workgroup
-constexpr int IT = 64;     // items per chunk
-constexpr int KMAX = 64;   // largest supported K
-constexpr int PITCH = 132; // floats per LDS row of a [rows][128] tile (+4 pad: conflict-light b128 reads)
-enum { M_IP = 0, M_L2 = 1, M_COS = 2 };
-
 struct TopkArgs {
   const float* q; int64_t ldq; int B;
   const float* table; int N, E;
@@ -44,8 +39,6 @@ struct TopkArgs {
 // the excluding kernel takes the mask of seen.h behind the same arguments, and a split that is a multiple of IT so that a chunk's 64
 // exclusion bits are one word (results do not depend on the split); the plain kernel keeps its argument block and its split
 struct TopkArgsX : TopkArgs { const uint64_t* mask; int64_t W; int per; };
-
-__device__ inline bool better(float s, int id, float s2, int id2) { return s > s2 || (s == s2 && id < id2); }
 
 template <int E_, bool EXCL = false>
 __global__ __launch_bounds__(256) void topk_scores_kernel(const std::conditional_t<EXCL, TopkArgsX, TopkArgs> a) {
@@ -190,10 +183,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     ci[j] = c < total ? pi[(int64_t)row * total + c] : 0x7FFFFFFF;
   }
   float qn = 0.f;
-  if (metric == M_L2) {
-    for (int k = lane; k < E; k += 64) { const float v = q[(int64_t)row * ldq + k]; qn += v * v; }
-    qn = wave_sum(qn);
-  }
+  if (metric == M_L2) qn = query_sqnorm(q, ldq, row, E, lane);
   for (int k = 0; k < K; ++k) {
     float bs = -INFINITY; int bi = 0x7FFFFFFF;
 #pragma unroll
@@ -248,30 +238,6 @@ __device__ __forceinline__ float rank_score(float s, float ax, int metric) {   /
   if (metric == M_L2) s = 2.f * s - ax;
   else if (metric == M_COS) s = s * ax;
   return s;
-}
-
-// 64 x 64 scores of the query tile against the 64 rows in Ts: the k order of topk_scores_kernel, which is the same for every element
-// of the tile
-__device__ __forceinline__ void score_tile(const float* Qs, const float* Ts, int wm0, int wn0, int fr, int fg, f32x4 (&acc)[2][2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int ks = 0; ks < 128 / 16; ++ks) {
-    float4 qa[2], tb[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) qa[i] = *(const float4*)&Qs[(wm0 + i * 16 + fr) * PITCH + ks * 16 + fg * 4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) tb[j] = *(const float4*)&Ts[(wn0 + j * 16 + fr) * PITCH + ks * 16 + fg * 4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(((const float*)&qa[i])[e], ((const float*)&tb[j])[e], acc[i][j], 0, 0, 0);
-  }
 }
 
 // Row b counts the items of its split that come before item g_b = targets[b].  The workgroup first gathers the target rows of its

@@ -1,5 +1,6 @@
 """The reference's `recnn/data/db_con.py` (`MilvusConnection`, `SearchResult`) without a server: a "collection" is a
-`recnn_amd.retrieval.FlatIndex` over `env.base.embeddings`, searched exactly on the GPU (csrc/topk.hip).
+`recnn_amd.retrieval.FlatIndex` over `env.base.embeddings`, searched exactly on the GPU (csrc/topk.hip), or, when `param` asks for
+`index_type="IVF_FLAT"`, a `recnn_amd.retrieval.IVFFlatIndex` (csrc/ivf.hip) whose search honours `nprobe`.
 
 The evaluation notebooks (`examples/[Results]/2. Diversity Test (Indexes).ipynb`, `3. Distances Test.ipynb`) and the demo's
 "Test Diversity" page run against it as written, except that without pymilvus installed their import line becomes
@@ -11,7 +12,9 @@ Conventions:
   `FlatIndex("L2")` / `FlatIndex("IP")` and faiss report, and what the demo assumes when it takes `D ** 0.5`
   ("l2 -> euclidean").  Whether a Milvus server reports the squared value as well has not been checked (pymilvus and a server
   were not available when this was written).
-* The search is exact: `nprobe` and every other search parameter is accepted and ignored.  Ties go to the smaller id.
+* Without `index_type` the search is exact: `nprobe` and every other search parameter is accepted and ignored.  Ties go to the
+  smaller id.  With `param={"index_type": "IVF_FLAT", "nlist": n}` the collection is an inverted-file index of n k-means lists and
+  a search scores the `search_param["nprobe"]` nearest lists (default 16, what the reference passes); other keys are still ignored.
 * Ids are rows of `env.base.embeddings` (the reference inserts the rows with `ids=range(N)`).
 * `topk` <= 64 and an embedding width of 128 are the limits of csrc/topk.hip and are reported with its errors.
 * No CPU fallback: without a GPU the constructor raises `recnn_amd._lib.RecnnHipError`.
@@ -22,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..retrieval import FlatIndex
+from ..retrieval import DEFAULT_NPROBE, FlatIndex, IVFFlatIndex
 
 
 class MetricType(enum.Enum):
@@ -98,12 +101,13 @@ class _Client:
     def search(self, collection_name, query_records, top_k, params=None, **_ignored):
         if collection_name != self._con.name:
             raise ValueError(f"collection {collection_name!r} is not this connection's ({self._con.name!r})")
-        return Status(), self._con._search(query_records, top_k)
+        return Status(), self._con._search(query_records, top_k, params)
 
 
 class MilvusConnection:
     """`MilvusConnection(env, name, port, param)` of the reference: `param` may carry `metric_type` (default L2) and `dimension`
-    (must equal the table's width); `port`, `index_file_size` and other keys are accepted and ignored."""
+    (must equal the table's width), and `index_type="IVF_FLAT"` with `nlist` (an `IVFFlatIndex` instead of the `FlatIndex`);
+    `port`, `index_file_size` and other keys are accepted and ignored."""
 
     def __init__(self, env, name="movies_L2", port="19530", param=None):
         param = {"collection_name": name, "metric_type": MetricType.L2, **(param or {})}
@@ -113,17 +117,24 @@ class MilvusConnection:
             raise ValueError("env.base.embeddings must be a [n_items, width] tensor")
         if param.get("dimension") is not None and int(param["dimension"]) != table.shape[1]:
             raise ValueError(f"param['dimension'] = {param['dimension']} but env.base.embeddings is {table.shape[1]} wide")
+        index_type = param.get("index_type")
+        index_type = getattr(index_type, "name", index_type)           # pymilvus' IndexType enum, or the name
+        if index_type not in (None, "FLAT", "IVF_FLAT", "IVFLAT"):
+            raise ValueError(f"param['index_type'] must be \"FLAT\" or \"IVF_FLAT\" (or absent), got {param['index_type']!r}")
+        self.ivf = index_type in ("IVF_FLAT", "IVFLAT")
+        if self.ivf and "nlist" not in param:
+            raise ValueError("param['index_type'] = \"IVF_FLAT\" needs param['nlist']")
         self.name = name
         self.statuses = {}
         if not table.is_cuda:
             if not torch.cuda.is_available():
                 raise L.RecnnHipError("MilvusConnection searches on the GPU and none is visible (no CPU fallback)")
             table = table.detach().to("cuda")           # once; env.base.embeddings itself stays where it is
-        self.index = FlatIndex(table, self.metric)
+        self.index = IVFFlatIndex(table, param["nlist"], self.metric) if self.ivf else FlatIndex(table, self.metric)
         self.client = _Client(self)
         self.statuses["created_collection"] = Status(f"{name}: {self.index.ntotal} x {self.index.dim}, {self.metric}")
 
-    def _search(self, search_vecs, topk):
+    def _search(self, search_vecs, topk, search_param=None):
         if isinstance(search_vecs, (list, tuple)) and len(search_vecs) and torch.is_tensor(search_vecs[0]):
             search_vecs = torch.stack(list(search_vecs))
         if not torch.is_tensor(search_vecs):
@@ -133,11 +144,14 @@ class MilvusConnection:
             q = q[None]
         if q.dim() != 2 or q.shape[1] != self.index.dim:
             raise ValueError(f"search vectors must be [B, {self.index.dim}] or [{self.index.dim}], got {tuple(search_vecs.shape)}")
-        dist, ids = self.index.search(q, int(topk))
+        if self.ivf:
+            dist, ids = self.index.search(q, int(topk), (search_param or {}).get("nprobe", DEFAULT_NPROBE))
+        else:
+            dist, ids = self.index.search(q, int(topk))
         return SearchResult(dist, ids)
 
     def search(self, search_vecs, topk=10, search_param=None):
-        result = self._search(search_vecs, topk)
+        result = self._search(search_vecs, topk, search_param)
         self.statuses["last_search"] = Status()
         return result
 

@@ -4,19 +4,27 @@ import torch
 
 from . import functional as F_hip
 from ..data.utils import gather_padded_rows
-from ..retrieval import MAX_K, CriticIndex, FlatIndex, TwoStageIndex
+from ..retrieval import MAX_K, CriticIndex, FlatIndex, IVFFlatIndex, TwoStageIndex
 
 
 class WolpertingerPolicy:
     """`actor` (state -> action of the table's width), `critic` (a three-layer `Critic`), `table` float32 [N, 128] on the GPU.
 
-    Owns a `FlatIndex(table, metric)`, a `CriticIndex(critic, table)` and the `TwoStageIndex` over them.  The actor runs in eval
+    Owns a `FlatIndex(table, metric)`, a `CriticIndex(critic, table)` and the `TwoStageIndex` over them.  `index="ivf"` makes the
+    first stage an `IVFFlatIndex(table, nlist, metric)` searched with `nprobe` probes (`rank_of` is then refused).  The actor runs in eval
     semantics (no dropout, whatever `actor.training` says) without gradient; the critic's weights are a snapshot: call `refresh()`
     after training steps."""
 
-    def __init__(self, actor, critic, table, n_candidates=MAX_K, metric="L2"):
+    def __init__(self, actor, critic, table, n_candidates=MAX_K, metric="L2", index="flat", nlist=None, nprobe=None):
+        if index not in ("flat", "ivf"):
+            raise ValueError(f"WolpertingerPolicy: index must be \"flat\" or \"ivf\", got {index!r}")
+        if index == "flat" and (nlist is not None or nprobe is not None):
+            raise ValueError("WolpertingerPolicy: nlist and nprobe apply to index=\"ivf\"")
+        if index == "ivf" and nlist is None:
+            raise ValueError("WolpertingerPolicy: index=\"ivf\" needs nlist")
         self.actor = actor
-        self.flat = FlatIndex(table, metric)
+        self.nprobe = nprobe
+        self.flat = FlatIndex(table, metric) if index == "flat" else IVFFlatIndex(table, nlist, metric)
         self.critic_index = CriticIndex(critic, table)
         self.index = TwoStageIndex(self.flat, self.critic_index, n_candidates)
         self.table = self.critic_index.table
@@ -33,7 +41,7 @@ class WolpertingerPolicy:
     def recommend(self, state, k=10, exclude=None):
         """(q float32 [B, k] descending, ids int64 [B, k]): the k candidates the critic values most among the `n_candidates` items
         nearest to the actor's action.  `exclude` as in `FlatIndex.search`."""
-        return self.index.search(self.proto_action(state), state, k, exclude)
+        return self.index.search(self.proto_action(state), state, k, exclude, self.nprobe)
 
     def act(self, state, exclude=None):
         """(ids int64 [B], actions float32 [B, 128], q float32 [B]): the best candidate, its table row and its value.  A row with

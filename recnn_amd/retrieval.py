@@ -9,6 +9,9 @@ It also takes the metrics of the reference's per-item scipy ranking loop (`examp
 `examples/[Results]/1. Ranking.ipynb`): the names of `scipy.spatial.distance.cdist` in `DIST_METRICS`, or the scipy
 functions themselves (`distance.canberra`).  `cdist(queries, table, metric)` gives the whole distance matrix.  Kernel in
 csrc/rank.hip; DESIGN.md section 11.
+
+`IVFFlatIndex(table, nlist, metric)` is the inverted-file counterpart (faiss's IndexIVFFlat, Milvus's IVF_FLAT): k-means lists and a
+search that scores only the `nprobe` nearest of them.  Kernels in csrc/ivf.hip; DESIGN.md section 24.
 """
 import ctypes as C
 
@@ -835,10 +838,13 @@ __all__ += ["topk_of_scores", "rank_in_scores", "CriticIndex"]
 class TwoStageIndex:
     """`flat` (a `FlatIndex`) retrieves the `n_candidates` <= 64 items nearest to an action, `critic_index` (a `CriticIndex` over
     the same table) sorts them by Q(state, item).  `search` is the flat search's launches, layer 1 of the states and one rerank
-    launch; the whole-catalogue `CriticIndex.search` stays the offline yardstick."""
+    launch; the whole-catalogue `CriticIndex.search` stays the offline yardstick.
+
+    `flat` may be an `IVFFlatIndex`: the candidates are then the nearest items of the `nprobe` lists `search` probes, and
+    `rank_of` is refused (its identity needs the candidates to be the head of the flat order)."""
 
     def __init__(self, flat, critic_index, n_candidates=MAX_K):
-        if not isinstance(flat, FlatIndex) or not isinstance(critic_index, CriticIndex):
+        if not isinstance(flat, (FlatIndex, IVFFlatIndex)) or not isinstance(critic_index, CriticIndex):
             raise TypeError(f"TwoStageIndex: need a FlatIndex and a CriticIndex, got {type(flat).__name__} and "
                             f"{type(critic_index).__name__}")
         if int(n_candidates) != n_candidates or not 1 <= n_candidates <= MAX_K:
@@ -862,20 +868,212 @@ class TwoStageIndex:
         """Re-reads the critic's weights (`CriticIndex.refresh`)."""
         self.critic_index.refresh()
 
-    def search(self, action, state, k=10, exclude=None):
+    def search(self, action, state, k=10, exclude=None, nprobe=None):
         """(q float32 [B, k] descending, ids int64 [B, k]): the k <= n_candidates candidates of highest value among the
         n_candidates items nearest to `action[b]`.  `exclude` as in `FlatIndex.search`; a row with fewer than k items left ends in
-        id -1 at -inf."""
-        cand = self.flat.search(action, self.n_candidates, exclude)[1]
+        id -1 at -inf.  `nprobe` (an `IVFFlatIndex` first stage only; default 16): the lists the first stage scores."""
+        if isinstance(self.flat, IVFFlatIndex):
+            cand = self.flat.search(action, self.n_candidates, DEFAULT_NPROBE if nprobe is None else nprobe, exclude)[1]
+        else:
+            if nprobe is not None:
+                raise ValueError("TwoStageIndex.search: nprobe applies to an IVFFlatIndex first stage; this one is a FlatIndex")
+            cand = self.flat.search(action, self.n_candidates, exclude)[1]
         return self.critic_index.rerank(state, cand, k)
 
     def rank_of(self, action, state, targets, exclude=None):
         """int32 [B]: the rank of item `targets[b]` in the order "the retrieved candidates by value, then every other item in the
         flat index's order": its position among the candidates if it is one, else `max(flat.rank_of, candidates retrieved)`;
         -1 for a target outside [0, n_items).  Feeds `RankingMeter.update` unchanged."""
+        if isinstance(self.flat, IVFFlatIndex):
+            raise ValueError("TwoStageIndex.rank_of: refused with an IVFFlatIndex first stage: the rank identity needs the "
+                             "candidates to be the head of the flat index's order, and the items of the probed lists are not")
         cand = self.flat.search(action, self.n_candidates, exclude)[1]
         behind = self.flat.rank_of(action, targets, exclude)
         return self.critic_index.rerank(state, cand, 1, targets, _fallback=behind)[2]
 
 
 __all__ += ["TwoStageIndex"]
+
+
+# ---- IVF-Flat (csrc/ivf.hip; DESIGN.md section 24): a k-means coarse quantiser over the table, the items stored per nearest
+# centroid, and a search that scores only the `nprobe` nearest lists: faiss's IndexIVFFlat, Milvus's IVF_FLAT.
+
+MAX_PROBE = 64
+DEFAULT_NPROBE = 16       # what the reference's MilvusConnection.search passes on every call
+IVF_METRICS = ("L2", "IP")
+
+
+def _check_count(v, lo, hi, what, name, why=""):
+    try:
+        whole = not isinstance(v, bool) and int(v) == v
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise TypeError(f"{what}: {name} must be an integer, got {v!r}")
+    if not lo <= v <= hi:
+        raise ValueError(f"{what}: {name} must be an integer from {lo} to {hi}{why}, got {v}")
+    return int(v)
+
+
+class IVFFlatIndex:
+    """Inverted-file search over the rows of `table` (float32 [N, 128] on the GPU): `nlist` k-means centroids, every item stored in
+    the list of its nearest centroid, and `search(queries, k, nprobe)` scoring only the items of the `nprobe` lists whose centroids
+    are nearest to (L2) or have the largest inner product with (IP) the query.  With `nprobe >= nlist` it is `FlatIndex.search`,
+    bit for bit; with fewer probes it is that search restricted to the probed lists, each (query, item) score still with
+    `FlatIndex`'s bits.  metric "L2" or "IP".
+
+    Training is Lloyd's k-means under L2 for both metrics, as in faiss: `niter` rounds of (assign every item to its nearest centroid,
+    ties to the smaller centroid id: `FlatIndex(centroids, "L2").search(table, 1)`; move every centroid to the fp32 mean of its list),
+    then one final assignment that defines the lists.  Initial centroids: `centroids` (float32 [nlist, 128]) if given, else the
+    table rows `torch.randperm(N, generator=<CPU generator seeded with seed>)[:nlist]`.  Deterministic: no float atomics, the order
+    of every sum is fixed by the item ids.  A list with no items keeps its previous centroid; faiss re-splits a large cluster
+    instead, this index does not.  `niter=0` with `centroids=` only builds the lists.
+
+    `centroids` float32 [nlist, 128], `assignment` int32 [N] (the list of every item), `list_start` int32 [nlist + 1] (CSR over the
+    lists), `list_ids` int32 [N] (item ids list by list, ascending id inside a list).  Items cannot be added or removed."""
+
+    def __init__(self, table, nlist, metric="L2", niter=10, centroids=None, seed=0):
+        what = "IVFFlatIndex"
+        nlist = self._check_table(table, nlist, metric, what)
+        niter = _check_count(niter, 0, 2 ** 31 - 1, what, "niter")
+        seed = _check_count(seed, -2 ** 63, 2 ** 63 - 1, what, "seed")
+        if centroids is not None:
+            centroids = self._check_centroids(centroids, nlist, what)
+        _on_gpu(table, f"{what}: the item table")
+        self._set_table(table, nlist, metric)
+        if centroids is None:
+            rows = torch.randperm(self.n_items, generator=torch.Generator().manual_seed(seed))[:nlist]
+            cent = self.table[rows.to(self.table.device)].contiguous()
+        else:
+            cent = centroids.detach().to(self.table.device, torch.float32).contiguous().clone()
+        for _ in range(niter):
+            _, start, ids = self._build_lists(self._nearest_centroid(cent))
+            L.call("recnn_ivf_update_centroids", L.ptr(self.table), self.n_items, L.ptr(start), L.ptr(ids), nlist, L.ptr(cent),
+                   L.current_stream())
+        self._finish(cent, self._nearest_centroid(cent))
+
+    @classmethod
+    def from_assignment(cls, table, centroids, assignment, metric="L2"):
+        """The index whose lists are `assignment` (integer [N], values in [0, nlist)) and whose centroids are `centroids`
+        (float32 [nlist, 128]) as given: no training."""
+        what = "IVFFlatIndex.from_assignment"
+        if not isinstance(centroids, torch.Tensor) or centroids.dim() != 2:
+            raise ValueError(f"{what}: centroids must be a float32 tensor [nlist, {ITEM_DIM}]")
+        self = object.__new__(cls)
+        nlist = self._check_table(table, centroids.shape[0], metric, what)
+        centroids = self._check_centroids(centroids, nlist, what)
+        a = torch.as_tensor(assignment)
+        if a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool or a.dim() != 1 or a.shape[0] != table.shape[0]:
+            raise ValueError(f"{what}: assignment must be a 1-D integer tensor of {table.shape[0]} entries, got {a.dtype} "
+                             f"{tuple(a.shape)}")
+        _on_gpu(table, f"{what}: the item table")
+        self._set_table(table, nlist, metric)
+        a = a.detach().to(self.table.device, torch.int64).contiguous()
+        lo, hi = int(a.min()), int(a.max())
+        if lo < 0 or hi >= nlist:
+            raise ValueError(f"{what}: assignment must hold list ids in [0, {nlist}), got values from {lo} to {hi}")
+        self._finish(centroids.detach().to(self.table.device, torch.float32).contiguous().clone(), a)
+        return self
+
+    # ---- construction
+    @staticmethod
+    def _check_table(table, nlist, metric, what):
+        name = metric if isinstance(metric, str) else getattr(metric, "__name__", None)
+        if name not in IVF_METRICS:
+            raise ValueError(f"{what}: metric must be \"L2\" or \"IP\", got {metric!r} (COS and the scipy metrics are FlatIndex's)")
+        if not isinstance(table, torch.Tensor):
+            raise TypeError(f"{what}: table must be a float32 tensor [N, {ITEM_DIM}], got {type(table).__name__}")
+        if table.dim() != 2 or table.shape[1] != ITEM_DIM or table.shape[0] < 1:
+            raise ValueError(f"{what}: table must be [N, {ITEM_DIM}] (the embedding width is {ITEM_DIM}), got {tuple(table.shape)}")
+        if table.shape[0] >= 2 ** 31:
+            raise ValueError(f"{what}: table holds {table.shape[0]} rows, the limit is 2^31 - 1")
+        return _check_count(nlist, 1, table.shape[0], what, "nlist", " (the number of table rows)")
+
+    @staticmethod
+    def _check_centroids(centroids, nlist, what):
+        if not isinstance(centroids, torch.Tensor) or centroids.dtype != torch.float32 or tuple(centroids.shape) != (nlist, ITEM_DIM):
+            got = f"{centroids.dtype} {tuple(centroids.shape)}" if isinstance(centroids, torch.Tensor) else type(centroids).__name__
+            raise ValueError(f"{what}: centroids must be a float32 tensor [{nlist}, {ITEM_DIM}] (nlist rows), got {got}")
+        return centroids
+
+    def _set_table(self, table, nlist, metric):
+        self.metric = metric if isinstance(metric, str) else metric.__name__
+        self.table = table.detach().to(torch.float32).contiguous()
+        self.n_items, self.dim = self.table.shape
+        self.nlist = nlist
+
+    def _nearest_centroid(self, cent):
+        """int64 [N]: the centroid of smallest squared L2 distance to every table row, ties to the smaller id."""
+        return FlatIndex(cent, "L2").search(self.table, 1)[1].view(-1)
+
+    def _build_lists(self, assign):
+        dev, N = self.table.device, self.n_items
+        assignment = torch.empty(N, dtype=torch.int32, device=dev)
+        start = torch.empty(self.nlist + 1, dtype=torch.int32, device=dev)
+        ids = torch.empty(N, dtype=torch.int32, device=dev)
+        ws = L.workspace("recnn_ivf_lists_workspace_bytes", N, self.nlist, device=dev)
+        L.call("recnn_ivf_build_lists", L.ptr(assign), N, self.nlist, L.ptr(assignment), L.ptr(start), L.ptr(ids), L.ptr(ws),
+               L.current_stream())
+        return assignment, start, ids
+
+    def _finish(self, cent, assign):
+        self.centroids = cent
+        self.assignment, self.list_start, self.list_ids = self._build_lists(assign)
+        # the table rows and the L2 |t|^2 term in list order: a list is one contiguous stream
+        self._rows = torch.empty_like(self.table)
+        L.call("recnn_ivf_gather_rows", L.ptr(self.table), self.n_items, L.ptr(self.list_ids), L.ptr(self._rows), L.current_stream())
+        self._aux = None
+        if self.metric == "L2":
+            self._aux = torch.empty(self.n_items, dtype=torch.float32, device=self.table.device)
+            L.call("recnn_topk_item_aux", L.ptr(self._rows), self.n_items, self.dim, METRICS["L2"], L.ptr(self._aux), L.current_stream())
+        self.quantizer = FlatIndex(self.centroids, self.metric)
+
+    # ---- search
+    @property
+    def ntotal(self):
+        return self.n_items
+
+    def _nprobe(self, nprobe, what):
+        return min(_check_count(nprobe, 1, MAX_PROBE, what, "nprobe"), self.nlist)
+
+    def _ivf_queries(self, queries, what):
+        if not isinstance(queries, torch.Tensor):
+            raise TypeError(f"{what}: queries must be a tensor [B, {ITEM_DIM}], got {type(queries).__name__}")
+        if queries.dim() not in (1, 2) or queries.shape[-1] != ITEM_DIM:
+            raise ValueError(f"{what}: queries must be [B, {ITEM_DIM}] or [{ITEM_DIM}], got {tuple(queries.shape)}")
+        return _queries(queries, self.table.device)
+
+    def probe(self, queries, nprobe):
+        """(score float32 [B, p], lists int64 [B, p]), p = min(nprobe, nlist): the lists a search of `nprobe` probes scores, nearest
+        centroid first under L2 (squared distances), largest inner product first under IP.  It is
+        `FlatIndex(centroids, metric).search(queries, p)`."""
+        what = "IVFFlatIndex.probe"
+        p = self._nprobe(nprobe, what)
+        return self.quantizer.search(self._ivf_queries(queries, what), p)
+
+    def search(self, queries, k=10, nprobe=DEFAULT_NPROBE, exclude=None):
+        """(distances float32 [B, k], ids int64 [B, k]) over the items of each query's `min(nprobe, nlist)` probed lists, in
+        `FlatIndex.search`'s order and conventions: L2 squared distances ascending, IP scores descending, ties to the smaller id.
+        k <= 64, nprobe <= 64.  `exclude` (a `SeenItems` or `SeenMask` of B rows) as in `FlatIndex.search`.  A row with fewer than k
+        items in reach ends in id -1 with distance +inf (L2) or -inf (IP)."""
+        what = "IVFFlatIndex.search"
+        k = _check_count(k, 1, MAX_K, what, "k")
+        if k > self.n_items:
+            raise ValueError(f"{what}: k = {k} but the index holds only {self.n_items} items")
+        p = self._nprobe(nprobe, what)
+        q = self._ivf_queries(queries, what)
+        B, dev = q.shape[0], q.device
+        m = None if exclude is None else _exclusion(exclude, B, self.n_items, dev, what)
+        dist = torch.empty(B, k, dtype=torch.float32, device=dev)
+        ids = torch.empty(B, k, dtype=torch.int64, device=dev)
+        if B == 0:
+            return dist, ids
+        lists = self.quantizer.search(q, p)[1]
+        ws = L.workspace("recnn_ivf_search_workspace_bytes", B, p, self.nlist, k, device=dev)
+        L.call("recnn_ivf_scan", L.ptr(q), q.stride(0), B, L.ptr(self._rows), L.ptr(self._aux), L.ptr(self.list_start),
+               L.ptr(self.list_ids), self.nlist, self.n_items, METRICS[self.metric], L.ptr(lists), p, k, L.ptr(dist), L.ptr(ids),
+               L.ptr(ws), L.current_stream(), None if m is None else L.ptr(m.words), 0 if m is None else m.words.shape[1])
+        return dist, ids
+
+
+__all__ += ["IVFFlatIndex"]

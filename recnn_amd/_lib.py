@@ -290,8 +290,22 @@ SIGNATURES = {
     "recnn_ivf_scan": (_I, [_P, _L, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L]),
 }
 
+class FrozenDebugArgs(C.Structure):
+    """recnn_amd/csrc/recnn_hip_debug.h recnn_debug_frozen_args: one frozen network on caller-supplied device buffers."""
+    _fields_ = [("A", C.c_void_p * 4), ("lda", C.c_int64 * 4), ("K", C.c_int * 4), ("w1_col", C.c_int * 4), ("nseg", C.c_int),
+                ("W1", C.c_void_p), ("ldw1", C.c_int64), ("W2", C.c_void_p), ("ldw2", C.c_int64), ("W3", C.c_void_p), ("ldw3", C.c_int64),
+                ("b1", C.c_void_p), ("b2", C.c_void_p), ("b3", C.c_void_p), ("w3row", C.c_void_p),
+                ("rows", C.c_int), ("H", C.c_int), ("out_dim", C.c_int), ("mask_mode", C.c_int),
+                ("seed", C.c_uint32), ("stream1", C.c_uint32), ("stream2", C.c_uint32),
+                ("step", C.c_int), ("rows_per_set", C.c_int),
+                ("h1", C.c_void_p), ("h2", C.c_void_p), ("ldh", C.c_int64), ("store_row0", C.c_int),
+                ("out", C.c_void_p), ("ldo", C.c_int64), ("addend", C.c_void_p), ("ld_add", C.c_int64), ("add_clip", C.c_float),
+                ("q", C.c_void_p), ("panel_rows", C.c_int)]
+
+
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header
 DEBUG_SIGNATURES = {
+    "recnn_debug_frozen_forward": (_I, [C.POINTER(FrozenDebugArgs), _L, _P]),
     "recnn_debug_mlp_fault": (None, [_I]),
     "recnn_debug_mlp_probe": (None, [_I]),
     "recnn_debug_mlp_trace": (None, [_P]),

@@ -17,8 +17,11 @@
 // cycle's state / action / next-rating arrays and the target actor's output), weights as the first MFMA operand, the same epilogues
 // (mlp_panel.h), the same q-dot lane map and reduction tree -- so `run()` in cycle mode equals the eager step loop bit for bit.
 #include <cstddef>
+#include <cstring>
+#include <type_traits>
 #include "mlp_panel.h"
 #include "split.h"
+#include "recnn_hip_debug.h"
 
 namespace {
 constexpr int NW = 16;
@@ -152,12 +155,33 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
           acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b[tn]), __builtin_bit_cast(bf16x8, a[tm]), acc[tm][tn], 0, 0, 0);
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  // ---- every argument field used from here on, into registers once: requested here, so that the wait below (the last fragment reads')
+  // covers them, and pinned -- the phases behind layer 1 are short latency chains, and a kernel-argument load with its lgkmcnt(0)
+  // between a phase's LDS reads and their use (the epilogues had 14, the output stage about 90: P.out, P.ldo, P.addend ... per block)
+  // waits for all of them (mlpt.hip got the same fix in round 6)
+  // (pinned in two statements of eleven: a statement's fields are all requested before its one wait; pinned one by one, every load
+  // was waited for on its own)
+  int H = P.H, rows = P.rows, out_dim = P.out_dim, store_row0 = P.store_row0, rows_per_set = P.rows_per_set, mask_mode = P.mask_mode;
+  int step_add = P.step_add, ldw2 = (int)P.ldw2;
+  uint32_t seed = P.seed, stream1 = P.stream1, stream2 = P.stream2;
+  asm volatile("" : "+s"(H), "+s"(rows), "+s"(out_dim), "+s"(store_row0), "+s"(rows_per_set), "+s"(mask_mode), "+s"(step_add), "+s"(ldw2), "+s"(seed),
+               "+s"(stream1), "+s"(stream2));
+  int64_t ldo = P.ldo, ld_add = P.ld_add, ldh = P.ldh;
+  const char* W2 = (const char*)P.W2;
+  const char* W3 = (const char*)P.W3;
+  bf16_t* h1 = (bf16_t*)P.h1;
+  bf16_t* h2 = (bf16_t*)P.h2;
+  bf16_t* out = (bf16_t*)P.out;
+  float* qout = P.q;
+  const float* addend = P.addend;
+  float add_clip = P.add_clip;
+  asm volatile("" : "+s"(ldo), "+s"(ld_add), "+s"(ldh), "+s"(W2), "+s"(W3), "+s"(h1), "+s"(h2), "+s"(out), "+s"(qout), "+s"(addend), "+s"(add_clip));
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(step_now) : : "memory");   // (also the mask step requested at entry)
   __builtin_amdgcn_s_barrier();                   // every wave is done with layer 1's ring: the second LDS plan takes over
   stamp(4);
 
   // ---- the later layers' stream: slab c = W2's k-slab c (c < 4), then (actor) W3's two double slabs; ring stage c % 3
-  const unsigned voff_sq = (unsigned)(l_row * (int)P.ldw2 * 2 + l_c);   // W2 / W3 share the pitch (mlpf_launch)
+  const unsigned voff_sq = (unsigned)(l_row * ldw2 * 2 + l_c);   // W2 / W3 share the pitch (mlpf_launch)
   const int npost = actor ? 6 : 4;
   int posted = 0;
   auto issue_post = [&]() {
@@ -165,11 +189,11 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
     const int c = posted++;
     const unsigned wb = lds0 + WR_OFF + (c % 3) * W_BYTES + wave_kb;
     if (c < 4) {
-      const char* b0 = (const char*)P.W2 + c * 128;
+      const char* b0 = W2 + c * 128;
       dma_s(voff_sq, b0, wb);
-      dma_s(voff_sq, b0 + 256 * P.ldw2, wb + NW * 1024);
+      dma_s(voff_sq, b0 + (int64_t)256 * ldw2, wb + NW * 1024);
     } else {                                      // W3: k-slabs 2 p and 2 p + 1 of its 128 rows as image rows 0..127 / 128..255
-      const char* b0 = (const char*)P.W3 + 2 * (c - 4) * 128;
+      const char* b0 = W3 + 2 * (c - 4) * 128;
       dma_s(voff_sq, b0, wb);
       dma_s(voff_sq, b0 + 128, wb + NW * 1024);
     }
@@ -192,20 +216,27 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   unsigned char* spanel = lds + wm * (2 * PANEL_HALF);
   const int sm0 = m0 + wm * 32;                   // first row of the sub-panel
   int mset = 0, mrow0 = sm0;
-  if (P.rows_per_set > 0) { mset = sm0 / P.rows_per_set; mrow0 = sm0 - mset * P.rows_per_set; }
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(step_now));
-  const int32_t step0 = step_now + P.step_add + mset;
-  const uint32_t key1 = P.mask_mode == RECNN_MASK_HASH ? mask_key(P.seed, step0, P.stream1) : 0u;
-  const uint32_t key2 = P.mask_mode == RECNN_MASK_HASH ? mask_key(P.seed, step0, P.stream2) : 0u;
+  if (rows_per_set > 0) { mset = sm0 / rows_per_set; mrow0 = sm0 - mset * rows_per_set; }
+  const int32_t step0 = step_now + step_add + mset;
+  const bool hash = mask_mode == RECNN_MASK_HASH;
+  const uint32_t key1 = hash ? mask_key(seed, step0, stream1) : 0u;
+  const uint32_t key2 = hash ? mask_key(seed, step0, stream2) : 0u;
   const float* cst = (const float*)(lds + CONST_OFF);
+  // the mask mode as a compile-time constant under ONE uniform branch per epilogue (this kernel sees hash masks or none: mlpf_launch): as a
+  // run-time value every element carried the external-mask, hash-mask and no-mask paths (2,280 instructions and 20 spilled registers in
+  // the 128-row form; the two target networks take the no-mask path, the shorter one)
+  auto epilogue = [&](const f32x4 (&bv)[TNH], uint32_t key) {
+    if (hash) hidden_epilogue<TNH>(acc, bv, H, rows - (sm0 - mrow0), mrow0, wn, fr, fg, RECNN_MASK_HASH, nullptr, 0, key, spanel);
+    else hidden_epilogue<TNH>(acc, bv, H, rows - (sm0 - mrow0), mrow0, wn, fr, fg, RECNN_MASK_NONE, nullptr, 0, 0u, spanel);
+  };
   {
     f32x4 b1v[TNH];
 #pragma unroll
     for (int tn = 0; tn < TNH; ++tn) {
       const int n = wn * (16 * TNH) + tn * 16 + fg * 4;
-      b1v[tn] = (n + 3 < P.H) ? *(const f32x4*)(cst + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+      b1v[tn] = (n + 3 < H) ? *(const f32x4*)(cst + n) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    hidden_epilogue<TNH>(acc, b1v, P.H, P.rows - (sm0 - mrow0), mrow0, wn, fr, fg, P.mask_mode, nullptr, 0, key1, spanel);
+    epilogue(b1v, key1);
   }
   stamp(5);
   // the later layers' constants (after the epilogue: the accumulators' registers are free again)
@@ -213,7 +244,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
 #pragma unroll
   for (int tn = 0; tn < TNH; ++tn) {
     const int n = wn * (16 * TNH) + tn * 16 + fg * 4;
-    b2v[tn] = (n + 3 < P.H) ? *(const f32x4*)(cst + 256 + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+    b2v[tn] = (n + 3 < H) ? *(const f32x4*)(cst + 256 + n) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   float v3[TN3][4];                               // actor: b3 of this lane's output columns 16 TN3 wn + 16 tn + 4 fg + r
   float w3v[4];                                   // critic: w3 of columns 4 lane .. 4 lane + 3
@@ -222,10 +253,10 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int no = wn * (16 * TN3) + tn * 16 + fg * 4 + r;
-      v3[tn][r] = (actor && no < P.out_dim) ? cst[512 + no] : 0.f;
+      v3[tn][r] = (actor && no < out_dim) ? cst[512 + no] : 0.f;
     }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) w3v[r] = (!actor && lane * 4 + r < P.H) ? cst[512 + lane * 4 + r] : 0.f;
+  for (int r = 0; r < 4; ++r) w3v[r] = (!actor && lane * 4 + r < H) ? cst[512 + lane * 4 + r] : 0.f;
   // (the constants sit in what becomes the later layers' ring stage 2: every wave has read them -- the lgkmcnt(0) of
   // next_post -- before the first rendezvous below lets slab 2 be requested)
 
@@ -236,9 +267,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
     for (int j = 0; j < TNH; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int q = 0; q < 4; ++q) {
     const unsigned char* st = next_post();        // (its barrier also completes the h1 panel for q = 0)
-    if (q == 0 && P.h1 && m0 + FR > P.store_row0) {   // (a workgroup wholly below the first stored row skips the pass)
+    if (q == 0 && h1 && m0 + FR > store_row0) {   // (a workgroup wholly below the first stored row skips the pass)
 #pragma unroll
-      for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h1, P.ldh, m0 + sp * 32, P.rows, tid, P.store_row0);
+      for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), h1, ldh, m0 + sp * 32, rows, tid, store_row0);
     }
     const unsigned char* sa = spanel + (q >> 1) * PANEL_HALF;
 #pragma unroll
@@ -260,7 +291,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                   // everyone is done reading the h1 panel
   stamp(6);
-  hidden_epilogue<TNH>(acc, b2v, P.H, P.rows - (sm0 - mrow0), mrow0, wn, fr, fg, P.mask_mode, nullptr, 0, key2, spanel);
+  epilogue(b2v, key2);
   stamp(7);
 
   if (actor) {
@@ -272,9 +303,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
       for (int j = 0; j < TN3; ++j) o[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < 2; ++p) {
       const unsigned char* st = next_post();      // (completes the h2 panel for p = 0)
-      if (p == 0 && P.h2 && m0 + FR > P.store_row0) {
+      if (p == 0 && h2 && m0 + FR > store_row0) {
 #pragma unroll
-        for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h2, P.ldh, m0 + sp * 32, P.rows, tid, P.store_row0);
+        for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), h2, ldh, m0 + sp * 32, rows, tid, store_row0);
       }
 #pragma unroll
       for (int hq = 0; hq < 2; ++hq) {            // k quarter q = 2 p + hq of the panel against image rows hq * 128 + output column
@@ -298,40 +329,56 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
       }
     }
     stamp(8);
+    // out = o + b3 (+ clip(addend)) as bf16.  The presence of an addend and a full 128-column output are uniform: decided once, not per
+    // element; one 64-bit row offset per row block instead of one per element.  Narrower outputs keep the column tests and the rule
+    // that padded columns hold bf16 +0.
+    auto out_stage = [&](auto FULLc, auto ADDc) {
+      constexpr bool FULL = decltype(FULLc)::value, ADD = decltype(ADDc)::value;
 #pragma unroll
-    for (int tm = 0; tm < 2; ++tm) {
-      const int m = sm0 + tm * 16 + fr;
+      for (int tm = 0; tm < 2; ++tm) {
+        const int m = sm0 + tm * 16 + fr;
+        const bool mrow = m < rows;
+        bf16_t* const orow = out + (int64_t)m * ldo;
+        const float* const arow = ADD ? addend + (int64_t)m * ld_add : nullptr;
 #pragma unroll
-      for (int tn = 0; tn < TN3; ++tn) {
-        const int no = wn * (16 * TN3) + tn * 16 + fg * 4;
-        float v[4];
+        for (int tn = 0; tn < TN3; ++tn) {
+          const int no = wn * (16 * TN3) + tn * 16 + fg * 4;
+          float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool ncol = no + r < P.out_dim;
-          v[r] = o[tm][tn][r] + v3[tn][r];
-          if (P.addend && ncol && m < P.rows) {
-            const float z = P.addend[(int64_t)m * P.ld_add + no + r];
-            v[r] += fminf(fmaxf(z, -P.add_clip), P.add_clip);
+          for (int r = 0; r < 4; ++r) {
+            const bool ncol = FULL || no + r < out_dim;
+            v[r] = o[tm][tn][r] + v3[tn][r];
+            if (ADD && ncol && mrow) {
+              const float z = arow[no + r];
+              v[r] += fminf(fmaxf(z, -add_clip), add_clip);
+            }
+            if (!ncol) v[r] = 0.f;
           }
-          if (!ncol) v[r] = 0.f;
-        }
-        uint2 packed = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
-        if (no + 3 >= P.out_dim) {                             // (padded columns hold bf16 +0, not -0)
-          if (no + 0 >= P.out_dim) packed.x &= 0xFFFF0000u;
-          if (no + 1 >= P.out_dim) packed.x &= 0x0000FFFFu;
-          if (no + 2 >= P.out_dim) packed.y &= 0xFFFF0000u;
-          if (no + 3 >= P.out_dim) packed.y &= 0x0000FFFFu;
-        }
-        if (m < P.rows) {
-          if (no + 3 < P.out_dim) {
-            *(uint2*)((bf16_t*)P.out + (int64_t)m * P.ldo + no) = packed;
-          } else {
+          uint2 packed = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+          if (!FULL && no + 3 >= out_dim) {                    // (padded columns hold bf16 +0, not -0)
+            if (no + 0 >= out_dim) packed.x &= 0xFFFF0000u;
+            if (no + 1 >= out_dim) packed.x &= 0x0000FFFFu;
+            if (no + 2 >= out_dim) packed.y &= 0xFFFF0000u;
+            if (no + 3 >= out_dim) packed.y &= 0x0000FFFFu;
+          }
+          if (mrow) {
+            if (FULL || no + 3 < out_dim) {
+              *(uint2*)(orow + no) = packed;
+            } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (no + r < P.out_dim) ((bf16_t*)P.out)[(int64_t)m * P.ldo + no + r] = (bf16_t)((r < 2 ? packed.x : packed.y) >> ((r & 1) * 16));
+              for (int r = 0; r < 4; ++r)
+                if (no + r < out_dim) orow[no + r] = (bf16_t)((r < 2 ? packed.x : packed.y) >> ((r & 1) * 16));
+            }
           }
         }
       }
+    };
+    if (out_dim == 128) {
+      if (addend) out_stage(std::true_type{}, std::true_type{});
+      else out_stage(std::true_type{}, std::false_type{});
+    } else {
+      if (addend) out_stage(std::false_type{}, std::true_type{});
+      else out_stage(std::false_type{}, std::false_type{});
     }
     stamp(9);
     return;
@@ -340,11 +387,12 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
   // ------------------------------------------------------------------ critic head: q[m] = h2[m, :] . w3 + b3, 8 rows per wave
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b3s) : : "memory");
   __builtin_amdgcn_s_barrier();                   // h2 panel complete
-  if (P.h2 && m0 + FR > P.store_row0) {
+  if (h2 && m0 + FR > store_row0) {
 #pragma unroll
-    for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), (bf16_t*)P.h2, P.ldh, m0 + sp * 32, P.rows, tid, P.store_row0);
+    for (int sp = 0; sp < PL::WMG; ++sp) panel_to_global<NW>(lds + sp * (2 * PANEL_HALF), h2, ldh, m0 + sp * 32, rows, tid, store_row0);
   }
-  for (int i = 0; i < FR / NW; ++i) {
+#pragma unroll
+  for (int i = 0; i < FR / NW; ++i) {           // (unrolled: the rows' panel reads and reduction trees interleave)
     const int prow = wave * (FR / NW) + i;        // row of the 128-row panel
     const unsigned char* pp = lds + (prow >> 5) * (2 * PANEL_HALF);
     const int row = prow & 31;
@@ -353,9 +401,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_frozen_kernel(const FrozenBatch b
     const float hf[4] = {bf2f((bf16_t)(hv.x & 0xFFFFu)), bf2f((bf16_t)(hv.x >> 16)), bf2f((bf16_t)(hv.y & 0xFFFFu)), bf2f((bf16_t)(hv.y >> 16))};
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s += lane * 4 + j < P.H ? hf[j] * w3v[j] : 0.f;
+    for (int j = 0; j < 4; ++j) s += lane * 4 + j < H ? hf[j] * w3v[j] : 0.f;
     s = wave_sum(s);
-    if (lane == 0 && m0 + prow < P.rows && P.q) P.q[m0 + prow] = s + b3s;
+    if (lane == 0 && m0 + prow < rows && qout) qout[m0 + prow] = s + b3s;
   }
   stamp(9);
 }
@@ -390,6 +438,9 @@ int mlpf_launch(const FrozenBatch& b, int nprob, hipStream_t s, int panel_rows) 
     RECNN_REQUIRE(p.store_row0 >= 0 && p.store_row0 <= p.rows, "mlp_frozen: the first stored activation row lies outside the problem");
     RECNN_REQUIRE(p.rows_per_set == 0 || p.rows_per_set % 32 == 0, "mlp_frozen: batches must be multiples of 32 rows");
     if (p.W3) RECNN_REQUIRE(p.out && p.ldw3 == p.ldw2 && (((uintptr_t)p.W3) & 15) == 0 && p.ldo % 4 == 0, "mlp_frozen: actor needs W3 (same pitch as W2) and an output");
+    // (b3 reaches LDS in groups of four floats, the last group shifted back to end at out_dim: a width that is no multiple of 4 would put
+    //  the last columns' biases two places off -- the engine's action widths are multiples of 8)
+    if (p.W3) RECNN_REQUIRE(p.out_dim >= 4 && p.out_dim % 4 == 0, "mlp_frozen: the actor's output width must be a multiple of 4");
     else RECNN_REQUIRE(p.w3row && p.q, "mlp_frozen: critic needs its last layer's row and a Q output");
   }
   FrozenBatch bb = b;
@@ -397,4 +448,26 @@ int mlpf_launch(const FrozenBatch& b, int nprob, hipStream_t s, int panel_rows) 
   if (panel_rows == 64) hipLaunchKernelGGL(mlp_frozen_kernel<64>, dim3((rows + 63) / 64, nprob), dim3(NW * 64), LDS_TOTAL, s, bb);
   else hipLaunchKernelGGL(mlp_frozen_kernel<128>, dim3((rows + 127) / 128, nprob), dim3(NW * 64), LDS_TOTAL, s, bb);
   return recnn_check_hip(hipGetLastError(), "mlp_frozen_kernel");
+}
+
+// One problem on caller-supplied device buffers (csrc/recnn_hip_debug.h): the kernel's edge cases -- two and three layer-1 slabs, every
+// segment boundary, narrow outputs, an addend without masks -- are out of the engine's reach (its networks give 21 or 23 slabs).
+extern "C" int recnn_debug_frozen_forward(const recnn_debug_frozen_args* a, int64_t sizeof_args, void* stream) {
+  RECNN_REQUIRE(a && sizeof_args == (int64_t)sizeof(*a), "debug_frozen_forward: null pointer or another layout of the argument block");
+  RECNN_REQUIRE(a->nseg >= 1 && a->nseg <= FROZEN_MAX_SEG, "debug_frozen_forward: 1..%d segments", FROZEN_MAX_SEG);
+  int rc = mlpf_init();
+  if (rc) return rc;
+  FrozenBatch fb;
+  memset(&fb, 0, sizeof(fb));
+  FrozenProb& p = fb.p[0];
+  for (int g = 0; g < a->nseg; ++g) { p.A[g] = a->A[g]; p.lda[g] = a->lda[g]; p.K[g] = a->K[g]; p.w1_col[g] = a->w1_col[g]; }
+  p.nseg = a->nseg;
+  p.W1 = a->W1; p.ldw1 = a->ldw1; p.W2 = a->W2; p.ldw2 = a->ldw2; p.W3 = a->W3; p.ldw3 = a->ldw3;
+  p.b1 = a->b1; p.b2 = a->b2; p.b3 = a->b3; p.w3row = a->w3row;
+  p.rows = a->rows; p.H = a->H; p.out_dim = a->out_dim;
+  p.mask_mode = a->mask_mode; p.seed = a->seed; p.stream1 = a->stream1; p.stream2 = a->stream2;
+  p.step_ptr = nullptr; p.step_add = a->step; p.rows_per_set = a->rows_per_set;
+  p.h1 = a->h1; p.h2 = a->h2; p.ldh = a->ldh; p.store_row0 = a->store_row0;
+  p.out = a->out; p.ldo = a->ldo; p.addend = a->addend; p.ld_add = a->ld_add; p.add_clip = a->add_clip; p.q = a->q;
+  return mlpf_launch(fb, 1, (hipStream_t)stream, a->panel_rows);
 }

@@ -3,6 +3,7 @@
  * garbage by design.  Used by tests/test_gpu_engine.py::test_broken_handoff_is_reported and tools/{mlp,split}_trace.py. */
 #ifndef RECNN_HIP_DEBUG_H
 #define RECNN_HIP_DEBUG_H
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -16,6 +17,26 @@ void recnn_debug_mlp_trace(void* device_u64_wg32);
 void recnn_debug_tail_trace(void* device_u64_wg16);
 void recnn_debug_frozen_trace(void* device_u64_wg16);   /* mlp_frozen_kernel: read at launch (= capture) time */
 void recnn_debug_l1_trace(void* device_u64_wg16);
+/* ONE frozen network (csrc/mlpf.hip mlp_frozen_kernel) on caller-supplied device buffers: the direct way to the kernel's edge cases (two
+ * and three layer-1 slabs, every segment boundary, ragged panels, a first stored row), which the engine's networks -- 21 or 23 slabs --
+ * never reach.  Layer 1 contracts nseg (1..4) k-contiguous bf16 segments A[g] [rows, lda[g]] (K[g] a multiple of 64) against columns
+ * w1_col[g] .. of W1 [H, ldw1]; W3 != NULL: an actor (out [rows, ldo] bf16 = h2 W3^T + b3 + clip(addend), out_dim <= 128), else a critic
+ * (q [rows] fp32 = h2 . w3row + b3[0]).  mask_mode RECNN_MASK_NONE | RECNN_MASK_HASH with (seed, step + batch index, stream1 | stream2),
+ * batches of rows_per_set rows (0: one batch); h1 / h2 optional bf16 [rows, ldh], rows store_row0 .. stored.  panel_rows 128 | 64 (the
+ * same numbers).  sizeof_args = sizeof(recnn_debug_frozen_args) as the caller sees it (refused if it differs). */
+typedef struct recnn_debug_frozen_args {
+  const void* A[4]; int64_t lda[4]; int K[4]; int w1_col[4]; int nseg;
+  const void* W1; int64_t ldw1; const void* W2; int64_t ldw2; const void* W3; int64_t ldw3;
+  const float* b1; const float* b2; const float* b3; const float* w3row;
+  int rows, H, out_dim, mask_mode;
+  uint32_t seed, stream1, stream2;
+  int step, rows_per_set;
+  void* h1; void* h2; int64_t ldh; int store_row0;
+  void* out; int64_t ldo; const float* addend; int64_t ld_add; float add_clip;
+  float* q;
+  int panel_rows;
+} recnn_debug_frozen_args;
+int recnn_debug_frozen_forward(const recnn_debug_frozen_args* a, int64_t sizeof_args, void* stream);
 /* kernel variant of the split-bf16 forward GEMM for the single-problem entry point recnn_gemm_fwd (engines carry their own:
  * recnn_engine_tuning::x3_fwd); -1 = off */
 void recnn_debug_x3_fwd(int variant);

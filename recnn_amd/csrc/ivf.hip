@@ -14,8 +14,8 @@
 //   gather    the table rows in list order, so that a list is one contiguous stream.
 //   scan      list-major.  The B * p (query, probe slot) pairs are inverted by list with scatter_index.h; a workgroup takes one list
 //             and up to 64 of the pairs that probe it, keeps their query rows in LDS, streams the list's rows in chunks of 64 through
-//             topk_dev.h's scoring tile (exact fp32 MFMA, the bits of topk.hip for every pair) and maintains each pair's sorted K best
-//             with the ballot insert of topk_scores_kernel.  Exclusion (seen.h): list order is a permutation of the ids, so a chunk's
+//             topk_dev.h's staging, scoring tile and key (exact fp32 MFMA, the bits of topk.hip for every pair) and maintains each
+//             pair's sorted K best with select_dev.h's ballot insert, under better() like topk_scores_kernel.  Exclusion (seen.h): list order is a permutation of the ids, so a chunk's
 //             bits are not one word; a lane looks up the bit of (row, item id) only when its item would enter the row's list.
 //   merge     one workgroup per query row folds the p sorted partial lists (up to 64 x 64 candidates) from LDS: a p-way merge, one lane
 //             per list, and reports topk.hip's conventions (L2: fmaxf(|q|^2 - key, 0) ascending; IP descending; ties to the smaller
@@ -29,9 +29,7 @@
 #include "topk_dev.h"
 
 namespace {
-constexpr int IVF_DIM = 128;
 constexpr int IVF_MAX_PROBE = 64;
-constexpr int NONE_ID = 0x7FFFFFFF;
 
 struct IdOfI64 {
   const int64_t* ids;
@@ -53,14 +51,14 @@ inline int64_t ivf_lists_bytes(int64_t n_items, int nlist) {
 // ---------------------------------------------------------------- centroid update
 __global__ __launch_bounds__(256) void ivf_update_kernel(const float* __restrict__ table, int n_items, const int* __restrict__ list_start,
                                                          const int* __restrict__ list_ids, float* __restrict__ centroids) {
-  __shared__ float part[4][IVF_DIM];
+  __shared__ float part[4][DIM];
   const int c = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int s0 = list_start[c], s1 = list_start[c + 1];
   if (s1 <= s0) return;                                  // an empty list keeps its centroid (uniform: no barrier is skipped by some)
   float2 sum = make_float2(0.f, 0.f);
   auto row = [&](int i) {
     const int id = list_ids[i];
-    return (unsigned)id < (unsigned)n_items ? *(const float2*)(table + (int64_t)id * IVF_DIM + 2 * lane) : make_float2(0.f, 0.f);
+    return (unsigned)id < (unsigned)n_items ? *(const float2*)(table + (int64_t)id * DIM + 2 * lane) : make_float2(0.f, 0.f);
   };
   int i = s0 + wave;
   for (; i + 12 < s1; i += 16) {                         // four rows in flight, added in list order
@@ -77,10 +75,10 @@ __global__ __launch_bounds__(256) void ivf_update_kernel(const float* __restrict
   part[wave][2 * lane] = sum.x;
   part[wave][2 * lane + 1] = sum.y;
   __syncthreads();
-  if (threadIdx.x < IVF_DIM) {
+  if (threadIdx.x < DIM) {
     const int d = threadIdx.x;
     const float total = (part[0][d] + part[1][d]) + (part[2][d] + part[3][d]);
-    centroids[(int64_t)c * IVF_DIM + d] = total / (float)(s1 - s0);      // IEEE division (hipcc's default), not a reciprocal multiply
+    centroids[(int64_t)c * DIM + d] = total / (float)(s1 - s0);      // IEEE division (hipcc's default), not a reciprocal multiply
   }
 }
 
@@ -93,8 +91,8 @@ __global__ __launch_bounds__(256) void ivf_gather_kernel(const float* __restrict
   if (r >= n_rows) return;
   const int id = list_ids[r];
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if ((unsigned)id < (unsigned)n_items) v = *(const float4*)(table + (int64_t)id * IVF_DIM + k4 * 4);
-  *(float4*)(out + r * IVF_DIM + k4 * 4) = v;
+  if ((unsigned)id < (unsigned)n_items) v = *(const float4*)(table + (int64_t)id * DIM + k4 * 4);
+  *(float4*)(out + r * DIM + k4 * 4) = v;
 }
 
 // ---------------------------------------------------------------- the scan's work list: (list, group of 64 pairs)
@@ -126,21 +124,24 @@ struct IvfScanArgs {
 };
 struct IvfScanArgsX : IvfScanArgs { const uint64_t* mask; int64_t W; };
 
-constexpr size_t ivf_scan_lds() {
-  return (size_t)(QT * PITCH + IT * PITCH + QT * (IT + 4) + QT * KMAX) * 4 + (size_t)QT * KMAX * 4 + (size_t)(2 * QT + IT) * 4;
-}
+struct IvfLds : ScanLds {
+  static constexpr size_t Pj = shared;                        // int [QT] pair index of each row, -1: none
+  static constexpr size_t Pb = Pj + QT * 4;                   // int [QT] its query row
+  static constexpr size_t Ci = Pb + QT * 4;                   // int [IT] item ids of the chunk
+  static constexpr size_t bytes = Ci + IT * 4;
+};
 
 template <bool EXCL>
 __global__ __launch_bounds__(256) void ivf_scan_kernel(const std::conditional_t<EXCL, IvfScanArgsX, IvfScanArgs> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* Qs = (float*)smem;                  // [QT][PITCH]
-  float* Ts = Qs + QT * PITCH;               // [IT][PITCH]
-  float* Ss = Ts + IT * PITCH;               // [QT][IT + 4]
-  float* Ls = Ss + QT * (IT + 4);            // [QT][KMAX] keys
-  int* Li = (int*)(Ls + QT * KMAX);          // [QT][KMAX] ids
-  int* Pj = Li + QT * KMAX;                  // [QT] pair index of each row, -1: none
-  int* Pb = Pj + QT;                         // [QT] its query row
-  int* Ci = Pb + QT;                         // [IT] item ids of the chunk
+  float* Qs = (float*)(smem + IvfLds::Qs);
+  float* Ts = (float*)(smem + IvfLds::Ts);
+  float* Ss = (float*)(smem + IvfLds::Ss);
+  float* Ls = (float*)(smem + IvfLds::Ls);
+  int* Li = (int*)(smem + IvfLds::Li);
+  int* Pj = (int*)(smem + IvfLds::Pj);
+  int* Pb = (int*)(smem + IvfLds::Pb);
+  int* Ci = (int*)(smem + IvfLds::Ci);
   if ((int)blockIdx.x >= a.gstart[a.nlist]) return;      // the grid is the host's upper bound of the work list
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int2 wk = a.work[blockIdx.x];
@@ -157,46 +158,21 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const std::conditional_t<
   }
   __syncthreads();
   // query rows of the group's pairs -> LDS (rows past the group are zero)
-  for (int c = tid; c < QT * (IVF_DIM / 4); c += 256) {
-    const int r = c / (IVF_DIM / 4), k4 = c % (IVF_DIM / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < pn) v = *(const float4*)(a.q + (int64_t)Pb[r] * a.ldq + k4 * 4);
-    *(float4*)&Qs[r * PITCH + k4 * 4] = v;
-  }
+  stage_rows(Qs, a.q, a.ldq, tid, [&](int r, int64_t& row) {
+    if (r < pn) row = Pb[r];
+    return r < pn;
+  });
   const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;   // wave tile: 32 queries x 32 items
   const int fr = lane & 15, fg = lane >> 4;
   __syncthreads();
 
   for (int n0 = n_begin; n0 < n_end; n0 += IT) {
-    // ---- list chunk -> LDS
-    for (int c = tid; c < IT * (IVF_DIM / 4); c += 256) {
-      const int r = c / (IVF_DIM / 4), k4 = c % (IVF_DIM / 4);
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n0 + r < n_end) v = *(const float4*)(a.rows + (int64_t)(n0 + r) * IVF_DIM + k4 * 4);
-      *(float4*)&Ts[r * PITCH + k4 * 4] = v;
-    }
+    stage_chunk(Ts, a.rows, n0, n_end, tid);
     if (tid < IT) Ci[tid] = n0 + tid < n_end ? a.list_ids[n0 + tid] : NONE_ID;
     __syncthreads();
     f32x4 acc[2][2];
     score_tile(Qs, Ts, wm0, wn0, fr, fg, acc);
-    // ---- ranking key (larger = better) into the score tile
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wn0 + j * 16 + fr;
-        const int n = n0 + col;
-        float ax = 0.f;
-        if (a.metric != M_IP && n < n_end) ax = a.aux[n];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm0 + i * 16 + fg * 4 + r;
-          float s = acc[i][j][r];
-          if (a.metric == M_L2) s = 2.f * s - ax;       // |q|^2 is constant per row: it does not change the order
-          if (n >= n_end) s = -INFINITY;
-          Ss[row * (IT + 4) + col] = s;
-        }
-      }
+    keys_to_tile(acc, Ss, a.aux, a.metric == M_L2 ? M_L2 : M_IP, n0, n_end, wm0, wn0, fr, fg);   // the lists know IP and L2 only
     __syncthreads();
     // ---- selection: wave w owns rows 16w .. 16w+15; lane = item of the chunk
     for (int rr = 0; rr < 16; ++rr) {
@@ -204,31 +180,13 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const std::conditional_t<
       if (row >= pn) break;
       float* ls = Ls + row * KMAX;
       int* li = Li + row * KMAX;
-      const float s = Ss[row * (IT + 4) + lane];
+      const float s = Ss[row * SPITCH + lane];
       const int id = Ci[lane];
       bool cand = n0 + lane < n_end && better(s, id, ls[K - 1], li[K - 1]);
       if constexpr (EXCL) {                             // the bit of (row, item id), for would-be survivors only
         if (cand) cand = !((a.mask[(int64_t)Pb[row] * a.W + (id >> 6)] >> (id & 63)) & 1ull);
       }
-      unsigned long long m = __ballot(cand);
-      while (m) {                                       // rare after the first chunks
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float cs = __shfl(s, src, 64);
-        const int cid = __shfl(id, src, 64);
-        if (!better(cs, cid, ls[K - 1], li[K - 1])) continue;
-        // insert (cs, cid) into the sorted list: lanes shift the tail in parallel
-        const float mine = lane < K ? ls[lane] : 0.f;
-        const int mine_id = lane < K ? li[lane] : 0;
-        const bool before = lane < K && better(mine, mine_id, cs, cid);       // entries that stay in front
-        const int pos = __popcll(__ballot(before));                            // insertion position
-        const float up = __shfl_up(mine, 1, 64);                               // (all lanes: no divergent shuffles)
-        const int up_id = __shfl_up(mine_id, 1, 64);
-        if (lane < K) {
-          if (lane == pos) { ls[lane] = cs; li[lane] = cid; }
-          else if (lane > pos) { ls[lane] = up; li[lane] = up_id; }
-        }
-      }
+      insert_survivors<better>(__ballot(cand), s, [&](int src) { return __shfl(id, src, 64); }, ls, li, K, lane);
     }
     __syncthreads();
   }
@@ -262,7 +220,7 @@ __global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict_
   __syncthreads();
   if (threadIdx.x >= 64) return;
   float qn = 0.f;
-  if (metric == M_L2) qn = query_sqnorm(q, ldq, row, IVF_DIM, lane);
+  if (metric == M_L2) qn = query_sqnorm(q, ldq, row, DIM, lane);
   int head = 0;
   for (int k = 0; k < K; ++k) {
     float hs = -INFINITY; int hi = NONE_ID;
@@ -313,10 +271,10 @@ template <bool EXCL>
 int ivf_scan_launch(std::conditional_t<EXCL, IvfScanArgsX, IvfScanArgs>& a, int groups, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)ivf_scan_kernel<EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ivf_scan_lds()));
+    RECNN_HIP(hipFuncSetAttribute((const void*)ivf_scan_kernel<EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IvfLds::bytes));
     attr = true;
   }
-  hipLaunchKernelGGL(ivf_scan_kernel<EXCL>, dim3(groups), dim3(256), ivf_scan_lds(), st, a);
+  hipLaunchKernelGGL(ivf_scan_kernel<EXCL>, dim3(groups), dim3(256), IvfLds::bytes, st, a);
   return 0;
 }
 }  // namespace
@@ -362,7 +320,7 @@ extern "C" int recnn_ivf_gather_rows(const float* table, int n_items, const int3
   RECNN_REQUIRE(table && list_ids && out_rows, "ivf_gather_rows: null pointer");
   RECNN_REQUIRE(n_items > 0, "ivf_gather_rows: need n_items > 0");
   RECNN_REQUIRE(aligned16(table, out_rows), "ivf_gather_rows: 16-byte alignment");
-  const int64_t chunks = (int64_t)n_items * (IVF_DIM / 4);
+  const int64_t chunks = (int64_t)n_items * (DIM / 4);
   hipLaunchKernelGGL(ivf_gather_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table, n_items, list_ids,
                      n_items, out_rows);
   return recnn_check_hip(hipGetLastError(), "ivf_gather_rows");
@@ -394,7 +352,7 @@ extern "C" int recnn_ivf_scan(const float* queries, int64_t ld_q, int n_queries,
   RECNN_REQUIRE(nprobe >= 1 && nprobe <= IVF_MAX_PROBE && nprobe <= nlist, "%s: need 1 <= nprobe <= min(64, nlist) (got %d)", fn, nprobe);
   RECNN_REQUIRE(k >= 1 && k <= KMAX, "%s: need 1 <= k <= 64 (got %d)", fn, k);
   RECNN_REQUIRE(metric == M_IP || (metric == M_L2 && list_aux), "%s: metric must be IP, or L2 with the |t|^2 array", fn);
-  RECNN_REQUIRE(aligned16(queries, list_rows) && ld_q % 4 == 0 && ld_q >= IVF_DIM, "%s: 16-byte alignment (rows and ld_q)", fn);
+  RECNN_REQUIRE(aligned16(queries, list_rows) && ld_q % 4 == 0 && ld_q >= DIM, "%s: 16-byte alignment (rows and ld_q)", fn);
   RECNN_REQUIRE((int64_t)n_queries * nprobe < (1LL << 31) / KMAX, "%s: n_queries * nprobe must stay below 2^25", fn);
   if (mask) {
     if (int rc = seen_check(fn, mask, words_per_row, n_queries, n_items)) return rc;

@@ -26,21 +26,20 @@
 // lane e; one ballot per row and 64 items against the row's current K-th, survivors inserted) and writes it as one partial list per (row, split); a
 // merge kernel then takes the K best of a row's sorted partial lists.  Order: distance ascending, NaN after every number, ties
 // to the smaller item id.  A third kernel, dist_rank_kernel, streams the table the same way and only counts, per row, the items that
-// come before one target item in that order.
+// come before one target item in that order.  Both kernels walk the table through the same device functions
+// (load_chunk, store_chunk, accumulate), and the host picks a kernel's <LOOP, TQ, TI> in one place (dispatch).
 #include <algorithm>
-
 #include <type_traits>
 
 #include "common.h"
 #include "seen.h"
+#include "select_dev.h"   // KMAX, PITCH, NONE_ID: no floating-point arithmetic in it, so nothing there depends on the pragma below
 #include "target_rank.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 constexpr int E = 128;          // embedding width (the reference's)
-constexpr int KMAX = 64;        // largest supported K
-constexpr int PITCH = 132;      // floats per LDS row of a [rows][128] tile (+4 pad: conflict-free b128 reads)
 constexpr int MERGE_CAND = 4096;  // largest splits * K the merge keeps in LDS
 constexpr int MAX_SPLITS = 256;   // the merge's wave holds 4 list heads per lane
 constexpr int TARGET_WG = 1024;   // workgroups to aim for: 4 per CU
@@ -114,11 +113,67 @@ template <int LOOP> __device__ __forceinline__ float finish(float a0, float a1, 
   } else return a0;
 }
 
+template <int LOOP> __device__ __forceinline__ void combine4(float& a0, float& a1, const float4& q, const float4& t, float p) {
+  combine<LOOP>(a0, a1, q.x, t.x, p);
+  combine<LOOP>(a0, a1, q.y, t.y, p);
+  combine<LOOP>(a0, a1, q.z, t.z, p);
+  combine<LOOP>(a0, a1, q.w, t.w, p);
+}
+
+// ---- a workgroup's walk over its split of the table, shared by dist_kernel and dist_rank_kernel
+
+// the wave's query rows, read with wave-uniform addresses (rows past B repeat row B-1; their results are not kept)
+template <int TQ> __device__ __forceinline__ void query_rows(const DistArgs& a, int q0, int wave, const float* (&qrow)[TQ]) {
+#pragma unroll
+  for (int i = 0; i < TQ; ++i) qrow[i] = a.q + (int64_t)min(q0 + wave * TQ + i, a.B - 1) * a.ldq;
+}
+
+// items n0 .. n0 + 64 TI - 1 -> registers, TI * 8 float4 per thread (rows from n_end on are zero) ...
+template <int TI> __device__ __forceinline__ void load_chunk(float4 (&stage)[TI * 8], const float* t, int n0, int n_end, int tid) {
+#pragma unroll
+  for (int s = 0; s < TI * 8; ++s) {
+    const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
+    stage[s] = n0 + r < n_end ? *(const float4*)(t + (int64_t)(n0 + r) * E + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// ... and from there into the LDS tile Ts [64 TI][PITCH], once the previous chunk's readers are done
+template <int TI> __device__ __forceinline__ void store_chunk(const float4 (&stage)[TI * 8], float* Ts, int tid) {
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < TI * 8; ++s) {
+    const int c = tid + s * 256;
+    *(float4*)&Ts[(c >> 5) * PITCH + (c & 31) * 4] = stage[s];
+  }
+  __syncthreads();
+}
+
+// the accumulators of the lane's TQ x TI pairs against the chunk in Ts: every pair runs over k = 0..127 in that order
+template <int LOOP, int TQ, int TI>
+__device__ __forceinline__ void accumulate(const float* Ts, const float* (&qrow)[TQ], int lane, float p, float (&a0)[TQ][TI],
+                                           float (&a1)[TQ][TI]) {
+#pragma unroll
+  for (int i = 0; i < TQ; ++i)
+#pragma unroll
+    for (int j = 0; j < TI; ++j) { a0[i][j] = 0.f; a1[i][j] = 0.f; }
+#pragma unroll 2
+  for (int k = 0; k < E; k += 4) {
+    float4 tv[TI];
+#pragma unroll
+    for (int j = 0; j < TI; ++j) tv[j] = *(const float4*)&Ts[(j * 64 + lane) * PITCH + k];
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) {
+      const float4 qv = *(const float4*)(qrow[i] + k);
+#pragma unroll
+      for (int j = 0; j < TI; ++j) combine4<LOOP>(a0[i][j], a1[i][j], qv, tv[j], p);
+    }
+  }
+}
+
 template <int LOOP, int TQ, int TI, bool TOPK, bool EXCL = false>
 __global__ __launch_bounds__(256) void dist_kernel(const DistArgsOf<EXCL> a) {
   static_assert(TOPK || !EXCL, "a matrix has no notion of absence");
   constexpr int QT = 4 * TQ, IT = 64 * TI;
-  constexpr int STAGE = IT * (E / 4) / 256;     // float4 per thread per chunk
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Ts = (float*)smem;                     // [IT][PITCH]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -130,55 +185,19 @@ __global__ __launch_bounds__(256) void dist_kernel(const DistArgsOf<EXCL> a) {
   float ld[TQ];
   int li[TQ];
 #pragma unroll
-  for (int i = 0; i < TQ; ++i) { ld[i] = __builtin_nanf(""); li[i] = 0x7FFFFFFF; }
-  // the wave's query rows, read with wave-uniform addresses (rows past B repeat row B-1; their results are not kept)
+  for (int i = 0; i < TQ; ++i) { ld[i] = __builtin_nanf(""); li[i] = NONE_ID; }
   const float* qrow[TQ];
-#pragma unroll
-  for (int i = 0; i < TQ; ++i) qrow[i] = a.q + (int64_t)min(q0 + wave * TQ + i, a.B - 1) * a.ldq;
-  float4 stage[STAGE];
-  auto load_chunk = [&](int n0) {
-#pragma unroll
-    for (int s = 0; s < STAGE; ++s) {
-      const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
-      stage[s] = n0 + r < n_end ? *(const float4*)(a.t + (int64_t)(n0 + r) * E + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  if (n_begin < n_end) load_chunk(n_begin);
+  query_rows<TQ>(a, q0, wave, qrow);
+  float4 stage[TI * 8];
+  if (n_begin < n_end) load_chunk<TI>(stage, a.t, n_begin, n_end, tid);
   const bool wave_live = q0 + wave * TQ < a.B;    // wave-uniform: rows of this wave exist
 
   for (int n0 = n_begin; n0 < n_end; n0 += IT) {
-    __syncthreads();                              // the previous chunk's readers are done
-#pragma unroll
-    for (int s = 0; s < STAGE; ++s) {
-      const int c = tid + s * 256;
-      *(float4*)&Ts[(c >> 5) * PITCH + (c & 31) * 4] = stage[s];
-    }
-    __syncthreads();
-    if (n0 + IT < n_end) load_chunk(n0 + IT);     // in flight while this chunk is scored
+    store_chunk<TI>(stage, Ts, tid);
+    if (n0 + IT < n_end) load_chunk<TI>(stage, a.t, n0 + IT, n_end, tid);     // in flight while this chunk is scored
     if (!wave_live) continue;
-
     float a0[TQ][TI], a1[TQ][TI];
-#pragma unroll
-    for (int i = 0; i < TQ; ++i)
-#pragma unroll
-      for (int j = 0; j < TI; ++j) { a0[i][j] = 0.f; a1[i][j] = 0.f; }
-#pragma unroll 2
-    for (int k = 0; k < E; k += 4) {
-      float4 tv[TI];
-#pragma unroll
-      for (int j = 0; j < TI; ++j) tv[j] = *(const float4*)&Ts[(j * 64 + lane) * PITCH + k];
-#pragma unroll
-      for (int i = 0; i < TQ; ++i) {
-        const float4 qv = *(const float4*)(qrow[i] + k);
-#pragma unroll
-        for (int j = 0; j < TI; ++j) {
-          combine<LOOP>(a0[i][j], a1[i][j], qv.x, tv[j].x, a.p);
-          combine<LOOP>(a0[i][j], a1[i][j], qv.y, tv[j].y, a.p);
-          combine<LOOP>(a0[i][j], a1[i][j], qv.z, tv[j].z, a.p);
-          combine<LOOP>(a0[i][j], a1[i][j], qv.w, tv[j].w, a.p);
-        }
-      }
-    }
+    accumulate<LOOP>(Ts, qrow, lane, a.p, a0, a1);
 
 #pragma unroll
     for (int i = 0; i < TQ; ++i) {
@@ -241,7 +260,6 @@ template <int LOOP, int TQ, int TI, bool EXCL = false>
 __global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgsOf<EXCL> a, const int64_t* __restrict__ targets,
                                                         int32_t* __restrict__ part) {   // part: [B][splits]
   constexpr int QT = 4 * TQ, IT = 64 * TI;
-  constexpr int STAGE = IT * (E / 4) / 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Ts = (float*)smem;                     // [IT][PITCH]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -249,17 +267,9 @@ __global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgsOf<EXCL> a
   const int n_begin = blockIdx.y * a.per, n_end = min(a.N, n_begin + a.per);
 
   const float* qrow[TQ];
-#pragma unroll
-  for (int i = 0; i < TQ; ++i) qrow[i] = a.q + (int64_t)min(q0 + wave * TQ + i, a.B - 1) * a.ldq;
-  float4 stage[STAGE];
-  auto load_chunk = [&](int n0) {
-#pragma unroll
-    for (int s = 0; s < STAGE; ++s) {
-      const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
-      stage[s] = n0 + r < n_end ? *(const float4*)(a.t + (int64_t)(n0 + r) * E + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  if (n_begin < n_end) load_chunk(n_begin);
+  query_rows<TQ>(a, q0, wave, qrow);
+  float4 stage[TI * 8];
+  if (n_begin < n_end) load_chunk<TI>(stage, a.t, n_begin, n_end, tid);
   const bool wave_live = q0 + wave * TQ < a.B;
 
   // the rows' target keys (wave-uniform)
@@ -272,12 +282,7 @@ __global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgsOf<EXCL> a
     const float* trow = a.t + (int64_t)g * E;
     float t0 = 0.f, t1 = 0.f;
     for (int k = 0; k < E; k += 4) {
-      const float4 qv = *(const float4*)(qrow[i] + k);
-      const float4 tv = *(const float4*)(trow + k);
-      combine<LOOP>(t0, t1, qv.x, tv.x, a.p);
-      combine<LOOP>(t0, t1, qv.y, tv.y, a.p);
-      combine<LOOP>(t0, t1, qv.z, tv.z, a.p);
-      combine<LOOP>(t0, t1, qv.w, tv.w, a.p);
+      combine4<LOOP>(t0, t1, *(const float4*)(qrow[i] + k), *(const float4*)(trow + k), a.p);
     }
     const uint64_t key = rank_key(finish<LOOP>(t0, t1, a.metric, a.invp), g);
     tkey[i] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(key >> 32)) << 32) |
@@ -286,38 +291,11 @@ __global__ __launch_bounds__(256) void dist_rank_kernel(const DistArgsOf<EXCL> a
   }
 
   for (int n0 = n_begin; n0 < n_end; n0 += IT) {
-    __syncthreads();                              // the previous chunk's readers are done
-#pragma unroll
-    for (int s = 0; s < STAGE; ++s) {
-      const int c = tid + s * 256;
-      *(float4*)&Ts[(c >> 5) * PITCH + (c & 31) * 4] = stage[s];
-    }
-    __syncthreads();
-    if (n0 + IT < n_end) load_chunk(n0 + IT);     // in flight while this chunk is scored
+    store_chunk<TI>(stage, Ts, tid);
+    if (n0 + IT < n_end) load_chunk<TI>(stage, a.t, n0 + IT, n_end, tid);     // in flight while this chunk is scored
     if (!wave_live) continue;
-
     float a0[TQ][TI], a1[TQ][TI];
-#pragma unroll
-    for (int i = 0; i < TQ; ++i)
-#pragma unroll
-      for (int j = 0; j < TI; ++j) { a0[i][j] = 0.f; a1[i][j] = 0.f; }
-#pragma unroll 2
-    for (int k = 0; k < E; k += 4) {
-      float4 tv[TI];
-#pragma unroll
-      for (int j = 0; j < TI; ++j) tv[j] = *(const float4*)&Ts[(j * 64 + lane) * PITCH + k];
-#pragma unroll
-      for (int i = 0; i < TQ; ++i) {
-        const float4 qv = *(const float4*)(qrow[i] + k);
-#pragma unroll
-        for (int j = 0; j < TI; ++j) {
-          combine<LOOP>(a0[i][j], a1[i][j], qv.x, tv[j].x, a.p);
-          combine<LOOP>(a0[i][j], a1[i][j], qv.y, tv[j].y, a.p);
-          combine<LOOP>(a0[i][j], a1[i][j], qv.z, tv[j].z, a.p);
-          combine<LOOP>(a0[i][j], a1[i][j], qv.w, tv[j].w, a.p);
-        }
-      }
-    }
+    accumulate<LOOP>(Ts, qrow, lane, a.p, a0, a1);
 #pragma unroll
     for (int i = 0; i < TQ; ++i)
 #pragma unroll
@@ -361,7 +339,7 @@ __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict_
     const int s = lane + 64 * j;
     head[j] = 0;
     hd[j] = s < S ? cd[s * K] : __builtin_nanf("");
-    hi[j] = s < S ? ci[s * K] : 0x7FFFFFFF;
+    hi[j] = s < S ? ci[s * K] : NONE_ID;
   }
   for (int r = 0; r < K; ++r) {
     float bd = hd[0];
@@ -378,7 +356,7 @@ __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict_
     // k <= n_items, so the best head is a real item; its id is unique across the lists.  EXCL: a row may have fewer than K items
     // left; then every head is the sentinel, nothing advances, and the slot reads (+inf, -1)
     if constexpr (EXCL) {
-      if (bi == 0x7FFFFFFF) { bd = INFINITY; bi = -1; }
+      if (bi == NONE_ID) { bd = INFINITY; bi = -1; }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -386,7 +364,7 @@ __global__ __launch_bounds__(64) void dist_merge_kernel(const float* __restrict_
         const int s = lane + 64 * j;
         ++head[j];
         hd[j] = head[j] < K ? cd[s * K + head[j]] : __builtin_nanf("");
-        hi[j] = head[j] < K ? ci[s * K + head[j]] : 0x7FFFFFFF;
+        hi[j] = head[j] < K ? ci[s * K + head[j]] : NONE_ID;
       }
     if (lane == 0) {
       out_d[(int64_t)row * K + r] = bd;
@@ -451,60 +429,44 @@ Plan make_plan(int B, int N, int K) {
 
 size_t lds_bytes(bool big) { return (size_t)(big ? 128 : 64) * PITCH * 4; }
 
-template <int LOOP, int TQ, int TI, bool TOPK, bool EXCL> int launch_one(const DistArgsOf<EXCL>& a, const Plan& pl, hipStream_t st) {
-  const size_t lds = lds_bytes(TQ == 8);
+// launches KERNEL over the plan's grid; each kernel raises its dynamic-LDS limit once
+template <auto KERNEL, class... Args> int launch_tiled(const Plan& pl, hipStream_t st, const Args&... args) {
+  const size_t lds = lds_bytes(pl.big);
   static bool attr = false;
   if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)dist_kernel<LOOP, TQ, TI, TOPK, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RECNN_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL((dist_kernel<LOOP, TQ, TI, TOPK, EXCL>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a);
+  hipLaunchKernelGGL(KERNEL, dim3(pl.tiles, pl.splits), dim3(256), lds, st, args...);
   return 0;
 }
 
-template <int LOOP, bool TOPK, bool EXCL> int launch_loop(const DistArgsOf<EXCL>& a, const Plan& pl, hipStream_t st) {
-  return pl.big ? launch_one<LOOP, 8, 2, TOPK, EXCL>(a, pl, st) : launch_one<LOOP, 1, 1, TOPK, EXCL>(a, pl, st);
+template <int V> using Int = std::integral_constant<int, V>;
+
+// f(loop kind, TQ, TI), as compile-time constants, for the metric's inner loop and the plan's tile
+template <class F> int dispatch(int metric, const Plan& pl, F f) {
+  auto tile = [&](auto loop) {
+    return pl.big ? f(loop, Int<8>{}, Int<2>{}) : f(loop, Int<1>{}, Int<1>{});
+  };
+  switch (metric) {
+    case SQEUCLIDEAN: case EUCLIDEAN: return tile(Int<L_SQ>{});
+    case CITYBLOCK: return tile(Int<L_ABS>{});
+    case CHEBYSHEV: return tile(Int<L_MAX>{});
+    case MINKOWSKI: return tile(Int<L_POW>{});
+    case CANBERRA: return tile(Int<L_CANB>{});
+    case BRAYCURTIS: return tile(Int<L_BRAY>{});
+    default: return tile(Int<L_DOT>{});
+  }
 }
 
 template <bool TOPK, bool EXCL = false> int launch(const DistArgsOf<EXCL>& a, const Plan& pl, hipStream_t st) {
-  switch (a.metric) {
-    case SQEUCLIDEAN: case EUCLIDEAN: return launch_loop<L_SQ, TOPK, EXCL>(a, pl, st);
-    case CITYBLOCK: return launch_loop<L_ABS, TOPK, EXCL>(a, pl, st);
-    case CHEBYSHEV: return launch_loop<L_MAX, TOPK, EXCL>(a, pl, st);
-    case MINKOWSKI: return launch_loop<L_POW, TOPK, EXCL>(a, pl, st);
-    case CANBERRA: return launch_loop<L_CANB, TOPK, EXCL>(a, pl, st);
-    case BRAYCURTIS: return launch_loop<L_BRAY, TOPK, EXCL>(a, pl, st);
-    default: return launch_loop<L_DOT, TOPK, EXCL>(a, pl, st);
-  }
-}
-
-template <int LOOP, int TQ, int TI, bool EXCL> int launch_rank_one(const DistArgsOf<EXCL>& a, const Plan& pl, const int64_t* targets, int32_t* part,
-                                                        hipStream_t st) {
-  const size_t lds = lds_bytes(TQ == 8);
-  static bool attr = false;
-  if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)dist_rank_kernel<LOOP, TQ, TI, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL((dist_rank_kernel<LOOP, TQ, TI, EXCL>), dim3(pl.tiles, pl.splits), dim3(256), lds, st, a, targets, part);
-  return 0;
-}
-
-template <int LOOP, bool EXCL> int launch_rank_loop(const DistArgsOf<EXCL>& a, const Plan& pl, const int64_t* targets, int32_t* part,
-                                                    hipStream_t st) {
-  return pl.big ? launch_rank_one<LOOP, 8, 2, EXCL>(a, pl, targets, part, st) : launch_rank_one<LOOP, 1, 1, EXCL>(a, pl, targets, part, st);
+  return dispatch(a.metric, pl, [&](auto loop, auto tq, auto ti) { return launch_tiled<dist_kernel<decltype(loop)::value, decltype(tq)::value, decltype(ti)::value, TOPK, EXCL>>(pl, st, a); });
 }
 
 template <bool EXCL = false> int launch_rank(const DistArgsOf<EXCL>& a, const Plan& pl, const int64_t* targets, int32_t* part, hipStream_t st) {
-  switch (a.metric) {
-    case SQEUCLIDEAN: case EUCLIDEAN: return launch_rank_loop<L_SQ, EXCL>(a, pl, targets, part, st);
-    case CITYBLOCK: return launch_rank_loop<L_ABS, EXCL>(a, pl, targets, part, st);
-    case CHEBYSHEV: return launch_rank_loop<L_MAX, EXCL>(a, pl, targets, part, st);
-    case MINKOWSKI: return launch_rank_loop<L_POW, EXCL>(a, pl, targets, part, st);
-    case CANBERRA: return launch_rank_loop<L_CANB, EXCL>(a, pl, targets, part, st);
-    case BRAYCURTIS: return launch_rank_loop<L_BRAY, EXCL>(a, pl, targets, part, st);
-    default: return launch_rank_loop<L_DOT, EXCL>(a, pl, targets, part, st);
-  }
+  return dispatch(a.metric, pl, [&](auto loop, auto tq, auto ti) {
+    return launch_tiled<dist_rank_kernel<decltype(loop)::value, decltype(tq)::value, decltype(ti)::value, EXCL>>(pl, st, a, targets, part);
+  });
 }
 
 int64_t query_prep_bytes(int B, int metric) { return needs_aux(metric) ? ((int64_t)B * E * 4 + 255) / 256 * 256 : 0; }

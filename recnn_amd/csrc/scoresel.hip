@@ -4,8 +4,9 @@
 // The other top-K and counting epilogues of the library are fused into their scoring kernels (topk.hip, rank.hip); these two take the
 // scores from memory: the Q block of CriticIndex (qrank.hip), or any [B, N] matrix such as DiscreteActor's probabilities.
 //
-// Order: larger score first, ties to the smaller id (-0 == +0), NaN after every number in id order -- `comes_before` of topk.hip.
-// An item whose bit is set in its row's mask (seen.h; the mask may be NULL) does not exist for that row.
+// Order: larger score first, ties to the smaller id (-0 == +0), NaN after every number in id order -- `comes_before` of select_dev.h,
+// whose list insert and merge the top-K kernels use under that order.  An empty list slot is (NaN, NONE_ID): every item comes before
+// it.  An item whose bit is set in its row's mask (seen.h; the mask may be NULL) does not exist for that row.
 //
 // One wave owns one (row, split of the items): it streams its split in blocks of 64 consecutive items that start at a multiple of 64
 // (one item per lane, coalesced; one mask word per block).  Ids are int32, nothing is sized by N: N is limited by int32 alone (by
@@ -14,20 +15,13 @@
 
 #include "common.h"
 #include "seen.h"
+#include "select_dev.h"
 #include "target_rank.h"
 
 namespace {
-constexpr int SS_KMAX = 64;         // largest k
 constexpr int SS_MAX_SPLITS = 8;    // the merge holds 8 x 64 candidates, 8 per lane
 constexpr int SS_TARGET_WAVES = 2048;
 constexpr int SS_MIN_PER = 256;     // items per split, at least
-constexpr int SS_NONE = 0x7FFFFFFF; // id of an empty list slot; its score is NaN, so every item comes before it
-
-__device__ inline bool ss_better(float s, int id, float s2, int id2) { return s > s2 || (s == s2 && id < id2); }
-__device__ inline bool ss_before(float s, int id, float s2, int id2) {
-  if (s != s) return s2 != s2 && id < id2;
-  return s2 != s2 || ss_better(s, id, s2, id2);
-}
 
 struct SelPlan { int splits, per; };
 SelPlan make_sel_plan(int B, int N) {
@@ -39,19 +33,19 @@ SelPlan make_sel_plan(int B, int N) {
   return pl;
 }
 
-// part_s / part_i: [B][splits][K], each list sorted, empty slots (NaN, SS_NONE)
+// part_s / part_i: [B][splits][K], each list sorted, empty slots (NaN, NONE_ID)
 __global__ __launch_bounds__(256) void scores_topk_kernel(const float* __restrict__ scores, int64_t ld, int B, int N, int K, int splits, int per,
                                                           const uint64_t* __restrict__ mask, int64_t W, float* __restrict__ part_s,
                                                           int32_t* __restrict__ part_i) {
-  __shared__ float Ls[4][SS_KMAX];
-  __shared__ int Li[4][SS_KMAX];
+  __shared__ float Ls[4][KMAX];
+  __shared__ int Li[4][KMAX];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= B) return;                                  // whole waves leave; no workgroup barrier below
   float* ls = Ls[wave];
   int* li = Li[wave];
   ls[lane] = __builtin_nanf("");
-  li[lane] = SS_NONE;
+  li[lane] = NONE_ID;
   const int n_begin = blockIdx.y * per, n_end = (int)min((int64_t)N, (int64_t)n_begin + per);
   const float* srow = scores + (int64_t)row * ld;
   float s_next = n_begin + lane < n_end ? srow[n_begin + lane] : 0.f;
@@ -59,25 +53,9 @@ __global__ __launch_bounds__(256) void scores_topk_kernel(const float* __restric
     const float s = s_next;
     const int id = n0 + lane;
     if (n0 + 64 < n_end) s_next = n0 + 64 + lane < n_end ? srow[n0 + 64 + lane] : 0.f;
-    unsigned long long m = __ballot(id < n_end && ss_before(s, id, ls[K - 1], li[K - 1]));
+    unsigned long long m = __ballot(id < n_end && comes_before(s, id, ls[K - 1], li[K - 1]));
     if (mask) m &= ~seen_word(mask, W, row, n0);
-    while (m) {
-      const int src = __ffsll((long long)m) - 1;
-      m &= m - 1;
-      const float cs = __shfl(s, src, 64);
-      const int cid = n0 + src;
-      if (!ss_before(cs, cid, ls[K - 1], li[K - 1])) continue;
-      const float mine = lane < K ? ls[lane] : 0.f;
-      const int mine_id = lane < K ? li[lane] : 0;
-      const bool before = lane < K && ss_before(mine, mine_id, cs, cid);      // entries that stay in front
-      const int pos = __popcll(__ballot(before));
-      const float up = __shfl_up(mine, 1, 64);
-      const int up_id = __shfl_up(mine_id, 1, 64);
-      if (lane < K) {
-        if (lane == pos) { ls[lane] = cs; li[lane] = cid; }
-        else if (lane > pos) { ls[lane] = up; li[lane] = up_id; }
-      }
-    }
+    insert_survivors<comes_before>(m, s, [&](int src) { return n0 + src; }, ls, li, K, lane);
   }
   if (lane < K) {
     const int64_t o = ((int64_t)row * splits + blockIdx.y) * K + lane;
@@ -92,33 +70,11 @@ __global__ __launch_bounds__(256) void scores_topk_merge_kernel(const float* __r
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= B) return;
-  const int total = splits * K;
-  float cs[8]; int ci[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = lane + j * 64;
-    cs[j] = c < total ? ps[(int64_t)row * total + c] : __builtin_nanf("");
-    ci[j] = c < total ? pi[(int64_t)row * total + c] : SS_NONE;
-  }
-  for (int k = 0; k < K; ++k) {
-    float bs = __builtin_nanf(""); int bi = SS_NONE;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (ss_before(cs[j], ci[j], bs, bi)) { bs = cs[j]; bi = ci[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float os = __shfl_xor(bs, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ss_before(os, oi, bs, bi)) { bs = os; bi = oi; }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (ci[j] == bi) { cs[j] = __builtin_nanf(""); ci[j] = SS_NONE; }     // ids are unique across the splits
-    if (lane == 0) {
-      out_s[(int64_t)row * K + k] = bi == SS_NONE ? -INFINITY : bs;
-      out_i[(int64_t)row * K + k] = bi == SS_NONE ? -1 : bi;
-    }
-  }
+  const int64_t total = splits * K;
+  merge_candidates<comes_before>(ps + row * total, pi + row * total, (int)total, K, __builtin_nanf(""), lane, [&](int k, float bs, int bi) {
+    out_s[(int64_t)row * K + k] = bi == NONE_ID ? -INFINITY : bs;
+    out_i[(int64_t)row * K + k] = bi == NONE_ID ? -1 : bi;
+  });
 }
 
 // part[row][split] = items of the split, other than the target and not excluded, that come before the row's target
@@ -147,7 +103,7 @@ __global__ __launch_bounds__(256) void scores_rank_kernel(const float* __restric
       const int64_t nb = (int64_t)n0 + c * 64;
       if (nb >= n_end) break;
       const int64_t id = nb + lane;
-      unsigned long long m = __ballot(id < n_end && id != tg && ss_before(s[c], (int)id, ts, tg));
+      unsigned long long m = __ballot(id < n_end && id != tg && comes_before(s[c], (int)id, ts, tg));
       if (mask) m &= ~seen_word(mask, W, row, (int)nb);
       cnt += __popcll(m);
     }
@@ -166,7 +122,7 @@ int scores_check(const char* fn, const float* scores, int64_t ld, int B, int N, 
 }  // namespace
 
 extern "C" int recnn_scores_topk_workspace_bytes(int n_rows, int k, int64_t* h_bytes) {
-  RECNN_REQUIRE(h_bytes && n_rows >= 0 && k > 0 && k <= SS_KMAX, "scores_topk_workspace_bytes: bad arguments (0 < k <= 64)");
+  RECNN_REQUIRE(h_bytes && n_rows >= 0 && k > 0 && k <= KMAX, "scores_topk_workspace_bytes: bad arguments (0 < k <= 64)");
   *h_bytes = (int64_t)n_rows * SS_MAX_SPLITS * k * 8;     // per split: k scores and k ids
   return 0;
 }
@@ -174,7 +130,7 @@ extern "C" int recnn_scores_topk_workspace_bytes(int n_rows, int k, int64_t* h_b
 extern "C" int recnn_scores_topk(const float* scores, int64_t ld, int n_rows, int n_items, int k, float* out_scores, int64_t* out_ids,
                                  void* workspace, void* stream, const uint64_t* mask, int64_t words_per_row) {
   if (int rc = scores_check("scores_topk", scores, ld, n_rows, n_items, mask, words_per_row)) return rc;
-  RECNN_REQUIRE(k > 0 && k <= SS_KMAX, "scores_topk: need 0 < k <= 64 (got %d)", k);
+  RECNN_REQUIRE(k > 0 && k <= KMAX, "scores_topk: need 0 < k <= 64 (got %d)", k);
   RECNN_REQUIRE((out_scores && out_ids && workspace) || n_rows == 0, "scores_topk: null pointer");
   if (n_rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;

@@ -25,12 +25,12 @@
 #include "common.h"
 #include "seen.h"
 #include "target_rank.h"
-#include "topk_dev.h"   // tile shape, better(), score_tile(), query_sqnorm(): shared with ivf.hip
+#include "topk_dev.h"   // tile shape, staging, score_tile(), rank_score(), the scan's LDS layout; select_dev.h: orders, insert, merge
 
 namespace {
 struct TopkArgs {
   const float* q; int64_t ldq; int B;
-  const float* table; int N, E;
+  const float* table; int N;
   const float* aux;        // L2: |t|^2 per item;  COS: 1/|t| per item;  IP: unused
   int metric, K, splits;
   float* part_score;       // [B][S][K]  internal key (larger = better)
@@ -40,15 +40,24 @@ struct TopkArgs {
 // exclusion bits are one word (results do not depend on the split); the plain kernel keeps its argument block and its split
 struct TopkArgsX : TopkArgs { const uint64_t* mask; int64_t W; int per; };
 
-template <int E_, bool EXCL = false>
+template <bool EXCL> struct TopkLds : ScanLds {
+  static constexpr size_t Xw = shared;                        // EXCL: uint64 [QT] the chunk's exclusion word of each query row
+  static constexpr size_t bytes = Xw + (EXCL ? QT * 8 : 0);
+};
+
+// The chunk stage, the key block and the list insert below are written out, although topk_dev.h (stage_chunk, keys_to_tile) and
+// select_dev.h (insert_survivors<better>) hold the same code for ivf_scan_kernel: through those functions this kernel measured
+// 1.0 to 1.9 % slower at B = 2048 (N = 26,744 and 100,000), so it keeps the instruction stream it had.
+template <bool EXCL = false>
 __global__ __launch_bounds__(256) void topk_scores_kernel(const std::conditional_t<EXCL, TopkArgsX, TopkArgs> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* Qs = (float*)smem;                  // [QT][PITCH]
-  float* Ts = Qs + QT * PITCH;               // [IT][PITCH]
-  float* Ss = Ts + IT * PITCH;               // [QT][IT + 4]
-  float* Ls = Ss + QT * (IT + 4);            // [QT][KMAX] keys
-  int* Li = (int*)(Ls + QT * KMAX);          // [QT][KMAX] ids
-  uint64_t* Xw = (uint64_t*)(Li + QT * KMAX);   // EXCL: [QT] the chunk's exclusion word of each query row
+  using Lds = TopkLds<EXCL>;
+  float* Qs = (float*)(smem + Lds::Qs);
+  float* Ts = (float*)(smem + Lds::Ts);
+  float* Ss = (float*)(smem + Lds::Ss);
+  float* Ls = (float*)(smem + Lds::Ls);
+  int* Li = (int*)(smem + Lds::Li);
+  uint64_t* Xw = (uint64_t*)(smem + Lds::Xw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q0 = blockIdx.x * QT;
   int per;
@@ -57,51 +66,26 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(const std::conditional
   const int n_begin = blockIdx.y * per, n_end = min(a.N, n_begin + per);
   const int K = a.K;
 
-  for (int i = tid; i < QT * KMAX; i += 256) { Ls[i] = -INFINITY; Li[i] = 0x7FFFFFFF; }
-  // query tile -> LDS (rows past B are zero)
-  for (int c = tid; c < QT * (E_ / 4); c += 256) {
-    const int r = c / (E_ / 4), k4 = c % (E_ / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q0 + r < a.B) v = *(const float4*)(a.q + (int64_t)(q0 + r) * a.ldq + k4 * 4);
-    *(float4*)&Qs[r * PITCH + k4 * 4] = v;
-  }
+  for (int i = tid; i < QT * KMAX; i += 256) { Ls[i] = -INFINITY; Li[i] = NONE_ID; }
+  stage_rows(Qs, a.q, a.ldq, tid, [&](int r, int64_t& row) { row = q0 + r; return q0 + r < a.B; });   // rows past B are zero
   const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;   // wave tile: 32 queries x 32 items
   const int fr = lane & 15, fg = lane >> 4;
   __syncthreads();
 
   for (int n0 = n_begin; n0 < n_end; n0 += IT) {
     // ---- table chunk -> LDS
-    for (int c = tid; c < IT * (E_ / 4); c += 256) {
-      const int r = c / (E_ / 4), k4 = c % (E_ / 4);
+    for (int c = tid; c < IT * (DIM / 4); c += 256) {
+      const int r = c / (DIM / 4), k4 = c % (DIM / 4);
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n0 + r < n_end) v = *(const float4*)(a.table + (int64_t)(n0 + r) * E_ + k4 * 4);
+      if (n0 + r < n_end) v = *(const float4*)(a.table + (int64_t)(n0 + r) * DIM + k4 * 4);
       *(float4*)&Ts[r * PITCH + k4 * 4] = v;
     }
     if constexpr (EXCL) {
       if (tid < QT) Xw[tid] = q0 + tid < a.B ? seen_word(a.mask, a.W, q0 + tid, n0) : 0ull;   // n0 is a multiple of 64
     }
     __syncthreads();
-    // ---- scores = Q T^T (exact fp32 MFMA)
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int ks = 0; ks < E_ / 16; ++ks) {
-      float4 qa[2], tb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) qa[i] = *(const float4*)&Qs[(wm0 + i * 16 + fr) * PITCH + ks * 16 + fg * 4];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) tb[j] = *(const float4*)&Ts[(wn0 + j * 16 + fr) * PITCH + ks * 16 + fg * 4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(((const float*)&qa[i])[e], ((const float*)&tb[j])[e], acc[i][j], 0, 0, 0);
-    }
+    score_tile(Qs, Ts, wm0, wn0, fr, fg, acc);                // scores = Q T^T (exact fp32 MFMA)
     // ---- ranking key (larger = better) into the score tile
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -114,9 +98,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(const std::conditional
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = wm0 + i * 16 + fg * 4 + r;
-          float s = acc[i][j][r];
-          if (a.metric == M_L2) s = 2.f * s - ax;       // |q|^2 is constant per row: it does not change the order
-          else if (a.metric == M_COS) s = s * ax;
+          float s = rank_score(acc[i][j][r], ax, a.metric);
           if (n >= n_end) s = -INFINITY;
           Ss[row * (IT + 4) + col] = s;
         }
@@ -166,43 +148,20 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(const std::conditional
   }
 }
 
-// merge S sorted partial lists per query; one wave per query row
+// merge S sorted partial lists per query (S*K <= 512); one wave per query row
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ ps, const int32_t* __restrict__ pi, int B, int S, int K,
                                                          int metric, const float* __restrict__ q, int64_t ldq, int E,
                                                          float* __restrict__ out_d, int64_t* __restrict__ out_i) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= B) return;
-  const int total = S * K;
-  // each lane caches up to 8 candidates (S*K <= 512)
-  float cs[8]; int ci[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = lane + j * 64;
-    cs[j] = c < total ? ps[(int64_t)row * total + c] : -INFINITY;
-    ci[j] = c < total ? pi[(int64_t)row * total + c] : 0x7FFFFFFF;
-  }
+  const int64_t total = S * K;
   float qn = 0.f;
   if (metric == M_L2) qn = query_sqnorm(q, ldq, row, E, lane);
-  for (int k = 0; k < K; ++k) {
-    float bs = -INFINITY; int bi = 0x7FFFFFFF;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (better(cs[j], ci[j], bs, bi)) { bs = cs[j]; bi = ci[j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float os = __shfl_xor(bs, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (better(os, oi, bs, bi)) { bs = os; bi = oi; }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (ci[j] == bi) { cs[j] = -INFINITY; ci[j] = 0x7FFFFFFF; }   // ids are unique across the splits
-    if (lane == 0) {
-      out_d[(int64_t)row * K + k] = metric == M_L2 ? fmaxf(qn - bs, 0.f) : bs;  // L2: |q|^2 - (2 q.t - |t|^2)
-      out_i[(int64_t)row * K + k] = bi == 0x7FFFFFFF ? -1 : bi;
-    }
-  }
+  merge_candidates<better>(ps + row * total, pi + row * total, (int)total, K, -INFINITY, lane, [&](int k, float bs, int bi) {
+    out_d[(int64_t)row * K + k] = metric == M_L2 ? fmaxf(qn - bs, 0.f) : bs;  // L2: |q|^2 - (2 q.t - |t|^2)
+    out_i[(int64_t)row * K + k] = bi == NONE_ID ? -1 : bi;
+  });
 }
 
 // per-item auxiliary term of the metric: L2 -> |t|^2, COS -> 1/|t|
@@ -227,19 +186,6 @@ struct TopkRankArgs {
 };
 struct TopkRankArgsX : TopkRankArgs { const uint64_t* mask; int64_t W; };
 
-// the total order the counting uses: better() wherever both keys are numbers; an item whose key is NaN comes after every number, and
-// NaN keys order by id
-__device__ inline bool comes_before(float s, int id, float s2, int id2) {
-  if (s != s) return s2 != s2 && id < id2;
-  return s2 != s2 || better(s, id, s2, id2);
-}
-
-__device__ __forceinline__ float rank_score(float s, float ax, int metric) {   // the internal key of topk_scores_kernel
-  if (metric == M_L2) s = 2.f * s - ax;
-  else if (metric == M_COS) s = s * ax;
-  return s;
-}
-
 // Row b counts the items of its split that come before item g_b = targets[b].  The workgroup first gathers the target rows of its
 // 64 queries into the chunk buffer and runs the scoring tile on them: the diagonal holds each row's target key, with the bits the
 // stream produces for that pair (an element's k order does not depend on its place in the tile).  Then it streams its split
@@ -250,8 +196,7 @@ __device__ __forceinline__ float rank_score(float s, float ax, int metric) {   /
 // register-staged table chunk into LDS; the target's own bit is never consulted (the target is skipped by id).
 template <bool EXCL = false>
 __global__ __launch_bounds__(256) void topk_rank_kernel(const std::conditional_t<EXCL, TopkRankArgsX, TopkRankArgs> a) {
-  constexpr int E_ = 128;
-  constexpr int STAGE = IT * (E_ / 4) / 256;
+  constexpr int STAGE = IT * (DIM / 4) / 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Qs = (float*)smem;                  // [QT][PITCH]
   float* Ts = Qs + QT * PITCH;               // [IT][PITCH]
@@ -268,19 +213,14 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const std::conditional_t
     Tg[tid] = (uint64_t)g < (uint64_t)a.N ? (int)g : -1;
     Cn[tid] = 0;
   }
-  for (int c = tid; c < QT * (E_ / 4); c += 256) {
-    const int r = c / (E_ / 4), k4 = c % (E_ / 4);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q0 + r < a.B) v = *(const float4*)(a.q + (int64_t)(q0 + r) * a.ldq + k4 * 4);
-    *(float4*)&Qs[r * PITCH + k4 * 4] = v;
-  }
+  stage_rows(Qs, a.q, a.ldq, tid, [&](int r, int64_t& row) { row = q0 + r; return q0 + r < a.B; });
   float4 stage[STAGE];
   uint64_t xstage = 0ull;
   auto load_chunk = [&](int n0) {
 #pragma unroll
     for (int s = 0; s < STAGE; ++s) {
       const int c = tid + s * 256, r = c >> 5, k4 = c & 31;
-      stage[s] = n0 + r < n_end ? *(const float4*)(a.table + (int64_t)(n0 + r) * E_ + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      stage[s] = n0 + r < n_end ? *(const float4*)(a.table + (int64_t)(n0 + r) * DIM + k4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if constexpr (EXCL) {
       if (tid < QT && q0 + tid < a.B) xstage = seen_word(a.mask, a.W, q0 + tid, n0);   // per and n0 are multiples of 64
@@ -291,13 +231,7 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const std::conditional_t
   const int fr = lane & 15, fg = lane >> 4;
   __syncthreads();
   // ---- target rows -> Ts, scored like a chunk; the diagonal is each row's target key
-  for (int c = tid; c < QT * (E_ / 4); c += 256) {
-    const int r = c / (E_ / 4), k4 = c % (E_ / 4);
-    const int g = Tg[r];
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g >= 0) v = *(const float4*)(a.table + (int64_t)g * E_ + k4 * 4);
-    *(float4*)&Ts[r * PITCH + k4 * 4] = v;
-  }
+  stage_rows(Ts, a.table, DIM, tid, [&](int r, int64_t& row) { row = Tg[r]; return row >= 0; });
   __syncthreads();
   f32x4 acc[2][2];
   score_tile(Qs, Ts, wm0, wn0, fr, fg, acc);
@@ -418,7 +352,7 @@ int topk_search_impl(const char* fn, const float* queries, int64_t ld_q, int n_q
   }
   if (n_queries == 0) return 0;
   std::conditional_t<EXCL, TopkArgsX, TopkArgs> a;
-  a.q = queries; a.ldq = ld_q; a.B = n_queries; a.table = table; a.N = n_items; a.E = emb_dim; a.aux = item_aux;
+  a.q = queries; a.ldq = ld_q; a.B = n_queries; a.table = table; a.N = n_items; a.aux = item_aux;
   a.metric = metric; a.K = k;
   const int tiles = (n_queries + QT - 1) / QT;
   int splits = 512 / tiles;               // enough workgroups to fill 256 CUs twice
@@ -433,13 +367,13 @@ int topk_search_impl(const char* fn, const float* queries, int64_t ld_q, int n_q
   a.splits = splits;
   a.part_score = (float*)workspace;
   a.part_id = (int32_t*)((char*)workspace + (int64_t)n_queries * 8 * k * 4);
-  const size_t lds = (size_t)(QT * PITCH + IT * PITCH + QT * (IT + 4) + QT * KMAX) * 4 + (size_t)QT * KMAX * 4 + (EXCL ? QT * 8 : 0);
+  const size_t lds = TopkLds<EXCL>::bytes;
   static bool attr = false;
   if (!attr) {
-    RECNN_HIP(hipFuncSetAttribute((const void*)topk_scores_kernel<128, EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RECNN_HIP(hipFuncSetAttribute((const void*)topk_scores_kernel<EXCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL((topk_scores_kernel<128, EXCL>), dim3(tiles, splits), dim3(256), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((topk_scores_kernel<EXCL>), dim3(tiles, splits), dim3(256), lds, (hipStream_t)stream, a);
   // a short row's trailing slots hold the lists' sentinel, which the merge reports as id -1 at -inf (L2: +inf)
   hipLaunchKernelGGL(topk_merge_kernel, dim3((n_queries + 3) / 4), dim3(256), 0, (hipStream_t)stream, a.part_score, a.part_id, n_queries,
                      splits, k, metric, queries, ld_q, emb_dim, out_dist, out_ids);

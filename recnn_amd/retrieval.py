@@ -120,25 +120,16 @@ class FlatIndex:
             m = self._exclusion(exclude, B, "FlatIndex.search")
             if B == 0:
                 return dist, ids
-            if self.metric in DIST_METRICS:
-                ws = L.workspace("recnn_dist_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], k, device=q.device)
-                L.call("recnn_dist_topk_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
-                       DIST_METRICS[self.metric], self.p, L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws),
-                       L.current_stream(), L.ptr(m.words), m.words.shape[1])
-            else:
-                ws = L.workspace("recnn_topk_workspace_bytes", B, k, device=q.device)
-                L.call("recnn_topk_search_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
-                       METRICS[self.metric], L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream(),
-                       L.ptr(m.words), m.words.shape[1])
-            return dist, ids
+        suffix, mask = ("", ()) if exclude is None else ("_excluding", (L.ptr(m.words), m.words.shape[1]))
+        head = (L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim)
         if self.metric in DIST_METRICS:
             ws = L.workspace("recnn_dist_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], k, device=q.device)
-            L.call("recnn_dist_topk", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
-                   DIST_METRICS[self.metric], self.p, L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream())
-            return dist, ids
-        ws = L.workspace("recnn_topk_workspace_bytes", B, k, device=q.device)
-        L.call("recnn_topk_search", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim, METRICS[self.metric],
-               L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws), L.current_stream())
+            L.call("recnn_dist_topk" + suffix, *head, DIST_METRICS[self.metric], self.p, L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids),
+                   L.ptr(ws), L.current_stream(), *mask)
+        else:
+            ws = L.workspace("recnn_topk_workspace_bytes", B, k, device=q.device)
+            L.call("recnn_topk_search" + suffix, *head, METRICS[self.metric], L.ptr(self.aux), k, L.ptr(dist), L.ptr(ids), L.ptr(ws),
+                   L.current_stream(), *mask)
         return dist, ids
 
     def _exclusion(self, exclude, B, what):
@@ -159,30 +150,17 @@ class FlatIndex:
         rank = torch.empty(B, dtype=torch.int32, device=q.device)
         if exclude is not None:
             m = self._exclusion(exclude, B, "FlatIndex.rank_of")
-            if B == 0:
-                return rank
-            if self.metric in DIST_METRICS:
-                ws = L.workspace("recnn_dist_target_rank_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric],
-                                 device=q.device)
-                L.call("recnn_dist_target_rank_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
-                       DIST_METRICS[self.metric], self.p, L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream(),
-                       L.ptr(m.words), m.words.shape[1])
-            else:
-                ws = L.workspace("recnn_topk_target_rank_workspace_bytes", B, self.n_items, device=q.device)
-                L.call("recnn_topk_target_rank_excluding", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
-                       METRICS[self.metric], L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream(),
-                       L.ptr(m.words), m.words.shape[1])
-            return rank
         if B == 0:                                                       # an empty batch has no storage to point at
             return rank
+        suffix, mask = ("", ()) if exclude is None else ("_excluding", (L.ptr(m.words), m.words.shape[1]))
+        head = (L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim)
+        tail = (L.ptr(self.aux), L.ptr(t), L.ptr(rank))
         if self.metric in DIST_METRICS:
             ws = L.workspace("recnn_dist_target_rank_workspace_bytes", B, self.n_items, DIST_METRICS[self.metric], device=q.device)
-            L.call("recnn_dist_target_rank", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim,
-                   DIST_METRICS[self.metric], self.p, L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream())
-            return rank
-        ws = L.workspace("recnn_topk_target_rank_workspace_bytes", B, self.n_items, device=q.device)
-        L.call("recnn_topk_target_rank", L.ptr(q), q.stride(0), B, L.ptr(self.table), self.n_items, self.dim, METRICS[self.metric],
-               L.ptr(self.aux), L.ptr(t), L.ptr(rank), L.ptr(ws), L.current_stream())
+            L.call("recnn_dist_target_rank" + suffix, *head, DIST_METRICS[self.metric], self.p, *tail, L.ptr(ws), L.current_stream(), *mask)
+        else:
+            ws = L.workspace("recnn_topk_target_rank_workspace_bytes", B, self.n_items, device=q.device)
+            L.call("recnn_topk_target_rank" + suffix, *head, METRICS[self.metric], *tail, L.ptr(ws), L.current_stream(), *mask)
         return rank
 
 
@@ -978,7 +956,10 @@ class IVFFlatIndex:
     # ---- construction
     @staticmethod
     def _check_table(table, nlist, metric, what):
-        name = metric if isinstance(metric, str) else getattr(metric, "__name__", None)
+        try:
+            name = metric_name(metric)
+        except ValueError:
+            name = None
         if name not in IVF_METRICS:
             raise ValueError(f"{what}: metric must be \"L2\" or \"IP\", got {metric!r} (COS and the scipy metrics are FlatIndex's)")
         if not isinstance(table, torch.Tensor):

@@ -62,6 +62,41 @@ def test_topk_ties_and_duplicates(cuda):
         assert np.allclose(d.cpu().numpy(), d_ref, atol=1e-6)
 
 
+NAN_ROWS = (0, 63, 64, 129)                                        # the ends of the chunks 0..63, 64..127, 128..129
+
+
+@pytest.fixture(scope="module")
+def nan_case():
+    """Integer-valued table [130, 128] and queries [3, 128] in [-3, 3]: every score is exact in float32 and ties abound.
+    Four rows of the table are NaN throughout."""
+    rng = np.random.default_rng(130)
+    table = rng.integers(-3, 4, size=(130, 128)).astype(np.float32)
+    table[100] = table[7]                                          # a twin pair: equal keys for every query
+    table[list(NAN_ROWS)] = np.nan
+    q = rng.integers(-3, 4, size=(3, 128)).astype(np.float32)
+    finite = np.array([i for i in range(130) if i not in NAN_ROWS])
+    return table, q, finite
+
+
+@pytest.mark.parametrize("metric", ["IP", "L2"])
+@pytest.mark.parametrize("k", [1, 5, 64])
+def test_an_item_whose_key_is_nan_is_never_returned(cuda, nan_case, metric, k):
+    """The flat search and the IVF scan select with `better`, under which a NaN key never wins: the result is the search over
+    the finite rows, ids and distances exact, ties to the smaller id."""
+    from recnn_amd.retrieval import FlatIndex, IVFFlatIndex
+    table, q, finite = nan_case
+    d_ref, pos = R.topk(q, table[finite], metric, k)               # float64; ascending position = ascending id
+    i_ref = finite[pos]
+    t, qq = torch.from_numpy(table).to(cuda), torch.from_numpy(q).to(cuda)
+    d, i = FlatIndex(t, metric).search(qq, k)
+    assert np.array_equal(i.cpu().numpy(), i_ref) and not set(i.flatten().tolist()) & set(NAN_ROWS)
+    assert np.array_equal(d.cpu().numpy().astype(np.float64), d_ref)
+    cent = torch.from_numpy(q.copy()).to(cuda)                      # three finite centroids; every list is probed
+    ivf = IVFFlatIndex.from_assignment(t, cent, torch.arange(130) % 3, metric)
+    d2, i2 = ivf.search(qq, k, nprobe=3)
+    assert torch.equal(i2, i) and np.array_equal(d2.cpu().numpy().view(np.int32), d.cpu().numpy().view(np.int32))
+
+
 def test_actor_output_to_items_roundtrip(cuda):
     """The demo's flow (streamlit_demo.py:190-231): generated action -> nearest items; a table row retrieves itself."""
     from recnn_amd.retrieval import FlatIndex

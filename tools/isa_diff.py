@@ -12,8 +12,17 @@ Per function symbol (kernels and any device function left out of line) it compar
   * the kernel's .amdhsa_* block (VGPRs, SGPRs, scratch, LDS, every other descriptor field),
 ignoring only what cannot matter: comments, .file / .ident / .loc / .cfi directives, the order of the symbols in the file and
 the names of local labels (.LBB7_3 is renamed by order of first appearance inside its function).
-One line per symbol; exit status 1 if any differs or exists on one side only.
+One line per symbol, with one of three verdicts:
+  identical   the same instruction stream and the same .amdhsa_* block;
+  equivalent  the same .amdhsa_* block and the same count of every instruction mnemonic, in another order or in other registers:
+              what moving code into a shared inline function typically gives;
+  DIFFERENT   anything else.
+Exit status 1 if any symbol is DIFFERENT or exists on one side only.
+
+A kernel whose symbol changes (a template parameter dropped, say) is paired by hand: compile both sides to directories of .s
+files, rename the old symbol in a copy, and compare the directories.
 """
+import collections
 import concurrent.futures
 import os
 import re
@@ -99,6 +108,11 @@ def parse(path):
     return out
 
 
+def mnemonics(lines):
+    """How often each mnemonic (a line's first word; labels and directives count as they stand) occurs."""
+    return collections.Counter(l.split(None, 1)[0] for l in lines)
+
+
 def hsa_summary(lines):
     d = dict(l.replace(".amdhsa_", "").split(None, 1) for l in lines if " " in l)
     return " ".join(f"{k}={d[k]}" for k in REPORT if k in d)
@@ -118,7 +132,7 @@ def main():
             else:
                 dirs.append(arg)
         files = [sorted(f for f in os.listdir(d) if f.endswith(".s")) for d in dirs]
-        bad = total = 0
+        bad = equivalent = total = 0
         for f in sorted(set(files[0]) | set(files[1])):
             if f not in files[0] or f not in files[1]:
                 print(f"{f}: only in {'OLD' if f in files[0] else 'NEW'}")
@@ -132,13 +146,16 @@ def main():
                     bad += 1
                 elif old[sym] == new[sym]:
                     print(f"{f} {sym}: identical ({len(new[sym][0])} lines)")
+                elif old[sym][1] == new[sym][1] and mnemonics(old[sym][0]) == mnemonics(new[sym][0]):
+                    print(f"{f} {sym}: equivalent ({len(new[sym][0])} lines: the same resources and the same count of every mnemonic)")
+                    equivalent += 1
                 else:
                     what = [w for w, i in (("instructions", 0), ("resources", 1)) if old[sym][i] != new[sym][i]]
                     first = next((k for k, (a, b) in enumerate(zip(old[sym][0], new[sym][0])) if a != b), min(len(old[sym][0]), len(new[sym][0])))
                     print(f"{f} {sym}: DIFFERENT {' + '.join(what)}; first at line {first}; {len(old[sym][0])} -> {len(new[sym][0])} lines; "
                           f"OLD [{hsa_summary(old[sym][1])}] NEW [{hsa_summary(new[sym][1])}]")
                     bad += 1
-        print(f"{total} symbols compared, {total - bad} identical, {bad} different")
+        print(f"{total} symbols compared, {total - bad - equivalent} identical, {equivalent} equivalent, {bad} different")
         sys.exit(1 if bad else 0)
 
 

@@ -1142,6 +1142,36 @@ int recnn_ivf_scan(const float* queries, int64_t ld_q, int n_queries, const floa
                    int nprobe, int k, float* out_dist, int64_t* out_ids, void* workspace, void* stream, const uint64_t* mask,
                    int64_t words_per_row);
 
+/* =====================================================================================
+ * 16. A candidate slate diversified (csrc/slate.hip): the similarity matrix of a row's candidates, the greedy
+ *    maximal-marginal-relevance pick over it, and the slate's intra-list distance.  table float32 [n_items][128], 16-byte aligned;
+ *    ids [n_rows][n_candidates] table row ids with row stride ld_ids (elements), int32 (ids_are_int64 = 0) or int64 (1),
+ *    1 <= n_candidates <= 64; a slot whose id is outside [0, n_items) is empty and reads nothing.  kind: 0 IP, 1 L2, 2 COS.
+ *      G = X X^T over the gathered rows X (exact fp32 MFMA), n_i = G_ii
+ *      IP  S_ij = G_ij     COS  S_ij = G_ij / (sqrt(n_i) sqrt(n_j)), 0 where a norm is 0     L2  S_ij = -max((n_i + n_j) - 2 G_ij, 0)
+ *    Entries of an empty slot are 0.  S is bitwise symmetric, and the bits of S_ij depend on the two table rows alone.
+ *    recnn_slate_similarity: out float32 [n_rows][n_candidates][n_candidates].
+ *    recnn_slate_rerank: rel float32 [n_rows][n_candidates] (row stride ld_rel), larger is better; 0 <= lam <= 1; 1 <= k <= n_candidates.
+ *      With mu = 1 - lam (fp32) step 1 scores slot j as lam * r_j, step t > 1 as (lam * r_j) - (mu * m_j), m_j the largest S_js over
+ *      the slots s chosen so far, every operation one correctly rounded fp32 operation; the slot chosen is the first one not yet
+ *      chosen in the order of section 14 (larger score first, -0 == +0, ties to the smaller id, equal ids to the smaller slot, NaN
+ *      after every number, empty slots last).  r_j = rel_j, or with normalize = 1 (rel_j - mn) / (mx - mn), mn and mx over the row's
+ *      non-empty slots of finite relevance (0 when mx == mn; a non-finite relevance passes through).  Writes out_score float32 (the
+ *      score at the moment of the choice), out_ids int64 and out_slot int32 (the slot's index in the list), [n_rows][k]; once the
+ *      non-empty slots run out: -inf, -1, -1.
+ *    recnn_slate_ild: out float64 [n_rows]: the mean over unordered pairs of non-empty slots of D_ij, formed in fp32 from S_ij (COS
+ *      1 - S_ij, L2 sqrt(-S_ij), IP -S_ij) and summed in float64; NaN with fewer than two non-empty slots.
+ *    One launch each up to 2^20 rows (more are looped inside the call), no workspace, no atomics.  Errors: RECNN_E_INVALID before any
+ *    HIP call, with a message that names the argument.  Zero rows launch nothing.
+ * ===================================================================================== */
+int recnn_slate_similarity(const float* table, int n_items, const void* ids, int64_t ld_ids, int n_rows, int n_candidates,
+                           int ids_are_int64, int kind, float* out, void* stream);
+int recnn_slate_rerank(const float* table, int n_items, const void* ids, int64_t ld_ids, int n_rows, int n_candidates,
+                       int ids_are_int64, int kind, const float* rel, int64_t ld_rel, float lam, int normalize, int k,
+                       float* out_score, int64_t* out_ids, int32_t* out_slot, void* stream);
+int recnn_slate_ild(const float* table, int n_items, const void* ids, int64_t ld_ids, int n_rows, int n_candidates, int ids_are_int64,
+                    int kind, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,9 @@ SIGNATURES = {
     "recnn_ivf_gather_rows": (_I, [_P, _I, _P, _P, _P]),
     "recnn_ivf_search_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
     "recnn_ivf_scan": (_I, [_P, _L, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L]),
+    "recnn_slate_similarity": (_I, [_P, _I, _P, _L, _I, _I, _I, _I, _P, _P]),
+    "recnn_slate_rerank": (_I, [_P, _I, _P, _L, _I, _I, _I, _I, _P, _L, _F, _I, _I, _P, _P, _P, _P]),
+    "recnn_slate_ild": (_I, [_P, _I, _P, _L, _I, _I, _I, _I, _P, _P]),
 }
 
 class FrozenDebugArgs(C.Structure):

@@ -19,6 +19,7 @@
 #include <climits>
 
 #include "common.h"
+#include "select_dev.h"   // slot_before: the order of a list's slots
 
 namespace {
 constexpr int QC_KS = 16;          // k values per W2 slab
@@ -39,15 +40,6 @@ struct CandArgs {
   int k_out; float* sq; int64_t* sid;               // sorted form: [B][k_out]
   const int64_t* targets; int32_t* pos; const int32_t* fallback;
 };
-
-// slot a (score qa, id ia >= 0 or -1 = empty, index sa) comes before slot b
-__device__ inline bool qc_before(float qa, int ia, int sa, float qb, int ib, int sb) {
-  const int ca = ia < 0 ? 2 : (qa != qa ? 1 : 0), cb = ib < 0 ? 2 : (qb != qb ? 1 : 0);
-  if (ca != cb) return ca < cb;
-  if (ca == 2) return sa < sb;
-  if (ca == 0 && qa != qb) return qa > qb;
-  return ia < ib || (ia == ib && sa < sb);
-}
 
 template <int HP, int MT, bool SORT>
 __global__ __launch_bounds__(256) void qcand_kernel(const CandArgs a) {
@@ -169,7 +161,7 @@ __global__ __launch_bounds__(256) void qcand_kernel(const CandArgs a) {
   const float q = qs[lane];
   const int id = is[lane];
   int place = 0;
-  for (int j = 0; j < QC_SLOTS; ++j) place += qc_before(qs[j], is[j], j, q, id, lane) ? 1 : 0;
+  for (int j = 0; j < QC_SLOTS; ++j) place += slot_before(qs[j], is[j], j, q, id, lane) ? 1 : 0;
   if (place < a.k_out) {
     a.sq[(int64_t)b * a.k_out + place] = id < 0 ? -INFINITY : q;
     a.sid[(int64_t)b * a.k_out + place] = id;

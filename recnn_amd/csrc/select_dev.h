@@ -1,5 +1,5 @@
-// select_dev.h -- what the top-K selections share (topk.hip, ivf.hip, scoresel.hip; rank.hip takes the limits and the empty slot): the
-// order of two candidates, the insert of a chunk's survivors into a row's sorted list, and the merge of a row's partial lists.
+// select_dev.h -- what the top-K selections share (topk.hip, ivf.hip, scoresel.hip; rank.hip takes the limits and the empty slot; qcand.hip
+// and slate.hip take the order of a candidate list's slots): the order of two candidates, the insert of a chunk's survivors into a row's sorted list, and the merge of a row's partial lists.
 // Comparisons, shuffles and moves only, no floating-point arithmetic: the header means the same under any contraction setting.
 #pragma once
 #include "common.h"
@@ -18,6 +18,29 @@ __device__ inline bool comes_before(float s, int id, float s2, int id2) {
   return s2 != s2 || better(s, id, s2, id2);
 }
 using Order = bool (*)(float, int, float, int);
+
+// The order of the slots of a per-row candidate list (qcand.hip's sorted form, slate.hip's greedy pick): slot a (score qa, id ia >= 0
+// or < 0 = empty, index sa) comes before slot b.  Larger score first, -0 == +0, ties to the smaller id, equal ids to the smaller slot,
+// NaN scores after every number in (id, slot) order, empty slots last in slot order.
+__device__ inline bool slot_before(float qa, int ia, int sa, float qb, int ib, int sb) {
+  const int ca = ia < 0 ? 2 : (qa != qa ? 1 : 0), cb = ib < 0 ? 2 : (qb != qb ? 1 : 0);
+  if (ca != cb) return ca < cb;
+  if (ca == 2) return sa < sb;
+  if (ca == 0 && qa != qb) return qa > qb;
+  return ia < ib || (ia == ib && sa < sb);
+}
+
+// The same order as one unsigned key, for a wave-wide maximum: a comes before b  <=>  slot_key(a) > slot_key(b), or the keys are equal
+// (one score or both NaN, one id) and sa < sb.  An empty slot's key is 0, below every other; empty slots are not ordered among themselves.
+__device__ inline uint64_t slot_key(float q, int id) {
+  if (id < 0) return 0;
+  uint32_t hi = 1u;                                                     // NaN: after every number (-inf maps to 0x007FFFFF)
+  if (q == q) {
+    const uint32_t u = q == 0.f ? 0u : __builtin_bit_cast(uint32_t, q);  // -0 == +0
+    hi = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                    // ascending with q
+  }
+  return ((uint64_t)hi << 32) | (uint32_t)(0x7FFFFFFF - id);
+}
 
 // A wave inserts a chunk's survivors into the sorted list (ls, li) of K <= 64 entries, entry e handled by lane e.  m: the ballot of
 // the lanes whose candidate beats the list's K-th; lane src offers (its s, id_of(src)).  Survivors enter in lane order, each checked

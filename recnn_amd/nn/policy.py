@@ -38,10 +38,11 @@ class WolpertingerPolicy:
         with torch.no_grad():
             return F_hip.mlp(state, self.actor, False)
 
-    def recommend(self, state, k=10, exclude=None):
+    def recommend(self, state, k=10, exclude=None, diversify=None):
         """(q float32 [B, k] descending, ids int64 [B, k]): the k candidates the critic values most among the `n_candidates` items
-        nearest to the actor's action.  `exclude` as in `FlatIndex.search`."""
-        return self.index.search(self.proto_action(state), state, k, exclude, self.nprobe)
+        nearest to the actor's action.  `exclude` as in `FlatIndex.search`.  `diversify=lam`: `TwoStageIndex.search`'s greedy MMR
+        stage over the candidates (cosine similarity); q is then in the order of the choice, not descending."""
+        return self.index.search(self.proto_action(state), state, k, exclude, self.nprobe, diversify)
 
     def act(self, state, exclude=None):
         """(ids int64 [B], actions float32 [B, 128], q float32 [B]): the best candidate, its table row and its value.  A row with

@@ -593,6 +593,26 @@ MAX_HIDDEN = 256          # the pair kernel keeps all hidden columns of its pair
 DEFAULT_WORKSPACE_BYTES = 256 << 20
 
 
+def _id_matrix(ids, device, what, B=None, rows_of=None):
+    """A candidate id matrix as the kernels take it: int32 or int64 [B, K] with unit column stride, any row stride, on `device`;
+    with `B`, of that many rows (the rows of the `rows_of` it goes with)."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+        raise ValueError(f"{what}: ids must be an integer tensor [B, K], got "
+                         f"{ids.dtype if isinstance(ids, torch.Tensor) else type(ids).__name__}")
+    if ids.dim() != 2 or ids.shape[1] < 1:
+        raise ValueError(f"{what}: ids must be [B, K] with K >= 1, got {tuple(ids.shape)}")
+    if ids.device != device:
+        raise ValueError(f"{what}: the ids live on {ids.device}, the index on {device}")
+    if B is not None and ids.shape[0] != B:
+        raise ValueError(f"{what}: {B} {rows_of} but ids of {ids.shape[0]} rows")
+    t = ids.detach()
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.to(torch.int64)
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
 class CriticIndex:
     """The catalogue ranked by a critic's Q-value: `Q[b, n] = critic(state[b], table[n])` for every item, eval semantics (no
     dropout, whatever `critic.training` says), without the [B N, H] activations ever reaching memory (csrc/qrank.hip).
@@ -745,21 +765,7 @@ class CriticIndex:
 
     def _ids(self, ids, B, what):
         """The id matrix as the kernel takes it: int32 or int64 [B, K] with unit column stride, any row stride."""
-        if not isinstance(ids, torch.Tensor) or ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
-            raise ValueError(f"{what}: ids must be an integer tensor [B, K], got "
-                             f"{ids.dtype if isinstance(ids, torch.Tensor) else type(ids).__name__}")
-        if ids.dim() != 2 or ids.shape[1] < 1:
-            raise ValueError(f"{what}: ids must be [B, K] with K >= 1, got {tuple(ids.shape)}")
-        if ids.device != self.table.device:
-            raise ValueError(f"{what}: the ids live on {ids.device}, the index on {self.table.device}")
-        if ids.shape[0] != B:
-            raise ValueError(f"{what}: {B} states but ids of {ids.shape[0]} rows")
-        t = ids.detach()
-        if t.dtype not in (torch.int32, torch.int64):
-            t = t.to(torch.int64)
-        if t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
-            t = t.contiguous()
-        return t
+        return _id_matrix(ids, self.table.device, what, B, "states")
 
     def _cand_args(self, s1, t):
         B, K = t.shape
@@ -810,6 +816,115 @@ class CriticIndex:
 __all__ += ["topk_of_scores", "rank_in_scores", "CriticIndex"]
 
 
+# ---- a diversifying rerank of a candidate slate (csrc/slate.hip): greedy maximal marginal relevance
+# (Carbonell & Goldstein 1998) over the similarity matrix of a row's candidates, and the slate's intra-list distance.
+
+class SlateDiversifier:
+    """Similarity, greedy MMR selection and intra-list distance of per-row candidate lists `ids` [B, K <= 64] (int32 or int64, any
+    row stride) over the rows of `table` (float32 [N, 128] on the GPU, snapshotted as the indexes do), one launch each.
+
+    `similarity` "IP" / "COS" / "L2": with G = X X^T over a row's gathered table rows and n_i = G_ii, S_ij = G_ij, G_ij / (sqrt(n_i)
+    sqrt(n_j)) (0 where a norm is 0), or -max((n_i + n_j) - 2 G_ij, 0).  A slot whose id is outside [0, N) (the -1 `search` pads
+    with) is empty: its entries of S are 0, and no selection picks it.  S is bitwise symmetric and S_ij depends on the two table
+    rows alone, not on B, K or the slots."""
+
+    def __init__(self, table, similarity="COS"):
+        what = "SlateDiversifier"
+        if similarity not in METRICS:
+            raise ValueError(f"{what}: similarity must be one of {sorted(METRICS)}, got {similarity!r}")
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != ITEM_DIM or table.shape[0] < 1:
+            raise ValueError(f"{what}: the item table must be [N, {ITEM_DIM}] (the embedding width is {ITEM_DIM}), got "
+                             f"{tuple(table.shape) if isinstance(table, torch.Tensor) else type(table).__name__}")
+        _on_gpu(table, f"{what}: the item table")
+        self.kind = similarity
+        self.table = table.detach().to(torch.float32).contiguous()
+        self.n_items, self.dim = self.table.shape
+
+    @property
+    def ntotal(self):
+        return self.n_items
+
+    def _lists(self, ids, what, B=None):
+        """The id matrix checked: `_id_matrix` with K <= 64."""
+        t = _id_matrix(ids, self.table.device, what, B, "rows of relevance")
+        if t.shape[1] > MAX_K:
+            raise ValueError(f"{what}: ids holds K = {t.shape[1]} candidates per row; a slate takes at most {MAX_K}")
+        return t
+
+    def _args(self, t, what):
+        """The arguments every entry point begins with."""
+        _on_gpu(t, f"{what}: ids")
+        B, K = t.shape
+        return (L.ptr(self.table), self.n_items, L.ptr(t), t.stride(0) if B > 1 else K, B, K, int(t.dtype == torch.int64),
+                METRICS[self.kind])
+
+    def similarity(self, ids):
+        """float32 [B, K, K]: S of every row's candidates."""
+        what = "SlateDiversifier.similarity"
+        t = self._lists(ids, what)
+        args = self._args(t, what)
+        B, K = t.shape
+        out = torch.empty(B, K, K, dtype=torch.float32, device=t.device)
+        if B:
+            L.call("recnn_slate_similarity", *args, L.ptr(out), L.current_stream())
+        return out
+
+    def rerank(self, relevance, ids, k=None, lam=0.5, normalize=False):
+        """(score float32 [B, k], ids int64 [B, k], slots int32 [B, k]): k (default K) slots of every row picked greedily.  With
+        lam32 = float32(lam) and mu32 = 1 - lam32, step 1 scores slot j as lam32 * r_j and step t > 1 as (lam32 * r_j) - (mu32 *
+        m_j), m_j the largest S_js over the slots chosen so far, each operation rounded to fp32; the slot picked is the first not
+        yet chosen in the order of `CriticIndex.rerank` (larger score first, ties to the smaller id, a repeated id to the smaller
+        slot, -0 == +0, NaN after every number, empty slots last).  `relevance` float32 [B, K], larger is better; r_j is the
+        relevance itself, or with `normalize` (rel_j - mn) / (mx - mn) over the row's non-empty slots of finite relevance (0 when
+        mx == mn; a non-finite relevance passes through).  `score` is the score at the moment of the pick, `slots` the picked
+        slot's index in the list; once the non-empty slots run out: score -inf, id -1, slot -1.  lam = 1 sorts by relevance,
+        lam = 0 spreads the slate regardless of it."""
+        what = "SlateDiversifier.rerank"
+        if not isinstance(relevance, torch.Tensor) or not relevance.dtype.is_floating_point or relevance.dim() != 2:
+            raise ValueError(f"{what}: relevance must be a floating-point tensor [B, K], got "
+                             f"{(relevance.dtype, tuple(relevance.shape)) if isinstance(relevance, torch.Tensor) else type(relevance).__name__}")
+        t = self._lists(ids, what, relevance.shape[0])
+        B, K = t.shape
+        if relevance.shape[1] != K:
+            raise ValueError(f"{what}: relevance is {tuple(relevance.shape)} but ids {tuple(t.shape)}")
+        if relevance.device != t.device:
+            raise ValueError(f"{what}: the relevance lives on {relevance.device}, the ids on {t.device}")
+        if k is None:
+            k = K
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= K:
+            raise ValueError(f"{what}: k must be an integer from 1 to the {K} candidates per row, got {k}")
+        k = int(k)
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"{what}: lam must be in [0, 1], got {lam}")
+        args = self._args(t, what)
+        r = relevance.detach().to(torch.float32)
+        if r.stride(1) != 1 or (B > 1 and r.stride(0) < K) or r.data_ptr() % 4:
+            r = r.contiguous()
+        score = torch.empty(B, k, dtype=torch.float32, device=t.device)
+        out = torch.empty(B, k, dtype=torch.int64, device=t.device)
+        slots = torch.empty(B, k, dtype=torch.int32, device=t.device)
+        if B:
+            L.call("recnn_slate_rerank", *args, L.ptr(r), r.stride(0) if B > 1 else K, lam, int(bool(normalize)), k, L.ptr(score),
+                   L.ptr(out), L.ptr(slots), L.current_stream())
+        return score, out, slots
+
+    def ild(self, ids):
+        """float64 [B]: the slate's intra-list distance, the mean over unordered pairs of non-empty slots of D_ij = 1 - S_ij (COS),
+        sqrt(-S_ij) (L2: the distance) or -S_ij (IP), formed in fp32 and summed in float64; NaN with fewer than two non-empty
+        slots."""
+        what = "SlateDiversifier.ild"
+        t = self._lists(ids, what)
+        args = self._args(t, what)
+        out = torch.empty(t.shape[0], dtype=torch.float64, device=t.device)
+        if t.shape[0]:
+            L.call("recnn_slate_ild", *args, L.ptr(out), L.current_stream())
+        return out
+
+
+__all__ += ["SlateDiversifier"]
+
+
 # ---- retrieve, then rerank (csrc/qcand.hip; DESIGN.md section 23): the actor's proto-action picks the candidates by geometry, the
 # critic orders them by value -- the Wolpertinger policy of Dulac-Arnold et al. (2015).
 
@@ -837,6 +952,7 @@ class TwoStageIndex:
             raise ValueError(f"TwoStageIndex: n_candidates = {n_candidates} but the table holds only {flat.n_items} items")
         self.flat, self.critic_index, self.n_candidates = flat, critic_index, int(n_candidates)
         self.n_items = flat.n_items
+        self._diversifiers = {}
 
     @property
     def ntotal(self):
@@ -846,17 +962,35 @@ class TwoStageIndex:
         """Re-reads the critic's weights (`CriticIndex.refresh`)."""
         self.critic_index.refresh()
 
-    def search(self, action, state, k=10, exclude=None, nprobe=None):
+    def search(self, action, state, k=10, exclude=None, nprobe=None, diversify=None, similarity="COS"):
         """(q float32 [B, k] descending, ids int64 [B, k]): the k <= n_candidates candidates of highest value among the
         n_candidates items nearest to `action[b]`.  `exclude` as in `FlatIndex.search`; a row with fewer than k items left ends in
-        id -1 at -inf.  `nprobe` (an `IVFFlatIndex` first stage only; default 16): the lists the first stage scores."""
+        id -1 at -inf.  `nprobe` (an `IVFFlatIndex` first stage only; default 16): the lists the first stage scores.
+
+        `diversify=lam` (0 <= lam <= 1; default None: no such stage): the n_candidates retrieved items, sorted by the critic, are
+        re-ranked by a `SlateDiversifier(flat.table, similarity)` with `normalize=True` (Q has no fixed scale), built on first use
+        and kept per similarity.  q is then the critic's value of the k chosen items in the order of their choice -- no longer
+        descending -- and -inf where the row ran out of items."""
         if isinstance(self.flat, IVFFlatIndex):
             cand = self.flat.search(action, self.n_candidates, DEFAULT_NPROBE if nprobe is None else nprobe, exclude)[1]
         else:
             if nprobe is not None:
                 raise ValueError("TwoStageIndex.search: nprobe applies to an IVFFlatIndex first stage; this one is a FlatIndex")
             cand = self.flat.search(action, self.n_candidates, exclude)[1]
-        return self.critic_index.rerank(state, cand, k)
+        if diversify is None:
+            return self.critic_index.rerank(state, cand, k)
+        if int(k) != k or not 1 <= k <= self.n_candidates:
+            raise ValueError(f"TwoStageIndex.search: k must be an integer from 1 to the {self.n_candidates} candidates per row, got {k}")
+        q, ids = self.critic_index.rerank(state, cand)
+        _, out, slots = self.diversifier(similarity).rerank(q, ids, int(k), diversify, normalize=True)
+        picked = torch.gather(q, 1, slots.clamp_min(0).to(torch.int64))
+        return picked.masked_fill_(slots < 0, float("-inf")), out
+
+    def diversifier(self, similarity="COS"):
+        """The `SlateDiversifier` over `flat.table` that `search(diversify=)` uses, built once per similarity."""
+        if similarity not in self._diversifiers:
+            self._diversifiers[similarity] = SlateDiversifier(self.flat.table, similarity)
+        return self._diversifiers[similarity]
 
     def rank_of(self, action, state, targets, exclude=None):
         """int32 [B]: the rank of item `targets[b]` in the order "the retrieved candidates by value, then every other item in the

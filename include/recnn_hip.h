@@ -834,7 +834,7 @@ int recnn_topk_stats(const float* dist, const int64_t* ids, int n_queries, int k
                      double* row_mean, double* row_std, double* totals, void* workspace, void* stream);
 
 /* =====================================================================================
- * 10. Dynamic-length user batches (csrc/seq.hip): the padded gathers behind recnn.data.utils.padder /
+ * 10. Dynamic-length user batches (csrc/seq.hip; the LSTM state encoder: csrc/lstm.hip over csrc/seq_chain.h): the padded gathers behind recnn.data.utils.padder /
  *    prepare_batch_dynamic_size, an LSTM state encoder over whole user histories, and the replay-buffer collect of SeqEnv.
  *    The replay store is the CSR triple of section 2 (items int32, ratings float, user_off int64) and `slots` int32[n_users] names
  *    the batch's users.  table float[n_items, emb_dim], 16-byte aligned rows.  An item id outside [0, n_items) gives NaN in whatever
@@ -871,7 +871,7 @@ int recnn_seq_collect(const float* h, int n_users, int T, int hidden, const int3
                       const float* ratings, const int64_t* user_off, const int32_t* slots, const float* table, int n_items,
                       int emb_dim, float* state, float* action, float* reward, float* next_state, void* stream);
 
-/* Training the encoder (csrc/seq_bwd.hip).  recnn_lstm_encode_train is recnn_lstm_encode -- the same h_out, h_T, c_T bit for bit,
+/* Training the encoder (csrc/lstm.hip over csrc/seq_chain.h and csrc/seq_bwd.h; the collect backward: csrc/seq.hip).  recnn_lstm_encode_train is recnn_lstm_encode -- the same h_out, h_T, c_T bit for bit,
  * either variant -- that also records, per (user, step, hidden unit), the gate activations i, f, g, o and the cell state c_t into
  * `saved` (saved_bytes of recnn_lstm_train_workspace_bytes: 5 * 16 ceil(n_users / 16) * T * hidden floats; 16-byte aligned; its
  * layout is private to the library).  `workspace` is that of recnn_lstm_workspace_bytes, as for recnn_lstm_encode.
@@ -893,7 +893,7 @@ int recnn_lstm_backward(const int32_t* items, const float* ratings, const int64_
                         const void* saved, const float* h_out, const float* h0, const float* c0, const float* g_h,
                         const float* g_hT, const float* g_cT, float* d_w_ih, float* d_w_hh, float* d_b, float* d_h0, float* d_c0,
                         void* workspace, void* stream);
-/* The gradient of the embedding table through the encoder (csrc/seq_bwd.hip).  recnn_lstm_backward_table is
+/* The gradient of the embedding table through the encoder (csrc/seq_bwd.h, csrc/seq_grad.h).  recnn_lstm_backward_table is
  * recnn_lstm_backward -- the same arguments, and the same bits in d_w_ih, d_w_hh, d_b, d_h0, d_c0 -- that also writes
  * d_table float[n_items, emb_dim] (required, 16-byte aligned; EVERY row is written, items the call's positions do not hold get exact
  * zeros): d_table[item] = sum of dX[u, t, 0:emb_dim] over the positions (u, t) with items_u[t0 + t] == item, where
@@ -918,7 +918,7 @@ int recnn_lstm_backward_table(const int32_t* items, const float* ratings, const 
 int recnn_seq_collect_bwd(const float* g_state, const float* g_next_state, int n_users, int T, int hidden, const int32_t* steps,
                           int n_steps, float* g_h, void* stream);
 
-/* A GRU as the state encoder (csrc/gru.hip): the recnn_lstm_* family for torch.nn.GRU(emb_dim + 1, hidden), one layer,
+/* A GRU as the state encoder (csrc/gru.hip over the same csrc/seq_chain.h and csrc/seq_bwd.h): the recnn_lstm_* family for torch.nn.GRU(emb_dim + 1, hidden), one layer,
  * one direction, gate order r, z, n, weights read in place: w_ih float[3 hidden, emb_dim + 1], w_hh float[3 hidden, hidden],
  * b_ih / b_hh float[3 hidden];
  *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z = sigmoid(W_iz x + b_iz + W_hz h + b_hz), n = tanh(W_in x + b_in + r (W_hn h + b_hn)),

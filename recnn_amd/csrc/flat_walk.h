@@ -1,4 +1,4 @@
-// flat_walk.h -- the element walk of the flat passes (optimizers, soft update, clip: optim.hip; padded gathers and collect: seq.hip).
+// flat_walk.h -- the element walk of the flat passes (optimizers, soft update, clip: optim.hip; padded gathers, collect and its backward: seq.hip; the W_hh transpose: seq_bwd.h).
 #pragma once
 #include <type_traits>
 

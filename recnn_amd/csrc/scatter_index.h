@@ -1,11 +1,11 @@
-// scatter_index.h -- the inverted index of the deterministic scatter-sums (dqn.hip: gradients of gathered embedding rows; seq_bwd.hip:
+// scatter_index.h -- the inverted index of the deterministic scatter-sums (dqn.hip: gradients of gathered embedding rows; seq_grad.h:
 // the table gradient of the LSTM encoder).  M contributions j = 0 .. M - 1, each with a destination id id_of(j); the index lists, per
 // destination, its contributions in ascending j: a stable counting sort (histogram, scan, placement, per-destination rank by j).
 // Integers only -- integer atomics for the counts, whose arrival order the rank pass removes again -- so the index, and with it the
 // order of every float sum taken over it, is a function of the ids alone.  The float passes over the index stay with their callers
 // (their row widths and weights differ).  Ids outside [0, n_dest) are dropped: they are in no list.
 //
-// id_of is a functor `int64_t operator()(int j) const` (device), passed by value: dqn reads an int64 matrix, seq_bwd an int32 history
+// id_of is a functor `int64_t operator()(int j) const` (device), passed by value: dqn reads an int64 matrix, seq_grad.h an int32 history
 // through the replay store.
 #pragma once
 #include "common.h"

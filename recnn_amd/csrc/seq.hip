@@ -1,33 +1,17 @@
 // seq.hip -- dynamic-length user batches (reference: recnn/data/utils.py padder / prepare_batch_dynamic_size and the SeqEnv design
-// of recnn/data/env.py) on gfx950: padded gathers, an LSTM state encoder over whole user histories, and the replay-buffer collect.
+// of recnn/data/env.py) on gfx950: padded gathers, and the replay-buffer collect with its backward.
 //
 //   padded gather   [U, Lmax] ids / ratings and [U, Lmax, E] embedding rows from the CSR replay store (or from an already padded id
 //                   tensor): a flat walk over 16-byte chunks, a pure copy.  A padded position holds id 0, so it gets table row 0.
-//   LSTM encode     h_t, c_t = LSTM([emb(item_t) | rating_t], h_{t-1}, c_{t-1}) for t = t0 .. t0 + T - 1, torch.nn.LSTM(E + 1, H) weights
-//                   read in place (gate order i, f, g, o).  One workgroup owns 16 users -- one M tile of v_mfma_f32_16x16x4_f32 --
-//                   for all steps of a launch: the chain of a sequence never leaves its workgroup, no workgroup waits on another
-//                   (variant 1 cuts T into a stream-ordered chain of launches, the state passing through h_T / c_T).  Eight waves;
-//                   wave w owns the hidden units of tiles w and w + 8, and for each the four gate tiles, so a lane holds i, f, g, o
-//                   of the same (user, hidden unit) and the cell update is lane-local; c lives in registers, h_{t-1} and x_t in LDS
-//                   (double-buffered: one barrier per step).  A pre-activation is one FIXED-ORDER chain:
-//                     fma(rating, w_ih[:, E], b_ih + b_hh), then the x products, then the h_{t-1} products, 16 columns per block,
-//                     MFMA e of a block taking columns k0 + e, k0 + 4 + e, k0 + 8 + e, k0 + 12 + e (how the instruction sums its
-//                     four products is the hardware's business, and the same every time)
-//                   -- the same order for every row, user and launch, so a user's bits do not depend on its row in the tile, on
-//                   the other users, or on how T is cut into calls.
-//                   The rating column (K = E + 1 = 129) is the rank-1 first link of that chain, on the VALU: no padded GEMM.
-//                   Item rows are gathered through the store one step ahead of their use; [U, T, E] is never materialised.
-//     variant 0     the input projection is fused into the step.
-//     variant 1     the first E + 1 links of every chain are computed by a grid-wide launch per chunk of LSTM_CHUNK steps into a
-//                   workspace in accumulator layout (a few MB: L2 / Infinity Cache resident), and the chain launch of that chunk
-//                   starts from them.  The same chains: bit-identical to variant 0.  W_hh is streamed from L2 every step in
-//                   both (how W_hh is best held is still open).
+//   state encoders  an LSTM (lstm.hip) or a GRU (gru.hip) over whole user histories: the chains of seq_chain.h / seq_bwd.h.
 //   collect         rows of the replay buffer for the kept steps of one user batch: state = h_{t-1}, action = emb(item_t),
 //                   reward = rating_t, next_state = h_t, one launch.
+//   collect backward g_h[u, t] = g_next_state[k U + u] where steps[k] == t, plus g_state[k' U + u] where steps[k'] == t + 1: a
+//                   gather over 16-byte chunks of g_h (flat_walk.h), each chunk summing its two or fewer sources.
 // No atomics, fixed orders: equal calls give equal bits.
 // gather_dev.h is not used here: its body is the sliding-window gather (rows of one user share F of F + 1 lines, packed / bf16 /
 // split destinations, a row plan); a padded batch has no shared lines and one fp32 destination, which is a flat walk over chunks.
-#include "seq_lstm.h"
+#include "seq_chain.h"
 
 namespace {
 
@@ -91,6 +75,35 @@ __global__ __launch_bounds__(256) void seq_collect_kernel(const float* __restric
   });
 }
 
+// ------------------------------------------------------------------------------------------------ collect backward
+__global__ __launch_bounds__(256) void seq_collect_bwd_kernel(const float* __restrict__ g_state, const float* __restrict__ g_next,
+                                                              int U, int T, int H, const int32_t* __restrict__ steps, int n_steps,
+                                                              float* __restrict__ g_h) {
+  const int H4 = H >> 2;
+  flat_walk<1>((int64_t)U * T * H4, [&](int64_t i, Width<1>) {
+    const int64_t cell = i / H4;
+    const int c = (int)(i - cell * H4);
+    const int u = (int)(cell / T), t = (int)(cell - (int64_t)u * T);
+    int lo = 0, hi = n_steps;                            // first k with steps[k] >= t (steps is strictly increasing)
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (steps[mid] < t) lo = mid + 1;
+      else hi = mid;
+    }
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    int k = lo;
+    if (k < n_steps && steps[k] == t) {
+      if (g_next) v = *(const float4*)(g_next + ((int64_t)k * U + u) * H + 4 * c);
+      ++k;
+    }
+    if (k < n_steps && steps[k] == t + 1 && g_state) {
+      const float4 w = *(const float4*)(g_state + ((int64_t)k * U + u) * H + 4 * c);
+      v = make_float4(v.x + w.x, v.y + w.y, v.z + w.z, v.w + w.w);
+    }
+    *(float4*)(g_h + cell * H + 4 * c) = v;
+  });
+}
+
 }  // namespace
 
 extern "C" int recnn_seq_gather(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
@@ -138,33 +151,15 @@ extern "C" int recnn_seq_collect(const float* h, int n_users, int T, int hidden,
   return recnn_check_hip(hipGetLastError(), "seq_collect");
 }
 
-extern "C" int recnn_lstm_workspace_bytes(int n_users, int T, int hidden, int variant, int64_t* h_bytes) {
-  RECNN_REQUIRE(h_bytes, "lstm_workspace_bytes: null pointer");
-  RECNN_REQUIRE(n_users >= 0 && T >= 0 && hidden > 0 && hidden % 16 == 0 && hidden <= 256 && (variant == 0 || variant == 1),
-                "lstm_workspace_bytes: need n_users >= 0, T >= 0, hidden a multiple of 16 up to 256, variant 0 or 1");
-  *h_bytes = variant == 1 ? pre_bytes(n_users, T, hidden) : 0;
-  return 0;
-}
-
-extern "C" int recnn_lstm_encode(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
-                                 int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* w_ih,
-                                 const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, const float* c0, float* h_out,
-                                 float* h_T, float* c_T, int variant, void* workspace, void* stream) {
-  RECNN_REQUIRE(store_ok(items, ratings, user_off, slots, table) && w_ih && w_hh && b_ih && b_hh && h_out && h_T && c_T,
-                "lstm_encode: null pointer");
-  RECNN_REQUIRE((h0 == nullptr) == (c0 == nullptr), "lstm_encode: h0 and c0 come together");
-  RECNN_LSTM_DIMS_OK("lstm_encode", emb_dim, hidden);
-  RECNN_REQUIRE(n_users >= 0 && t0 >= 0 && T >= 0 && n_items > 0, "lstm_encode: need n_users, t0, T >= 0 and n_items > 0");
-  RECNN_REQUIRE(variant == 0 || variant == 1, "lstm_encode: variant must be 0 (fused input projection) or 1 (chunked), got %d", variant);
-  RECNN_REQUIRE(variant == 0 || workspace, "lstm_encode: variant 1 needs the workspace of recnn_lstm_workspace_bytes");
-  RECNN_REQUIRE(aligned16(table, w_hh, workspace), "lstm_encode: table, w_hh and workspace must be 16-byte aligned");
-  if (n_users == 0) return 0;
-  EncArgs a{};
-  a.s = SeqStore{items, ratings, user_off, slots, n_users, table, n_items, emb_dim};
-  a.H = hidden;
-  a.w_ih = w_ih; a.w_hh = w_hh; a.b_ih = b_ih; a.b_hh = b_hh;
-  a.h_out = h_out; a.h_T = h_T; a.c_T = c_T;
-  a.pre = (float*)workspace;
-  launch_encode<false>(a, t0, T, h0, c0, variant, (hipStream_t)stream);
-  return recnn_check_hip(hipGetLastError(), "lstm_encode");
+extern "C" int recnn_seq_collect_bwd(const float* g_state, const float* g_next_state, int n_users, int T, int hidden,
+                                     const int32_t* steps, int n_steps, float* g_h, void* stream) {
+  RECNN_REQUIRE(g_h && (steps || n_steps == 0), "seq_collect_bwd: null pointer");
+  RECNN_REQUIRE(n_users >= 0 && T >= 0 && n_steps >= 0, "seq_collect_bwd: negative size");
+  RECNN_REQUIRE(hidden > 0 && hidden % 4 == 0, "seq_collect_bwd: hidden must be a positive multiple of 4 (got %d)", hidden);
+  RECNN_REQUIRE(aligned16(g_state, g_next_state, g_h), "seq_collect_bwd: 16-byte alignment");
+  const int64_t chunks = (int64_t)n_users * T * (hidden / 4);
+  if (chunks == 0) return 0;
+  hipLaunchKernelGGL(seq_collect_bwd_kernel, dim3(grid_for(chunks, 256, 2048)), dim3(256), 0, (hipStream_t)stream, g_state,
+                     g_next_state, n_users, T, hidden, steps, n_steps, g_h);
+  return recnn_check_hip(hipGetLastError(), "seq_collect_bwd");
 }

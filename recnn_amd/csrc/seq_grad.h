@@ -1,10 +1,33 @@
-// seq_grad.h -- what the backward calls of the two state encoders (seq_bwd.hip: LSTM, gru.hip: GRU) share once their reverse chain has
+// seq_grad.h -- what the backward calls of the two state encoders (lstm.hip: LSTM, gru.hip: GRU) share once their reverse chain has
 // written the gate pre-activation gradients da of a chunk: the weight-gradient tiles, the dX contraction, the packed W_ih^T and the
 // deterministic scatter-sum of the table gradient.  Everything here is written over the number of gate rows G (4H for the LSTM, 3H for
-// the GRU) and the row stride lda of da; seq_bwd.hip describes the method.
+// the GRU) and the row stride lda of da; backward_impl of seq_bwd.h launches them.  The method:
+//
+//   weight gradients  per chunk, grid-wide: dW[m, n] = sum over the chunk's (user, step) samples of da[s, m] X[s, n], X = h_{t-1}
+//                     rows (dW_hh) or table rows gathered through the store (dW_ih; [U, T, E] is never materialised).  One
+//                     workgroup owns a 64 x 64 tile of dW and walks ALL samples in order, 16 per LDS stage, on the exact-f32 MFMA:
+//                     no partial sums between workgroups.  The rating column of dW_ih and db are rank-1 / plain sums on the VALU
+//                     of the same stage.  Chunks are added into dW in launch order (last chunk first).  No atomics anywhere.
+//                     Only the rows of real users are walked: the clamped rows of a partly filled tile give nothing.
+//                     (Which panel columns are a dW's rows is the cell's business: its launch_dw.)
+//                     (dw_tile.h / gemm.h are bf16 tiles; the gradients here are exact f32, so they are not reused.)
+//   table gradient   (recnn_*_backward_table only) d_table[item] = sum of dX[u, t, 0:E] over the call's positions (u, t) that hold
+//                     `item`, dX[u, t, n] = sum_m da[u, t, m] W_ih[m, n].  dX: one launch per chunk after its chain launch, a grid
+//                     over tiles of 16 samples (real users only), wave w of a workgroup owning column tiles w and w + 4, on the
+//                     exact-f32 MFMA.  One accumulator per element, from zero; the contraction walks m in blocks of 16 upwards,
+//                     four MFMAs e = 0 .. 3 per block, MFMA e adding the products m = m0 + e, m0 + 4 + e, m0 + 8 + e, m0 + 12 + e.
+//                     W_ih[:, 0:E] (row stride E + 1: 4-byte aligned only) is read from a packed transposed copy [E][NG H] made
+//                     once per call, so the contraction index is contiguous and a lane loads 16 bytes of either operand.  dX is
+//                     written to a [U, T, E] buffer for the WHOLE call -- the one place where [U, T, E] is materialised -- so that
+//                     the scatter's order does not depend on the chunk cut.  The scatter-sum runs once per call over the inverted
+//                     index of scatter_index.h (stable counting sort by item id, per item its contributions in ascending
+//                     j = u T + t; built before the chain starts, it does not depend on da): the sorted entries are cut into
+//                     pieces of 16, a wave sums the run of each item inside its piece in list order from zero, and one wave per
+//                     item adds the piece partials of its list in piece order from zero.  Every row of d_table is written
+//                     (untouched items: exact zeros).  No float atomics.  Ids outside the table are in no list.
 #pragma once
 #include "scatter_index.h"
-#include "seq_lstm.h"
+#include "seq_chain.h"
 
 namespace {
 

@@ -1260,7 +1260,7 @@ def duel_dqn_forward(x, net):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# LSTM state encoder over whole user histories (csrc/seq.hip): what SeqEnv turns a user batch into states with.
+# LSTM state encoder over whole user histories (csrc/lstm.hip over csrc/seq_chain.h): what SeqEnv turns a user batch into states with.
 LSTM_VARIANTS = {"fused": 0, "chunked": 1}
 _lstm_variant = "chunked"
 
@@ -1304,8 +1304,59 @@ def _check_cell(module, cell):
             raise L.RecnnHipError(f"{cell}_encode: {name} must be a contiguous float32 tensor (got {p.dtype})")
 
 
-def _check_lstm(lstm):
-    _check_cell(lstm, "lstm")
+def _encode_call_args(name, cell, module, store, table, slots, T, states, t0):
+    """The checks of `lstm_encode` / `gru_encode`, for the encode entry points: (dev, E, H, U, T, t0, slots, states), `states` the
+    carried tensors as [U, H] each, or None."""
+    _check_cell(module, cell)
+    dev = module.weight_ih_l0.device
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()):
+        raise L.RecnnHipError(f"{name}: table must be a contiguous float32 GPU tensor")
+    E, H = table.shape[1], module.hidden_size
+    if module.input_size != E + 1:
+        raise L.RecnnHipError(f"{name}: input_size={module.input_size} but the table has {E} columns (needs E + 1: the rating)")
+    slots = store.checked_slots(slots, name, dev)
+    U, T, t0 = len(slots), int(T), int(t0)
+    if table.device != dev:
+        raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
+    if T < 1 or t0 < 0:
+        raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
+    if U and int(store.lengths[slots].min()) < t0 + T:
+        raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
+    if states is not None:
+        states = tuple(t.to(dev, torch.float32).reshape(U, H).contiguous() for t in states)
+    return dev, E, H, U, T, t0, slots, states
+
+
+def _train_call_args(name, cell, module, store, table, slots, T, states, t0, train_table):
+    """The prologue of `lstm_encode_train` / `gru_encode_train`: the refusal of a table gradient nobody asked for, then
+    `_encode_call_args`' tuple with (params, live) appended -- the four weights, and whether anything wants a graph."""
+    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
+        raise L.RecnnHipError(f"{name}: table.requires_grad is set, but gradients with respect to the embedding table are "
+                              "computed only on request; pass train_table=True to train it, or table.detach()")
+    *head, states = _encode_call_args(name, cell, module, store, table, slots, T, states, t0)
+    params = (module.weight_ih_l0, module.weight_hh_l0, module.bias_ih_l0, module.bias_hh_l0)
+    live = torch.is_grad_enabled() and (table.requires_grad               # (the table: only with train_table)
+                                        or any(t.requires_grad for t in (*params, *(states or ()))))
+    return (*head, states, params, live)
+
+
+def _store_args(store, slots_d, U, t0, T, table, E, H):
+    """The leading arguments of every encode and backward entry point: the replay store, the step range, the table, the sizes."""
+    return (L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T, L.ptr(table), table.shape[0],
+            E, H)
+
+
+def _encode_buffers(cell, nstate, dev, U, T, E, H, train=False):
+    """What one encode call allocates: (variant, projection workspace, `saved` record, bytes of the backward's workspace, h [U, T, H],
+    a tuple of the `nstate` final states [U, H] each); `saved` is None and the bytes 0 unless `train`."""
+    variant = LSTM_VARIANTS[_lstm_variant]
+    saved, nsaved, nbwd = None, C.c_int64(), C.c_int64()
+    if train:
+        L.call(f"recnn_{cell}_train_workspace_bytes", U, T, H, E, variant, C.byref(nsaved), C.byref(nbwd))
+        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+    ws = L.workspace(f"recnn_{cell}_workspace_bytes", U, T, H, variant, device=dev)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    return variant, ws, saved, nbwd.value, new(U, T, H), tuple(new(U, H) for _ in range(nstate))
 
 
 @torch.no_grad()
@@ -1323,33 +1374,13 @@ def lstm_encode(lstm, store, table, slots, T, h0c0=None, *, t0=0):
     `batch_first` is ignored: the users are always the batch and time always runs along a user's own history.  (The
     reference's commented-out SeqEnv feeds [1, U, E + 1] to its encoder, which a batch_first=True LSTM reads as ONE sequence
     running across the users -- the bug that makes its notebook "not work yet".  It is not reproduced.)"""
-    _check_lstm(lstm)
-    dev = lstm.weight_ih_l0.device
-    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()):
-        raise L.RecnnHipError("lstm_encode: table must be a contiguous float32 GPU tensor")
-    E, H = table.shape[1], lstm.hidden_size
-    if lstm.input_size != E + 1:
-        raise L.RecnnHipError(f"lstm_encode: input_size={lstm.input_size} but the table has {E} columns (needs E + 1: the rating)")
-    slots = store.checked_slots(slots, "lstm_encode", dev)
-    U, T, t0 = len(slots), int(T), int(t0)
-    if table.device != dev:
-        raise ValueError(f"lstm_encode: the table lives on {table.device}, the module on {dev}")
-    if T < 1 or t0 < 0:
-        raise ValueError(f"lstm_encode: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
-    if U and int(store.lengths[slots].min()) < t0 + T:
-        raise ValueError(f"lstm_encode: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
-    h0 = c0 = None
-    if h0c0 is not None:
-        h0, c0 = (t.to(dev, torch.float32).reshape(U, H).contiguous() for t in h0c0)
-    h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
-    hT = torch.empty(U, H, dtype=torch.float32, device=dev)
-    cT = torch.empty(U, H, dtype=torch.float32, device=dev)
-    variant = LSTM_VARIANTS[_lstm_variant]
-    ws = L.workspace("recnn_lstm_workspace_bytes", U, T, H, variant, device=dev)
+    dev, E, H, U, T, t0, slots, hc = _encode_call_args("lstm_encode", "lstm", lstm, store, table, slots, T, h0c0, t0)
+    h0, c0 = hc if hc is not None else (None, None)
+    variant, ws, _, _, h, (hT, cT) = _encode_buffers("lstm", 2, dev, U, T, E, H)
     slots_d = torch.from_numpy(slots).to(dev)
-    L.call("recnn_lstm_encode", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
-           L.ptr(table), table.shape[0], E, H, L.ptr(lstm.weight_ih_l0), L.ptr(lstm.weight_hh_l0), L.ptr(lstm.bias_ih_l0),
-           L.ptr(lstm.bias_hh_l0), L.ptr(h0), L.ptr(c0), L.ptr(h), L.ptr(hT), L.ptr(cT), variant, L.ptr(ws), L.current_stream())
+    L.call("recnn_lstm_encode", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(lstm.weight_ih_l0), L.ptr(lstm.weight_hh_l0),
+           L.ptr(lstm.bias_ih_l0), L.ptr(lstm.bias_hh_l0), L.ptr(h0), L.ptr(c0), L.ptr(h), L.ptr(hT), L.ptr(cT), variant, L.ptr(ws),
+           L.current_stream())
     return h, (hT, cT)
 
 
@@ -1398,36 +1429,7 @@ def seq_collect(h, steps, store, table, slots, views):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# Training the encoder (csrc/seq_bwd.hip): backward through time for the encode chain, a differentiable collect.
-def _encode_call_args(name, cell, module, store, table, slots, T, states, t0):
-    """The checks of `lstm_encode` / `gru_encode`, for the encode entry points: (dev, E, H, U, T, t0, slots, states), `states` the
-    carried tensors as [U, H] each, or None."""
-    _check_cell(module, cell)
-    dev = module.weight_ih_l0.device
-    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()):
-        raise L.RecnnHipError(f"{name}: table must be a contiguous float32 GPU tensor")
-    E, H = table.shape[1], module.hidden_size
-    if module.input_size != E + 1:
-        raise L.RecnnHipError(f"{name}: input_size={module.input_size} but the table has {E} columns (needs E + 1: the rating)")
-    slots = store.checked_slots(slots, name, dev)
-    U, T, t0 = len(slots), int(T), int(t0)
-    if table.device != dev:
-        raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
-    if T < 1 or t0 < 0:
-        raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
-    if U and int(store.lengths[slots].min()) < t0 + T:
-        raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
-    if states is not None:
-        states = tuple(t.to(dev, torch.float32).reshape(U, H).contiguous() for t in states)
-    return dev, E, H, U, T, t0, slots, states
-
-
-def _lstm_call_args(name, lstm, store, table, slots, T, h0c0, t0):
-    """`_encode_call_args` for the LSTM: (dev, E, H, U, T, t0, slots, h0, c0)."""
-    *head, hc = _encode_call_args(name, "lstm", lstm, store, table, slots, T, h0c0, t0)
-    return (*head, *(hc if hc is not None else (None, None)))
-
-
+# Training the encoder (csrc/seq_bwd.h): backward through time for the encode chain, a differentiable collect.
 class LSTMEncodeFunction(torch.autograd.Function):
     """(h, h_T, c_T) of the encode chain with the gates and cell states recorded, and backward through time for them
     (`recnn_lstm_encode_train` / `recnn_lstm_backward`).  Differentiable in the four weights, in h0 / c0 and in the embedding
@@ -1435,20 +1437,11 @@ class LSTMEncodeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w_ih, w_hh, b_ih, b_hh, h0, c0, store, table, slots_d, T, t0):
-        dev = w_ih.device
         U, E, H = slots_d.shape[0], table.shape[1], w_hh.shape[1]
-        variant = LSTM_VARIANTS[_lstm_variant]
-        nsaved, nbwd = C.c_int64(), C.c_int64()
-        L.call("recnn_lstm_train_workspace_bytes", U, T, H, E, variant, C.byref(nsaved), C.byref(nbwd))
-        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
-        ws = L.workspace("recnn_lstm_workspace_bytes", U, T, H, variant, device=dev)
-        h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
-        hT = torch.empty(U, H, dtype=torch.float32, device=dev)
-        cT = torch.empty(U, H, dtype=torch.float32, device=dev)
-        L.call("recnn_lstm_encode_train", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
-               L.ptr(table), table.shape[0], E, H, L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), L.ptr(h0), L.ptr(c0),
-               L.ptr(h), L.ptr(hT), L.ptr(cT), variant, L.ptr(ws), L.ptr(saved), L.current_stream())
-        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
+        variant, ws, saved, nbwd, h, (hT, cT) = _encode_buffers("lstm", 2, w_ih.device, U, T, E, H, train=True)
+        L.call("recnn_lstm_encode_train", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih),
+               L.ptr(b_hh), L.ptr(h0), L.ptr(c0), L.ptr(h), L.ptr(hT), L.ptr(cT), variant, L.ptr(ws), L.ptr(saved), L.current_stream())
+        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd
         ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None and is passed as NULL
         ctx.has_h0 = h0 is not None
         ctx.save_for_backward(w_hh, table, slots_d, saved, h, w_ih, *((h0, c0) if h0 is not None else ()))
@@ -1473,8 +1466,7 @@ class LSTMEncodeFunction(torch.autograd.Function):
         d_c0 = new(U, H) if need[5] else None
         d_table = new(table.shape[0], E) if need[7] else None
         ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
-        head = (L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T, L.ptr(table),
-                table.shape[0], E, H)
+        head = _store_args(store, slots_d, U, t0, T, table, E, H)
         mid = (L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(c0), L.ptr(g_h), L.ptr(g_hT), L.ptr(g_cT), L.ptr(d_w_ih),
                L.ptr(d_w_hh), L.ptr(d_b), L.ptr(d_h0), L.ptr(d_c0))
         if d_table is None:
@@ -1492,7 +1484,7 @@ def lstm_encode_train(lstm, store, table, slots, T, h0c0=None, *, t0=0, train_ta
     they require grad, so truncated BPTT over calls with `t0` moved on works: carry (h_T, c_T) into the next call.
 
     The forward also records the gate activations and cell states (5 U T H floats, U rounded up to 16); the backward is one HIP
-    launch chain backward through time plus the weight-gradient launches per chunk of steps (csrc/seq_bwd.hip), in fixed
+    launch chain backward through time plus the weight-gradient launches per chunk of steps (csrc/seq_bwd.h), in fixed
     summation orders: equal calls give equal gradients bit for bit.  It is once differentiable.
 
     The embedding table: by default a `table` that requires grad is refused with RecnnHipError (pass `table.detach()` to keep the
@@ -1502,18 +1494,12 @@ def lstm_encode_train(lstm, store, table, slots, T, h0c0=None, *, t0=0, train_ta
     rows of items the batch's steps do not hold.  The weight gradients, dh0 and dc0 keep their bits.
 
     Under `torch.no_grad()`, or when nothing requires grad, this IS `lstm_encode`: nothing is recorded."""
-    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
-        raise L.RecnnHipError("lstm_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
-                              "computed only on request; pass train_table=True to train it, or table.detach()")
-    dev, E, H, U, T, t0, slots, h0, c0 = _lstm_call_args("lstm_encode_train", lstm, store, table, slots, T, h0c0, t0)
-    params = (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
-    live = [p for p in params if p.requires_grad] + [t for t in (h0, c0) if t is not None and t.requires_grad]
-    if table.requires_grad:                               # (only with train_table)
-        live.append(table)
-    if not torch.is_grad_enabled() or not live:
-        return lstm_encode(lstm, store, table.detach(), slots, T, None if h0 is None else (h0, c0), t0=t0)
-    slots_d = torch.from_numpy(slots).to(dev)
-    h, hT, cT = LSTMEncodeFunction.apply(*params, h0, c0, store, table, slots_d, T, t0)
+    dev, E, H, U, T, t0, slots, hc, params, live = _train_call_args("lstm_encode_train", "lstm", lstm, store, table, slots, T, h0c0, t0,
+                                                                    train_table)
+    if not live:
+        return lstm_encode(lstm, store, table.detach(), slots, T, hc, t0=t0)
+    h0, c0 = hc if hc is not None else (None, None)
+    h, hT, cT = LSTMEncodeFunction.apply(*params, h0, c0, store, table, torch.from_numpy(slots).to(dev), T, t0)
     return h, (hT, cT)
 
 
@@ -1533,14 +1519,10 @@ def gru_encode(gru, store, table, slots, T, h0=None, *, t0=0):
     dropout != 0, bias=False, a CPU module, a non-contiguous or non-float32 weight, input_size != E + 1.  `batch_first` is ignored."""
     dev, E, H, U, T, t0, slots, h0 = _encode_call_args("gru_encode", "gru", gru, store, table, slots, T, None if h0 is None else (h0,), t0)
     h0 = None if h0 is None else h0[0]
-    h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
-    hT = torch.empty(U, H, dtype=torch.float32, device=dev)
-    variant = LSTM_VARIANTS[_lstm_variant]
-    ws = L.workspace("recnn_gru_workspace_bytes", U, T, H, variant, device=dev)
+    variant, ws, _, _, h, (hT,) = _encode_buffers("gru", 1, dev, U, T, E, H)
     slots_d = torch.from_numpy(slots).to(dev)
-    L.call("recnn_gru_encode", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
-           L.ptr(table), table.shape[0], E, H, L.ptr(gru.weight_ih_l0), L.ptr(gru.weight_hh_l0), L.ptr(gru.bias_ih_l0),
-           L.ptr(gru.bias_hh_l0), L.ptr(h0), L.ptr(h), L.ptr(hT), variant, L.ptr(ws), L.current_stream())
+    L.call("recnn_gru_encode", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(gru.weight_ih_l0), L.ptr(gru.weight_hh_l0),
+           L.ptr(gru.bias_ih_l0), L.ptr(gru.bias_hh_l0), L.ptr(h0), L.ptr(h), L.ptr(hT), variant, L.ptr(ws), L.current_stream())
     return h, hT
 
 
@@ -1551,19 +1533,11 @@ class GRUEncodeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w_ih, w_hh, b_ih, b_hh, h0, store, table, slots_d, T, t0):
-        dev = w_ih.device
         U, E, H = slots_d.shape[0], table.shape[1], w_hh.shape[1]
-        variant = LSTM_VARIANTS[_lstm_variant]
-        nsaved, nbwd = C.c_int64(), C.c_int64()
-        L.call("recnn_gru_train_workspace_bytes", U, T, H, E, variant, C.byref(nsaved), C.byref(nbwd))
-        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
-        ws = L.workspace("recnn_gru_workspace_bytes", U, T, H, variant, device=dev)
-        h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
-        hT = torch.empty(U, H, dtype=torch.float32, device=dev)
-        L.call("recnn_gru_encode_train", L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T,
-               L.ptr(table), table.shape[0], E, H, L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), L.ptr(h0), L.ptr(h), L.ptr(hT),
-               variant, L.ptr(ws), L.ptr(saved), L.current_stream())
-        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
+        variant, ws, saved, nbwd, h, (hT,) = _encode_buffers("gru", 1, w_ih.device, U, T, E, H, train=True)
+        L.call("recnn_gru_encode_train", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih),
+               L.ptr(b_hh), L.ptr(h0), L.ptr(h), L.ptr(hT), variant, L.ptr(ws), L.ptr(saved), L.current_stream())
+        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd
         ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None and is passed as NULL
         ctx.has_h0 = h0 is not None
         ctx.save_for_backward(w_hh, table, slots_d, saved, h, w_ih, *((h0,) if h0 is not None else ()))
@@ -1588,8 +1562,7 @@ class GRUEncodeFunction(torch.autograd.Function):
         d_h0 = new(U, H) if need[4] else None
         d_table = new(table.shape[0], E) if need[6] else None
         ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
-        head = (L.ptr(store.items), L.ptr(store.ratings), L.ptr(store.user_off), L.ptr(slots_d), U, t0, T, L.ptr(table),
-                table.shape[0], E, H)
+        head = _store_args(store, slots_d, U, t0, T, table, E, H)
         mid = (L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(g_h), L.ptr(g_hT), L.ptr(d_w_ih), L.ptr(d_w_hh), L.ptr(d_b_ih),
                L.ptr(d_b_hh), L.ptr(d_h0))
         if d_table is None:
@@ -1615,20 +1588,12 @@ def gru_encode_train(gru, store, table, slots, T, h0=None, *, t0=0, train_table=
     steps do not hold -- also with every encoder parameter frozen.  The weight gradients and dh0 keep their bits.
 
     Under `torch.no_grad()`, or when nothing requires grad, this IS `gru_encode`: nothing is recorded."""
-    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
-        raise L.RecnnHipError("gru_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
-                              "computed only on request; pass train_table=True to train it, or table.detach()")
-    dev, E, H, U, T, t0, slots, h0 = _encode_call_args("gru_encode_train", "gru", gru, store, table, slots, T,
-                                                       None if h0 is None else (h0,), t0)
+    dev, E, H, U, T, t0, slots, h0, params, live = _train_call_args("gru_encode_train", "gru", gru, store, table, slots, T,
+                                                                    None if h0 is None else (h0,), t0, train_table)
     h0 = None if h0 is None else h0[0]
-    params = (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)
-    live = [p for p in params if p.requires_grad] + [t for t in (h0,) if t is not None and t.requires_grad]
-    if table.requires_grad:                               # (only with train_table)
-        live.append(table)
-    if not torch.is_grad_enabled() or not live:
+    if not live:
         return gru_encode(gru, store, table.detach(), slots, T, h0, t0=t0)
-    slots_d = torch.from_numpy(slots).to(dev)
-    return GRUEncodeFunction.apply(*params, h0, store, table, slots_d, T, t0)
+    return GRUEncodeFunction.apply(*params, h0, store, table, torch.from_numpy(slots).to(dev), T, t0)
 
 
 def state_encode(encoder, store, table, slots, T, *, train=False, train_table=False):

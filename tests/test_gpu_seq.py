@@ -1,4 +1,4 @@
-"""Dynamic-length path on the GPU (csrc/seq.hip): padded gathers, the LSTM encode against torch.nn.LSTM in float64 on the CPU, and
+"""Dynamic-length path on the GPU (csrc/seq.hip, csrc/lstm.hip): padded gathers, the LSTM encode against torch.nn.LSTM in float64 on the CPU, and
 SeqEnv end to end against the same loop over that reference (tests/seq_reference.py).
 
 The encode bound comes from the reference alone: 4 x max |LSTM_fp32_cpu - LSTM_fp64_cpu| on the same inputs, floored at 1e-6

@@ -1,4 +1,4 @@
-"""Training the LSTM state encoder on the GPU (csrc/seq_bwd.hip): the training forward against `lstm_encode` bit for bit, the
+"""Training the LSTM state encoder on the GPU (csrc/lstm.hip, csrc/seq_bwd.h): the training forward against `lstm_encode` bit for bit, the
 gradients of `lstm_encode_train` against torch.nn.LSTM under autograd in float64 on the CPU (tests/seq_grad_reference.py), the
 differentiable collect, `SeqEnv.user_batch`, and one small problem on which the encoder must actually learn.
 

@@ -1,4 +1,4 @@
-"""The LSTM encode, its backward through time and the weight-gradient launches (csrc/seq_lstm.h, csrc/seq.hip, csrc/seq_bwd.hip) at the
+"""The LSTM encode, its backward through time and the weight-gradient launches (csrc/lstm.hip, csrc/seq_chain.h, csrc/seq_bwd.h, csrc/seq_grad.h) at the
 shapes BETWEEN the two ends tests/test_gpu_seq.py and tests/test_gpu_seq_grad.py run at: every instantiation and masking path the
 kernels take as (E, H), U and T move through their tiles.
 

@@ -1,4 +1,4 @@
-"""Training the item embeddings through the LSTM state encoder on the GPU (csrc/seq_bwd.hip): the table gradient of
+"""Training the item embeddings through the LSTM state encoder on the GPU (csrc/seq_bwd.h, csrc/seq_grad.h): the table gradient of
 `lstm_encode_train(..., train_table=True)` against torch.nn.LSTM under autograd in float64 on the CPU over cat([table[idx], rating])
 (tests/seq_table_grad_reference.py), what must stay bit-equal, the carry across calls, `SeqEnv.user_batch(..., table=P)`, one
 `ddpg_update` with P in the policy optimizer, and one small problem on which encoder AND table must actually learn.

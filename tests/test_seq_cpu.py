@@ -1,5 +1,5 @@
 """Dynamic-length path, host side (no GPU): padder, ReplayBuffer, the recnn shim, the no-fallback refusals and the error paths of
-the C ABI of csrc/seq.hip (which return before any launch)."""
+the C ABI of csrc/seq.hip and csrc/lstm.hip (which return before any launch)."""
 import ctypes as C
 
 import numpy as np
@@ -100,7 +100,7 @@ def test_seq_abi_error_paths_launch_nothing():
 
 
 def test_encode_workspace_at_the_in_between_shapes():
-    """The projection workspace against the layout seq_lstm.h documents for `pre`, written out: [user tile][min(T, 32) steps][H / 16
+    """The projection workspace against the layout seq_chain.h documents for `pre`, written out: [user tile][min(T, 32) steps][H / 16
     hidden tiles][4 gates][64 lanes] 16-byte vectors.  An undersized workspace would be an out-of-bounds write on the GPU."""
     from recnn_amd import _lib as L
     lib = L.load()
@@ -111,7 +111,7 @@ def test_encode_workspace_at_the_in_between_shapes():
             assert lib.recnn_lstm_workspace_bytes(U, T, H, 1, C.byref(n)) == 0
             assert n.value == tiles * min(T, 32) * (H // 16) * 4 * 64 * 16, (U, T, H, n.value)
             assert lib.recnn_lstm_workspace_bytes(U, T, H, 0, C.byref(n)) == 0 and n.value == 0
-    for H in (8, 24, 272):                     # (this query takes no embedding width: seq_bwd.hip's, which does, refuses E by name too)
+    for H in (8, 24, 272):                     # (this query takes no embedding width: the training query's, which does, refuses E by name too)
         assert lib.recnn_lstm_workspace_bytes(33, 70, H, 1, C.byref(n)) != 0
         assert b"lstm_workspace_bytes" in lib.recnn_last_error() and b"hidden" in lib.recnn_last_error()
 

@@ -1,5 +1,5 @@
 """Training the LSTM state encoder, host side (no GPU): the no-fallback refusals of the new entry points, the host-only
-workspace query of csrc/seq_bwd.hip, and the reference helper's float64 autograd gradients against a hand-written BPTT of the
+workspace query of csrc/lstm.hip, and the reference helper's float64 autograd gradients against a hand-written BPTT of the
 equations the reverse-chain kernel is written from."""
 import ctypes as C
 
@@ -57,7 +57,7 @@ def test_train_workspace_query_is_host_only_and_validates():
 
 
 def test_train_workspaces_at_the_in_between_shapes():
-    """Both training workspaces against the layouts seq_lstm.h (`saved`) and seq_bwd.hip (`bwd_ws`) document, written out, at the
+    """Both training workspaces against the layouts seq_chain.h (`saved`) and seq_bwd.h (`bwd_ws`) document, written out, at the
     shapes tests/test_gpu_seq_shapes.py launches.  An undersized workspace would be an out-of-bounds write on the GPU.
       saved     [user tile][T][H / 16][i, f, g, o, c][64 lanes] 16-byte vectors
       backward  W_hh^T (H x 4H floats), dh and dc (U x H floats each, rounded up to 16 bytes), one chunk of da

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""LSTM state encoder over whole user histories (csrc/seq.hip): `recnn_amd.nn.functional.lstm_encode` against `torch.nn.LSTM`
+"""LSTM state encoder over whole user histories (csrc/lstm.hip, csrc/seq_chain.h): `recnn_amd.nn.functional.lstm_encode` against `torch.nn.LSTM`
 on the same GPU, at the reference SeqEnv's defaults (U = 25 users, H = 256, E = 128, T = 1000 steps) and at U = 256.
   hip_fused_ms / hip_chunked_ms   one lstm_encode call (every launch of it), input projection fused into the step / projected per
                                   chunk of steps by a grid-wide launch; both gather the item rows through the replay store
@@ -8,7 +8,7 @@ on the same GPU, at the reference SeqEnv's defaults (U = 25 users, H = 256, E = 
 Device-event times around the whole Python call, median of `--repeats` calls after one warm-up call: the HIP figures include the call's
 host work (a pageable upload of the slots, the workspace and the three output allocations), microseconds against tens of milliseconds.
 Also reports max |hip - torch| over h.  Prints one JSON line.
-  --backward   training instead (csrc/seq_bwd.hip): `lstm_encode_train` forward + backward of the loss h.sum() (every
+  --backward   training instead (csrc/seq_bwd.h): `lstm_encode_train` forward + backward of the loss h.sum() (every
                step live) against torch.nn.LSTM forward + backward of the same loss, the training forward alone against the inference
                encode, and max |hip - torch| relative to max |torch| per weight gradient.  Same shapes, same timing method.
   --backward --table-grad   the embedding table trained as well: `lstm_encode_train(..., train_table=True)` forward +

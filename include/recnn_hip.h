@@ -648,7 +648,10 @@ typedef struct recnn_engine_tuning {
   int frozen_acts_policy_only;  /* 1 (default): the cycle-batched actor launch (csrc/mlpf.hip) stores its hidden activations only for the
                                batch that reads them -- the policy step's, a segment's last -- and for none in a segment without a policy
                                step; 0: for every batch of the segment.  Bit-identical */
-  int reserved[1];
+  int gather_cycle;         /* 1 (default): the cycle gather without next rows (frozen_window) runs 32 consecutive plan rows per workgroup,
+                               loads every embedding line of a user's run once and writes 16 bytes per store (csrc/gather.hip) where the
+                               rows' alignment allows; 0: the generic gather body, four rows per workgroup.  Took the last reserved slot:
+                               the struct's size is unchanged.  Bit-identical */
 } recnn_engine_tuning;
 void recnn_engine_tuning_init(recnn_engine_tuning* h_t);
 int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* h_t);
@@ -670,7 +673,9 @@ int recnn_engine_unit_backward(recnn_engine* e);
  * ("next_action", "expected", "q1", "gen_action", ...).  Returns NULL if unknown.  Cycle mode's arrays (MSET_MAX x max_rows rows each):
  * "cycle_gen_action", "cycle_actor_h1" / "cycle_actor_h2" (the actor's hidden activations: with tuning.frozen_acts_policy_only only the
  * policy step's batch of a batched segment is written), "cycle_target_q1" / "2", "cycle_next_action0" / "1" (the target actor's output of window mode, per copy) and
- * "cycle_xn0" / "1" (the packed next rows whose action slot holds it otherwise: the engine's own allocation, NULL while it has none). */
+ * "cycle_xn0" / "1" (the packed next rows whose action slot holds it otherwise: the engine's own allocation, NULL while it has none);
+ * what the cycle gather writes, per copy: "cycle_xs0" / "1" (packed [action | state] rows), "cycle_tail_n0" / "1" (window mode's next
+ * ratings; NULL where the dims do not allow that mode), "cycle_reward0" / "1", "cycle_done0" / "1". */
 const void* recnn_engine_buffer(recnn_engine* e, const char* name, int64_t* h_rows, int64_t* h_cols,
                                 int64_t* h_ld, int* h_is_f32);
 

@@ -104,7 +104,7 @@ class Sampler(C.Structure):
 TUNING_FIELDS = ("fused_mlp", "chain_target_critic", "bwd_panel", "policy_chain", "split_fwd", "cycle_min_len", "cycle_min_seg",
                  "frozen_fused", "frozen_gemm", "graph_run", "pregather", "defer_policy_fwd", "sampler_f32_rows", "dw_splits", "comm_fused",
                  "l1_big", "gemm_variant", "gemm_v0_threshold", "gemm_dma", "gemm_dma_depth", "gemm_dma_waves", "gemm_waves", "dw_dma", "x3_tail", "x3_fwd", "dw_fuse", "tail_half", "l1_ws", "frozen_half",
-                 "frozen_window", "run_align", "frozen_acts_policy_only")
+                 "frozen_window", "run_align", "frozen_acts_policy_only", "gather_cycle")
 
 
 RUN_MAX = 64
@@ -119,7 +119,7 @@ class RunFamily(C.Structure):
 
 class EngineTuning(C.Structure):
     """include/recnn_hip.h recnn_engine_tuning: schedule / tile choices of ONE engine (all compute the same numbers)."""
-    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS] + [("reserved", C.c_int * 1)]
+    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS]
 
 
 _P = C.c_void_p
@@ -306,8 +306,21 @@ class FrozenDebugArgs(C.Structure):
                 ("q", C.c_void_p), ("panel_rows", C.c_int)]
 
 
+class GatherCycleDebugArgs(C.Structure):
+    """recnn_amd/csrc/recnn_hip_debug.h recnn_debug_gather_cycle_args: the cycle gather on caller-supplied device buffers."""
+    _fields_ = [("items", C.c_void_p), ("ratings", C.c_void_p), ("table", C.c_void_p),
+                ("plan", C.c_void_p), ("plan_stride", C.c_int64),
+                ("cursor", C.c_void_p), ("cursor_add", C.c_int), ("cursor_mod", C.c_int),
+                ("rows", C.c_int), ("frame", C.c_int), ("emb", C.c_int), ("n_sets", C.c_int),
+                ("state_h", C.c_void_p), ("action_h", C.c_void_p), ("next_h", C.c_void_p), ("ld_h", C.c_int64),
+                ("tail_n", C.c_void_p), ("ld_tail", C.c_int64),
+                ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("gather_cycle", C.c_int)]
+
+
 # private debug / test hooks (recnn_amd/csrc/recnn_hip_debug.h): exported, but not part of the public header
 DEBUG_SIGNATURES = {
+    "recnn_debug_gather_cycle": (_I, [C.POINTER(GatherCycleDebugArgs), _L, _P]),
     "recnn_debug_frozen_forward": (_I, [C.POINTER(FrozenDebugArgs), _L, _P]),
     "recnn_debug_mlp_fault": (None, [_I]),
     "recnn_debug_mlp_probe": (None, [_I]),

@@ -573,6 +573,11 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
       {"cycle_target_q1", e->m_tq[0], 1, 1, 1},                    {"cycle_target_q2", e->m_tq[1], 1, 1, 1},
       {"cycle_gen_action", e->m_ga, e->A, e->Ap, 0},
       {"cycle_actor_h1", e->m_pa_h1, e->H, Hp, 0},                 {"cycle_actor_h2", e->m_pa_h2, e->H, Hp, 0},
+      // what the cycle gather writes, per copy: the packed [action | state] rows, the next ratings of window mode, reward, done
+      {"cycle_xs0", e->m_xs_b[0], e->ldx, e->ldx, 0},              {"cycle_xs1", e->m_xs_b[1], e->ldx, e->ldx, 0},
+      {"cycle_tail_n0", e->m_tail_n_b[0], e->win_tail, e->win_tail, 0}, {"cycle_tail_n1", e->m_tail_n_b[1], e->win_tail, e->win_tail, 0},
+      {"cycle_reward0", e->m_reward_b[0], 1, 1, 1},                {"cycle_reward1", e->m_reward_b[1], 1, 1, 1},
+      {"cycle_done0", e->m_done_b[0], 1, 1, 1},                    {"cycle_done1", e->m_done_b[1], 1, 1, 1},
   };
   for (const Ent& t : cyc)
     if (!strcmp(t.n, name)) {

@@ -275,6 +275,7 @@ extern "C" void recnn_engine_tuning_init(recnn_engine_tuning* t) {
   t->gemm_waves = 8; t->dw_dma = 2; t->x3_tail = 1; t->x3_fwd = 2; t->dw_fuse = 1; t->tail_half = 1; t->l1_ws = 1; t->frozen_half = 1;
   t->frozen_window = 1;
   t->run_align = 1; t->frozen_acts_policy_only = 1;
+  t->gather_cycle = 1;
 }
 extern "C" int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* t) {
   RECNN_REQUIRE(e && t, "set_tuning: null pointer");
@@ -1549,7 +1550,7 @@ int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipSt
   else if (!batched) { RECNN_REQUIRE(n <= recnn_engine::SHORT_SETS, "cycle gather: %d batches of a short segment", n); g.next_h = (bf16_t*)e->m_xn_short + e->A; }
   else { g.next_h = nullptr; g.tail_n = (bf16_t*)e->m_tail_n_b[b]; g.ld_tail = e->win_tail; }
   g.reward = e->m_reward_b[b]; g.done = e->m_done_b[b];
-  return slot(e, "frame_gather_cycle", 0, s, [&] { return frame_gather_multi_launch(g, n, s); });
+  return slot(e, "frame_gather_cycle", 0, s, [&] { return frame_gather_multi_launch(g, n, s, e->tune.gather_cycle); });
 }
 
 int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s, bool ends_on_policy) {

@@ -37,6 +37,8 @@ struct GatherArgs {
 
 
 int frame_gather_launch(GatherArgs a, hipStream_t s);
-// batches cursor_add .. cursor_add + n_sets - 1 of the plan; batch j lands j * a.rows rows below the given outputs (bf16 rows only)
-int frame_gather_multi_launch(const GatherArgs& a, int n_sets, hipStream_t s);
+// batches cursor_add .. cursor_add + n_sets - 1 of the plan; batch j lands j * a.rows rows below the given outputs (bf16 rows only).
+// cycle_body (recnn_engine_tuning::gather_cycle) != 0: the form without next rows runs the long-run body (gather.hip) where its
+// alignment checks hold; 0, or anything that body does not cover: the generic body, four rows per workgroup.  The same bytes.
+int frame_gather_multi_launch(const GatherArgs& a, int n_sets, hipStream_t s, int cycle_body);
 size_t frame_gather_lds_bytes(const GatherArgs& a, int rows_per_wg);

@@ -13,6 +13,7 @@
 // loads, (R+F)..R*(F+1) lines of E floats per workgroup) by the threads that own it and stored straight
 // to every output that uses it with the widest store the output alignment allows (gather_dev.h).
 #include "gather_dev.h"
+#include "recnn_hip_debug.h"
 
 // ------------------------------------------------------------------ plan: row prefix sums
 __global__ __launch_bounds__(1024) void frame_plan_kernel(const int64_t* __restrict__ user_off,
@@ -215,7 +216,174 @@ __global__ __launch_bounds__(256) void frame_gather_multi_kernel(const GatherArg
   frame_gather_body<4, 4>(a, blockIdx.x, smem_raw);
 }
 
-int frame_gather_multi_launch(const GatherArgs& a, int n_sets, hipStream_t s) {
+// ------------------------------------------------------------------ cycle gather: long row runs per workgroup
+// The body of the cycle launch in the form the engine's window mode runs (bf16 rows from the epoch plan, no next rows: state rows,
+// action rows, the next ratings r1..rF into tail_n; gather.h).  R consecutive plan rows of one batch per workgroup: a user's run of
+// n windows owns n + F distinct embedding lines, so a long run reads each line ONCE per workgroup (R = 4: 3.5 lines per row,
+// R = 32: 1.3) and stores it to every (row, slot) of the run that holds it -- up to F state slots and the action row.  Wave 0 reads
+// the R plan entries and lists the distinct lines in LDS (CSR offset of the item; first row, first slot, rows of the run that follow);
+// after ONE barrier every thread takes 8 fp32 of a line, rounds them as the generic body does (pack_bf2) and writes 16 bytes per
+// destination; the last wave writes each row's ratings, reward and done from one lane.
+// Measured on the ten-batch launch (profiles/NOTES_gather_cycle.md): R = 8 / 16 / 32 with 16-byte stores 18.4 / 15.4 / 14.3 us, with
+// 8-byte stores 18.1 / 15.5 / 17.4, the generic body 26.3 -- 32 rows and 16-byte stores stayed, the rest is gone.
+constexpr int GC_MAXF1 = 16;                     // frame + 1 <= 16: a row's ratings live in one lane's registers
+constexpr int GC_ROWS = 32;                      // rows per workgroup
+constexpr int GC_CHUNK = 8;                      // floats per chunk of a line: one 16-byte bf16 store per destination
+
+// n bf16 roundings of v[OFF ..] to d, by the widest stores d's alignment allows (the same bits as n f2bf stores)
+template <int OFF>
+__device__ __forceinline__ void store_bf_run(bf16_t* d, const float (&v)[GC_MAXF1 + 4], const int n) {
+  const uintptr_t al = (uintptr_t)d;
+#pragma unroll
+  for (int k = 0; k < GC_MAXF1; k += 4) {
+    if (!(al & 7) && k + 4 <= n) {
+      *(uint2*)(d + k) = make_uint2(pack_bf2(v[OFF + k], v[OFF + k + 1]), pack_bf2(v[OFF + k + 2], v[OFF + k + 3]));
+    } else {
+#pragma unroll
+      for (int h = k; h < k + 4; h += 2) {
+        if (!(al & 3) && h + 2 <= n) {
+          *(uint32_t*)(d + h) = pack_bf2(v[OFF + h], v[OFF + h + 1]);
+        } else {
+          if (h < n) d[h] = f2bf(v[OFF + h]);
+          if (h + 1 < n) d[h + 1] = f2bf(v[OFF + h + 1]);
+        }
+      }
+    }
+  }
+}
+
+static size_t gather_runs_lds_bytes(const GatherArgs& a, int R) {
+  return (size_t)R * 8 + (size_t)R * (a.frame + 1) * (8 + 4) + 16;     // worst case: every row a user's only window
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void frame_gather_multi_kernel_runs(const GatherArgs a) {
+  static_assert(R <= 32, "wave 0 lists the lines with one row per lane and room to shift; the row index takes 8 bits of the line word");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int F = a.frame, E = a.emb, F1 = F + 1;
+  long long* s_plan = (long long*)smem_raw;      // [R] the rows' plan entries
+  long long* s_off = s_plan + R;                 // [R * F1] per distinct line: CSR offset of its item
+  int* s_meta = (int*)(s_off + R * F1);          // [R * F1] first row | first slot << 8 | rows of the run after it << 16
+  int* s_total = s_meta + R * F1;                // distinct lines of the workgroup
+  const int tid = threadIdx.x, set = blockIdx.y, row0 = blockIdx.x * R;
+
+  if (tid < 64) {
+    int cur = 0;
+    if (a.cursor) {
+      cur = *a.cursor + a.cursor_add + set;
+      if (a.cursor_mod > 0 && cur >= a.cursor_mod) cur -= a.cursor_mod;
+    }
+    const int r = tid;
+    long long p = -1;
+    if (r < R && row0 + r < a.rows) p = a.plan[(int64_t)cur * a.plan_stride + row0 + r];
+    const bool valid = p >= 0;
+    const long long src = p >> 1;
+    // a run: consecutive windows of one user -- the previous row is valid, not the user's last, and one item earlier
+    const long long psrc = __shfl_up(src, 1, 64);
+    const int pgo = __shfl_up(valid && !(p & 1) ? 1 : 0, 1, 64);
+    const bool cont = r > 0 && valid && pgo && src == psrc + 1;
+    const int cnt = valid ? (cont ? 1 : F1) : 0;
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(incl, o, 64);
+      if (r >= o) incl += t;
+    }
+    const int base = incl - cnt;
+    const unsigned long long cm = __ballot(cont);
+    const int follow = __builtin_ctzll(~((cm >> r) >> 1));       // rows after r that continue its run (rows >= R never do)
+    if (r < R) {
+      s_plan[r] = p;
+      for (int i = 0; i < cnt; ++i) {
+        const int j = cont ? F : i;
+        s_off[base + i] = src + j;
+        s_meta[base + i] = r | (j << 8) | (follow << 16);
+      }
+    }
+    if (r == 63) *s_total = incl;
+  }
+  __syncthreads();
+
+  const int64_t out0 = (int64_t)set * a.rows + row0;           // batch `set` lands set * rows rows below the given outputs
+  const int FE = F * E;
+  if (tid >= 192 && tid - 192 < R) {
+    const int r = tid - 192;
+    const long long p = s_plan[r];
+    if (p >= 0) {
+      const long long src = p >> 1;
+      const int64_t row = out0 + r;
+      float rt[GC_MAXF1 + 4];
+#pragma unroll
+      for (int k = 0; k < GC_MAXF1 + 4; ++k) rt[k] = k < F1 ? a.ratings[src + k] : 0.f;
+      float rew = 0.f;
+#pragma unroll
+      for (int k = 1; k < GC_MAXF1; ++k) rew = k == F ? rt[k] : rew;
+      a.reward[row] = rew;
+      a.done[row] = (p & 1) ? 1.f : 0.f;
+      store_bf_run<0>(a.state_h + row * a.ld_h + FE, rt, F);
+      store_bf_run<1>(a.tail_n + row * a.ld_tail, rt, F);
+    }
+  }
+
+  // ---- embedding lines: chunk c (GC_CHUNK floats) of line l; U chunks per thread in flight (ids, then lines, then stores)
+  constexpr int U = 4;
+  const int total = *s_total;
+  const int EC = E / GC_CHUNK, dl = 256 / EC, dc = 256 - dl * EC;
+  int l = tid / EC, c = tid - l * EC;
+  bf16_t* const st = a.state_h + out0 * a.ld_h;
+  bf16_t* const ac = a.action_h + out0 * a.ld_h;
+  const int64_t back = a.ld_h - E;                              // one row down, one slot back
+  while (l < total) {
+    int m[U], ee[U], item[U];
+    float4 v[U], w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      m[u] = -1;
+      if (l < total) {
+        m[u] = s_meta[l];
+        ee[u] = c * GC_CHUNK;
+        item[u] = a.items[s_off[l]];
+      }
+      l += dl; c += dc;
+      if (c >= EC) { c -= EC; ++l; }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (m[u] >= 0) {
+        const float* t = a.table + (int64_t)item[u] * E + ee[u];
+        v[u] = *(const float4*)t;
+        w[u] = *(const float4*)(t + 4);
+      }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (m[u] < 0) continue;
+      const int r = m[u] & 255, j = (m[u] >> 8) & 255, follow = m[u] >> 16;
+      const int n = min(follow, j) + 1;                          // row r + k holds the line in slot j - k
+      const uint4 h = make_uint4(pack_bf2(v[u].x, v[u].y), pack_bf2(v[u].z, v[u].w), pack_bf2(w[u].x, w[u].y), pack_bf2(w[u].z, w[u].w));
+      int k = 0;
+      if (j == F) {                                              // the row's action; the rows after it hold it as state
+        *(uint4*)(ac + r * a.ld_h + ee[u]) = h;
+        k = 1;
+      }
+      bf16_t* d = st + (r + k) * a.ld_h + (j - k) * E + ee[u];
+      for (; k < n; ++k, d += back) *(uint4*)d = h;
+    }
+  }
+}
+
+// what frame_gather_multi_kernel_runs covers (everything else: the generic body, frame_gather_multi_kernel)
+static bool gather_runs_ok(const GatherArgs& a, int R) {
+  const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  return a.plan && a.state_h && a.action_h && !a.state && !a.x3 && !a.next_h && a.tail_n && a.frame + 1 <= GC_MAXF1 && a.emb % GC_CHUNK == 0 &&
+         al16(a.state_h) && al16(a.action_h) && (a.ld_h * 2) % 16 == 0 && gather_runs_lds_bytes(a, R) <= 48 * 1024;
+}
+
+template <int R> static int launch_gather_runs(const GatherArgs& a, int n_sets, hipStream_t s) {
+  hipLaunchKernelGGL((frame_gather_multi_kernel_runs<R>), dim3((a.rows + R - 1) / R, n_sets), dim3(256), gather_runs_lds_bytes(a, R), s, a);
+  return recnn_check_hip(hipGetLastError(), "frame_gather_multi (runs)");
+}
+
+int frame_gather_multi_launch(const GatherArgs& a, int n_sets, hipStream_t s, int cycle_body) {
   const size_t lds = frame_gather_lds_bytes(a, 4);
   if (lds > 48 * 1024 || !a.state_h || a.state || (a.emb % 4) || a.rows <= 0 || n_sets <= 0 || n_sets > 65535) {
     recnn_set_error("frame_gather_multi: needs the bf16-only gather with a tile that fits 48 KB of LDS");
@@ -225,8 +393,28 @@ int frame_gather_multi_launch(const GatherArgs& a, int n_sets, hipStream_t s) {
     recnn_set_error("frame_gather_multi: without next rows the next ratings need a bf16 array of at least `frame` columns");
     return RECNN_E_INVALID;
   }
+  if (cycle_body && gather_runs_ok(a, GC_ROWS)) return launch_gather_runs<GC_ROWS>(a, n_sets, s);
   hipLaunchKernelGGL(frame_gather_multi_kernel, dim3((a.rows + 3) / 4, n_sets), dim3(256), lds, s, a);
   return recnn_check_hip(hipGetLastError(), "frame_gather_multi");
+}
+
+// The cycle gather on caller-supplied device buffers (csrc/recnn_hip_debug.h): shapes and alignments out of the engine's reach.
+extern "C" int recnn_debug_gather_cycle(const recnn_debug_gather_cycle_args* d, int64_t sizeof_args, void* stream) {
+  RECNN_REQUIRE(d && sizeof_args == (int64_t)sizeof(*d), "debug_gather_cycle: null pointer or another layout of the argument block");
+  RECNN_REQUIRE(d->items && d->ratings && d->table && d->plan && d->state_h && d->action_h && d->reward && d->done, "debug_gather_cycle: null pointer");
+  RECNN_REQUIRE(d->rows > 0 && d->frame > 0 && d->emb > 0 && d->plan_stride >= d->rows, "debug_gather_cycle: bad sizes");
+  RECNN_REQUIRE(((uintptr_t)d->table & 15) == 0 && ((uintptr_t)d->state_h & 7) == 0 && ((uintptr_t)d->action_h & 7) == 0 && (d->ld_h * 2) % 8 == 0 &&
+                (!d->next_h || ((uintptr_t)d->next_h & 7) == 0), "debug_gather_cycle: the table needs 16-byte, the rows 8-byte alignment");
+  GatherArgs a;
+  memset(&a, 0, sizeof(a));
+  a.items = d->items; a.ratings = d->ratings; a.table = d->table;
+  a.plan = d->plan; a.plan_stride = d->plan_stride;
+  a.cursor = d->cursor; a.cursor_add = d->cursor_add; a.cursor_mod = d->cursor_mod;
+  a.rows = d->rows; a.frame = d->frame; a.emb = d->emb;
+  a.state_h = (bf16_t*)d->state_h; a.action_h = (bf16_t*)d->action_h; a.next_h = (bf16_t*)d->next_h; a.ld_h = d->ld_h;
+  a.tail_n = (bf16_t*)d->tail_n; a.ld_tail = d->ld_tail;
+  a.reward = d->reward; a.done = d->done;
+  return frame_gather_multi_launch(a, d->n_sets, (hipStream_t)stream, d->gather_cycle);
 }
 
 size_t frame_gather_lds_bytes(const GatherArgs& a, int R) {

@@ -37,6 +37,23 @@ typedef struct recnn_debug_frozen_args {
   int panel_rows;
 } recnn_debug_frozen_args;
 int recnn_debug_frozen_forward(const recnn_debug_frozen_args* a, int64_t sizeof_args, void* stream);
+/* The cycle gather (csrc/gather.hip frame_gather_multi_launch) on caller-supplied device buffers: shapes the engine never produces (small
+ * embeddings and frames, ragged row counts, plans that end early, rows whose alignment sends the launch to the generic body).  Batch j
+ * (0 .. n_sets - 1) reads plan row (*cursor + cursor_add + j) mod cursor_mod (cursor NULL: row 0 for every j) of plan [.., plan_stride]
+ * and lands j * rows rows below the given outputs: bf16 state_h / action_h (row stride ld_h elements; state = frame * emb embeddings +
+ * frame ratings), fp32 reward / done, and either next_h (bf16, ld_h) or, with next_h NULL, the next ratings into bf16 tail_n [.., ld_tail].
+ * gather_cycle as recnn_engine_tuning::gather_cycle.  sizeof_args = sizeof(recnn_debug_gather_cycle_args) as the caller sees it. */
+typedef struct recnn_debug_gather_cycle_args {
+  const int32_t* items; const float* ratings; const float* table;
+  const int64_t* plan; int64_t plan_stride;
+  const int32_t* cursor; int cursor_add, cursor_mod;
+  int rows, frame, emb, n_sets;
+  void* state_h; void* action_h; void* next_h; int64_t ld_h;
+  void* tail_n; int64_t ld_tail;
+  float* reward; float* done;
+  int gather_cycle;
+} recnn_debug_gather_cycle_args;
+int recnn_debug_gather_cycle(const recnn_debug_gather_cycle_args* a, int64_t sizeof_args, void* stream);
 /* kernel variant of the split-bf16 forward GEMM for the single-problem entry point recnn_gemm_fwd (engines carry their own:
  * recnn_engine_tuning::x3_fwd); -1 = off */
 void recnn_debug_x3_fwd(int variant);

@@ -116,7 +116,11 @@ typedef struct recnn_gemm_args {
   /* contraction segment 0 and optional segment 1 (accumulated into the same tile) */
   const void* A[2];       /* fwd/dx: [M, lda] (k contiguous).  dw: [Kc, lda] (m = row index) */
   const void* B[2];       /* fwd: [N, ldb] (k contiguous).  dx/dw: [Kc, ldb]                 */
-  int64_t lda[2], ldb[2];
+  int64_t lda[2], ldb[2]; /* row pitches in elements of the operand's memory type, 16-byte multiples.  The k-strided operands (B of
+                             dx, A and B of dw) are read in whole 64-column tiles on every one of their Kc rows: dx needs
+                             ldb >= roundup(N, 64), dw lda >= roundup(M, 64) and ldb >= roundup(N, 64) (RECNN_BF16X3: twice that,
+                             the split width of the tiles); the padding columns may hold anything, they only reach outputs that
+                             are never stored.  A smaller pitch is refused with RECNN_E_INVALID before any launch. */
   int K[2];               /* contraction length per segment; K[1] = 0 if unused.  fwd/dx: a multiple of
                              one 16-byte chunk of the compute type (4 fp32 / 8 bf16); multiples of 64 (128 for
                              bf16) take the LDS-DMA kernels.  dw: the number of valid rows (any value). */

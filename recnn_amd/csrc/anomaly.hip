@@ -30,11 +30,16 @@ __host__ __device__ constexpr int lin_in(int l) { return l == 0 ? 128 : l == 1 ?
 __host__ __device__ constexpr int lin_out(int l) { return l == 0 ? 64 : l == 1 ? 32 : l == 2 ? 64 : 128; }
 __host__ __device__ constexpr int w_off(int l) { return l == 0 ? 0 : l == 1 ? 64 * 128 : l == 2 ? 64 * 128 + 32 * 64 : 64 * 128 + 2 * 32 * 64; }
 
-// act layout (floats, N = rows): a0 [N,64] | a1 [N,32] | a2 [N,64] | h0 [N,64] | h1 [N,32] | h2 [N,64] | stats [3][2][64]
+// Row pitch of the matrices recnn_gemm_dw reads (h_l, dz_l): its operands are read in whole 64-column tiles on every row, so a
+// 32-column matrix sits in rows of 64 (include/recnn_hip.h recnn_gemm_args; the padding columns are never written and only
+// reach outputs that are never stored).
+__host__ __device__ constexpr int dw_pitch(int cols) { return cols < 64 ? 64 : cols; }
+
+// act layout (floats, N = rows): a0 [N,64] | a1 [N,32] | a2 [N,64] | h0 [N,64] | h1 [N,32 of pitch 64] | h2 [N,64] | stats [3][2][64]
 __host__ __device__ inline int64_t act_a_off(int l, int64_t n) { return l == 0 ? 0 : l == 1 ? 64 * n : 96 * n; }
-__host__ __device__ inline int64_t act_h_off(int l, int64_t n) { return 160 * n + act_a_off(l, n); }
-__host__ __device__ inline int64_t act_st_off(int64_t n) { return 320 * n; }
-__host__ __device__ inline int64_t act_floats(int64_t n) { return 320 * n + 3 * 2 * 64; }
+__host__ __device__ inline int64_t act_h_off(int l, int64_t n) { return 160 * n + 64 * l * n; }
+__host__ __device__ inline int64_t act_st_off(int64_t n) { return 352 * n; }
+__host__ __device__ inline int64_t act_floats(int64_t n) { return 352 * n + 3 * 2 * 64; }
 
 // workspace layout (floats), P panels, S dW slabs; every region starts on a 64-float boundary
 struct WsLayout {
@@ -53,7 +58,7 @@ __host__ __device__ inline WsLayout ws_layout(int rows) {
   w.dbpart = o; o += r64((int64_t)4 * w.P * MAXC);       // [layer][panel][128]
   w.slabs = o;  o += r64((int64_t)w.S * GW_SLAB);        // [slab][all four dW]
   for (int l = 0; l < 3; ++l) { w.g[l] = o; o += r64(n * lin_out(l)); }    // g_l: gradient w.r.t. h_l
-  for (int l = 0; l < 4; ++l) { w.dz[l] = o; o += r64(n * lin_out(l)); }   // dz_l: gradient w.r.t. Linear l's output
+  for (int l = 0; l < 4; ++l) { w.dz[l] = o; o += r64(n * dw_pitch(lin_out(l))); }   // dz_l: gradient w.r.t. Linear l's output
   w.total = o;
   return w;
 }
@@ -308,7 +313,7 @@ __global__ __launch_bounds__(NT) void ae_fwd_seg_kernel(const recnn_ae_params p,
         v = *(const f32x4*)(act + act_a_off(L - 1, n) + (int64_t)m * K + 4 * c4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = v[j] * ssc[4 * c4 + j] + ssh[4 * c4 + j];
-        if (keep) *(f32x4*)(act + act_h_off(L - 1, n) + (int64_t)m * K + 4 * c4) = v;
+        if (keep) *(f32x4*)(act + act_h_off(L - 1, n) + (int64_t)m * dw_pitch(K) + 4 * c4) = v;
       }
     }
     *(f32x4*)(sin + row * (K + PAD) + 4 * c4) = v;
@@ -465,7 +470,7 @@ __global__ __launch_bounds__(NT) void ae_bwd_seg_kernel(const recnn_ae_params p,
         const float xh = (a - smean[c]) * sinv[c];
         dz = a > 0.f ? sca[c] * (gv - scb[c] - xh * scc[c]) : 0.f;
       }
-      dzg[(int64_t)m * NO + c] = dz;
+      dzg[(int64_t)m * dw_pitch(NO) + c] = dz;
     }
     sdz[row * (NO + PAD) + c] = dz;
   }
@@ -687,9 +692,9 @@ int recnn_ae_backward(const recnn_ae_params* h_p, const recnn_ae_grads* h_g, int
     a.M = lin_out(l);
     a.N = lin_in(l);
     a.A[0] = ws + wl.dz[l];
-    a.lda[0] = lin_out(l);
+    a.lda[0] = dw_pitch(lin_out(l));
     a.B[0] = l == 0 ? (const void*)x : (const void*)(act + act_h_off(l - 1, rows));
-    a.ldb[0] = l == 0 ? ldx : lin_in(l);
+    a.ldb[0] = l == 0 ? ldx : dw_pitch(lin_in(l));
     a.K[0] = rows;
     a.C = ws + wl.slabs + w_off(l);
     a.ldc = lin_in(l);

@@ -1683,6 +1683,18 @@ int gemm_launch(GemmLaunch* L, hipStream_t stream) {
       if (((uintptr_t)g.A | (uintptr_t)g.B) & 15) { recnn_set_error("gemm: operand not 16-byte aligned"); return RECNN_E_INVALID; }
       const int64_t ea = (L->a_f32 || L->dtype == RECNN_F32) ? 4 : 2, eb = (L->b_f32 || L->dtype == RECNN_F32) ? 4 : 2;
       if ((g.lda * ea) % 16 || (g.ldb * eb) % 16) { recnn_set_error("gemm: leading dimension not 16-byte aligned"); return RECNN_E_INVALID; }
+      // k-strided operands (KSLoader, gemm_dw_dma_kernel) are read in whole 16-byte units up to the end of the 64-wide tile,
+      // on every k row: the pitch has to hold the last tile
+      const int64_t wm = (int64_t)(p.M + 63) / 64 * 64, wn = (int64_t)(p.N + 63) / 64 * 64;
+      if (L->mode == GEMM_DX && g.ldb < wn) {
+        recnn_set_error("gemm dx: operand pitch below the tile width (ldb=%lld N=%d, need %lld)", (long long)g.ldb, p.N, (long long)wn);
+        return RECNN_E_INVALID;
+      }
+      if (L->mode == GEMM_DW && (g.lda < wm || g.ldb < wn)) {
+        recnn_set_error("gemm dw: operand pitch below the tile width (lda=%lld M=%d, ldb=%lld N=%d)", (long long)g.lda, p.M,
+                        (long long)g.ldb, p.N);
+        return RECNN_E_INVALID;
+      }
     }
     if (!p.C) { recnn_set_error("gemm: null output"); return RECNN_E_INVALID; }
   }

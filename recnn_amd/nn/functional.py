@@ -1233,7 +1233,8 @@ class DuelDQNFunction(torch.autograd.Function):
         ha, hv = h2[:, :H], h2[:, H:]
         W = la2.weight.detach()
         gW = torch.empty(N, H, device=dev)
-        _dw(dQp, N, ha, H, gW)                       # dQ^T ha: contraction over the batch
+        # dQ^T ha: contraction over the batch; the product reads dQ in whole 64-column tiles along N (recnn_gemm_args: pitch rule)
+        _dw(_pad(dQp, B, _r64(N)), N, ha, H, gW)
         gW -= s * sh[None, :]
         gc = dQp[:, :N].sum(0) - s * B
         Wp = _pad(W, N4, H)

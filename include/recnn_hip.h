@@ -1181,6 +1181,35 @@ int recnn_slate_rerank(const float* table, int n_items, const void* ids, int64_t
 int recnn_slate_ild(const float* table, int n_items, const void* ids, int64_t ld_ids, int n_rows, int n_candidates, int ids_are_int64,
                     int kind, double* out, void* stream);
 
+/* =====================================================================================
+ * 17. Off-policy evaluation of the discrete policies (csrc/logprob.hip, csrc/ope.hip).
+ *    recnn_catalogue_logprob: x float32 [B][K] (row stride ld_x), W [N][K] (row stride ld_w; float32, or bf16 with w_bf16 = 1, x then
+ *      rounded to bf16 on load), c float32 [N], actions int64 [B].  With z[b, n] = x[b] . W[n] + c[n] (exact-fp32 or bf16 MFMA, fp32
+ *      accumulation) it writes lse[b] = log sum_n exp(z[b, n]) and logprob[b] = min(z[b, a_b] - lse[b], 0), float32 [B] each; the
+ *      [B, N] matrix is never stored.  An action outside [0, N) gives NaN in logprob[b]; lse[b] is valid and no other row changes.
+ *      The catalogue is cut into slices of items_per_slice items (a positive multiple of 128), one workgroup column each, merged per
+ *      row in slice order: no atomics, equal calls give equal bits, and a row's bits depend on that row, W, c and items_per_slice
+ *      alone, not on B or the row's position.  K a multiple of 32 (float32) / 64 (bf16), rows 16-byte aligned, ld_x, ld_w >= K.
+ *      x, W and c must be finite: a row whose logits are all -inf, or hold +inf or NaN, gets NaN (no other row is affected).
+ *      workspace: recnn_catalogue_logprob_workspace_bytes(B, N, items_per_slice) bytes, 4-byte aligned (host arithmetic only).
+ *    recnn_ope_accumulate: lp_pi, lp_beta, reward float32 [n]; mask uint8 [n] or NULL (a zero byte skips the row); q_logged, v_dm
+ *      float32 [n], both or both NULL; cap > 0, +inf for none; top_k >= 0, 0 for off.  A masked-out row counts nowhere; an unmasked
+ *      row with a NaN in lp_pi or lp_beta counts in acc_i[1] and nowhere else.  For every other row, in float64,
+ *        w = exp(lp_pi - lp_beta);  top_k >= 1: w *= top_k (1 - exp(lp_pi))^(top_k - 1);  wc = min(w, cap)
+ *      and the call adds to acc_f float64 [8]: sum w, sum w^2, sum w r, sum wc, sum wc r, sum r, sum v_dm + w (r - q_logged), and
+ *      takes the maximum of acc_f[7] and max w; to acc_i int64 [3]: rows counted, invalid rows, rows with w > cap.  The sums have one
+ *      order that depends on n alone (recnn_rank_metrics', section 11); no atomics: equal call sequences give equal bits.
+ *      workspace: recnn_ope_accumulate_workspace_bytes(n) bytes, 8-byte aligned.
+ *    Errors: RECNN_E_INVALID before any HIP call, with a message.  Zero rows launch nothing.
+ * ===================================================================================== */
+int recnn_catalogue_logprob_workspace_bytes(int B, int N, int items_per_slice, int64_t* h_bytes);
+int recnn_catalogue_logprob(const float* x, int64_t ld_x, int B, int K, const void* W, int64_t ld_w, int w_bf16, const float* c, int N,
+                            const int64_t* actions, int items_per_slice, float* logprob, float* lse, void* workspace, void* stream);
+int recnn_ope_accumulate_workspace_bytes(int n, int64_t* h_bytes);
+int recnn_ope_accumulate(const float* lp_pi, const float* lp_beta, const float* reward, const uint8_t* mask, const float* q_logged,
+                         const float* v_dm, int n, double cap, int top_k, double* acc_f, int64_t* acc_i, void* workspace,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,9 +18,9 @@ import sys as _sys
 from . import _lib  # noqa: F401
 from . import data, utils, nn  # noqa: F401
 from .data import pd  # noqa: F401
-from . import optim, parallel  # noqa: F401
+from . import optim, parallel, ope  # noqa: F401
 
-__all__ = ["data", "utils", "nn", "optim", "parallel", "pd", "install_as"]
+__all__ = ["data", "utils", "nn", "optim", "parallel", "ope", "pd", "install_as"]
 
 
 def install_as(name: str = "recnn") -> None:

@@ -880,6 +880,116 @@ def beta_train_forward(state, target, weight, bias):
     return p[:, :N], loss, gw, gb
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# Off-policy evaluation (csrc/logprob.hip): log pi(a | s) of ONE action per row under a softmax over the whole
+# catalogue, the [B, n_items] logits never in memory.
+
+def default_items_per_slice(B, N):
+    """Catalogue slice length of `catalogue_log_prob`: a multiple of the 128-item tile, chosen from (B, N) alone so that the
+    row tiles (128 rows) x slices come to about two workgroups on each of the 256 compute units."""
+    row_tiles = max(1, (B + 127) // 128)
+    tiles = (N + 127) // 128
+    slices = max(1, min(tiles, 512 // row_tiles))
+    return (tiles + slices - 1) // slices * 128
+
+
+def _current_derived(w, kind):
+    """The cached layout `kind` of `w` if one exists and is current (see `_derived_of`), else None."""
+    hit = _derived.get((id(w), kind))
+    if hit is None or hit[0]() is not w or hit[1] != (w._version, w.data_ptr(), tuple(w.shape), _written.get(id(w), 0)):
+        return None
+    return hit[2]
+
+
+def catalogue_log_prob(x, weight, bias, actions, *, dtype=None, items_per_slice=None, _x_padded=False):
+    """(log_prob, lse), float32 [B] each, of the logits z = x weight^T + bias over the catalogue:
+    lse = logsumexp(z, 1), log_prob = min(z[b, actions[b]] - lse[b], 0), not clamped below.  x float32 [B, K], weight [N, K],
+    bias [N] or None, all finite; actions
+    int64 [B]; an action outside [0, N) gives NaN in its row only.  One fused launch plus a per-row merge
+    (recnn_catalogue_logprob): two floats per row and catalogue slice reach memory, never a [B, N] matrix.  `dtype` 'fp32' (exact
+    fp32 MFMA) or 'bf16' (bf16 MFMA over the bf16 shadow of the weight, x rounded on load); None follows `set_catalogue_dtype`.
+    Operands are zero-padded as `DiscretePolicyFunction` / `beta_train_forward` pad theirs, and the padded / bf16 copies of the
+    weight are the ones those keep per weight version.  `items_per_slice` (a multiple of 128) defaults to
+    `default_items_per_slice(B, N)`; with it fixed a row's bits do not depend on the batch around it.  No gradient is recorded."""
+    if not (x.is_cuda and weight.is_cuda):
+        raise L.RecnnHipError("recnn_amd catalogue_log_prob: needs GPU tensors (no CPU fallback)")
+    dtype = _catalogue_dtype if dtype is None else dtype
+    if dtype not in ("fp32", "bf16"):
+        raise ValueError(dtype)
+    if x.dim() != 2 or weight.dim() != 2:
+        raise ValueError(f"catalogue_log_prob: x {tuple(x.shape)} and weight {tuple(weight.shape)} must be matrices")
+    B = x.shape[0]
+    N, K = weight.shape
+    dev = x.device
+    bf16 = dtype == "bf16"
+    Kp = _r128(K) if bf16 else _r64(K)
+    # (_x_padded, discrete_log_prob's hidden layer: x comes [B, Kp] with zero columns past K and is used as it is)
+    if x.shape[1] != (Kp if _x_padded else K):
+        raise ValueError(f"catalogue_log_prob: x {tuple(x.shape)} does not match weight {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise ValueError(f"catalogue_log_prob: bias {tuple(bias.shape)} does not match weight {tuple(weight.shape)}")
+    xp = x.detach()
+    if xp.dtype != torch.float32 or xp.shape[1] != Kp or xp.stride(1) != 1 or xp.stride(0) % 4 or xp.data_ptr() % 16:
+        xp = _pad(xp.float(), B, Kp)
+    if bf16:
+        def shadow(w):
+            t = torch.zeros(_r4(N), Kp, dtype=torch.bfloat16, device=dev)
+            t[:N, :K] = w
+            return t
+        wp = _current_derived(weight, "bf16")       # the policy head's shadow [N, Kp], if DiscretePolicyFunction has made it
+        if wp is None or wp.shape[1] != Kp:
+            wp = _derived_of(weight, "bf16_padded", shadow)
+    elif K != Kp or N != _r4(N) or weight.dtype != torch.float32 or not weight.is_contiguous() or weight.data_ptr() % 16:
+        def padded(w):
+            p = _pad(w.detach(), _r4(N), Kp)
+            return p.clone() if p.data_ptr() % 16 else p      # (an aligned shape at an unaligned offset: a view into a larger tensor)
+        wp = _derived_of(weight, "padded", padded)
+    else:
+        wp = weight.detach()
+    c = torch.zeros(N, device=dev) if bias is None else bias.detach().float().contiguous()
+    act = actions.detach().to(device=dev, dtype=torch.int64).contiguous()
+    if act.shape != (B,):
+        raise ValueError(f"catalogue_log_prob: {B} rows but actions of shape {tuple(act.shape)}")
+    ips = default_items_per_slice(B, N) if items_per_slice is None else int(items_per_slice)
+    lp = torch.empty(B, device=dev)
+    lse = torch.empty(B, device=dev)
+    ws = L.workspace("recnn_catalogue_logprob_workspace_bytes", B, N, ips, device=dev)
+    L.call("recnn_catalogue_logprob", L.ptr(xp), xp.stride(0), B, Kp, L.ptr(wp), wp.stride(0), int(bf16), L.ptr(c), N, L.ptr(act),
+           ips, L.ptr(lp), L.ptr(lse), L.ptr(ws), L.current_stream())
+    return lp, lse
+
+
+def action_ids(actions):
+    """int64 ids of a batch of logged actions given as integer ids [B] or [B, 1], as a tensor made by `onehot_rows`, or as dense
+    one-hot rows [B, n_items]."""
+    integer = not (actions.dtype.is_floating_point or actions.dtype == torch.bool)
+    if actions.dim() == 2 and actions.shape[1] == 1 and integer:
+        actions = actions[:, 0]
+    if actions.dim() == 1:
+        if not integer:
+            raise ValueError(f"action ids must be integers, got {actions.dtype}")
+        return actions.to(torch.int64)
+    if actions.dim() != 2:
+        raise ValueError(f"actions must be ids [B] or one-hot rows [B, n_items], got shape {tuple(actions.shape)}")
+    idx = onehot_index_of(actions)
+    return idx if idx is not None else actions.argmax(1)
+
+
+def discrete_log_prob(state, module, actions):
+    """`catalogue_log_prob` of a DiscreteActor's head for given actions: the hidden layer by the GEMM kernel, nothing stored."""
+    if not state.is_cuda:
+        raise L.RecnnHipError("recnn_amd networks run on the GPU only (no CPU fallback): move the module and its inputs to 'cuda'")
+    x = state.detach().float()
+    B, K = x.shape
+    w1 = module.linear1.weight
+    H = w1.shape[0]
+    Kp, Hp = _r64(K), (_r128(H) if _catalogue_dtype == "bf16" else _r64(H))
+    h = torch.zeros(B, Hp, device=x.device)
+    _fwd(_pad(x, B, Kp), Kp, _pad(w1, Hp, Kp), module.linear1.bias.detach().float().contiguous(), h, Hp, H, True, None)
+    # h goes in at its padded width (its columns past H are zero): no second padded copy inside
+    return catalogue_log_prob(h, module.linear2.weight, module.linear2.bias, action_ids(actions), _x_padded=True)
+
+
 def onehot_rows(idx, n):
     """float[B, n] one-hot rows of int64 indices (recnn/data/utils.py:108-109: zeros + scatter_).  The result remembers
     its indices (`onehot_index`): a Critic reading it gathers the B weight columns instead of multiplying a [B, n] matrix

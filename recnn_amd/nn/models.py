@@ -158,6 +158,13 @@ class Beta(nn.Module):
         self.last_loss = loss
         return p
 
+    def log_prob(self, state, actions):
+        """(log beta(a | s), logsumexp of the logits), float32 [B] each, for logged actions (int64 ids, `onehot_rows` rows or dense
+        one-hot rows) -- `functional.catalogue_log_prob`: no [B, num_items] matrix, no clamp, and unlike `forward` nothing is
+        trained: no optimizer is made or stepped."""
+        lin = self.net[0]
+        return F_hip.catalogue_log_prob(state, lin.weight, lin.bias, F_hip.action_ids(actions))
+
 
 class DiscreteActor(nn.Module):
     """state -> probabilities over the catalogue: softmax(L2(relu(L1(state))))  (models.py:76-184), the REINFORCE policy.
@@ -198,6 +205,12 @@ class DiscreteActor(nn.Module):
         if actions is None and self.forced_actions:
             actions = self.forced_actions.pop(0)
         return F_hip.discrete_policy(state, self, actions=actions, sample=actions is None)
+
+    def log_prob(self, state, actions):
+        """(log pi(a | s), logsumexp of the logits), float32 [B] each, for logged actions (int64 ids, `onehot_rows` rows or dense
+        one-hot rows), for offline evaluation (`recnn_amd.ope`): `functional.catalogue_log_prob` over the hidden layer -- no
+        [B, action_dim] matrix, no clamp, no gradient, and the episode lists and `forced_actions` are left alone."""
+        return F_hip.discrete_log_prob(state, self, actions)
 
     def _select_action(self, state, **kwargs):
         # plain REINFORCE: there is no behaviour policy, `action_source` is not consulted (models.py:103-111)

@@ -1210,6 +1210,30 @@ int recnn_ope_accumulate(const float* lp_pi, const float* lp_beta, const float* 
                          const float* v_dm, int n, double cap, int top_k, double* acc_f, int64_t* acc_i, void* workspace,
                          void* stream);
 
+/* =====================================================================================
+ * 18. Backward of the catalogue log-prob: full-softmax cross-entropy training (csrc/logprob_bwd.hip).
+ *    recnn_catalogue_logprob_bwd: x, W, c, actions, K, N, w_bf16, the strides and items_per_slice as recnn_catalogue_logprob takes
+ *      them (section 17); lse float32 [B] as that call wrote it; g_lp, g_lse float32 [B], the gradients arriving at logprob and lse,
+ *      either may be NULL for zeros.  With p[b, n] = exp(z[b, n] - lse[b]) and
+ *        D[b, n] = (g_lse[b] - g_lp[b]) p[b, n] + g_lp[b] [n == a_b]
+ *      (the derivative of z_a - lse: the forward's min(., 0) is a rounding guard) it writes dx = D W float32 [B][K] (row stride
+ *      ld_dx), dW = D^T x float32 [N][K] (row stride ld_dw) and dc[n] = sum_b D[b, n] float32 [N].  D is recomputed tile by tile
+ *      and never stored.  A row whose action lies outside [0, N) takes g_lp[b] as 0: no one-hot term, no NaN; g_lse[b] still flows.
+ *      dx NULL skips the dx kernels; dW and dc both NULL skip the other kernel; dW or dc alone may be NULL.  B == 0 launches nothing
+ *      and zero-fills dW / dc where given.  w_bf16 = 1: W is the bf16 copy, x is rounded to bf16 on load and D before the second
+ *      product; dW is float32 either way.
+ *      K (as passed, i.e. padded) is at most 256: the output tile stays in registers, and a larger K is refused before any launch.
+ *      No atomics: equal calls give equal bits, and with items_per_slice fixed a row's dx bits depend on that row, W, c, its lse and
+ *      gradients and items_per_slice alone.  dx, dW rows and the workspace 16-byte aligned, ld_dx, ld_dw >= K and multiples of 4.
+ *      workspace: recnn_catalogue_logprob_bwd_workspace_bytes(B, N, K, items_per_slice) bytes (host arithmetic only): one [B][K]
+ *      partial of dx per catalogue slice.  Needed for dx only.
+ *    Errors: RECNN_E_INVALID before any HIP call, with a message.
+ * ===================================================================================== */
+int recnn_catalogue_logprob_bwd_workspace_bytes(int B, int N, int K, int items_per_slice, int64_t* h_bytes);
+int recnn_catalogue_logprob_bwd(const float* x, int64_t ld_x, int B, int K, const void* W, int64_t ld_w, int w_bf16, const float* c, int N,
+                                const int64_t* actions, const float* lse, const float* g_lp, const float* g_lse, int items_per_slice,
+                                float* dx, int64_t ld_dx, float* dW, int64_t ld_dw, float* dc, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

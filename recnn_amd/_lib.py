@@ -293,6 +293,8 @@ SIGNATURES = {
     "recnn_slate_ild": (_I, [_P, _I, _P, _L, _I, _I, _I, _I, _P, _P]),
     "recnn_catalogue_logprob_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
     "recnn_catalogue_logprob": (_I, [_P, _L, _I, _I, _P, _L, _I, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "recnn_catalogue_logprob_bwd_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_catalogue_logprob_bwd": (_I, [_P, _L, _I, _I, _P, _L, _I, _P, _I, _P, _P, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P]),
     "recnn_ope_accumulate_workspace_bytes": (_I, [_I, C.POINTER(_L)]),
     "recnn_ope_accumulate": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_double, _I, _P, _P, _P, _P]),
 }

@@ -17,116 +17,10 @@
 // The longest chain of additions a term of s passes through: 7 (in lane) + 4 (butterfly) + tiles per slice + slices.
 #include <math.h>
 
-#include "common.h"
+#include "logprob_tile.h"
 
 namespace {
-
-constexpr int BM = 128;         // rows per workgroup
-constexpr int BN = 128;         // items per tile
-constexpr int NTN = BN / 16;    // 16-column MFMA blocks per tile
-constexpr int WCH = BN * 8 / 256;   // 16-byte chunks of a W stage per thread
-constexpr int ROWB = 128;       // bytes of one operand row per k-stage: 32 fp32 / 64 bf16
-constexpr int STAGE_BYTES = (BM + BN) * ROWB;
-// byte offset of 16-byte chunk j (of 8) of stage row `row`: the chunk index xor the row's low bits
-__device__ inline int lds_at(int row, int j) { return row * ROWB + ((j ^ (row & 7)) << 4); }
-
-template <typename T>
-struct Stage;
-// fp32: 32 k per stage; the 16-byte chunk j (of 8) of a row holds k 4j .. 4j + 3
-template <>
-struct Stage<float> {
-  static constexpr int BK = ROWB / 4;
-  uint4 xr[4], wr[WCH];
-  __device__ void fetch(const float* __restrict__ x, int64_t ldx, int B, int b0, const float* __restrict__ W, int64_t ldw, int N, int n0,
-                        int k0, int tid) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-      const int b = b0 + row;
-      xr[i] = b < B ? *(const uint4*)(x + (int64_t)b * ldx + k0 + 4 * j) : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < WCH; ++i) {
-      const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-      const int n = n0 + row;
-      wr[i] = n < N ? *(const uint4*)(W + (int64_t)n * ldw + k0 + 4 * j) : make_uint4(0, 0, 0, 0);
-    }
-  }
-};
-// bf16: 64 k per stage; x is fp32 in memory and rounded here (nearest even), W is bf16 in memory
-template <>
-struct Stage<bf16_t> {
-  static constexpr int BK = ROWB / 2;
-  uint4 xr[4], wr[WCH];
-  __device__ void fetch(const float* __restrict__ x, int64_t ldx, int B, int b0, const bf16_t* __restrict__ W, int64_t ldw, int N, int n0,
-                        int k0, int tid) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-      const int b = b0 + row;
-      if (b < B) {
-        const f32x4* p = (const f32x4*)(x + (int64_t)b * ldx + k0 + 8 * j);
-        const f32x4 lo = p[0], hi = p[1];
-        xr[i] = make_uint4(cvt_pk_bf16(lo[0], lo[1]), cvt_pk_bf16(lo[2], lo[3]), cvt_pk_bf16(hi[0], hi[1]), cvt_pk_bf16(hi[2], hi[3]));
-      } else {
-        xr[i] = make_uint4(0, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < WCH; ++i) {
-      const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-      const int n = n0 + row;
-      wr[i] = n < N ? *(const uint4*)(W + (int64_t)n * ldw + k0 + 8 * j) : make_uint4(0, 0, 0, 0);
-    }
-  }
-};
-
-template <typename T>
-__device__ inline void stage_store(const Stage<T>& st, char* buf, int tid) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-    *(uint4*)(buf + lds_at(row, j)) = st.xr[i];
-  }
-#pragma unroll
-  for (int i = 0; i < WCH; ++i) {
-    const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-    *(uint4*)(buf + lds_at(BM + row, j)) = st.wr[i];
-  }
-}
-
-// One stage of the wave's 32 x 128 block, in two halves of the stage's k.  Lane (q, r16) reads chunks 2 q + h of rows r16 (+ 16 per
-// block) of both operands: the same k for A and B, which is all the MFMA needs.
-template <typename T>
-__device__ inline void stage_mma(const char* buf, int wave, int q, int r16, f32x4 (&acc)[2][NTN]) {
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    uint4 a[2], w[NTN];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) a[tm] = *(const uint4*)(buf + lds_at(32 * wave + 16 * tm + r16, 2 * q + h));
-#pragma unroll
-    for (int tn = 0; tn < NTN; ++tn) w[tn] = *(const uint4*)(buf + lds_at(BM + 16 * tn + r16, 2 * q + h));
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < NTN; ++tn) {
-            const uint32_t av = e == 0 ? a[tm].x : e == 1 ? a[tm].y : e == 2 ? a[tm].z : a[tm].w;
-            const uint32_t wv = e == 0 ? w[tn].x : e == 1 ? w[tn].y : e == 2 ? w[tn].z : w[tn].w;
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(av), __uint_as_float(wv), acc[tm][tn], 0, 0, 0);
-          }
-    } else {
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < NTN; ++tn)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[tm]), __builtin_bit_cast(bf16x8, w[tn]),
-                                                                acc[tm][tn], 0, 0, 0);
-    }
-  }
-}
+using namespace logprob_tile;      // Stage, stage_store, stage_mma, lds_at: shared with logprob_bwd.hip
 
 // ws_m, ws_s: [n_slices][B]; ws_za: [B] (written by the one lane of the one slice that holds a valid a[b])
 template <typename T>
@@ -171,7 +65,7 @@ __global__ __launch_bounds__(256) void logprob_slice_kernel(const float* __restr
     for (int kt = 0; kt < nk; ++kt) {
       const bool more = kt + 1 < nk;
       if (more) st.fetch(x, ldx, B, b0, W, ldw, N, n0, (kt + 1) * Stage<T>::BK, tid);
-      stage_mma<T>(lds + (kt & 1) * STAGE_BYTES, wave, q, r16, acc);
+      stage_mma<T, 2, NTN>(lds + (kt & 1) * STAGE_BYTES, 32 * wave, BM, q, r16, acc);
       if (more) stage_store(st, lds + ((kt + 1) & 1) * STAGE_BYTES, tid);
       __syncthreads();
     }
@@ -243,11 +137,6 @@ __global__ __launch_bounds__(256) void logprob_merge_kernel(const float* __restr
   logprob[b] = (a >= 0 && a < N) ? fminf(ws_za[b] - l, 0.f) : __int_as_float(0x7FC00000);
 }
 
-inline bool slices_of(int N, int items_per_slice, int* n_slices) {
-  if (N < 1 || items_per_slice < BN || items_per_slice % BN) return false;
-  *n_slices = (int)(((int64_t)N + items_per_slice - 1) / items_per_slice);
-  return true;
-}
 }  // namespace
 
 extern "C" int recnn_catalogue_logprob_workspace_bytes(int B, int N, int items_per_slice, int64_t* h_bytes) {

@@ -535,6 +535,28 @@ class SeqEnv(StoreEnv):
         return {"state": state, "action": action, "reward": reward, "next_state": next_state,
                 "done": torch.zeros(state.shape[0], device=state.device), "meta": meta}
 
+    def target_items(self, batch):
+        """int64 [rows] on the env's device: the table row id of each row's action -- for row k * U + u of a `user_batch`, the item
+        at position `steps[k]` of user u's history.  What a next-item loss over `batch["state"]` is trained on
+        (`recnn_amd.nn.next_item_update`) and what `FlatIndex.rank_of` ranks.  Built from `batch["meta"]` (users, step) through
+        the replay store, like `FrameEnv.target_items`; a generator batch whose rows stem from more than one user batch (its meta
+        names the last one only) is refused."""
+        st = self.store
+        meta = batch["meta"]
+        try:
+            slots = np.asarray(st.slots(list(meta["users"])), dtype=np.int64)
+        except KeyError as e:
+            raise ValueError(f"target_items: user {e} of the batch is not in the replay store") from None
+        steps = np.asarray([int(t) for t in meta["step"]], dtype=np.int64)
+        rows = int(meta.get("rows", batch["state"].shape[0]))
+        if rows != len(steps) * len(slots):
+            raise ValueError(f"target_items: the batch has {rows} rows, its meta describes {len(steps)} steps of {len(slots)} users")
+        if len(steps) and (steps.min() < 0 or steps.max() >= int(st.lengths[slots].min())):
+            raise ValueError("target_items: the batch's steps do not lie inside its users' histories")
+        off = np.concatenate([[0], np.cumsum(st.lengths)]).astype(np.int64)
+        pos = (steps[:, None] + off[slots][None, :]).reshape(-1)
+        return st.items[torch.from_numpy(pos).to(self.device)].long()
+
     def train_batch(self):
         return self._generate(self.train_dataloader, self.train_buffer)
 

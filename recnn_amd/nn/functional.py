@@ -911,6 +911,11 @@ def catalogue_log_prob(x, weight, bias, actions, *, dtype=None, items_per_slice=
     Operands are zero-padded as `DiscretePolicyFunction` / `beta_train_forward` pad theirs, and the padded / bf16 copies of the
     weight are the ones those keep per weight version.  `items_per_slice` (a multiple of 128) defaults to
     `default_items_per_slice(B, N)`; with it fixed a row's bits do not depend on the batch around it.  No gradient is recorded."""
+    return _catalogue_forward(_catalogue_operands(x, weight, bias, actions, dtype, items_per_slice, _x_padded))[:2]
+
+
+def _catalogue_operands(x, weight, bias, actions, dtype, items_per_slice, _x_padded=False):
+    """The checked, padded operands of one `recnn_catalogue_logprob` call: (xp, wp, c, act, B, N, K, Kp, bf16, ips)."""
     if not (x.is_cuda and weight.is_cuda):
         raise L.RecnnHipError("recnn_amd catalogue_log_prob: needs GPU tensors (no CPU fallback)")
     dtype = _catalogue_dtype if dtype is None else dtype
@@ -951,12 +956,19 @@ def catalogue_log_prob(x, weight, bias, actions, *, dtype=None, items_per_slice=
     if act.shape != (B,):
         raise ValueError(f"catalogue_log_prob: {B} rows but actions of shape {tuple(act.shape)}")
     ips = default_items_per_slice(B, N) if items_per_slice is None else int(items_per_slice)
+    return xp, wp, c, act, B, N, K, Kp, bf16, ips
+
+
+def _catalogue_forward(ops):
+    """(log_prob, lse, operands): the one `recnn_catalogue_logprob` call of `catalogue_log_prob` and `catalogue_log_prob_train`."""
+    xp, wp, c, act, B, N, K, Kp, bf16, ips = ops
+    dev = xp.device
     lp = torch.empty(B, device=dev)
     lse = torch.empty(B, device=dev)
     ws = L.workspace("recnn_catalogue_logprob_workspace_bytes", B, N, ips, device=dev)
     L.call("recnn_catalogue_logprob", L.ptr(xp), xp.stride(0), B, Kp, L.ptr(wp), wp.stride(0), int(bf16), L.ptr(c), N, L.ptr(act),
            ips, L.ptr(lp), L.ptr(lse), L.ptr(ws), L.current_stream())
-    return lp, lse
+    return lp, lse, ops
 
 
 def action_ids(actions):
@@ -988,6 +1000,104 @@ def discrete_log_prob(state, module, actions):
     _fwd(_pad(x, B, Kp), Kp, _pad(w1, Hp, Kp), module.linear1.bias.detach().float().contiguous(), h, Hp, H, True, None)
     # h goes in at its padded width (its columns past H are zero): no second padded copy inside
     return catalogue_log_prob(h, module.linear2.weight, module.linear2.bias, action_ids(actions), _x_padded=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Next-item training (csrc/logprob_bwd.hip): the catalogue log-prob with its backward, and the full-softmax
+# cross-entropy over it.  Neither pass stores a [B, n_items] matrix.
+
+CATALOGUE_BWD_KMAX = 256       # padded width the backward's register-resident output tile is built for
+
+
+def catalogue_bwd_items_per_slice(B, N, K):
+    """Catalogue slice length of the dx kernel of `catalogue_log_prob_train`'s backward when none was given: a function of
+    (B, N, K) alone.  Row tiles x slices come to about one workgroup per place on the 256 compute units: one place each, two where
+    K <= 128 lets the fp32 kernel keep its output tile in half the register file."""
+    row_tiles = max(1, (B + 127) // 128)
+    tiles = (N + 127) // 128
+    slices = max(1, min(tiles, (512 if K <= 128 else 256) // row_tiles))
+    return (tiles + slices - 1) // slices * 128
+
+
+def _padded_width(K, dtype):
+    return _r128(K) if (_catalogue_dtype if dtype is None else dtype) == "bf16" else _r64(K)
+
+
+class CatalogueLogProbFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, actions, dtype, items_per_slice):
+        lp, lse, ops = _catalogue_forward(_catalogue_operands(x, weight, bias, actions, dtype, items_per_slice))
+        ctx.ops, ctx.lse, ctx.user_ips = ops, lse.detach(), items_per_slice      # (detach: the output itself would tie ctx into a cycle)
+        ctx.dtypes = (x.dtype, weight.dtype, None if bias is None else bias.dtype)
+        ctx.save_for_backward(x, weight)       # (for autograd's check that neither was written in between)
+        ctx.set_materialize_grads(False)
+        return lp, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_lp, g_lse):
+        ctx.saved_tensors
+        xp, wp, c, act, B, N, K, Kp, bf16, _ = ctx.ops
+        need_x, need_w, need_c = ctx.needs_input_grad[:3]
+        need_c = need_c and ctx.dtypes[2] is not None
+        if (g_lp is None and g_lse is None) or not (need_x or need_w or need_c):
+            return None, None, None, None, None, None
+        dev = xp.device
+        g_lp = None if g_lp is None else g_lp.float().contiguous()
+        g_lse = None if g_lse is None else g_lse.float().contiguous()
+        ips = catalogue_bwd_items_per_slice(B, N, K) if ctx.user_ips is None else int(ctx.user_ips)
+        dx = torch.empty(B, Kp, device=dev) if need_x else None
+        dw = torch.empty(N, Kp, device=dev) if need_w else None
+        dc = torch.empty(N, device=dev) if need_c else None
+        ws = L.workspace("recnn_catalogue_logprob_bwd_workspace_bytes", B, N, Kp, ips, device=dev) if need_x else None
+        L.call("recnn_catalogue_logprob_bwd", L.ptr(xp), xp.stride(0), B, Kp, L.ptr(wp), wp.stride(0), int(bf16), L.ptr(c), N, L.ptr(act),
+               L.ptr(ctx.lse), L.ptr(g_lp), L.ptr(g_lse), ips, L.ptr(dx), Kp, L.ptr(dw), Kp, L.ptr(dc), L.ptr(ws), L.current_stream())
+
+        def strip(t, dt):
+            if t is None:
+                return None
+            t = t if K == Kp else t[:, :K].contiguous()
+            return t if t.dtype == dt else t.to(dt)
+        return strip(dx, ctx.dtypes[0]), strip(dw, ctx.dtypes[1]), (None if dc is None else dc.to(ctx.dtypes[2])), None, None, None
+
+
+def catalogue_log_prob_train(x, weight, bias, actions, *, dtype=None, items_per_slice=None):
+    """`catalogue_log_prob` with a gradient: (log_prob, lse) with the bits `catalogue_log_prob` gives on the same inputs (the very
+    same call, padding, cached weight copies and default slice length), attached to x, weight and bias.  The backward is one
+    `recnn_catalogue_logprob_bwd` call (csrc/logprob_bwd.hip): with p = exp(z - lse) and D = (g_lse - g_lp) p + g_lp [n == a] it
+    returns dx = D W, dW = D^T x and dbias = sum_b D, D recomputed tile by tile and never stored; only the gradients that are
+    needed are computed.  The derivative is that of z_a - lse (the forward's clamp at 0 is a rounding guard).  A row whose action
+    lies outside [0, n_items) gives NaN in its log_prob, as in `catalogue_log_prob`, and its log_prob gradient counts as 0: no
+    NaN reaches any gradient, and its lse gradient still flows.  The padded width of K (a multiple of 64, of 128 in bf16 mode)
+    may not exceed 256; a wider product is refused before anything is launched (the policy head of `DiscreteActor` and `Beta`,
+    2048 and 1290 wide, stay on their own training paths).  The dx kernel's slice length is `items_per_slice` when given, else
+    `catalogue_bwd_items_per_slice(B, N, K)`; with it fixed a row's dx bits do not depend on the batch around it.  No float
+    atomics: equal calls give equal bits.  Not twice differentiable."""
+    if weight.dim() == 2 and _padded_width(weight.shape[1], dtype) > CATALOGUE_BWD_KMAX:
+        raise ValueError(f"catalogue_log_prob_train: K = {weight.shape[1]} pads to {_padded_width(weight.shape[1], dtype)}, above the "
+                         f"backward's limit of {CATALOGUE_BWD_KMAX} (its output tile is register-resident; there is no K-chunked path)")
+    return CatalogueLogProbFunction.apply(x, weight, bias, actions, dtype, items_per_slice)
+
+
+def catalogue_cross_entropy(x, weight, bias, targets, *, reduction="mean", ignore_index=-100, dtype=None):
+    """Full-softmax cross-entropy of the logits x weight^T + bias against `targets` (int64 [B]) without the logits:
+    -`catalogue_log_prob_train(...)[0]`, reduced by `reduction` ('mean', 'sum' or 'none').  Rows whose target equals `ignore_index`
+    contribute 0 and are left out of the mean (torch.nn.functional.cross_entropy's semantics, for padded sequences); any other
+    target outside [0, n_items) raises ValueError."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"catalogue_cross_entropy: reduction {reduction!r} is not 'mean', 'sum' or 'none'")
+    if not (x.is_cuda and weight.is_cuda):
+        raise L.RecnnHipError("recnn_amd catalogue_cross_entropy: needs GPU tensors (no CPU fallback)")
+    t = action_ids(targets).to(x.device)
+    keep = t != int(ignore_index)
+    N = weight.shape[0]
+    if bool((keep & ((t < 0) | (t >= N))).any()):
+        raise ValueError(f"catalogue_cross_entropy: a target lies outside [0, {N}) and is not ignore_index = {ignore_index}")
+    lp, _ = catalogue_log_prob_train(x, weight, bias, torch.where(keep, t, torch.full_like(t, -1)), dtype=dtype)
+    loss = torch.where(keep, -lp, torch.zeros_like(lp))
+    if reduction == "none":
+        return loss
+    return loss.sum() if reduction == "sum" else loss.sum() / keep.sum()
 
 
 def onehot_rows(idx, n):

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import functional as F_hip
 
-__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor"]
+__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead"]
 
 
 class DuelDQN(nn.Module):
@@ -415,3 +415,54 @@ class StochasticActor(nn.Module):
         log_prob = -((action - mean) ** 2) / (2 * std ** 2) - std.log() - math.log(math.sqrt(2 * math.pi))
         log_prob = log_prob - torch.log(1 - action.pow(2) + epsilon)
         return action, log_prob, z, mean, log_std
+
+
+class NextItemHead:
+    """Full-softmax next-item head over the catalogue: logits = x weight^T + bias, trained with the fused cross-entropy
+    (`functional.catalogue_cross_entropy`, csrc/logprob_bwd.hip) -- the [rows, n_items] logits are never stored,
+    forward or backward.
+
+    `weight` is a contiguous float32 GPU tensor or Parameter [n_items, K] and is used as it is, never copied: it may be the very
+    tensor passed as `SeqEnv.user_batch(table=)`, which ties the output weights to the input embeddings.  `bias` float32
+    [n_items] or None.  The padded K may not exceed 256 (`functional.catalogue_log_prob_train`); the 2048- and 1290-wide heads of
+    `DiscreteActor` and `Beta` keep their own training paths."""
+
+    def __init__(self, weight, bias=None):
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 2 or weight.dtype != torch.float32 or not weight.is_contiguous():
+            raise ValueError("NextItemHead: weight must be a contiguous float32 tensor [n_items, K]")
+        if not weight.is_cuda:
+            raise F_hip.L.RecnnHipError("NextItemHead: the weight must live on the GPU (no CPU fallback)")
+        if bias is not None and not (isinstance(bias, torch.Tensor) and bias.dtype == torch.float32 and bias.is_cuda
+                                     and tuple(bias.shape) == (weight.shape[0],)):
+            raise ValueError(f"NextItemHead: bias must be a float32 GPU tensor [{weight.shape[0]}] or None")
+        self.weight, self.bias = weight, bias
+
+    @classmethod
+    def new(cls, n_items, dim, bias=True, device="cuda"):
+        """A head of its own: weight ~ N(0, 1 / dim), zero bias, both Parameters."""
+        w = nn.Parameter(torch.randn(int(n_items), int(dim), device=device) / math.sqrt(dim))
+        return cls(w, nn.Parameter(torch.zeros(int(n_items), device=device)) if bias else None)
+
+    n_items = property(lambda self: self.weight.shape[0])
+
+    def parameters(self):
+        """The tensors of the head that require grad (for an optimizer)."""
+        return [t for t in (self.weight, self.bias) if t is not None and t.requires_grad]
+
+    def loss(self, x, targets, reduction="mean", ignore_index=-100, dtype=None):
+        """`catalogue_cross_entropy` of x [rows, K] against the item ids `targets`."""
+        return F_hip.catalogue_cross_entropy(x, self.weight, self.bias, targets, reduction=reduction, ignore_index=ignore_index,
+                                             dtype=dtype)
+
+    def log_prob(self, x, targets):
+        """(log_prob, lse) of `catalogue_log_prob`: detached, for the off-policy meters."""
+        return F_hip.catalogue_log_prob(x, self.weight, self.bias, F_hip.action_ids(targets))
+
+    def index(self):
+        """`FlatIndex(weight, "IP")` for `rank_of` / `RankingMeter`: a snapshot of the weight as it is now.  Refused when the head
+        has a bias: the order of the logits is then not the inner-product order."""
+        if self.bias is not None:
+            raise ValueError("NextItemHead.index: the head has a bias, so its logits do not rank the items as the inner product "
+                             "does; evaluate a bias-free head, or rank by the logits yourself")
+        from ..retrieval import FlatIndex
+        return FlatIndex(self.weight, "IP")

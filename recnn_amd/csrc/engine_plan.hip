@@ -139,6 +139,158 @@ int apply_net(recnn_engine* e, int ni, int rows, bool do_adam, int opt_idx, floa
               [&] { return apply_launch(L, a, s, pg); }, !do_adam && target_ni < 0);
 }
 
+// ---- what a problem is: stated once, whatever the schedule that launches it ----------------
+constexpr int POL = RECNN_NET_POLICY, TPOL = RECNN_NET_TARGET_POLICY;
+constexpr int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2}, TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
+
+// Dropout of one hidden layer: none, an external keep-mask [max_rows, H] per stream, or the counter-based hash keyed by (seed, stream,
+// *step_ptr + step_add).  The kernel structs name these fields their own way (stream / stream_id / stream1, stream2; mask / mask1, mask2):
+// every builder copies from here.  A network's second hidden layer takes the stream after its first's (mask2_idx).
+struct MaskSel {
+  int mode = RECNN_MASK_NONE;
+  const uint8_t* ext = nullptr; int64_t pitch = 0;
+  uint32_t seed = 0, stream = 0;
+  const int32_t* step_ptr = nullptr; int step_add = 0;
+};
+MaskSel mask_sel(const recnn_engine* e, int mask_idx, int step_add, bool hash_only = false) {
+  MaskSel m;
+  const int mode = e->cfg.mask_mode;
+  if (mask_idx < 0 || mode == RECNN_MASK_NONE || (hash_only && mode != RECNN_MASK_HASH)) return m;
+  m.mode = mode;
+  if (mode == RECNN_MASK_EXTERNAL) {
+    m.ext = e->ext_masks + (int64_t)mask_idx * e->cfg.max_rows * e->H; m.pitch = e->H;
+  } else {
+    m.seed = e->cfg.seed; m.stream = (uint32_t)mask_idx; m.step_ptr = e->counters; m.step_add = step_add;
+  }
+  return m;
+}
+inline int mask2_idx(int mask_idx) { return mask_idx < 0 ? -1 : mask_idx + 1; }
+
+// A network's weights as the forward and backward launches read them: the compute-type shadows of W1 / W2 (/ W3: an actor's), the
+// canonical fp32 biases, a critic's last layer as its canonical fp32 row.  (critic <=> out_dim == 1: net_dims gives a critic one output
+// and an actor A of them, and the launch that asks by out_dim -- x3tail.hip -- only runs at A == 128.)
+struct NetView {
+  const char *W1, *W2, *W3; int64_t ldw1, ldw2, ldw3;
+  const float *b1, *b2, *b3, *w3row;
+};
+NetView net_view(const recnn_engine* e, int ni) {
+  const Net& n = e->net[ni];
+  NetView v;
+  v.W1 = sh_ptr(e, ni, W1); v.ldw1 = n.ld_w1;
+  v.W2 = sh_ptr(e, ni, W2); v.ldw2 = n.ld_w2;
+  v.W3 = n.critic ? nullptr : sh_ptr(e, ni, W3); v.ldw3 = n.critic ? 0 : n.ld_w3;
+  v.b1 = n.p + n.off[B1]; v.b2 = n.p + n.off[B2]; v.b3 = n.p + n.off[B3];
+  v.w3row = n.critic ? n.p + n.off[W3] : nullptr;
+  return v;
+}
+
+// One application of a network in a step: what it reads, its dropout streams, where its results go.  Every schedule turns a role into a
+// problem of its own launches (fill_fwd per layer, fill_mlp, fill_l1 + fill_tail, fill_x3tail, ph_frozen_batched's fill).
+struct Role {
+  int ni;
+  const void* A0; int64_t lda0; int K0; int col0;                            // layer-1 input: first segment, its first W1-shadow column
+  const void* A1 = nullptr; int64_t lda1 = 0; int K1 = 0; int col1 = 0;      // optional second segment, contracted after the first
+  int mask_idx = -1;   // dropout stream of the first hidden layer (second: + 1); -1 = eval mode
+  int step_add = 0;    // mask key step on top of the device counter
+  void* h1 = nullptr; void* h2 = nullptr;                                    // hidden activations ...
+  bool keep = false;   // ... which a backward reads: the row-panel launches store them too (layer-by-layer launches always do)
+  void* out = nullptr; int64_t ldo = 0;                                      // an actor's output
+  const float* addend = nullptr; int64_t ld_add = 0; float add_clip = 0.f;   // ... + clipped noise (TD3's target action)
+  float* q = nullptr;  // a critic's Q per row (b3 included)
+};
+
+// The buffers the roles live in: the step's own, or a whole policy cycle's (cycle mode: n batches side by side, M = n * rows rows).
+struct StepBufs {
+  char *xs, *xn;                                       // packed rows [action | state], pitch e->ldx
+  char *tp_h1, *tp_h2, *pa_h1, *pa_h2, *ga, *tq_h1[2], *tq_h2[2];
+  float* tq[2];
+  const float* noise;
+  int step_add;
+};
+StepBufs step_bufs(const recnn_engine* e) {
+  StepBufs b;
+  b.xs = e->xcs; b.xn = e->xcn;
+  b.tp_h1 = e->tp.h1; b.tp_h2 = e->tp.h2; b.pa_h1 = e->pa.h1; b.pa_h2 = e->pa.h2; b.ga = e->gen_action;
+  for (int c = 0; c < 2; ++c) { b.tq_h1[c] = e->tq[c].h1; b.tq_h2[c] = e->tq[c].h2; b.tq[c] = e->tqv[c]; }
+  b.noise = e->ext_noise ? e->ext_noise : e->noise_buf;
+  b.step_add = e->run_off;
+  return b;
+}
+// ... of the cycle whose first batch is step run_off0 of the run; the actor's operands from batch actor_set0 on (its batches may be dealt
+// out over two launches).  (bf16 only: 2 bytes per element.)
+StepBufs cycle_bufs(const recnn_engine* e, int rows, int run_off0, int actor_set0 = 0) {
+  const int64_t r0 = (int64_t)actor_set0 * rows;
+  StepBufs b;
+  b.xs = e->m_xs + r0 * e->ldx * 2; b.xn = e->m_xn;
+  b.tp_h1 = e->m_tp_h1; b.tp_h2 = e->m_tp_h2;
+  b.pa_h1 = e->m_pa_h1 + r0 * e->Hp * 2; b.pa_h2 = e->m_pa_h2 + r0 * e->Hp * 2; b.ga = e->m_ga + r0 * e->Ap * 2;
+  for (int c = 0; c < 2; ++c) {
+    b.tq_h1[c] = e->m_tq_h1[c]; b.tq[c] = e->m_tq[c];
+    b.tq_h2[c] = c == 0 ? e->m_tp_h2 : e->m_tp_h1;     // (layer-by-layer form: the target actor's panels are done with by then)
+  }
+  b.noise = e->ext_noise ? e->ext_noise : e->m_noise;
+  b.step_add = run_off0 + actor_set0;
+  return b;
+}
+
+// target actor on s': next_action into the action slot of the packed next rows (+ TD3's clipped noise, td3.py:74-78)
+Role role_target_actor(const recnn_engine* e, const StepBufs& b) {
+  Role r{TPOL, b.xn + tc_off(e, e->A), e->ldx, e->K1a, 0};
+  r.step_add = b.step_add;
+  r.h1 = b.tp_h1; r.h2 = b.tp_h2; r.out = b.xn; r.ldo = e->ldx;
+  if (e->td3) { r.addend = b.noise; r.ld_add = e->A; r.add_clip = e->hy.noise_clip; }
+  return r;
+}
+// actor on s: gen_action, activations kept for the policy step's backward
+Role role_actor(const recnn_engine* e, const StepBufs& b) {
+  Role r{POL, b.xs + tc_off(e, e->A), e->ldx, e->K1a, 0};
+  r.mask_idx = e->td3 ? 4 : 2; r.step_add = b.step_add;
+  r.h1 = b.pa_h1; r.h2 = b.pa_h2; r.keep = true; r.out = b.ga; r.ldo = e->Ap;
+  return r;
+}
+// learning critic c on [action | state]
+Role role_critic(const recnn_engine* e, const StepBufs& b, int c) {
+  Role r{VAL[c], b.xs, e->ldx, e->K1c, 0};
+  r.mask_idx = 2 * c; r.step_add = b.step_add;
+  r.h1 = e->cv[c].h1; r.h2 = e->cv[c].h2; r.keep = true; r.q = e->q[c];
+  return r;
+}
+// target critic c on [next_action | next_state].  whole: the packed row as one segment; otherwise the state part first, then the action
+// columns (the order of mlps.hip's chained form, whose state part does not wait for the target actor)
+Role role_target_critic(const recnn_engine* e, const StepBufs& b, int c, bool whole) {
+  Role r{TVAL[c], b.xn, e->ldx, e->K1c, 0};
+  if (!whole) {
+    r.A0 = b.xn + tc_off(e, e->A); r.K0 = e->K1a; r.col0 = e->A;
+    r.A1 = b.xn; r.lda1 = e->ldx; r.K1 = e->Ap; r.col1 = 0;
+  }
+  r.step_add = b.step_add;
+  r.h1 = b.tq_h1[c]; r.h2 = b.tq_h2[c]; r.q = b.tq[c];
+  return r;
+}
+// policy-loss critic: critic 1 on [pi(s) | s], two contraction segments over the rotated W1 shadow.  (gen_action is zero padded to Ap
+// columns, so segment 0 may run over the padded width: the W1 shadow columns it meets there are multiplied by zeros.)
+Role role_policy_critic(const recnn_engine* e, const char* xs, const char* ga, int step_add) {
+  Role r{RECNN_NET_VALUE1, ga, e->Ap, e->Ap, 0};
+  r.A1 = xs + tc_off(e, e->A); r.lda1 = e->ldx; r.K1 = e->K1a; r.col1 = e->A;
+  r.mask_idx = e->td3 ? 6 : 4; r.step_add = step_add;
+  r.h1 = e->pc.h1; r.h2 = e->pc.h2;
+  return r;
+}
+// ... of the PREVIOUS step of this run, riding in this step's forward (run graphs: nothing of this or later steps depends on it, the
+// weights are as that step's optimizer left them = the current ones): that step's batch and mask key, Q into that step's pl_part slot
+Role role_deferred_critic(const recnn_engine* e) {
+  const recnn_engine::PendingPc& pp = e->pending_pc;
+  Role r = role_policy_critic(e, pp.xs, pp.ga, pp.run_off);
+  r.q = e->pl_part_base + (int64_t)pp.slot * e->pl_cap;
+  return r;
+}
+// the partial sums of a step's policy loss (sums of Q, b3 included) as the loss history will read them
+int note_policy_parts(recnn_engine* e, int slot, int parts) {
+  RECNN_REQUIRE(parts > 0 && parts <= e->pl_cap, "policy loss: %d partial sums do not fit %d", parts, e->pl_cap);
+  if (slot < LOSS_HIST_MAX) { e->hist_pol_count[slot] = parts; e->hist_pol_add[slot] = 0; }
+  return 0;
+}
+
 // ---- GEMM problem builders ---------------------------------------------------------------
 struct FwdSpec {
   int ni;               // network whose weights are used
@@ -149,8 +301,8 @@ struct FwdSpec {
   void* C; int64_t ldc; int c_f32;
   int relu;
   int mask_idx;         // -1 = none
+  int step_add = -1;    // mask key step on top of the device counter; -1 = e->run_off
   const float* addend = nullptr; int64_t ld_add = 0; float add_clip = 0.f;
-  const float* dot_w = nullptr; const float* dot_bias = nullptr; float* dot_part = nullptr;
 };
 
 double fill_fwd(const recnn_engine* e, const FwdSpec& f, int rows, GemmProb* p) {
@@ -173,22 +325,29 @@ double fill_fwd(const recnn_engine* e, const FwdSpec& f, int rows, GemmProb* p) 
   p->C = f.C; p->ldc = f.ldc; p->c_f32 = f.c_f32;
   p->bias = n.p + n.off[bi];
   p->relu = f.relu;
-  p->mask_mode = RECNN_MASK_NONE;
-  if (f.mask_idx >= 0 && e->cfg.mask_mode != RECNN_MASK_NONE) {
-    p->mask_mode = e->cfg.mask_mode;
-    if (e->cfg.mask_mode == RECNN_MASK_EXTERNAL) {
-      p->mask = e->ext_masks + (int64_t)f.mask_idx * e->cfg.max_rows * e->H;
-      p->ld_mask = e->H;
-    } else {
-      p->seed = e->cfg.seed;
-      p->stream_id = (uint32_t)f.mask_idx;
-      p->step_ptr = e->counters; p->step_add = e->run_off;
-    }
-  }
+  const MaskSel m = mask_sel(e, f.mask_idx, f.step_add < 0 ? e->run_off : f.step_add);
+  p->mask_mode = m.mode; p->mask = m.ext; p->ld_mask = m.pitch;
+  p->seed = m.seed; p->stream_id = m.stream; p->step_ptr = m.step_ptr; p->step_add = m.step_add;
   p->addend = f.addend; p->ld_add = f.ld_add; p->add_clip = f.add_clip;
-  p->dot_w = f.dot_w; p->dot_bias = f.dot_bias; p->dot_part = f.dot_part;
   const double kreal = f.layer == 1 ? n.in_dim : e->H;
   return 2.0 * rows * p->N * kreal;
+}
+// layer 1 of a role from its input segments, layer 2 from its h1, layer 3 (an actor's) from its h2
+FwdSpec role_layer(const recnn_engine* e, const Role& r, int layer) {
+  const int Hp = e->Hp;
+  FwdSpec f{r.ni, layer, layer == 1 ? r.A0 : (layer == 2 ? r.h1 : r.h2), layer == 1 ? r.lda0 : Hp, 0, layer == 1 ? r.K0 : Hp};
+  f.c_f32 = 0; f.step_add = r.step_add;
+  if (layer == 1) {
+    f.b_col = r.col0;
+    if (r.A1) { f.A2 = r.A1; f.lda2 = r.lda1; f.K2 = r.K1; f.b2_col = r.col1; }
+    f.C = r.h1; f.ldc = Hp; f.relu = 1; f.mask_idx = r.mask_idx;
+  } else if (layer == 2) {
+    f.C = r.h2; f.ldc = Hp; f.relu = 1; f.mask_idx = mask2_idx(r.mask_idx);
+  } else {
+    f.C = r.out; f.ldc = r.ldo; f.relu = 0; f.mask_idx = -1;
+    f.addend = r.addend; f.ld_add = r.ld_add; f.add_clip = r.add_clip;
+  }
+  return f;
 }
 
 struct Group {
@@ -209,6 +368,31 @@ struct Group {
     return slot(eng, name, flops, s, [&] { return gemm_launch(&L, s); });
   }
 };
+
+GemmProb* add_layer(Group& g, const Role& r, int layer, int rows) {
+  GemmProb* p = g.add();
+  g.flops += fill_fwd(g.eng, role_layer(g.eng, r, layer), rows, p);
+  return p;
+}
+// One layer of several roles as one GEMM launch (layer 3: of those that have an output, the actors).  dot: one more layer-2 problem whose
+// sums of Q -- the last layer's dot, b3 included -- come out of the epilogue as partial sums in dot->q (a policy-loss critic);
+// *dot_parts = how many it wrote, -1 if the group had no room for it.
+int fwd_layer(recnn_engine* e, int rows, int layer, const Role* r, int n, const char* name, hipStream_t s, const Role* dot = nullptr,
+              int* dot_parts = nullptr) {
+  Group g(e, GEMM_FWD, 0, 0);
+  for (int i = 0; i < n; ++i)
+    if (layer < 3 || r[i].out) add_layer(g, r[i], layer, rows);
+  int di = -1;
+  if (dot && g.L.nprob < GEMM_MAX_GROUP) {
+    const NetView v = net_view(e, dot->ni);
+    di = g.L.nprob;
+    GemmProb* p = add_layer(g, *dot, 2, rows);
+    p->dot_w = v.w3row; p->dot_bias = v.b3; p->dot_part = dot->q;
+  }
+  const int rc = g.run(s, name);
+  if (!rc && dot_parts) *dot_parts = di >= 0 ? g.L.batch.p[di].dot_parts : -1;
+  return rc;
+}
 
 // dX problem: C[rows, N] = (A[rows, Kc] * Wshadow[Kc, N(+col0)]) * scale*[yref>0]
 double fill_dx(const recnn_engine* e, GemmProb* p, int rows, const void* A, int64_t lda, int Kc, int ni, int which, int col0,
@@ -306,42 +490,21 @@ bool fused_mlp_ok(const recnn_engine* e, int nprob) {
   return e->tune.fused_mlp && e->bf16 && e->Hp == 256 && e->Ap == 128 && (nprob >= 3 || e->tune.fused_mlp >= 2);
 }
 
-struct MlpSpec {
-  int ni;
-  const void* A0; int64_t lda0; int K0; int col0;
-  const void* A1 = nullptr; int64_t lda1 = 0; int K1 = 0; int col1 = 0;
-  void* h1 = nullptr; void* h2 = nullptr;
-  void* out = nullptr; int64_t ldo = 0;
-  float* q = nullptr;  // critic: Q per row
-  int mask_idx = -1;   // external mask index of the first hidden layer (second = +1); -1 = eval mode
-  const float* addend = nullptr; int64_t ld_add = 0; float add_clip = 0.f;
-};
-
-double fill_mlp(const recnn_engine* e, const MlpSpec& f, int rows, MlpProb* p) {
+// a role's whole network as a problem of the fused row-panel launch (mlps.hip)
+double fill_mlp(const recnn_engine* e, const Role& f, int rows, MlpProb* p) {
   const Net& n = e->net[f.ni];
+  const NetView v = net_view(e, f.ni);
   memset(p, 0, sizeof(*p));
   p->A[0] = f.A0; p->lda[0] = f.lda0; p->K[0] = f.K0; p->w1_col[0] = f.col0;
   p->nseg = 1;
   if (f.A1) { p->A[1] = f.A1; p->lda[1] = f.lda1; p->K[1] = f.K1; p->w1_col[1] = f.col1; p->nseg = 2; }
-  p->W1 = sh_ptr(e, f.ni, W1); p->ldw1 = n.ld_w1;
-  p->W2 = sh_ptr(e, f.ni, W2); p->ldw2 = n.ld_w2;
-  if (!n.critic) { p->W3 = sh_ptr(e, f.ni, W3); p->ldw3 = n.ld_w3; }
-  p->b1 = n.p + n.off[B1]; p->b2 = n.p + n.off[B2]; p->b3 = n.p + n.off[B3];
-  p->w3row = n.critic ? n.p + n.off[W3] : nullptr;
+  p->W1 = v.W1; p->ldw1 = v.ldw1; p->W2 = v.W2; p->ldw2 = v.ldw2; p->W3 = v.W3; p->ldw3 = v.ldw3;
+  p->b1 = v.b1; p->b2 = v.b2; p->b3 = v.b3; p->w3row = v.w3row;
   p->rows = rows; p->H = e->H; p->out_dim = n.out_dim;
-  p->mask_mode = RECNN_MASK_NONE;
-  if (f.mask_idx >= 0 && e->cfg.mask_mode != RECNN_MASK_NONE) {
-    p->mask_mode = e->cfg.mask_mode;
-    if (e->cfg.mask_mode == RECNN_MASK_EXTERNAL) {
-      p->mask1 = e->ext_masks + (int64_t)f.mask_idx * e->cfg.max_rows * e->H;
-      p->mask2 = e->ext_masks + (int64_t)(f.mask_idx + 1) * e->cfg.max_rows * e->H;
-      p->ld_mask = e->H;
-    } else {
-      p->seed = e->cfg.seed; p->stream1 = (uint32_t)f.mask_idx; p->stream2 = (uint32_t)f.mask_idx + 1;
-      p->step_ptr = e->counters; p->step_add = e->run_off;
-    }
-  }
-  p->h1 = f.h1; p->h2 = f.h2; p->ldh = e->Hp;
+  const MaskSel m1 = mask_sel(e, f.mask_idx, f.step_add), m2 = mask_sel(e, mask2_idx(f.mask_idx), f.step_add);
+  p->mask_mode = m1.mode; p->mask1 = m1.ext; p->mask2 = m2.ext; p->ld_mask = m1.pitch;
+  p->seed = m1.seed; p->stream1 = m1.stream; p->stream2 = m2.stream; p->step_ptr = m1.step_ptr; p->step_add = m1.step_add;
+  p->h1 = f.keep ? f.h1 : nullptr; p->h2 = f.keep ? f.h2 : nullptr; p->ldh = e->Hp;
   p->out = f.out; p->ldo = f.ldo;
   p->q = f.q;
   p->cbwd_idx = -1;
@@ -349,49 +512,159 @@ double fill_mlp(const recnn_engine* e, const MlpSpec& f, int rows, MlpProb* p) {
   return 2.0 * rows * ((double)e->H * n.in_dim + (double)e->H * e->H + (double)n.out_dim * e->H);
 }
 
+// ---- the TD head of the learning critics (recnn/nn/update/misc.py:6-7,33-39, td3.py:83-93), whichever launch evaluates it:
+// y = r + (1 - done) gamma min_t Q'_t clamped to [lo, hi] (TD3: not clamped), d_c = 2 (Q_c - y) / rows, loss partials; value_bwd: the
+// small tensors' gradient partial sums go to the critics' slabs
+struct TdDesc {
+  int nc;
+  const float *reward, *done;
+  float gamma, lo, hi;
+  float *expected, *target_q;
+  float *tq[2], *q[2], *delta[2], *loss_part[2];
+  bool train; float scale;                                         // the backward's relu gates times 2 when dropout is active
+  float *dw3_part[2], *db2_part[2], *db1_part[2], *db3_part[2];    // NULL: no parameter gradients wanted
+};
+int td_desc(recnn_engine* e, bool value_bwd, TdDesc* d) {
+  memset(d, 0, sizeof(*d));
+  d->nc = e->n_critic;
+  d->reward = e->reward; d->done = e->done; d->gamma = e->hy.gamma;
+  d->lo = e->td3 ? -INFINITY : e->hy.min_value;
+  d->hi = e->td3 ? INFINITY : e->hy.max_value;
+  d->expected = e->expected; d->target_q = e->target_q;
+  d->train = e->cfg.mask_mode != RECNN_MASK_NONE;
+  d->scale = d->train ? 2.0f : 1.0f;
+  for (int c = 0; c < d->nc; ++c) {
+    const Net& v = e->net[VAL[c]];
+    d->tq[c] = e->tqv[c]; d->q[c] = e->q[c]; d->delta[c] = e->delta[c]; d->loss_part[c] = e->loss_part[c];
+    if (value_bwd) {
+      RECNN_REQUIRE(v.g, "value backward: network %d has no gradient arena bound", VAL[c]);
+      d->dw3_part[c] = v.gp[W3]; d->db2_part[c] = v.gp[B2]; d->db1_part[c] = v.gp[B1]; d->db3_part[c] = v.gp[B3];
+    }
+  }
+  return 0;
+}
+// ... into critic c's problem of the split forward's tail launch (mlpt.hip)
+void td_write(const TdDesc& d, int c, TailProb* p) {
+  p->n_target = d.nc;
+  for (int t = 0; t < d.nc; ++t) p->tq[t] = d.tq[t];
+  p->reward = d.reward; p->done = d.done; p->gamma = d.gamma; p->lo = d.lo; p->hi = d.hi;
+  if (c == 0) { p->expected = d.expected; p->target_q = d.target_q; }
+  p->delta_out = d.delta[c]; p->loss_part = d.loss_part[c];
+  p->scale = d.scale;
+  p->dw3_part = d.dw3_part[c]; p->db2_part = d.db2_part[c]; p->db1_part = d.db1_part[c]; p->db3_part = d.db3_part[c];
+}
+// ... into the head the target actor's workgroup evaluates inside the fused forward (mlps.hip); Q arrives through the hand-off slots
+void td_write(const TdDesc& d, const recnn_engine* e, MlpHead* h) {
+  h->n_critic = d.nc;
+  for (int c = 0; c < d.nc; ++c) {
+    h->q_slot[c] = e->q_slot[c];
+    h->delta_out[c] = d.delta[c]; h->loss_part[c] = d.loss_part[c];
+    h->db3_part[c] = d.db3_part[c];
+  }
+  h->reward = d.reward; h->done = d.done; h->gamma = d.gamma; h->lo = d.lo; h->hi = d.hi;
+  h->expected = d.expected; h->target_q = d.target_q;
+}
+// ... into critic c's problem of the row-panel backward launch (bwd.hip, mode 0)
+void td_write(const TdDesc& d, int c, BwdPanelProb* b) {
+  b->q = d.q[c]; b->n_target = d.nc;
+  for (int t = 0; t < d.nc; ++t) b->tq[t] = d.tq[t];
+  b->reward = d.reward; b->done = d.done; b->gamma = d.gamma; b->lo = d.lo; b->hi = d.hi;
+  if (c == 0) { b->expected = d.expected; b->target_q = d.target_q; }
+  b->delta_out = d.delta[c]; b->loss_part = d.loss_part[c];
+  b->scale = d.scale;
+  b->dw3_part = d.dw3_part[c]; b->db2_part = d.db2_part[c]; b->db3_part = d.db3_part[c]; b->colsum = d.db1_part[c];
+}
+// ... into the head launch (head.hip)
+void td_write(const TdDesc& d, HeadArgs* h) {
+  h->n_target = d.nc; h->n_critic = d.nc;
+  for (int c = 0; c < d.nc; ++c) {
+    h->q[c] = d.q[c]; h->delta[c] = d.delta[c]; h->loss_part[c] = d.loss_part[c];
+    h->dw3_part[c] = d.dw3_part[c]; h->db2_part[c] = d.db2_part[c]; h->db3_part[c] = d.db3_part[c];
+  }
+  h->reward = d.reward; h->done = d.done; h->gamma = d.gamma; h->lo = d.lo; h->hi = d.hi;
+  h->expected = d.expected; h->target_q = d.target_q;
+  h->train = d.train;
+}
+
 // ------------------------------------------------------------------------------------ phases
-// ---- split forward (split.h): problem builders
-void fill_l1(const recnn_engine* e, L1Prob* p, int ni, int rows, const void* A0, int64_t lda0, int K0, int col0, void* h1, int mask_idx,
-             int step_add) {
-  const Net& n = e->net[ni];
+// TD3's target-action noise (td3.py:74-78) for n_sets consecutive batches of `rows` rows, batch j under the key of step + step_add + j;
+// nothing to launch for DDPG or when the caller supplies the noise
+int ph_td3_noise(recnn_engine* e, float* out, int rows, int step_add, int n_sets, hipStream_t s) {
+  if (!e->td3 || e->ext_noise) return 0;
+  return slot(e, "td3_noise", 0, s, [&] { return noise_fill_launch(out, (int64_t)rows * e->A, e->hy.noise_std, e->cfg.seed, e->counters, step_add, s, n_sets); });
+}
+
+// The head launch: TD target, Q, dQ, loss partials (+ with value_bwd: dz2 and the last layer's gradient partials) from the layer-2
+// activations of the critics and target critics.  tq_ready: Q' per row came out of an earlier launch.
+int ph_td_head(recnn_engine* e, int rows, bool value_bwd, bool tq_ready, hipStream_t s) {
+  TdDesc td;
+  int rc;
+  if ((rc = td_desc(e, value_bwd, &td))) return rc;
+  HeadArgs h;
+  memset(&h, 0, sizeof(h));
+  h.rows = rows; h.H = e->H; h.tc_bf16 = e->cfg.dtype; h.ld_h = e->Hp;
+  td_write(td, &h);
+  for (int c = 0; c < td.nc; ++c) {
+    const NetView t = net_view(e, TVAL[c]), v = net_view(e, VAL[c]);
+    h.th2[c] = e->tq[c].h2; h.tw3[c] = t.w3row; h.tb3[c] = t.b3;
+    if (tq_ready) h.tq_in[c] = e->tqv[c];
+    h.ch2[c] = e->cv[c].h2; h.cw3[c] = v.w3row; h.cb3[c] = v.b3;
+    if (value_bwd) h.dz2[c] = e->dzc2[c];
+  }
+  h.policy_mode = 0;
+  h.do_bwd = value_bwd;
+  const GatherArgs* hg = (value_bwd && e->head_gather) ? e->head_gather : nullptr;   // (armed by step_impl: the next step's gather rides here)
+  if ((rc = slot(e, hg ? "head_td_target+gather" : "head_td_target", 0, s, [&] { return head_launch(h, s, hg); }, hg == nullptr))) return rc;
+  if (hg) e->head_gather = nullptr;         // consumed
+  return 0;
+}
+
+// The policy loss's backward seed d = -1/B for every row through the critic's last two layers: dz_e2 and dz_e1 in one row-panel launch
+// (bwd.hip, mode 1), no critic parameter gradients
+int ph_head_dx_pcritic(recnn_engine* e, int rows, hipStream_t s) {
+  BwdPanelBatch bb;
+  memset(&bb, 0, sizeof(bb));
+  BwdPanelProb& b = bb.p[0];
+  const NetView v = net_view(e, RECNN_NET_VALUE1);
+  b.rows = rows; b.H = e->H; b.mode = 1; b.delta_const = -1.0f / (float)rows;
+  b.h2 = e->pc.h2; b.ldh = e->Hp; b.w3 = v.w3row; b.scale = e->cfg.mask_mode != RECNN_MASK_NONE ? 2.0f : 1.0f;
+  b.dz2 = e->dze2; b.W2 = v.W2; b.ldw2 = v.ldw2; b.h1 = e->pc.h1; b.dz1 = e->dze1;
+  return slot(e, "head_dx_pcritic", 2.0 * rows * (double)e->H * e->H, s, [&] { return bwd_panel_launch(bb, 1, s); });
+}
+
+// ---- split forward (split.h): a role's layer 1 as a problem of the tiled launch (l1gemm.hip), its layers 2 / 3 of the tail launch (mlpt.hip)
+void fill_l1(const recnn_engine* e, L1Prob* p, const Role& f, int rows) {
+  const NetView v = net_view(e, f.ni);
   memset(p, 0, sizeof(*p));
-  p->A[0] = A0; p->lda[0] = lda0; p->K[0] = K0; p->w1_col[0] = col0; p->nseg = 1;
-  p->W1 = sh_ptr(e, ni, W1); p->ldw1 = n.ld_w1;
-  p->b1 = n.p + n.off[B1];
+  p->A[0] = f.A0; p->lda[0] = f.lda0; p->K[0] = f.K0; p->w1_col[0] = f.col0; p->nseg = 1;
+  if (f.A1) { p->A[1] = f.A1; p->lda[1] = f.lda1; p->K[1] = f.K1; p->w1_col[1] = f.col1; p->nseg = 2; }
+  p->W1 = v.W1; p->ldw1 = v.ldw1;
+  p->b1 = v.b1;
   p->rows = rows; p->H = e->H;
-  p->mask_mode = RECNN_MASK_NONE;
-  if (mask_idx >= 0 && e->cfg.mask_mode != RECNN_MASK_NONE) {
-    p->mask_mode = e->cfg.mask_mode;
-    if (e->cfg.mask_mode == RECNN_MASK_EXTERNAL) {
-      p->mask = e->ext_masks + (int64_t)mask_idx * e->cfg.max_rows * e->H; p->ld_mask = e->H;
-    } else {
-      p->seed = e->cfg.seed; p->stream = (uint32_t)mask_idx; p->step_ptr = e->counters; p->step_add = step_add;
-    }
-  }
-  p->h1 = h1; p->ldh = e->Hp;
+  const MaskSel m = mask_sel(e, f.mask_idx, f.step_add);
+  p->mask_mode = m.mode; p->mask = m.ext; p->ld_mask = m.pitch;
+  p->seed = m.seed; p->stream = m.stream; p->step_ptr = m.step_ptr; p->step_add = m.step_add;
+  p->h1 = f.h1; p->ldh = e->Hp;
 }
-void l1_seg1(L1Prob* p, const void* A1, int64_t lda1, int K1, int col1) {
-  p->A[1] = A1; p->lda[1] = lda1; p->K[1] = K1; p->w1_col[1] = col1; p->nseg = 2;
-}
-void fill_tail(const recnn_engine* e, TailProb* p, int kind, int ni, int rows, const void* h1, int mask2_idx, int step_add) {
-  const Net& n = e->net[ni];
+// (TailProb and the split-bf16 type's X3TailProb name what they share alike)
+template <class P> void fill_layers23(const recnn_engine* e, P* p, const Role& f, int rows) {
+  const NetView v = net_view(e, f.ni);
   memset(p, 0, sizeof(*p));
+  p->h1 = f.h1; p->ldh = e->Hp;
+  p->W2 = v.W2; p->ldw2 = v.ldw2; p->W3 = v.W3; p->ldw3 = v.ldw3;
+  p->b2 = v.b2; p->b3 = v.b3; p->w3row = v.w3row;
+  p->rows = rows; p->H = e->H; p->out_dim = e->net[f.ni].out_dim;
+  const MaskSel m = mask_sel(e, mask2_idx(f.mask_idx), f.step_add);
+  p->mask_mode = m.mode; p->mask2 = m.ext; p->ld_mask = m.pitch;
+  p->seed = m.seed; p->stream2 = m.stream; p->step_ptr = m.step_ptr; p->step_add = m.step_add;
+  p->h2 = f.keep ? f.h2 : nullptr;
+  p->out = f.out; p->ldo = f.ldo;
+  p->addend = f.addend; p->ld_add = f.ld_add; p->add_clip = f.add_clip;
+  p->q = f.q;
+}
+void fill_tail(const recnn_engine* e, TailProb* p, int kind, const Role& f, int rows) {
+  fill_layers23(e, p, f, rows);
   p->kind = kind;
-  p->h1 = h1; p->ldh = e->Hp;
-  p->W2 = sh_ptr(e, ni, W2); p->ldw2 = n.ld_w2;
-  if (!n.critic) { p->W3 = sh_ptr(e, ni, W3); p->ldw3 = n.ld_w3; }
-  p->b2 = n.p + n.off[B2]; p->b3 = n.p + n.off[B3];
-  p->w3row = n.critic ? n.p + n.off[W3] : nullptr;
-  p->rows = rows; p->H = e->H; p->out_dim = n.out_dim;
-  p->mask_mode = RECNN_MASK_NONE;
-  if (mask2_idx >= 0 && e->cfg.mask_mode != RECNN_MASK_NONE) {
-    p->mask_mode = e->cfg.mask_mode;
-    if (e->cfg.mask_mode == RECNN_MASK_EXTERNAL) {
-      p->mask2 = e->ext_masks + (int64_t)mask2_idx * e->cfg.max_rows * e->H; p->ld_mask = e->H;
-    } else {
-      p->seed = e->cfg.seed; p->stream2 = (uint32_t)mask2_idx; p->step_ptr = e->counters; p->step_add = step_add;
-    }
-  }
 }
 
 // The forward of one step, split (e->tune.split_fwd): frozen networks first (target actor -> target critics on its action; the
@@ -399,39 +672,28 @@ void fill_tail(const recnn_engine* e, TailProb* p, int kind, int ni, int rows, c
 // inside run graphs the frozen half is hoisted out of the step and applied to a whole policy cycle at once (capture_run).
 int ph_forward_split(recnn_engine* e, int rows, bool value_side, bool actor_side, bool value_bwd, hipStream_t s, bool frozen_done = false) {
   const int A = e->A, nc = e->n_critic;
-  const int POL = RECNN_NET_POLICY, TPOL = RECNN_NET_TARGET_POLICY;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2}, TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
-  const int actor_m1 = e->td3 ? 4 : 2;
-  const int64_t aoff = tc_off(e, A);
+  const StepBufs B = step_bufs(e);
   const double l1_fl_a = 2.0 * rows * (double)e->H * e->S, l1_fl_c = 2.0 * rows * (double)e->H * (e->S + A);
   const double t_fl_a = 2.0 * rows * ((double)e->H * e->H + (double)A * e->H), t_fl_c = 2.0 * rows * ((double)e->H * e->H + e->H);
   int rc = 0;
-  if (!frozen_done && value_side && e->td3 && !e->ext_noise) {
-    if ((rc = slot(e, "td3_noise", 0, s, [&] { return noise_fill_launch(e->noise_buf, (int64_t)rows * A, e->hy.noise_std, e->cfg.seed, e->counters, e->run_off, s); }))) return rc;
-  }
-  if (!frozen_done) {  // ---- frozen networks, layer 1: target actor on s', actor on s
+  if (!frozen_done && value_side && (rc = ph_td3_noise(e, e->noise_buf, rows, e->run_off, 1, s))) return rc;
+  if (!frozen_done) {  // ---- frozen networks: target actor on s', actor on s
     L1Batch lb;
-    int np = 0;
-    double fl = 0;
-    if (value_side) { fill_l1(e, &lb.p[np++], TPOL, rows, e->xcn + aoff, e->ldx, e->K1a, 0, e->tp.h1, -1, e->run_off); fl += l1_fl_a; }
-    if (actor_side) { fill_l1(e, &lb.p[np++], POL, rows, e->xcs + aoff, e->ldx, e->K1a, 0, e->pa.h1, actor_m1, e->run_off); fl += l1_fl_a; }
-    if (np && (rc = slot(e, "l1_actors", fl, s, [&] { return l1gemm_launch(lb, np, 0, s, e->tune.l1_ws); }))) return rc;
     TailBatch tb;
-    np = 0; fl = 0;
-    if (value_side) {   // next_action into the action slot of the packed next rows (+ TD3's clipped noise, td3.py:74-78)
-      TailProb* p = &tb.p[np++];
-      fill_tail(e, p, TAIL_ACTOR, TPOL, rows, e->tp.h1, -1, e->run_off);
-      p->out = e->xcn; p->ldo = e->ldx;
-      if (e->td3) { p->addend = e->ext_noise ? e->ext_noise : e->noise_buf; p->ld_add = A; p->add_clip = e->hy.noise_clip; }
-      fl += t_fl_a;
+    int np = 0;
+    double fl = 0, tfl = 0;
+    if (value_side) {
+      const Role r = role_target_actor(e, B);
+      fill_l1(e, &lb.p[np], r, rows); fill_tail(e, &tb.p[np++], TAIL_ACTOR, r, rows);
+      fl += l1_fl_a; tfl += t_fl_a;
     }
     if (actor_side) {
-      TailProb* p = &tb.p[np++];
-      fill_tail(e, p, TAIL_ACTOR, POL, rows, e->pa.h1, actor_m1 + 1, e->run_off);
-      p->h2 = e->pa.h2; p->out = e->gen_action; p->ldo = e->Ap;
-      fl += t_fl_a;
+      const Role r = role_actor(e, B);
+      fill_l1(e, &lb.p[np], r, rows); fill_tail(e, &tb.p[np++], TAIL_ACTOR, r, rows);
+      fl += l1_fl_a; tfl += t_fl_a;
     }
-    if (np && (rc = slot(e, "tail_actors", fl, s, [&] { return mlpt_launch(tb, np, s); }))) return rc;
+    if (np && (rc = slot(e, "l1_actors", fl, s, [&] { return l1gemm_launch(lb, np, 0, s, e->tune.l1_ws); }))) return rc;
+    if (np && (rc = slot(e, "tail_actors", tfl, s, [&] { return mlpt_launch(tb, np, s); }))) return rc;
   }
   e->panel_bwd_done = false;
   e->unit_bwd = false;
@@ -443,15 +705,13 @@ int ph_forward_split(recnn_engine* e, int rows, bool value_side, bool actor_side
   // + rows / 32 panels of the deferred policy-loss critic <= 256.  DDPG at 2048 rows: 192 (53.9 vs 57.3 us/step); TD3 at 4096 rows would be
   // 640 -- measured 130.5 vs 124.1 us/step with 32-row panels (profiles/NOTES_r06.md)
   const bool half = e->tune.tail_half && value_bwd && rows % 32 == 0 && (2 * nc + 1) * (rows / 32) <= 256;
-  if (!frozen_done) {  // ---- target critics on [next_state | next_action]: state part first, then the action columns (mlps.hip's chained order)
+  if (!frozen_done) {  // ---- target critics on [next_state | next_action]
     L1Batch lb;
     TailBatch tb;
     double fl = 0, tfl = 0;
     for (int c = 0; c < nc; ++c) {
-      fill_l1(e, &lb.p[c], TVAL[c], rows, e->xcn + aoff, e->ldx, e->K1a, A, e->tq[c].h1, -1, e->run_off);
-      l1_seg1(&lb.p[c], e->xcn, e->ldx, e->Ap, 0);
-      fill_tail(e, &tb.p[c], TAIL_CRITIC_Q, TVAL[c], rows, e->tq[c].h1, -1, e->run_off);
-      tb.p[c].q = e->tqv[c];
+      const Role r = role_target_critic(e, B, c, false);
+      fill_l1(e, &lb.p[c], r, rows); fill_tail(e, &tb.p[c], TAIL_CRITIC_Q, r, rows);
       fl += l1_fl_c; tfl += t_fl_c;
     }
     if ((rc = slot(e, "l1_target_critic", fl, s, [&] { return l1gemm_launch(lb, nc, 0, s, e->tune.l1_ws); }))) return rc;
@@ -462,37 +722,21 @@ int ph_forward_split(recnn_engine* e, int rows, bool value_side, bool actor_side
     TailBatch tb;
     int np = 0;
     double fl = 0, tfl = 0;
-    const bool train = e->cfg.mask_mode != RECNN_MASK_NONE;
+    TdDesc td;
+    if ((rc = td_desc(e, value_bwd, &td))) return rc;
     for (int c = 0; c < nc; ++c) {
-      Net& v = e->net[VAL[c]];
-      fill_l1(e, &lb.p[np], VAL[c], rows, e->xcs, e->ldx, e->K1c, 0, e->cv[c].h1, 2 * c, e->run_off);
+      const Role r = role_critic(e, B, c);
+      fill_l1(e, &lb.p[np], r, rows);
       TailProb* p = &tb.p[np++];
-      fill_tail(e, p, TAIL_CRITIC_LEARN, VAL[c], rows, e->cv[c].h1, 2 * c + 1, e->run_off);
-      p->h2 = e->cv[c].h2; p->q = e->q[c];
-      p->n_target = nc;
-      for (int t = 0; t < nc; ++t) p->tq[t] = e->tqv[t];
-      p->reward = e->reward; p->done = e->done; p->gamma = e->hy.gamma;
-      p->lo = e->td3 ? -INFINITY : e->hy.min_value;
-      p->hi = e->td3 ? INFINITY : e->hy.max_value;
-      if (c == 0) { p->expected = e->expected; p->target_q = e->target_q; }
-      p->delta_out = e->delta[c]; p->loss_part = e->loss_part[c];
-      p->scale = train ? 2.0f : 1.0f;
+      fill_tail(e, p, TAIL_CRITIC_LEARN, r, rows);
+      td_write(td, c, p);
       p->half_panels = half;
       p->dz2 = e->dzc2[c]; p->dz1 = e->dzc1[c];
-      if (value_bwd) {
-        RECNN_REQUIRE(v.g, "value backward: network %d has no gradient arena bound", VAL[c]);
-        p->dw3_part = v.gp[W3]; p->db2_part = v.gp[B2]; p->db1_part = v.gp[B1]; p->db3_part = v.gp[B3];
-      }
       fl += l1_fl_c; tfl += t_fl_c + 2.0 * rows * (double)e->H * e->H;
     }
     if (e->pending_pc.on && np < L1_MAX_GROUP) {
-      const auto& pp = e->pending_pc;
-      const int m0 = e->td3 ? 6 : 4;
-      fill_l1(e, &lb.p[np], RECNN_NET_VALUE1, rows, pp.ga, e->Ap, e->Ap, 0, e->pc.h1, m0, pp.run_off);
-      l1_seg1(&lb.p[np], pp.xs + aoff, e->ldx, e->K1a, A);
-      TailProb* p = &tb.p[np++];
-      fill_tail(e, p, TAIL_CRITIC_Q, RECNN_NET_VALUE1, rows, e->pc.h1, m0 + 1, pp.run_off);
-      p->q = e->pl_part_base + (int64_t)pp.slot * e->pl_cap;   // that step's policy-loss slot: Q per row, b3 included
+      const Role r = role_deferred_critic(e);
+      fill_l1(e, &lb.p[np], r, rows); fill_tail(e, &tb.p[np++], TAIL_CRITIC_Q, r, rows);
       fl += l1_fl_c; tfl += t_fl_c;
       e->pending_pc.on = false;
     }
@@ -508,23 +752,8 @@ int ph_forward_split(recnn_engine* e, int rows, bool value_side, bool actor_side
   return 0;
 }
 
-// layers 2 (+ 3) of network ni as a problem of the split-bf16 row-panel launch (x3tail.hip); mask_idx: dropout stream of layer 2
-void fill_x3tail(const recnn_engine* e, X3TailProb* p, int ni, int rows, const void* h1, int mask_idx, int step_add) {
-  const Net& n = e->net[ni];
-  memset(p, 0, sizeof(*p));
-  p->h1 = h1; p->ldh = e->Hp;
-  p->W2 = sh_ptr(e, ni, W2); p->ldw2 = n.ld_w2;
-  p->b2 = n.p + n.off[B2]; p->b3 = n.p + n.off[B3];
-  if (n.out_dim > 1) { p->W3 = sh_ptr(e, ni, W3); p->ldw3 = n.ld_w3; }
-  else p->w3row = n.p + n.off[W3];
-  p->rows = rows; p->H = e->H; p->out_dim = n.out_dim;
-  p->mask_mode = RECNN_MASK_NONE;
-  if (mask_idx >= 0 && e->cfg.mask_mode != RECNN_MASK_NONE) {
-    p->mask_mode = e->cfg.mask_mode;
-    if (e->cfg.mask_mode == RECNN_MASK_EXTERNAL) { p->mask2 = e->ext_masks + (int64_t)mask_idx * e->cfg.max_rows * e->H; p->ld_mask = e->H; }
-    else { p->seed = e->cfg.seed; p->stream2 = (uint32_t)mask_idx; p->step_ptr = e->counters; p->step_add = step_add; }
-  }
-}
+// layers 2 (+ 3) of a role as a problem of the split-bf16 row-panel launch (x3tail.hip)
+void fill_x3tail(const recnn_engine* e, X3TailProb* p, const Role& f, int rows) { fill_layers23(e, p, f, rows); }
 bool x3_tail_ok(const recnn_engine* e) {
   return e->x3 && e->tune.x3_tail && e->H == 256 && e->Hp == 512 && e->A == 128 && e->net[RECNN_NET_POLICY].ld_w2 == e->net[RECNN_NET_POLICY].ld_w3;
 }
@@ -542,72 +771,51 @@ bool x3_tail_ok(const recnn_engine* e) {
 // summation order of the target critic's layer 1.
 int ph_forward_x3(recnn_engine* e, int rows, bool value_side, bool actor_side, bool value_bwd, hipStream_t s) {
   const int A = e->A, Hp = e->Hp, nc = e->n_critic;
-  const int POL = RECNN_NET_POLICY, TPOL = RECNN_NET_TARGET_POLICY;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2}, TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
-  const int actor_m1 = e->td3 ? 4 : 2;
-  const int64_t aoff = tc_off(e, A);
   const int ldp = e->Hl > 256 ? e->Hl : 256;     // row pitch of the fp32 layer-1 parts
   int rc;
   const bool pend = e->pending_pc.on;
-  const recnn_engine::PendingPc pp = e->pending_pc;
+  const int pend_slot = e->pending_pc.slot;
+  Role pc{};                                     // the deferred policy-loss critic on [pi(s) | s] of the previous batch
+  if (pend) pc = role_deferred_critic(e);
   e->pending_pc.on = false;
-  const int m0 = e->td3 ? 6 : 4;
   // DDPG's first launch is exactly one round of 64 x 128 tiles on 256 CUs without the deferred policy-loss critic (4 problems x 64
   // tiles); a fifth problem would cost a whole second round (measured 44.6 us against ~28).  It rides with the target critic's
   // k = 128 launch and panel tail instead, which fill a quarter of the machine.  (TD3's first launch is two rounds either way.)
   const bool pend_late = pend && value_side && !e->td3 && x3_tail_ok(e);
-  auto pc_l1 = [&](Group& g) {     // layer 1 of the deferred policy-loss critic on [pi(s) | s] of the previous batch
-    FwdSpec f{RECNN_NET_VALUE1, 1, pp.ga, e->Ap, 0, e->Ap};
-    f.b_col = 0;
-    f.A2 = pp.xs + aoff; f.lda2 = e->ldx; f.K2 = e->K1a; f.b2_col = A;
-    f.C = e->pc.h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = m0;
-    GemmProb* p = g.add();
-    g.flops += fill_fwd(e, f, rows, p);
-    p->step_add = pp.run_off;
-  };
-  auto pc_tail = [&](X3TailProb* p) -> int {
-    fill_x3tail(e, p, RECNN_NET_VALUE1, rows, e->pc.h1, m0 + 1, pp.run_off);
-    p->q_part = e->pl_part_base + (int64_t)pp.slot * e->pl_cap;
-    const int parts = ((rows + 31) / 32) * x3tail_parts_per_panel();
-    RECNN_REQUIRE(parts <= e->pl_cap, "policy loss: %d partial sums do not fit %d", parts, e->pl_cap);
-    if (pp.slot < LOSS_HIST_MAX) { e->hist_pol_count[pp.slot] = parts; e->hist_pol_add[pp.slot] = 0; }
-    return 0;
+  const StepBufs B = step_bufs(e);
+  Role net[4], tc[2] = {};                       // target actor, critics, actor: the order of every launch that carries them
+  int nn = 0;
+  if (value_side) {
+    net[nn++] = role_target_actor(e, B);
+    for (int c = 0; c < nc; ++c) {
+      net[nn] = role_critic(e, B, c);
+      net[nn++].q = nullptr;                     // (Q comes out of the head launch here)
+      tc[c] = role_target_critic(e, B, c, false);
+    }
+  }
+  if (actor_side) net[nn++] = role_actor(e, B);
+  auto pc_tail = [&](X3TailProb* p) -> int {     // ... its sums of Q per panel into that step's policy-loss slot
+    fill_x3tail(e, p, pc, rows);
+    p->q = nullptr; p->q_part = pc.q;
+    return note_policy_parts(e, pend_slot, ((rows + 31) / 32) * x3tail_parts_per_panel());
   };
   {  // ---- L1
     Group g(e, GEMM_FWD, 0, 0);
-    if (value_side) {
-      FwdSpec f{TPOL, 1, e->xcn + aoff, e->ldx, 0, e->K1a};
-      f.C = e->tp.h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-      for (int c = 0; c < nc; ++c) {
-        FwdSpec fc{VAL[c], 1, e->xcs, e->ldx, 0, e->K1c};
-        fc.C = e->cv[c].h1; fc.ldc = Hp; fc.c_f32 = 0; fc.relu = 1; fc.mask_idx = 2 * c;
-        g.flops += fill_fwd(e, fc, rows, g.add());
-      }
+    for (int i = 0; i < nn; ++i) add_layer(g, net[i], 1, rows);
+    for (int c = 0; c < nc && value_side; ++c) {   // state columns of the target critic's W1 shadow ([action | state] order): raw fp32, no bias
+      FwdSpec f{tc[c].ni, 1, tc[c].A0, tc[c].lda0, 0, tc[c].K0};
+      f.b_col = tc[c].col0;
+      f.C = e->tc_part[c]; f.ldc = ldp; f.c_f32 = 1; f.relu = 0; f.mask_idx = -1;
+      GemmProb* p = g.add();
+      fill_fwd(e, f, rows, p);
+      p->bias = nullptr;
+      g.flops += 2.0 * rows * (double)e->H * e->S;
     }
-    if (actor_side) {
-      FwdSpec f{POL, 1, e->xcs + aoff, e->ldx, 0, e->K1a};
-      f.C = e->pa.h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = actor_m1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if (value_side) {
-      for (int c = 0; c < nc; ++c) {   // state columns of the target critic's W1 shadow ([action | state] order): raw fp32, no bias
-        FwdSpec f{TVAL[c], 1, e->xcn + aoff, e->ldx, 0, e->K1a};
-        f.b_col = A;
-        f.C = e->tc_part[c]; f.ldc = ldp; f.c_f32 = 1; f.relu = 0; f.mask_idx = -1;
-        GemmProb* p = g.add();
-        fill_fwd(e, f, rows, p);
-        p->bias = nullptr;
-        g.flops += 2.0 * rows * (double)e->H * e->S;
-      }
-    }
-    if (pend && !pend_late && g.L.nprob < GEMM_MAX_GROUP) pc_l1(g);
+    if (pend && !pend_late && g.L.nprob < GEMM_MAX_GROUP) add_layer(g, pc, 1, rows);
     if ((rc = g.run(s, "fwd_l1"))) return rc;
   }
   const bool tails = x3_tail_ok(e);
-  if (value_side && e->td3 && !e->ext_noise) {
-    if ((rc = slot(e, "td3_noise", 0, s, [&] { return noise_fill_launch(e->noise_buf, (int64_t)rows * A, e->hy.noise_std, e->cfg.seed, e->counters, e->run_off, s); }))) return rc;
-  }
+  if (value_side && (rc = ph_td3_noise(e, e->noise_buf, rows, e->run_off, 1, s))) return rc;
   if (tails) {
     // ---- layers 2 + 3 of everything whose layer 1 exists, ONE launch of 32-row panels (x3tail.hip): target actor -> next_action
     // (+ TD3 noise), critics -> h2 (the head and the backward read it), actor -> h2, gen_action, deferred policy-loss critic -> sums of Q
@@ -615,24 +823,9 @@ int ph_forward_x3(recnn_engine* e, int rows, bool value_side, bool actor_side, b
     int np = 0;
     double fl = 0;
     const double fl2 = 2.0 * rows * (double)e->H * e->H;
-    if (value_side) {
-      X3TailProb* p = &tb.p[np++];
-      fill_x3tail(e, p, TPOL, rows, e->tp.h1, -1, e->run_off);
-      p->out = e->xcn; p->ldo = e->ldx;
-      if (e->td3) { p->addend = e->ext_noise ? e->ext_noise : e->noise_buf; p->ld_add = A; p->add_clip = e->hy.noise_clip; }
-      fl += fl2 + 2.0 * rows * (double)e->H * A;
-      for (int c = 0; c < nc; ++c) {
-        p = &tb.p[np++];
-        fill_x3tail(e, p, VAL[c], rows, e->cv[c].h1, 2 * c + 1, e->run_off);
-        p->h2 = e->cv[c].h2;
-        fl += fl2;
-      }
-    }
-    if (actor_side) {
-      X3TailProb* p = &tb.p[np++];
-      fill_x3tail(e, p, POL, rows, e->pa.h1, actor_m1 + 1, e->run_off);
-      p->h2 = e->pa.h2; p->out = e->gen_action; p->ldo = e->Ap;
-      fl += fl2 + 2.0 * rows * (double)e->H * A;
+    for (int i = 0; i < nn; ++i) {
+      fill_x3tail(e, &tb.p[np++], net[i], rows);
+      fl += net[i].out ? fl2 + 2.0 * rows * (double)e->H * A : fl2;
     }
     if (pend && !pend_late) {
       if ((rc = pc_tail(&tb.p[np++]))) return rc;
@@ -640,56 +833,10 @@ int ph_forward_x3(recnn_engine* e, int rows, bool value_side, bool actor_side, b
     }
     if (np && (rc = slot(e, "x3_tail", fl, s, [&] { return x3tail_launch(tb, np, s); }))) return rc;
   } else {
-  {  // ---- L2
-    Group g(e, GEMM_FWD, 0, 0);
-    if (value_side) {
-      FwdSpec f{TPOL, 2, e->tp.h1, Hp, 0, Hp};
-      f.C = e->tp.h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-      for (int c = 0; c < nc; ++c) {
-        FwdSpec fc{VAL[c], 2, e->cv[c].h1, Hp, 0, Hp};
-        fc.C = e->cv[c].h2; fc.ldc = Hp; fc.c_f32 = 0; fc.relu = 1; fc.mask_idx = 2 * c + 1;
-        g.flops += fill_fwd(e, fc, rows, g.add());
-      }
-    }
-    if (actor_side) {
-      FwdSpec f{POL, 2, e->pa.h1, Hp, 0, Hp};
-      f.C = e->pa.h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = actor_m1 + 1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    int pend_idx = -1;
-    if (pend && g.L.nprob < GEMM_MAX_GROUP) {   // the deferred policy-loss critic: -mean Q from the epilogue's partial dots (b3 included)
-      const Net& v = e->net[RECNN_NET_VALUE1];
-      FwdSpec f{RECNN_NET_VALUE1, 2, e->pc.h1, Hp, 0, Hp};
-      f.C = e->pc.h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = m0 + 1;
-      f.dot_w = v.p + v.off[W3]; f.dot_bias = v.p + v.off[B3]; f.dot_part = e->pl_part_base + (int64_t)pp.slot * e->pl_cap;
-      pend_idx = g.L.nprob;
-      GemmProb* p = g.add();
-      g.flops += fill_fwd(e, f, rows, p);
-      p->step_add = pp.run_off;
-    }
-    if ((rc = g.run(s, "fwd_l2"))) return rc;
-    if (pend_idx >= 0) {
-      const int parts = g.L.batch.p[pend_idx].dot_parts;
-      RECNN_REQUIRE(parts > 0 && parts <= e->pl_cap, "policy loss: %d partial sums do not fit %d", parts, e->pl_cap);
-      if (pp.slot < LOSS_HIST_MAX) { e->hist_pol_count[pp.slot] = parts; e->hist_pol_add[pp.slot] = 0; }
-    }
-  }
-  {  // ---- L3 of the actors: next_action into the action slot of the packed next rows, gen_action
-    Group g(e, GEMM_FWD, 0, 0);
-    if (value_side) {
-      FwdSpec f{TPOL, 3, e->tp.h2, Hp, 0, Hp};
-      f.C = e->xcn; f.ldc = e->ldx; f.c_f32 = 0; f.relu = 0; f.mask_idx = -1;
-      if (e->td3) { f.addend = e->ext_noise ? e->ext_noise : e->noise_buf; f.ld_add = A; f.add_clip = e->hy.noise_clip; }
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if (actor_side) {
-      FwdSpec f{POL, 3, e->pa.h2, Hp, 0, Hp};
-      f.C = e->gen_action; f.ldc = e->Ap; f.c_f32 = 0; f.relu = 0; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if ((rc = g.run(s, "fwd_l3_actors"))) return rc;
-  }
+    int parts = -1;   // L2: the deferred policy-loss critic rides here, -mean Q from the epilogue's partial dots
+    if ((rc = fwd_layer(e, rows, 2, net, nn, "fwd_l2", s, pend ? &pc : nullptr, &parts))) return rc;
+    if (parts >= 0 && (rc = note_policy_parts(e, pend_slot, parts))) return rc;
+    if ((rc = fwd_layer(e, rows, 3, net, nn, "fwd_l3_actors", s))) return rc;
   }
   e->panel_bwd_done = false;
   e->half_panels = false;
@@ -698,80 +845,35 @@ int ph_forward_x3(recnn_engine* e, int rows, bool value_side, bool actor_side, b
   {  // ---- target critics: the action part on top of the state part
     Group g(e, GEMM_FWD, 0, 0);
     for (int c = 0; c < nc; ++c) {
-      FwdSpec f{TVAL[c], 1, e->xcn, e->ldx, 0, e->Ap};
-      f.C = e->tq[c].h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
+      FwdSpec f{tc[c].ni, 1, tc[c].A1, tc[c].lda1, 0, tc[c].K1};
+      f.b_col = tc[c].col1;
+      f.C = tc[c].h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
       f.addend = e->tc_part[c]; f.ld_add = ldp; f.add_clip = INFINITY;
       g.flops += 2.0 * rows * (double)e->H * A;
       fill_fwd(e, f, rows, g.add());
     }
-    if (pend_late) pc_l1(g);
+    if (pend_late) add_layer(g, pc, 1, rows);
     if ((rc = g.run(s, "fwd_l1_target_critic"))) return rc;
   }
   if (tails) {   // Q'(s', a') per row: layer 2 and the last layer's dot in one panel launch
     X3TailBatch tb;
-    for (int c = 0; c < nc; ++c) {
-      fill_x3tail(e, &tb.p[c], TVAL[c], rows, e->tq[c].h1, -1, e->run_off);
-      tb.p[c].q = e->tqv[c];
-    }
+    for (int c = 0; c < nc; ++c) fill_x3tail(e, &tb.p[c], tc[c], rows);
     int np = nc;
     if (pend_late && (rc = pc_tail(&tb.p[np++]))) return rc;
     if ((rc = slot(e, "x3_tail_target_critic", np * 2.0 * rows * (double)e->H * e->H, s, [&] { return x3tail_launch(tb, np, s); }))) return rc;
-  } else {
-    Group g(e, GEMM_FWD, 0, 0);
-    for (int c = 0; c < nc; ++c) {
-      FwdSpec f{TVAL[c], 2, e->tq[c].h1, Hp, 0, Hp};
-      f.C = e->tq[c].h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if ((rc = g.run(s, "fwd_l2_target_critic"))) return rc;
+  } else if ((rc = fwd_layer(e, rows, 2, tc, nc, "fwd_l2_target_critic", s))) {
+    return rc;
   }
-  {  // heads: TD target, Q, dQ, loss partials (+ dz2 and the last layer's gradient partials)
-    HeadArgs h;
-    memset(&h, 0, sizeof(h));
-    h.rows = rows; h.H = e->H; h.tc_bf16 = e->cfg.dtype; h.ld_h = Hp;
-    h.n_target = nc;
-    for (int c = 0; c < nc; ++c) {
-      const Net& t = e->net[TVAL[c]];
-      h.th2[c] = e->tq[c].h2; h.tw3[c] = t.p + t.off[W3]; h.tb3[c] = t.p + t.off[B3];
-      if (tails) h.tq_in[c] = e->tqv[c];
-      const Net& v = e->net[VAL[c]];
-      h.ch2[c] = e->cv[c].h2; h.cw3[c] = v.p + v.off[W3]; h.cb3[c] = v.p + v.off[B3];
-      h.q[c] = e->q[c]; h.delta[c] = e->delta[c]; h.loss_part[c] = e->loss_part[c];
-    }
-    h.reward = e->reward; h.done = e->done;
-    h.gamma = e->hy.gamma;
-    h.lo = e->td3 ? -INFINITY : e->hy.min_value;
-    h.hi = e->td3 ? INFINITY : e->hy.max_value;
-    h.expected = e->expected; h.target_q = e->target_q;
-    h.n_critic = nc;
-    h.policy_mode = 0;
-    h.do_bwd = value_bwd;
-    h.train = e->cfg.mask_mode != RECNN_MASK_NONE;
-    if (value_bwd) {
-      for (int c = 0; c < nc; ++c) {
-        Net& v = e->net[VAL[c]];
-        RECNN_REQUIRE(v.g, "value backward: network %d has no gradient arena bound", VAL[c]);
-        h.dz2[c] = e->dzc2[c]; h.dw3_part[c] = v.gp[W3]; h.db2_part[c] = v.gp[B2]; h.db3_part[c] = v.gp[B3];
-      }
-    }
-    {
-      const GatherArgs* hg = (value_bwd && e->head_gather) ? e->head_gather : nullptr;   // (armed by step_impl: the next step's gather rides here)
-      if ((rc = slot(e, hg ? "head_td_target+gather" : "head_td_target", 0, s, [&] { return head_launch(h, s, hg); }, hg == nullptr))) return rc;
-      if (hg) e->head_gather = nullptr;         // consumed
-    }
-  }
-  return 0;
+  return ph_td_head(e, rows, value_bwd, tails, s);   // (+ dz2 and the last layer's gradient partials)
 }
 
 // Forward of the value side (+ optionally the actor forward, which is independent of it).
 int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool value_bwd, hipStream_t s) {
   const int A = e->A, Hp = e->Hp, nc = e->n_critic;
-  const int POL = RECNN_NET_POLICY, TPOL = RECNN_NET_TARGET_POLICY;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2}, TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
-  const int actor_m1 = e->td3 ? 4 : 2;  // external mask index of the actor's first dropout
   int rc;
   if (e->x3) return ph_forward_x3(e, rows, value_side, actor_side, value_bwd, s);
   if (e->tune.split_fwd >= 2 && value_chain_ok(e) && e->tune.bwd_panel >= 2 && e->H % 8 == 0) return ph_forward_split(e, rows, value_side, actor_side, value_bwd, s);
+  const StepBufs B = step_bufs(e);
   bool chained = false;  // target critics computed inside the first fused launch
   bool fwd_did_bwd = false;  // ... and the critics' head + layer-2 backward too
   // chained target critics add nc producer problems, so a value-side launch always has >= 3 problems
@@ -779,198 +881,101 @@ int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool
   const int n_first = (value_side ? 1 + nc : 0) + (actor_side ? 1 : 0) + (can_chain ? nc : 0);
   if (fused_mlp_ok(e, n_first)) {
     // whole networks per launch: {target actor, critic(s), actor}
-    if (value_side && e->td3 && !e->ext_noise) {
-      if ((rc = slot(e, "td3_noise", 0, s, [&] { return noise_fill_launch(e->noise_buf, (int64_t)rows * A, e->hy.noise_std, e->cfg.seed, e->counters, e->run_off, s); }))) return rc;
+    if (value_side && (rc = ph_td3_noise(e, e->noise_buf, rows, e->run_off, 1, s))) return rc;
+    MlpBatch mb;
+    memset(&mb, 0, sizeof(mb));
+    int np = 0;
+    double fl = 0;
+    chained = can_chain;
+    const bool in_fwd_bwd = chained && e->tune.bwd_panel >= 2 && mlp_waves() == 16;
+    fwd_did_bwd = in_fwd_bwd;
+    TdDesc td;
+    if (in_fwd_bwd && (rc = td_desc(e, value_bwd, &td))) return rc;
+    if (chained) {
+      // producers first (launch order = dispatch order): state part of each target critic's layer 1, nothing else of the network
+      for (int c = 0; c < nc; ++c) {
+        Role r = role_target_critic(e, B, c, false);
+        r.A1 = nullptr;                          // (the action part: in the target actor's workgroup, MlpTail below)
+        MlpProb* p = &mb.p[np++];
+        fill_mlp(e, r, rows, p);
+        p->W2 = nullptr; p->W3 = nullptr; p->q = nullptr;
+        p->part_out = e->tc_part[c]; p->part_flag = e->tc_flag[c];
+        fl += 2.0 * rows * (double)e->H * e->S;
+      }
     }
-    const int64_t aoff = tc_off(e, A);
-    {
-      MlpBatch mb;
-      memset(&mb, 0, sizeof(mb));
-      int np = 0;
-      double fl = 0;
-      chained = can_chain;
-      const bool in_fwd_bwd = chained && e->tune.bwd_panel >= 2 && mlp_waves() == 16;
-      fwd_did_bwd = in_fwd_bwd;
+    if (value_side) {
+      // launch order = dispatch order, and a workgroup may only wait for workgroups dispatched before it: the critics
+      // (whose Q(s, a) the head in the target actor's workgroup picks up) come BEFORE the target actor, like the
+      // target critics' layer-1 producers -- otherwise a batch with more panels than CUs would dead-lock (bounded)
+      for (int c = 0; c < nc; ++c) {
+        MlpProb* pc = &mb.p[np++];
+        fl += fill_mlp(e, role_critic(e, B, c), rows, pc);
+        if (in_fwd_bwd) {
+          MlpCriticBwd& cb = mb.cbwd[c];
+          pc->cbwd_idx = c;
+          cb.enabled = 1;
+          cb.q_slot = e->q_slot[c];
+          cb.scale = td.scale;
+          cb.dz2 = e->dzc2[c]; cb.dz1 = e->dzc1[c];   // UNIT tensors: the dW launch applies the per-row seed e->delta[c]
+          fl += 2.0 * rows * (double)e->H * e->H;
+        }
+      }
+      MlpProb* pt = &mb.p[np++];
+      fl += fill_mlp(e, role_target_actor(e, B), rows, pt);
+      if (in_fwd_bwd) td_write(td, e, &mb.head);
       if (chained) {
-        // producers first (launch order = dispatch order): state part of each target critic's layer 1
+        pt->n_tail = nc;
         for (int c = 0; c < nc; ++c) {
-          MlpSpec fp{TVAL[c], e->xcn + aoff, e->ldx, e->K1a, A};
-          MlpProb* p = &mb.p[np++];
-          fill_mlp(e, fp, rows, p);
-          p->W2 = nullptr; p->W3 = nullptr; p->q = nullptr;
-          p->part_out = e->tc_part[c]; p->part_flag = e->tc_flag[c];
-          fl += 2.0 * rows * (double)e->H * e->S;
+          const NetView t = net_view(e, TVAL[c]);
+          MlpTail& T = mb.tail[c];
+          T.part = e->tc_part[c]; T.flag = e->tc_flag[c];
+          T.W1a = t.W1; T.ldw1 = t.ldw1;
+          T.W2 = t.W2; T.ldw2 = t.ldw2;
+          T.b1 = t.b1; T.b2 = t.b2; T.b3 = t.b3; T.w3row = t.w3row;
+          T.q = B.tq[c];
+          fl += 2.0 * rows * ((double)e->H * A + (double)e->H * e->H + e->H);
         }
       }
-      if (value_side) {
-        // launch order = dispatch order, and a workgroup may only wait for workgroups dispatched before it: the critics
-        // (whose Q(s, a) the head in the target actor's workgroup picks up) come BEFORE the target actor, like the
-        // target critics' layer-1 producers -- otherwise a batch with more panels than CUs would dead-lock (bounded)
-        for (int c = 0; c < nc; ++c) {
-          MlpSpec fc{VAL[c], e->xcs, e->ldx, e->K1c, 0};
-          fc.h1 = e->cv[c].h1; fc.h2 = e->cv[c].h2; fc.mask_idx = 2 * c;
-          fc.q = e->q[c];
-          MlpProb* pc = &mb.p[np];
-          fl += fill_mlp(e, fc, rows, &mb.p[np++]);
-          if (in_fwd_bwd) {
-            MlpCriticBwd& B = mb.cbwd[c];
-            pc->cbwd_idx = c;
-            B.enabled = 1;
-            B.q_slot = e->q_slot[c];
-            B.scale = e->cfg.mask_mode != RECNN_MASK_NONE ? 2.0f : 1.0f;
-            B.dz2 = e->dzc2[c]; B.dz1 = e->dzc1[c];   // UNIT tensors: the dW launch applies the per-row seed e->delta[c]
-            if (value_bwd) RECNN_REQUIRE(e->net[VAL[c]].g, "value backward: network %d has no gradient arena bound", VAL[c]);
-            fl += 2.0 * rows * (double)e->H * e->H;
-          }
-        }
-        MlpSpec f{TPOL, e->xcn + aoff, e->ldx, e->K1a, 0};
-        f.out = e->xcn; f.ldo = e->ldx;
-        if (e->td3) { f.addend = e->ext_noise ? e->ext_noise : e->noise_buf; f.ld_add = A; f.add_clip = e->hy.noise_clip; }
-        MlpProb* pt = &mb.p[np];
-        fl += fill_mlp(e, f, rows, &mb.p[np++]);
-        if (chained && in_fwd_bwd) {
-          MlpHead& Hd = mb.head;
-          Hd.n_critic = nc;
-          for (int c = 0; c < nc; ++c) {
-            Hd.q_slot[c] = e->q_slot[c];
-            Hd.delta_out[c] = e->delta[c]; Hd.loss_part[c] = e->loss_part[c];
-            Hd.db3_part[c] = value_bwd ? e->net[VAL[c]].gp[B3] : nullptr;
-          }
-          Hd.reward = e->reward; Hd.done = e->done; Hd.gamma = e->hy.gamma;
-          Hd.lo = e->td3 ? -INFINITY : e->hy.min_value;
-          Hd.hi = e->td3 ? INFINITY : e->hy.max_value;
-          Hd.expected = e->expected; Hd.target_q = e->target_q;
-        }
-        if (chained) {
-          pt->n_tail = nc;
-          for (int c = 0; c < nc; ++c) {
-            const Net& t = e->net[TVAL[c]];
-            MlpTail& T = mb.tail[c];
-            T.part = e->tc_part[c]; T.flag = e->tc_flag[c];
-            T.W1a = sh_ptr(e, TVAL[c], W1); T.ldw1 = t.ld_w1;
-            T.W2 = sh_ptr(e, TVAL[c], W2); T.ldw2 = t.ld_w2;
-            T.b1 = t.p + t.off[B1]; T.b2 = t.p + t.off[B2]; T.b3 = t.p + t.off[B3]; T.w3row = t.p + t.off[W3];
-            T.q = e->tqv[c];
-            fl += 2.0 * rows * ((double)e->H * A + (double)e->H * e->H + e->H);
-          }
-        }
-      }
-      if (actor_side) {
-        MlpSpec f{POL, e->xcs + aoff, e->ldx, e->K1a, 0};
-        f.h1 = e->pa.h1; f.h2 = e->pa.h2; f.out = e->gen_action; f.ldo = e->Ap; f.mask_idx = actor_m1;
-        fl += fill_mlp(e, f, rows, &mb.p[np++]);
-      }
-      if (e->pending_pc.on && np < MLP_MAX_GROUP) {
-        // the policy-loss forward of the PREVIOUS step of this run (critic on [gen_action | state] of that step's
-        // batch, weights as that step's optimizer left them = the current ones) rides here as one more problem: nothing
-        // of this or later steps depends on it, and the launch has idle CUs once its short workgroups are done
-        const auto& pp = e->pending_pc;
-        MlpSpec f{RECNN_NET_VALUE1, pp.ga, e->Ap, e->Ap, 0};
-        f.A1 = pp.xs + aoff; f.lda1 = e->ldx; f.K1 = e->K1a; f.col1 = A;
-        f.q = e->pl_part_base + (int64_t)pp.slot * e->pl_cap;   // that step's policy-loss slot: Q per row, b3 included
-        f.mask_idx = e->td3 ? 6 : 4;
-        MlpProb* pd = &mb.p[np++];
-        fl += fill_mlp(e, f, rows, pd);
-        pd->step_add = pp.run_off;
-        e->pending_pc.on = false;
-      }
-      mb.err = (int32_t*)(e->losses + 4);
-      if ((rc = slot(e, "mlp_fwd_nets", fl, s, [&] { return mlp_launch(mb, np, s); }))) return rc;
     }
+    if (actor_side) fl += fill_mlp(e, role_actor(e, B), rows, &mb.p[np++]);
+    if (e->pending_pc.on && np < MLP_MAX_GROUP) {   // the launch has idle CUs once its short workgroups are done
+      fl += fill_mlp(e, role_deferred_critic(e), rows, &mb.p[np++]);
+      e->pending_pc.on = false;
+    }
+    mb.err = (int32_t*)(e->losses + 4);
+    if ((rc = slot(e, "mlp_fwd_nets", fl, s, [&] { return mlp_launch(mb, np, s); }))) return rc;
   } else {
-  {  // layer 1: packed rows (compute type) in, tc hidden out
-    Group g(e, GEMM_FWD, 0, 0);
+    // layer by layer: packed rows (compute type) in, tc hidden out; layer 3 of the actors: next_action into the action slot of the packed
+    // next rows, gen_action
+    Role net[4];
+    int nn = 0;
     if (value_side) {
-      FwdSpec f{TPOL, 1, e->xcn + tc_off(e, A), e->ldx, 0, e->K1a};
-      f.C = e->tp.h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-      for (int c = 0; c < nc; ++c) {
-        FwdSpec fc{VAL[c], 1, e->xcs, e->ldx, 0, e->K1c};
-        fc.C = e->cv[c].h1; fc.ldc = Hp; fc.c_f32 = 0; fc.relu = 1; fc.mask_idx = 2 * c;
-        g.flops += fill_fwd(e, fc, rows, g.add());
-      }
+      net[nn++] = role_target_actor(e, B);
+      for (int c = 0; c < nc; ++c) net[nn++] = role_critic(e, B, c);
     }
-    if (actor_side) {
-      FwdSpec f{POL, 1, e->xcs + tc_off(e, A), e->ldx, 0, e->K1a};
-      f.C = e->pa.h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = actor_m1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if ((rc = g.run(s, "fwd_l1"))) return rc;
+    if (actor_side) net[nn++] = role_actor(e, B);
+    if ((rc = fwd_layer(e, rows, 1, net, nn, "fwd_l1", s))) return rc;
+    if ((rc = fwd_layer(e, rows, 2, net, nn, "fwd_l2", s))) return rc;
+    if (value_side && (rc = ph_td3_noise(e, e->noise_buf, rows, e->run_off, 1, s))) return rc;
+    if ((rc = fwd_layer(e, rows, 3, net, nn, "fwd_l3_actors", s))) return rc;
   }
-  {  // layer 2
-    Group g(e, GEMM_FWD, 0, 0);
-    if (value_side) {
-      FwdSpec f{TPOL, 2, e->tp.h1, Hp, 0, Hp};
-      f.C = e->tp.h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-      for (int c = 0; c < nc; ++c) {
-        FwdSpec fc{VAL[c], 2, e->cv[c].h1, Hp, 0, Hp};
-        fc.C = e->cv[c].h2; fc.ldc = Hp; fc.c_f32 = 0; fc.relu = 1; fc.mask_idx = 2 * c + 1;
-        g.flops += fill_fwd(e, fc, rows, g.add());
-      }
-    }
-    if (actor_side) {
-      FwdSpec f{POL, 2, e->pa.h1, Hp, 0, Hp};
-      f.C = e->pa.h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = actor_m1 + 1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if ((rc = g.run(s, "fwd_l2"))) return rc;
-  }
-  if (value_side && e->td3 && !e->ext_noise) {
-    if ((rc = slot(e, "td3_noise", 0, s, [&] { return noise_fill_launch(e->noise_buf, (int64_t)rows * A, e->hy.noise_std, e->cfg.seed, e->counters, e->run_off, s); }))) return rc;
-  }
-  {  // layer 3 of the actors: next_action into the action slot of the packed next rows, gen_action
-    Group g(e, GEMM_FWD, 0, 0);
-    if (value_side) {
-      FwdSpec f{TPOL, 3, e->tp.h2, Hp, 0, Hp};
-      f.C = e->xcn; f.ldc = e->ldx; f.c_f32 = 0; f.relu = 0; f.mask_idx = -1;
-      if (e->td3) {  // td3.py:74-78: next_action += clamp(noise)
-        f.addend = e->ext_noise ? e->ext_noise : e->noise_buf;
-        f.ld_add = A;
-        f.add_clip = e->hy.noise_clip;
-      }
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if (actor_side) {
-      FwdSpec f{POL, 3, e->pa.h2, Hp, 0, Hp};
-      f.C = e->gen_action; f.ldc = e->Ap; f.c_f32 = 0; f.relu = 0; f.mask_idx = -1;
-      g.flops += fill_fwd(e, f, rows, g.add());
-    }
-    if ((rc = g.run(s, "fwd_l3_actors"))) return rc;
-  }
-  }  // first group
   if (chained) {
     // nothing left to launch for the target critics
-  } else if (value_side && fused_mlp_ok(e, nc)) {
-    {
+  } else if (value_side) {   // target critics on [next_action | next_state]
+    Role tc[2] = {};
+    for (int c = 0; c < nc; ++c) tc[c] = role_target_critic(e, B, c, true);
+    if (fused_mlp_ok(e, nc)) {
       MlpBatch mb;
       memset(&mb, 0, sizeof(mb));
       double fl = 0;
       for (int c = 0; c < nc; ++c) {
-        MlpSpec f{TVAL[c], e->xcn, e->ldx, e->K1c, 0};
-        f.h2 = e->tq[c].h2;
-        fl += fill_mlp(e, f, rows, &mb.p[c]);
+        fl += fill_mlp(e, tc[c], rows, &mb.p[c]);
+        mb.p[c].h2 = tc[c].h2; mb.p[c].q = nullptr;     // (the head launch takes Q' from the layer-2 activations)
       }
       if ((rc = slot(e, "mlp_fwd_target_critic", fl, s, [&] { return mlp_launch(mb, nc, s); }))) return rc;
-    }
-  } else if (value_side) {
-    {  // target critics on [next_action | next_state]
-      Group g(e, GEMM_FWD, 0, 0);
-      for (int c = 0; c < nc; ++c) {
-        FwdSpec f{TVAL[c], 1, e->xcn, e->ldx, 0, e->K1c};
-        f.C = e->tq[c].h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-        g.flops += fill_fwd(e, f, rows, g.add());
-      }
-      if ((rc = g.run(s, "fwd_l1_target_critic"))) return rc;
-    }
-    {
-      Group g(e, GEMM_FWD, 0, 0);
-      for (int c = 0; c < nc; ++c) {
-        FwdSpec f{TVAL[c], 2, e->tq[c].h1, Hp, 0, Hp};
-        f.C = e->tq[c].h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = -1;
-        g.flops += fill_fwd(e, f, rows, g.add());
-      }
-      if ((rc = g.run(s, "fwd_l2_target_critic"))) return rc;
+    } else {
+      if ((rc = fwd_layer(e, rows, 1, tc, nc, "fwd_l1_target_critic", s))) return rc;
+      if ((rc = fwd_layer(e, rows, 2, tc, nc, "fwd_l2_target_critic", s))) return rc;
     }
   }
   e->panel_bwd_done = false;
@@ -985,66 +990,24 @@ int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool
     // critic head + dz2 + dz1 in one row-panel launch (bwd.hip); Q comes from the forward launch, Q' from its tails
     BwdPanelBatch bb;
     memset(&bb, 0, sizeof(bb));
-    const bool train = e->cfg.mask_mode != RECNN_MASK_NONE;
+    TdDesc td;
+    if ((rc = td_desc(e, value_bwd, &td))) return rc;
     double fl = 0;
     for (int c = 0; c < nc; ++c) {
       BwdPanelProb& b = bb.p[c];
-      Net& v = e->net[VAL[c]];
+      const NetView v = net_view(e, VAL[c]);
       b.rows = rows; b.H = e->H; b.mode = 0;
-      b.q = e->q[c]; b.n_target = nc;
-      for (int t = 0; t < nc; ++t) b.tq[t] = e->tqv[t];
-      b.reward = e->reward; b.done = e->done; b.gamma = e->hy.gamma;
-      b.lo = e->td3 ? -INFINITY : e->hy.min_value;
-      b.hi = e->td3 ? INFINITY : e->hy.max_value;
-      if (c == 0) { b.expected = e->expected; b.target_q = e->target_q; }
-      b.delta_out = e->delta[c]; b.loss_part = e->loss_part[c];
-      b.h2 = e->cv[c].h2; b.ldh = Hp; b.w3 = v.p + v.off[W3]; b.scale = train ? 2.0f : 1.0f;
+      td_write(td, c, &b);
+      b.h2 = e->cv[c].h2; b.ldh = Hp; b.w3 = v.w3row;
       b.dz2 = e->dzc2[c];
-      b.W2 = sh_ptr(e, VAL[c], W2); b.ldw2 = v.ld_w2;
+      b.W2 = v.W2; b.ldw2 = v.ldw2;
       b.h1 = e->cv[c].h1; b.dz1 = e->dzc1[c];
-      if (value_bwd) {
-        RECNN_REQUIRE(v.g, "value backward: network %d has no gradient arena bound", VAL[c]);
-        b.dw3_part = v.gp[W3]; b.db2_part = v.gp[B2]; b.db3_part = v.gp[B3]; b.colsum = v.gp[B1];
-      }
       fl += 2.0 * rows * (double)e->H * e->H;
     }
     if ((rc = slot(e, "head_dx_critic", fl, s, [&] { return bwd_panel_launch(bb, nc, s); }))) return rc;
     e->panel_bwd_done = true;
   } else if (value_side) {
-    // heads: TD target, Q, dQ, loss partials
-    HeadArgs h;
-    memset(&h, 0, sizeof(h));
-    h.rows = rows; h.H = e->H; h.tc_bf16 = e->cfg.dtype; h.ld_h = Hp;
-    h.n_target = nc;
-    for (int c = 0; c < nc; ++c) {
-      const Net& t = e->net[TVAL[c]];
-      h.th2[c] = e->tq[c].h2; h.tw3[c] = t.p + t.off[W3]; h.tb3[c] = t.p + t.off[B3];
-      if (chained) h.tq_in[c] = e->tqv[c];
-      const Net& v = e->net[VAL[c]];
-      h.ch2[c] = e->cv[c].h2; h.cw3[c] = v.p + v.off[W3]; h.cb3[c] = v.p + v.off[B3];
-      h.q[c] = e->q[c]; h.delta[c] = e->delta[c]; h.loss_part[c] = e->loss_part[c];
-    }
-    h.reward = e->reward; h.done = e->done;
-    h.gamma = e->hy.gamma;
-    h.lo = e->td3 ? -INFINITY : e->hy.min_value;
-    h.hi = e->td3 ? INFINITY : e->hy.max_value;
-    h.expected = e->expected; h.target_q = e->target_q;
-    h.n_critic = nc;
-    h.policy_mode = 0;
-    h.do_bwd = value_bwd;
-    h.train = e->cfg.mask_mode != RECNN_MASK_NONE;
-    if (value_bwd) {
-      for (int c = 0; c < nc; ++c) {
-        Net& v = e->net[VAL[c]];
-        RECNN_REQUIRE(v.g, "value backward: network %d has no gradient arena bound", VAL[c]);
-        h.dz2[c] = e->dzc2[c]; h.dw3_part[c] = v.gp[W3]; h.db2_part[c] = v.gp[B2]; h.db3_part[c] = v.gp[B3];
-      }
-    }
-    {
-      const GatherArgs* hg = (value_bwd && e->head_gather) ? e->head_gather : nullptr;   // (armed by step_impl: the next step's gather rides here)
-      if ((rc = slot(e, hg ? "head_td_target+gather" : "head_td_target", 0, s, [&] { return head_launch(h, s, hg); }, hg == nullptr))) return rc;
-      if (hg) e->head_gather = nullptr;         // consumed
-    }
+    return ph_td_head(e, rows, value_bwd, chained, s);
   }
   return 0;
 }
@@ -1053,7 +1016,6 @@ int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool
 // (summed by the slab-reducing Adam launch, or by grad_reduce into the flat arenas when `reduce`: the phase API / data parallel).
 int ph_value_backward(recnn_engine* e, int rows, bool reduce, hipStream_t s, bool dx_only) {
   const int Hp = e->Hp, H = e->H, nc = e->n_critic;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2};
   int rc;
   if (!e->panel_bwd_done) {
     Group g(e, GEMM_DX, 0, 0);
@@ -1103,8 +1065,8 @@ int ph_value_backward(recnn_engine* e, int rows, bool reduce, hipStream_t s, boo
 // the loss is summed in the layer-2 GEMM's epilogue and the backward seed comes from the row-panel kernel (bwd.hip).
 int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_t s, bool need_rows) {
   const int A = e->A, Hp = e->Hp, H = e->H, Ap = e->Ap;
-  const int POL = RECNN_NET_POLICY, V1 = RECNN_NET_VALUE1;
-  const int m0 = e->td3 ? 6 : 4;
+  const int V1 = RECNN_NET_VALUE1;
+  const NetView v = net_view(e, V1);
   const bool train = e->cfg.mask_mode != RECNN_MASK_NONE;
   int rc;
   // (split bf16: the loss of a step without backward comes from the layer-2 epilogue's partial dots; with backward the head kernel
@@ -1113,40 +1075,23 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
   const bool use_dot = (!need_rows && value_panel_ok(e) && !fused_mlp_ok(e, 1)) || x3_dot;
   bool chain_done = false;
   e->pl_dot_parts = 0;
-  if (fused_mlp_ok(e, 1)) {
-    // critic on [gen_action | state] with the UPDATED weights: one launch, two layer-1 contraction segments
+  // critic on [gen_action | state] of the current batch with the UPDATED weights
+  Role pcr = role_policy_critic(e, e->xcs, e->gen_action, e->run_off);
+  pcr.keep = true;
+  if (fused_mlp_ok(e, 1)) {   // one launch, two layer-1 contraction segments
     MlpBatch mb;
     memset(&mb, 0, sizeof(mb));
-    MlpSpec f{V1, e->gen_action, Ap, Ap, 0};
-    f.A1 = e->xcs + tc_off(e, A); f.lda1 = e->ldx; f.K1 = e->K1a; f.col1 = A;
-    f.h1 = e->pc.h1; f.h2 = e->pc.h2; f.mask_idx = m0;
-    const double fl = fill_mlp(e, f, rows, &mb.p[0]);
+    const double fl = fill_mlp(e, pcr, rows, &mb.p[0]);
     if ((rc = slot(e, "mlp_fwd_pcritic", fl, s, [&] { return mlp_launch(mb, 1, s); }))) return rc;
   } else {
-  {  // critic L1 on [gen_action | state]: two contraction segments over the rotated W1 shadow
-    Group g(e, GEMM_FWD, 0, 0);
-    FwdSpec f{V1, 1, e->gen_action, Ap, 0, Ap};
-    f.b_col = 0;
-    f.A2 = e->xcs + tc_off(e, A); f.lda2 = e->ldx; f.K2 = e->K1a; f.b2_col = A;
-    f.C = e->pc.h1; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = m0;
-    // gen_action is zero padded to Ap columns, so segment 0 may run over the padded width: the W1
-    // shadow columns it meets there (the first state columns) are multiplied by zeros.
-    g.flops += fill_fwd(e, f, rows, g.add());
-    if ((rc = g.run(s, "fwd_l1_pcritic"))) return rc;
-  }
-  {
-    Group g(e, GEMM_FWD, 0, 0);
-    FwdSpec f{V1, 2, e->pc.h1, Hp, 0, Hp};
-    f.C = e->pc.h2; f.ldc = Hp; f.c_f32 = 0; f.relu = 1; f.mask_idx = m0 + 1;
-    if (use_dot) { f.dot_w = e->net[V1].p + e->net[V1].off[W3]; f.dot_bias = e->net[V1].p + e->net[V1].off[B3]; f.dot_part = e->pl_part; }
-    g.flops += fill_fwd(e, f, rows, g.add());
-    if ((rc = g.run(s, "fwd_l2_pcritic"))) return rc;
-    if (use_dot) {
-      e->pl_dot_parts = g.L.batch.p[0].dot_parts;
-      RECNN_REQUIRE(e->pl_dot_parts > 0 && e->pl_dot_parts <= e->pl_cap, "policy loss: %d partial sums do not fit %d", e->pl_dot_parts, e->pl_cap);
-      if (e->run_off < LOSS_HIST_MAX) { e->hist_pol_count[e->run_off] = e->pl_dot_parts; e->hist_pol_add[e->run_off] = 0; }
+    if ((rc = fwd_layer(e, rows, 1, &pcr, 1, "fwd_l1_pcritic", s))) return rc;
+    if (use_dot) {            // the loss from the layer-2 epilogue's partial dots, into the step's pl_part slot
+      pcr.q = e->pl_part;
+      if ((rc = fwd_layer(e, rows, 2, nullptr, 0, "fwd_l2_pcritic", s, &pcr, &e->pl_dot_parts))) return rc;
+      if ((rc = note_policy_parts(e, e->run_off, e->pl_dot_parts))) return rc;
+    } else if ((rc = fwd_layer(e, rows, 2, &pcr, 1, "fwd_l2_pcritic", s))) {
+      return rc;
     }
-  }
   }
   if (use_dot) {
     if (!backward) return 0;
@@ -1156,13 +1101,13 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
       // the whole chain dz_e2 -> dz_e1 -> dact -> dz_p2 -> dz_p1 on a row panel that never leaves the CU (bwd.hip)
       BwdChainArgs c;
       memset(&c, 0, sizeof(c));
-      const Net& v = e->net[V1];
+      const NetView a = net_view(e, POL);
       c.rows = rows; c.H = H; c.A = A; c.delta_const = -1.0f / (float)rows; c.scale = train ? 2.0f : 1.0f; c.ldh = Hp;
-      c.e2 = e->pc.h2; c.e1 = e->pc.h1; c.w3c = v.p + v.off[W3];
-      c.W2c = sh_ptr(e, V1, W2); c.ldw2c = v.ld_w2;
-      c.W1c = sh_ptr(e, V1, W1); c.ldw1c = v.ld_w1;
-      c.W3a = sh_ptr(e, POL, W3); c.ldw3a = pn0.ld_w3;
-      c.W2a = sh_ptr(e, POL, W2); c.ldw2a = pn0.ld_w2;
+      c.e2 = e->pc.h2; c.e1 = e->pc.h1; c.w3c = v.w3row;
+      c.W2c = v.W2; c.ldw2c = v.ldw2;
+      c.W1c = v.W1; c.ldw1c = v.ldw1;
+      c.W3a = a.W3; c.ldw3a = a.ldw3;
+      c.W2a = a.W2; c.ldw2a = a.ldw2;
       c.p2 = e->pa.h2; c.p1 = e->pa.h1;
       c.dact = e->dag; c.ldact = Ap; c.dzp2 = e->dzp2; c.dzp1 = e->dzp1;
       c.db3_part = pn0.gp[B3]; c.db2_part = pn0.gp[B2]; c.db1_part = pn0.gp[B1];
@@ -1171,23 +1116,14 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
       chain_done = true;
       e->dze1_ok = false;   // dz_e2 / dz_e1 stayed on chip (ph_state_grads makes them when it is asked for the policy loss's gradient)
     } else {
-    // backward seed d = -1/B for every row: dz_e2 and dz_e1 in one row-panel launch, no critic parameter gradients
-    BwdPanelBatch bb;
-    memset(&bb, 0, sizeof(bb));
-    BwdPanelProb& b = bb.p[0];
-    const Net& v = e->net[V1];
-    b.rows = rows; b.H = H; b.mode = 1; b.delta_const = -1.0f / (float)rows;
-    b.h2 = e->pc.h2; b.ldh = Hp; b.w3 = v.p + v.off[W3]; b.scale = train ? 2.0f : 1.0f;
-    b.dz2 = e->dze2; b.W2 = sh_ptr(e, V1, W2); b.ldw2 = v.ld_w2; b.h1 = e->pc.h1; b.dz1 = e->dze1;
-    if ((rc = slot(e, "head_dx_pcritic", 2.0 * rows * (double)H * H, s, [&] { return bwd_panel_launch(bb, 1, s); }))) return rc;
+      if ((rc = ph_head_dx_pcritic(e, rows, s))) return rc;
     }
   } else {
     HeadArgs h;
     memset(&h, 0, sizeof(h));
-    const Net& v = e->net[V1];
     h.rows = rows; h.H = H; h.tc_bf16 = e->cfg.dtype; h.ld_h = Hp;
     h.n_target = 0; h.n_critic = 1; h.policy_mode = 1;
-    h.ch2[0] = e->pc.h2; h.cw3[0] = v.p + v.off[W3]; h.cb3[0] = v.p + v.off[B3];
+    h.ch2[0] = e->pc.h2; h.cw3[0] = v.w3row; h.cb3[0] = v.b3;
     h.q[0] = e->qpi; h.loss_part[0] = e->loss_part[2];
     if (e->x3 && !need_rows) {    // the step's policy-loss partial sums (sum of Q incl. b3 per block) in its pl_part slot
       const int nblk = (rows + HEAD_ROWS_PER_BLOCK - 1) / HEAD_ROWS_PER_BLOCK;
@@ -1241,8 +1177,7 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
 // optimizer, and their rows are 16-byte aligned and zero padded whatever S is -- the master's rows (stride S + A floats) are not.
 // Where the fused forward left UNIT tensors, each critic's segment carries its own per-row seed (delta[c]), as its dW launch does.
 int ph_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_out, hipStream_t s) {
-  const int A = e->A, H = e->H, S = e->S, V1 = RECNN_NET_VALUE1, POL = RECNN_NET_POLICY;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2};
+  const int A = e->A, H = e->H, S = e->S, V1 = RECNN_NET_VALUE1;
   const Net& v = e->net[V1];
   const Net& p = e->net[POL];
   const int vec = 16 / e->esz;
@@ -1270,14 +1205,8 @@ int ph_state_grads(recnn_engine* e, int rows, int which, float* out, int64_t ld_
     name = "state_grad_value12";
   } else {
     if (!e->dze1_ok) {
-      // the row-panel chain kept the critic's dz on chip: the same two tensors from the same activations and weights, one row-panel launch
-      BwdPanelBatch bb;
-      memset(&bb, 0, sizeof(bb));
-      BwdPanelProb& b = bb.p[0];
-      b.rows = rows; b.H = H; b.mode = 1; b.delta_const = -1.0f / (float)rows;
-      b.h2 = e->pc.h2; b.ldh = e->Hp; b.w3 = v.p + v.off[W3]; b.scale = e->cfg.mask_mode != RECNN_MASK_NONE ? 2.0f : 1.0f;
-      b.dz2 = e->dze2; b.W2 = sh_ptr(e, V1, W2); b.ldw2 = v.ld_w2; b.h1 = e->pc.h1; b.dz1 = e->dze1;
-      if ((rc = slot(e, "head_dx_pcritic", 2.0 * rows * (double)H * H, s, [&] { return bwd_panel_launch(bb, 1, s); }))) return rc;
+      // the row-panel chain kept the critic's dz on chip: the same two tensors from the same activations and weights
+      if ((rc = ph_head_dx_pcritic(e, rows, s))) return rc;
       e->dze1_ok = true;
     }
     a.nseg = 2;
@@ -1351,7 +1280,6 @@ int ph_policy_l1(recnn_engine* e, hipStream_t s) {
 // rows > 0: fused single-GPU path, Adam sums the gradient slabs itself (no separate reduction launch)
 int value_apply(recnn_engine* e, bool soft, float grad_scale, hipStream_t s, int rows) {
   int rc;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2}, TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
   for (int c = 0; c < e->n_critic; ++c)
     if ((rc = apply_net(e, VAL[c], rows, true, 1, grad_scale, false, soft ? TVAL[c] : -1, e->hy.soft_tau, s, rows > 0)))
       return rc;
@@ -1368,7 +1296,6 @@ bool dwadam_ok(const recnn_engine* e, int rows) {
     // ph_value_dwadam issues first.  (The generic split-bf16 forward only: Hp = 512 physical.)
     if (e->cfg.dtype != RECNN_BF16X3 || e->panel_bwd_done || e->Hp != 512) return false;
   } else if (e->cfg.dtype != RECNN_BF16 || !e->panel_bwd_done || e->Hp != 256) return false;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2};
   for (int c = 0; c < e->n_critic; ++c) {
     const Net& n = e->net[VAL[c]];
     if (!n.g || !n.m || !n.v || !n.critic) return false;
@@ -1380,7 +1307,6 @@ bool dwadam_ok(const recnn_engine* e, int rows) {
 }
 
 int ph_value_dwadam(recnn_engine* e, int rows, bool soft, hipStream_t s) {
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2}, TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
   DwAdamBatch b;
   memset(&b, 0, sizeof(b));
   double fl = 0;
@@ -1555,34 +1481,34 @@ int ph_gather_cycle(recnn_engine* e, int rows, int n, int run_off0, int b, hipSt
 
 int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_t s, bool ends_on_policy) {
   const int A = e->A, nc = e->n_critic;
-  const int POL = RECNN_NET_POLICY, TPOL = RECNN_NET_TARGET_POLICY;
-  const int TVAL[2] = {RECNN_NET_TARGET_VALUE1, RECNN_NET_TARGET_VALUE2};
-  const int actor_m1 = e->td3 ? 4 : 2;
-  const int64_t aoff = (int64_t)A * 2;
   const int M = n * rows;
   int rc;
-  if (e->td3 && !e->ext_noise)     // the cycle's batches in one launch (batch j: the key of step run_off0 + j)
-    if ((rc = slot(e, "td3_noise", 0, s, [&] { return noise_fill_launch(e->m_noise, (int64_t)rows * A, e->hy.noise_std, e->cfg.seed, e->counters, run_off0, s, n); }))) return rc;
+  // the cycle's batches in one launch (batch j: the key of step run_off0 + j)
+  if ((rc = ph_td3_noise(e, e->m_noise, rows, run_off0, n, s))) return rc;
   const double l1_fl_a = 2.0 * M * (double)e->H * e->S, l1_fl_c = 2.0 * M * (double)e->H * (e->S + A);
   const double t_fl_a = 2.0 * M * ((double)e->H * e->H + (double)A * e->H), t_fl_c = 2.0 * M * ((double)e->H * e->H + e->H);
+  const StepBufs CB = cycle_bufs(e, rows, run_off0);
+  const Role ta = role_target_actor(e, CB), ac = role_actor(e, CB);
+  Role tc[2] = {};
+  for (int c = 0; c < nc; ++c) tc[c] = role_target_critic(e, CB, c, false);
   if (e->tune.frozen_fused) {
-    auto fill = [&](FrozenProb* p, int ni, const void* A0, int K0, int col0, int mask_idx) {
-      const Net& n = e->net[ni];
+    // a role's whole network on prows rows of the cycle as a problem of the frozen launch (mlpf.hip): hash masks only
+    auto fill = [&](FrozenProb* p, const Role& f, int prows) {
+      const NetView v = net_view(e, f.ni);
       memset(p, 0, sizeof(*p));
-      p->A[0] = A0; p->lda[0] = e->ldx; p->K[0] = K0; p->w1_col[0] = col0; p->nseg = 1;
-      p->W1 = sh_ptr(e, ni, W1); p->ldw1 = n.ld_w1;
-      p->W2 = sh_ptr(e, ni, W2); p->ldw2 = n.ld_w2;
-      if (!n.critic) { p->W3 = sh_ptr(e, ni, W3); p->ldw3 = n.ld_w3; }
-      p->b1 = n.p + n.off[B1]; p->b2 = n.p + n.off[B2]; p->b3 = n.p + n.off[B3];
-      p->w3row = n.critic ? n.p + n.off[W3] : nullptr;
-      p->rows = M; p->H = e->H; p->out_dim = n.out_dim;
-      p->mask_mode = RECNN_MASK_NONE;
-      if (mask_idx >= 0 && e->cfg.mask_mode == RECNN_MASK_HASH) {
-        p->mask_mode = RECNN_MASK_HASH;
-        p->seed = e->cfg.seed; p->stream1 = (uint32_t)mask_idx; p->stream2 = (uint32_t)mask_idx + 1;
-        p->step_ptr = e->counters; p->step_add = run_off0; p->rows_per_set = rows;
-      }
-      p->ldh = e->Hp;
+      p->A[0] = f.A0; p->lda[0] = f.lda0; p->K[0] = f.K0; p->w1_col[0] = f.col0; p->nseg = 1;
+      if (f.A1) { p->A[1] = f.A1; p->lda[1] = f.lda1; p->K[1] = f.K1; p->w1_col[1] = f.col1; p->nseg = 2; }
+      p->W1 = v.W1; p->ldw1 = v.ldw1; p->W2 = v.W2; p->ldw2 = v.ldw2; p->W3 = v.W3; p->ldw3 = v.ldw3;
+      p->b1 = v.b1; p->b2 = v.b2; p->b3 = v.b3; p->w3row = v.w3row;
+      p->rows = prows; p->H = e->H; p->out_dim = e->net[f.ni].out_dim;
+      const MaskSel m1 = mask_sel(e, f.mask_idx, f.step_add, true), m2 = mask_sel(e, mask2_idx(f.mask_idx), f.step_add, true);
+      p->mask_mode = m1.mode; p->seed = m1.seed; p->stream1 = m1.stream; p->stream2 = m2.stream;
+      p->step_ptr = m1.step_ptr; p->step_add = m1.step_add;
+      if (m1.mode != RECNN_MASK_NONE) p->rows_per_set = rows;
+      p->h1 = f.keep ? f.h1 : nullptr; p->h2 = f.keep ? f.h2 : nullptr; p->ldh = e->Hp;
+      p->out = f.out; p->ldo = f.ldo;
+      p->addend = f.addend; p->ld_add = f.ld_add; p->add_clip = f.add_clip;
+      p->q = f.q;
     };
     // Two launches (the target critics need the target actor's output).  A launch is 128-row workgroups at ONE per CU, so what
     // counts is how many rounds of 256 it takes: {target actor, actor} = 2 x 160 workgroups at 10 x 2048 rows = two rounds
@@ -1606,23 +1532,19 @@ int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_
           }
     }
     auto actor_part = [&](FrozenProb* p, int set0, int nsets) {      // the actor on batches set0 .. set0 + nsets - 1
-      const int64_t r0 = (int64_t)set0 * rows;
-      fill(p, POL, e->m_xs + r0 * e->ldx * 2 + aoff, e->K1a, 0, actor_m1);
-      p->rows = nsets * rows;
-      p->step_add = run_off0 + set0;
-      p->h1 = e->m_pa_h1 + r0 * e->Hp * 2; p->h2 = e->m_pa_h2 + r0 * e->Hp * 2;
+      fill(p, role_actor(e, cycle_bufs(e, rows, run_off0, set0)), nsets * rows);
       if (e->tune.frozen_acts_policy_only) {
         // h1 / h2 have one reader: the backward of the policy step (bwd_chain / the actor's dW), on the segment's LAST batch
         const int pol_set = n - 1 - set0;                            // ... as a batch of this part
         if (!ends_on_policy || pol_set < 0 || pol_set >= nsets) p->h1 = p->h2 = nullptr;
         else p->store_row0 = pol_set * rows;
       }
-      p->out = e->m_ga + r0 * e->Ap * 2; p->ldo = e->Ap;
     };
     // Window mode (tuning.frozen_window): no next rows exist.  s' = [e1..eF | r1..rF | 0] of a transition is, column for column,
     // [state row from its second embedding on | action row | next ratings]: three contraction segments with constant offsets into
     // m_xs and m_tail_n, against the same W1 columns in the same ascending k order -- the same bits as the materialised row.
     const bool win = e->win;
+    const int64_t aoff = (int64_t)A * 2;
     const int FE = e->K1a - e->win_tail;                             // frame x emb embedding columns of a state
     auto window = [&](FrozenProb* p, int col0) {
       p->A[0] = e->m_xs + aoff + (int64_t)A * 2; p->lda[0] = e->ldx; p->K[0] = FE - A; p->w1_col[0] = col0;            // e1..e(F-1)
@@ -1632,96 +1554,79 @@ int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_
     };
     FrozenBatch fb;
     int np = 0;
-    fill(&fb.p[np], TPOL, e->m_xn + aoff, e->K1a, 0, -1);            // target actor on s' -> next_action into the rows' action slot
-    fb.p[np].out = e->m_xn; fb.p[np].ldo = e->ldx;
+    fill(&fb.p[np], ta, M);                                          // target actor on s' -> next_action into the rows' action slot
     if (win) { window(&fb.p[np], 0); fb.p[np].out = e->m_na; fb.p[np].ldo = e->Ap; }    // ... or into its own compact array
-    if (e->td3) { fb.p[np].addend = e->m_noise; fb.p[np].ld_add = A; fb.p[np].add_clip = e->hy.noise_clip; }
     ++np;
     if (sets_a > 0) actor_part(&fb.p[np++], 0, sets_a);              // actor on s -> gen_action, activations kept for the policy step
     if ((rc = slot(e, "frozen_actors", l1_fl_a + t_fl_a + (l1_fl_a + t_fl_a) * sets_a / n, s, [&] { return mlpf_launch(fb, np, s, fr_a); }))) return rc;
     FrozenBatch fc;
     int nq = 0;
     for (int c = 0; c < nc; ++c) {                                  // target critics on [s' | next_action]: state part first
-      fill(&fc.p[nq], TVAL[c], e->m_xn + aoff, e->K1a, A, -1);
-      fc.p[nq].A[1] = e->m_xn; fc.p[nq].lda[1] = e->ldx; fc.p[nq].K[1] = e->Ap; fc.p[nq].w1_col[1] = 0; fc.p[nq].nseg = 2;
+      fill(&fc.p[nq], tc[c], M);
       if (win) {
         window(&fc.p[nq], A);
         fc.p[nq].A[3] = e->m_na; fc.p[nq].lda[3] = e->Ap; fc.p[nq].K[3] = e->Ap; fc.p[nq].w1_col[3] = 0; fc.p[nq].nseg = 4;
       }
-      fc.p[nq].q = e->m_tq[c];
       ++nq;
     }
     if (sets_a < n) actor_part(&fc.p[nq++], sets_a, n - sets_a);
     return slot(e, "frozen_target_critics", nc * (l1_fl_c + t_fl_c) + (l1_fl_a + t_fl_a) * (n - sets_a) / n, s, [&] { return mlpf_launch(fc, nq, s, fr_b); });
   }
 
+  // The tiled form: layer 1 of a whole cycle as GEMMs (l1gemm.hip), the later layers either likewise (tuning.frozen_gemm) or as tail panels.
+  // Layer 2 / 3 of a role as a problem of the layer-1 kernel (K = 256): per output element the arithmetic of the row-panel tail kernel (k
+  // ascending in steps of 32 from a zero accumulator, + bias, relu, dropout / + clipped noise, round to bf16), without 1280 workgroups each
+  // starting a 192 KB weight stream for 32 rows.  (Written out here: this borrowed use of L1Prob has no second caller.)
+  auto later = [&](L1Prob* p, const Role& r, int layer) {
+    const NetView v = net_view(e, r.ni);
+    Role g{r.ni, layer == 2 ? r.h1 : r.h2, e->Hp, e->Hp, 0};
+    g.h1 = layer == 2 ? r.h2 : r.out; g.mask_idx = layer == 2 ? mask2_idx(r.mask_idx) : -1; g.step_add = r.step_add;
+    fill_l1(e, p, g, M);
+    p->W1 = layer == 2 ? v.W2 : v.W3; p->ldw1 = layer == 2 ? v.ldw2 : v.ldw3; p->b1 = layer == 2 ? v.b2 : v.b3;
+    if (layer == 3) {
+      p->H = A; p->w_rows = e->Ap; p->no_relu = 1; p->ldh = r.ldo;
+      p->addend = r.addend; p->ld_add = r.ld_add; p->add_clip = r.add_clip;
+    }
+  };
   {
     L1Batch lb;
-    fill_l1(e, &lb.p[0], TPOL, M, e->m_xn + aoff, e->ldx, e->K1a, 0, e->m_tp_h1, -1, run_off0);
-    fill_l1(e, &lb.p[1], POL, M, e->m_xs + aoff, e->ldx, e->K1a, 0, e->m_pa_h1, actor_m1, run_off0);
+    fill_l1(e, &lb.p[0], ta, M);
+    fill_l1(e, &lb.p[1], ac, M);
     lb.p[1].rows_per_set = rows;
     if ((rc = slot(e, "l1_frozen_actors", 2 * l1_fl_a, s, [&] { return l1gemm_launch(lb, 2, e->tune.l1_big, s); }))) return rc;
     if (e->tune.frozen_gemm) {
-      // layers 2 and 3 of both actors as cycle-wide GEMMs through the same tiled kernel (K = 256): per output element the
-      // arithmetic of the row-panel tail kernel (k ascending in steps of 32 from a zero accumulator, + bias, relu, dropout /
-      // + clipped noise, round to bf16), without 1280 workgroups each starting a 192 KB weight stream for 32 rows
-      const Net& tn = e->net[TPOL];
-      const Net& pn = e->net[POL];
       L1Batch l2;
-      fill_l1(e, &l2.p[0], TPOL, M, e->m_tp_h1, e->Hp, e->Hp, 0, e->m_tp_h2, -1, run_off0);
-      l2.p[0].W1 = sh_ptr(e, TPOL, W2); l2.p[0].ldw1 = tn.ld_w2; l2.p[0].b1 = tn.p + tn.off[B2];
-      fill_l1(e, &l2.p[1], POL, M, e->m_pa_h1, e->Hp, e->Hp, 0, e->m_pa_h2, actor_m1 + 1, run_off0);
-      l2.p[1].W1 = sh_ptr(e, POL, W2); l2.p[1].ldw1 = pn.ld_w2; l2.p[1].b1 = pn.p + pn.off[B2];
+      later(&l2.p[0], ta, 2);
+      later(&l2.p[1], ac, 2);
       l2.p[1].rows_per_set = rows;
       if ((rc = slot(e, "l2_frozen_actors", 4.0 * M * (double)e->H * e->H, s, [&] { return l1gemm_launch(l2, 2, e->tune.l1_big, s); }))) return rc;
       L1Batch l3;
-      fill_l1(e, &l3.p[0], TPOL, M, e->m_tp_h2, e->Hp, e->Hp, 0, e->m_xn, -1, run_off0);
-      l3.p[0].W1 = sh_ptr(e, TPOL, W3); l3.p[0].ldw1 = tn.ld_w3; l3.p[0].b1 = tn.p + tn.off[B3];
-      l3.p[0].H = A; l3.p[0].w_rows = e->Ap; l3.p[0].no_relu = 1; l3.p[0].ldh = e->ldx;
-      if (e->td3) { l3.p[0].addend = e->ext_noise ? e->ext_noise : e->m_noise; l3.p[0].ld_add = A; l3.p[0].add_clip = e->hy.noise_clip; }
-      fill_l1(e, &l3.p[1], POL, M, e->m_pa_h2, e->Hp, e->Hp, 0, e->m_ga, -1, run_off0);
-      l3.p[1].W1 = sh_ptr(e, POL, W3); l3.p[1].ldw1 = pn.ld_w3; l3.p[1].b1 = pn.p + pn.off[B3];
-      l3.p[1].H = A; l3.p[1].w_rows = e->Ap; l3.p[1].no_relu = 1; l3.p[1].ldh = e->Ap;
+      later(&l3.p[0], ta, 3);
+      later(&l3.p[1], ac, 3);
       if ((rc = slot(e, "l3_frozen_actors", 4.0 * M * (double)A * e->H, s, [&] { return l1gemm_launch(l3, 2, e->tune.l1_big, s); }))) return rc;
     } else {
       TailBatch tb;
-      TailProb* p = &tb.p[0];
-      fill_tail(e, p, TAIL_ACTOR, TPOL, M, e->m_tp_h1, -1, run_off0);
-      p->out = e->m_xn; p->ldo = e->ldx;
-      if (e->td3) { p->addend = e->ext_noise ? e->ext_noise : e->m_noise; p->ld_add = A; p->add_clip = e->hy.noise_clip; }
-      p = &tb.p[1];
-      fill_tail(e, p, TAIL_ACTOR, POL, M, e->m_pa_h1, actor_m1 + 1, run_off0);
-      p->rows_per_set = rows;
-      p->h2 = e->m_pa_h2; p->out = e->m_ga; p->ldo = e->Ap;
+      fill_tail(e, &tb.p[0], TAIL_ACTOR, ta, M);
+      fill_tail(e, &tb.p[1], TAIL_ACTOR, ac, M);
+      tb.p[1].rows_per_set = rows;
       if ((rc = slot(e, "tail_frozen_actors", 2 * t_fl_a, s, [&] { return mlpt_launch(tb, 2, s); }))) return rc;
     }
   }
   {
     L1Batch lb;
-    for (int c = 0; c < nc; ++c) {
-      fill_l1(e, &lb.p[c], TVAL[c], M, e->m_xn + aoff, e->ldx, e->K1a, A, e->m_tq_h1[c], -1, run_off0);
-      l1_seg1(&lb.p[c], e->m_xn, e->ldx, e->Ap, 0);
-    }
+    for (int c = 0; c < nc; ++c) fill_l1(e, &lb.p[c], tc[c], M);
     if ((rc = slot(e, "l1_frozen_target_critic", nc * l1_fl_c, s, [&] { return l1gemm_launch(lb, nc, e->tune.l1_big, s); }))) return rc;
     if (e->tune.frozen_gemm) {
       L1Batch l2;
-      for (int c = 0; c < nc; ++c) {
-        const Net& t = e->net[TVAL[c]];
-        fill_l1(e, &l2.p[c], TVAL[c], M, e->m_tq_h1[c], e->Hp, e->Hp, 0, c == 0 ? e->m_tp_h2 : e->m_tp_h1, -1, run_off0);   // (the target actor's panels are done with)
-        l2.p[c].W1 = sh_ptr(e, TVAL[c], W2); l2.p[c].ldw1 = t.ld_w2; l2.p[c].b1 = t.p + t.off[B2];
-      }
+      for (int c = 0; c < nc; ++c) later(&l2.p[c], tc[c], 2);
       if ((rc = slot(e, "l2_frozen_target_critic", nc * 2.0 * M * (double)e->H * e->H, s, [&] { return l1gemm_launch(l2, nc, e->tune.l1_big, s); }))) return rc;
       for (int c = 0; c < nc; ++c) {
-        const Net& t = e->net[TVAL[c]];
-        const void* h2 = c == 0 ? e->m_tp_h2 : e->m_tp_h1;
-        if ((rc = slot(e, "q_frozen_target_critic", 2.0 * M * e->H, s, [&] { return qdot_launch(h2, e->Hp, t.p + t.off[W3], t.p + t.off[B3], e->H, M, e->m_tq[c], s); }))) return rc;
+        const NetView t = net_view(e, TVAL[c]);
+        if ((rc = slot(e, "q_frozen_target_critic", 2.0 * M * e->H, s, [&] { return qdot_launch(tc[c].h2, e->Hp, t.w3row, t.b3, e->H, M, tc[c].q, s); }))) return rc;
       }
     } else {
       TailBatch tb;
-      for (int c = 0; c < nc; ++c) {
-        fill_tail(e, &tb.p[c], TAIL_CRITIC_Q, TVAL[c], M, e->m_tq_h1[c], -1, run_off0);
-        tb.p[c].q = e->m_tq[c];
-      }
+      for (int c = 0; c < nc; ++c) fill_tail(e, &tb.p[c], TAIL_CRITIC_Q, tc[c], M);
       if ((rc = slot(e, "tail_frozen_target_critic", nc * t_fl_c, s, [&] { return mlpt_launch(tb, nc, s); }))) return rc;
     }
   }
@@ -1733,7 +1638,6 @@ int ph_frozen_batched(recnn_engine* e, int rows, int n, int run_off0, hipStream_
 // workgroup.
 bool comm_fused_ok(recnn_engine* e, int rows) {
   if (!e->comm || !e->comm_region || !e->tune.comm_fused) return false;
-  const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2};
   for (int c = 0; c < e->n_critic; ++c) {
     const NetLayout L = make_layout(e, VAL[c], rows);
     if (L.nblk > COMM_MAX_WG || !L.t[W1].nslab) return false;
@@ -1787,7 +1691,6 @@ int step_impl(recnn_engine* e, int rows, bool learn, bool policy_step, hipStream
     if (e->comm) {
       // data parallel: finished gradients into the flat arenas, summed over the ranks by one launch per arena, then the
       // replicated optimizer step on grad / world (recnn_amd/parallel.py; the arithmetic of the global batch mean)
-      const int VAL[2] = {RECNN_NET_VALUE1, RECNN_NET_VALUE2};
       if (comm_fused_ok(e, rows)) {
         // ... with the exchange inside the critics' optimizer launches (optim.hip exchange_grads): the launches of the
         // single-GPU step

@@ -1234,6 +1234,51 @@ int recnn_catalogue_logprob_bwd(const float* x, int64_t ld_x, int B, int K, cons
                                 const int64_t* actions, const float* lse, const float* g_lp, const float* g_lse, int items_per_slice,
                                 float* dx, int64_t ld_dx, float* dW, int64_t ld_dw, float* dc, void* workspace, void* stream);
 
+/* =====================================================================================
+ * 19. Sampled softmax with negatives shared by the batch (csrc/sampled.hip).
+ *    x, W, K, N, w_bf16 and the strides as in section 17; c float32 [N] or NULL (zeros); targets int64 [B]; negatives int64 [S],
+ *    S >= 1, one list for every row, repeats allowed; target_log_q float32 [B] and negative_log_q float32 [S], either may be NULL.
+ *        z_t[b]  = x[b] . W[a_b] + c[a_b] - target_log_q[b]          z[b, s] = x[b] . W[n_s] + c[n_s] - negative_log_q[s]
+ *        lse[b]  = log(exp z_t[b] + sum_s exp z[b, s])               logprob[b] = min(z_t[b] - lse[b], 0)
+ *    A negative outside [0, N) is an absent column for every row; with remove_hits != 0 a negative equal to a row's target is absent in
+ *    that row.  A target outside [0, N): logprob[b] = NaN, lse[b] over the negatives alone, g_lp[b] counts as 0, g_lse[b] flows.
+ *    Neither pass stores a [B][S] matrix or a gathered [S][K] copy of W: the rows are read through the ids.
+ *    recnn_sampled_logprob writes logprob, lse and z_target (z_t; NaN for an invalid target), float32 [B] each.  The negatives are cut
+ *      into slices of items_per_slice (a positive multiple of 128), merged per row in slice order, the target's term last.
+ *      workspace: recnn_sampled_logprob_workspace_bytes(B, S, items_per_slice) bytes, 4-byte aligned.
+ *    recnn_sampled_logprob_bwd: lse and z_target as the forward wrote them; g_lp, g_lse float32 [B] or NULL for zeros.  With
+ *      p = exp(z - lse), gd = g_lse - g_lp:   D[b, s] = gd_b p[b, s]   D_t[b] = gd_b p_t[b] + g_lp[b]
+ *      it writes d_target = D_t float32 [B] (always), dx = D W[n] + D_t W[a] float32 [B][K], the compact dWs[s] = sum_b D[b, s] x[b]
+ *      float32 [S][K] and dcs[s] = sum_b D[b, s] float32 [S], and dWt[b] = D_t[b] x[b] float32 [B][K]; each of dx, dWs, dcs, dWt may
+ *      be NULL.  dWs / dcs are summed over chunks of the rows, merged in chunk order; the chunk count depends on (B, S) alone.
+ *      w_bf16 = 1: x is rounded to bf16 where it meets W or D, D before the second product; D_t is not rounded.  B == 0 launches
+ *      nothing and zero-fills dWs / dcs.  workspace: recnn_sampled_logprob_bwd_workspace_bytes(B, S, K, items_per_slice) bytes,
+ *      16-byte aligned.
+ *    recnn_sampled_scatter sums the S + B contributions by item id: dW[n] = sum_{s: n_s = n} dWs[s] + sum_{b: a_b = n} D_t[b] x[b]
+ *      float32 [N][K] (x rounded to bf16 first when x_bf16 != 0), dc[n] likewise from dcs and D_t; dW or dc may be NULL.  Ids outside
+ *      [0, N) contribute nothing.  Every row of dW and dc is written once, exact +0 where nothing landed; a row's contributions are
+ *      added in the order negatives (by s), then targets (by b).  workspace: recnn_sampled_scatter_workspace_bytes(B, S, N, K).
+ *    K (as passed, i.e. padded) is at most 256; a wider K and S = 0 are refused by name before any launch.  No float atomics: equal
+ *    calls give equal bits, and with items_per_slice fixed a row's logprob, lse and dx bits depend on that row, W, c, the negatives
+ *    and the corrections alone.  The *_workspace_bytes queries are host arithmetic only.
+ *    Errors: RECNN_E_INVALID before any HIP call, with a message.
+ * ===================================================================================== */
+int recnn_sampled_logprob_workspace_bytes(int B, int S, int items_per_slice, int64_t* h_bytes);
+int recnn_sampled_logprob(const float* x, int64_t ld_x, int B, int K, const void* W, int64_t ld_w, int w_bf16, const float* c, int N,
+                          const int64_t* targets, const int64_t* negatives, int S, const float* target_log_q,
+                          const float* negative_log_q, int remove_hits, int items_per_slice, float* logprob, float* lse,
+                          float* z_target, void* workspace, void* stream);
+int recnn_sampled_logprob_bwd_workspace_bytes(int B, int S, int K, int items_per_slice, int64_t* h_bytes);
+int recnn_sampled_logprob_bwd(const float* x, int64_t ld_x, int B, int K, const void* W, int64_t ld_w, int w_bf16, const float* c, int N,
+                              const int64_t* targets, const int64_t* negatives, int S, const float* negative_log_q, int remove_hits,
+                              const float* lse, const float* z_target, const float* g_lp, const float* g_lse, int items_per_slice,
+                              float* dx, int64_t ld_dx, float* dWs, int64_t ld_dws, float* dcs, float* d_target, float* dWt,
+                              int64_t ld_dwt, void* workspace, void* stream);
+int recnn_sampled_scatter_workspace_bytes(int B, int S, int N, int K, int64_t* h_bytes);
+int recnn_sampled_scatter(const int64_t* negatives, int S, const int64_t* targets, int B, const float* dWs, int64_t ld_dws,
+                          const float* dcs, const float* x, int64_t ld_x, int x_bf16, const float* d_target, int K, int N, float* dW,
+                          int64_t ld_dw, float* dc, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

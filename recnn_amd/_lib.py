@@ -297,6 +297,13 @@ SIGNATURES = {
     "recnn_catalogue_logprob_bwd": (_I, [_P, _L, _I, _I, _P, _L, _I, _P, _I, _P, _P, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P]),
     "recnn_ope_accumulate_workspace_bytes": (_I, [_I, C.POINTER(_L)]),
     "recnn_ope_accumulate": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_double, _I, _P, _P, _P, _P]),
+    "recnn_sampled_logprob_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
+    "recnn_sampled_logprob": (_I, [_P, _L, _I, _I, _P, _L, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "recnn_sampled_logprob_bwd_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_sampled_logprob_bwd": (_I, [_P, _L, _I, _I, _P, _L, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I,
+                                       _P, _L, _P, _L, _P, _P, _P, _L, _P, _P]),
+    "recnn_sampled_scatter_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_sampled_scatter": (_I, [_P, _I, _P, _I, _P, _L, _P, _P, _L, _I, _P, _I, _I, _P, _L, _P, _P, _P]),
 }
 
 class FrozenDebugArgs(C.Structure):

@@ -15,112 +15,9 @@
 // No atomics at all.  A row's bits depend on that row, W, c and the slice length alone: an MFMA output row reads one row of the A
 // operand, and the reduction pattern is the same for every row position.
 // The longest chain of additions a term of s passes through: 7 (in lane) + 4 (butterfly) + tiles per slice + slices.
-#include <math.h>
-
-#include "logprob_tile.h"
+#include "logprob_kernels.h"      // logprob_slice_kernel<T, DenseCols>: shared with sampled.hip
 
 namespace {
-using namespace logprob_tile;      // Stage, stage_store, stage_mma, lds_at: shared with logprob_bwd.hip
-
-// ws_m, ws_s: [n_slices][B]; ws_za: [B] (written by the one lane of the one slice that holds a valid a[b])
-template <typename T>
-__global__ __launch_bounds__(256) void logprob_slice_kernel(const float* __restrict__ x, int64_t ldx, int B, int K, const T* __restrict__ W,
-                                                            int64_t ldw, const float* __restrict__ c, int N,
-                                                            const int64_t* __restrict__ actions, int tiles_per_slice,
-                                                            float* __restrict__ ws_m, float* __restrict__ ws_s, float* __restrict__ ws_za) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * STAGE_BYTES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int q = lane >> 4, r16 = lane & 15;
-  const int b0 = blockIdx.x * BM;
-  const int ntiles = (N + BN - 1) / BN;
-  const int t0 = blockIdx.y * tiles_per_slice;
-  const int t1 = min(ntiles, t0 + tiles_per_slice);
-  const int nk = K / Stage<T>::BK;
-
-  // rows of this lane's accumulator elements: b0 + 32 wave + 16 tm + 4 q + r
-  float m[2][4], s[2][4];
-  int64_t act[2][4];
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      m[tm][r] = -INFINITY;
-      s[tm][r] = 0.f;
-      const int b = b0 + 32 * wave + 16 * tm + 4 * q + r;
-      act[tm][r] = b < B ? actions[b] : -1;
-    }
-
-  Stage<T> st;
-  for (int t = t0; t < t1; ++t) {
-    const int n0 = t * BN;
-    f32x4 acc[2][NTN];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < NTN; ++tn) acc[tm][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    st.fetch(x, ldx, B, b0, W, ldw, N, n0, 0, tid);
-    stage_store(st, lds, tid);      // (the previous tile's k-loop ended at a barrier: nobody still reads the stage)
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool more = kt + 1 < nk;
-      if (more) st.fetch(x, ldx, B, b0, W, ldw, N, n0, (kt + 1) * Stage<T>::BK, tid);
-      stage_mma<T, 2, NTN>(lds + (kt & 1) * STAGE_BYTES, 32 * wave, BM, q, r16, acc);
-      if (more) stage_store(st, lds + ((kt + 1) & 1) * STAGE_BYTES, tid);
-      __syncthreads();
-    }
-
-    // fold the tile: lane holds rows 4 q + r of each 16-row block, column n0 + 16 tn + r16
-    float cn[NTN];
-    bool live[NTN];
-#pragma unroll
-    for (int tn = 0; tn < NTN; ++tn) {
-      const int n = n0 + 16 * tn + r16;
-      live[tn] = n < N;
-      cn[tn] = live[tn] ? c[n] : 0.f;
-    }
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float z[NTN];
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int tn = 0; tn < NTN; ++tn) {
-          z[tn] = live[tn] ? acc[tm][tn][r] + cn[tn] : -INFINITY;
-          tmax = fmaxf(tmax, z[tn]);
-          if (live[tn] && act[tm][r] == (int64_t)(n0 + 16 * tn + r16)) ws_za[b0 + 32 * wave + 16 * tm + 4 * q + r] = z[tn];
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 8));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 4));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 2));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 1));
-        const float mn = fmaxf(m[tm][r], tmax);      // column n0 of the tile is below N, so finite for finite operands (the header asks for them)
-        float e = expf(z[0] - mn);
-#pragma unroll
-        for (int tn = 1; tn < NTN; ++tn) e += expf(z[tn] - mn);
-        e += __shfl_xor(e, 8);
-        e += __shfl_xor(e, 4);
-        e += __shfl_xor(e, 2);
-        e += __shfl_xor(e, 1);
-        s[tm][r] = s[tm][r] * expf(m[tm][r] - mn) + e;
-        m[tm][r] = mn;
-      }
-  }
-
-  if (r16 == 0) {
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = b0 + 32 * wave + 16 * tm + 4 * q + r;
-        if (b < B) {
-          ws_m[(int64_t)blockIdx.y * B + b] = m[tm][r];
-          ws_s[(int64_t)blockIdx.y * B + b] = s[tm][r];
-        }
-      }
-  }
-}
 
 __global__ __launch_bounds__(256) void logprob_merge_kernel(const float* __restrict__ ws_m, const float* __restrict__ ws_s,
                                                             const float* __restrict__ ws_za, const int64_t* __restrict__ actions, int B,
@@ -170,12 +67,13 @@ extern "C" int recnn_catalogue_logprob(const float* x, int64_t ld_x, int B, int 
   float* ws_za = ws_s + (int64_t)n_slices * B;
   const dim3 grid((B + BM - 1) / BM, n_slices);
   const int tiles = items_per_slice / BN;
+  const DenseCols cols{c, N};
   if (w_bf16)
-    hipLaunchKernelGGL(logprob_slice_kernel<bf16_t>, grid, dim3(256), 0, s, x, ld_x, B, K, (const bf16_t*)W, ld_w, c, N, actions, tiles, ws_m,
-                       ws_s, ws_za);
+    hipLaunchKernelGGL((logprob_slice_kernel<bf16_t, DenseCols>), grid, dim3(256), 0, s, x, ld_x, B, K, (const bf16_t*)W, ld_w, cols, actions,
+                       tiles, ws_m, ws_s, ws_za);
   else
-    hipLaunchKernelGGL(logprob_slice_kernel<float>, grid, dim3(256), 0, s, x, ld_x, B, K, (const float*)W, ld_w, c, N, actions, tiles, ws_m,
-                       ws_s, ws_za);
+    hipLaunchKernelGGL((logprob_slice_kernel<float, DenseCols>), grid, dim3(256), 0, s, x, ld_x, B, K, (const float*)W, ld_w, cols, actions,
+                       tiles, ws_m, ws_s, ws_za);
   hipLaunchKernelGGL(logprob_merge_kernel, dim3((B + 255) / 256), dim3(256), 0, s, (const float*)ws_m, (const float*)ws_s,
                      (const float*)ws_za, actions, B, N, n_slices, logprob, lse);
   return recnn_check_hip(hipGetLastError(), "catalogue_logprob");

@@ -5,6 +5,10 @@
 // chunks of a row are xor-swizzled by the row, so the fragment reads of 16 rows spread over the banks without padding.  The forward
 // and the dW / dc kernel put x on the A side and W on the B side; the dx kernel stores them swapped (stage_store<T, true>) and gets
 // the transposed tile from the same k-step.
+//
+// Which table row stands behind a B-side column, and which bias it carries, is a policy (`Cols`): DenseCols is the whole catalogue in
+// its own order (logprob.hip, logprob_bwd.hip), GatheredCols a list of item ids (sampled.hip), whose rows are read through the ids
+// straight into the stage -- a gathered copy of the table never exists.
 #pragma once
 #include "common.h"
 
@@ -19,6 +23,32 @@ constexpr int STAGE_BYTES = (BM + BN) * ROWB;
 // byte offset of 16-byte chunk j (of 8) of stage row `row`: the chunk index xor the row's low bits
 __device__ inline int lds_at(int row, int j) { return row * ROWB + ((j ^ (row & 7)) << 4); }
 
+// Column n of the logits is table row n; columns at or past N are absent.  The column that equals a row's action is its picked logit.
+struct DenseCols {
+  const float* c;
+  int N;
+  static constexpr bool PICK = true;
+  __host__ __device__ int count() const { return N; }
+  __device__ int64_t row(int n) const { return n < N ? n : -1; }      // table row of column n, -1: absent
+  __device__ float bias(int n, int64_t) const { return c[n]; }
+};
+// Column n is table row ids[n], its bias c[ids[n]] - log_q[n] (c, log_q may be NULL: 0).  An id outside [0, N) is an absent column.
+// No column is picked; with drop_hits a column whose id equals a row's action is absent in that row.
+struct GatheredCols {
+  const int64_t* ids;
+  const float* c;
+  const float* log_q;
+  int S, N, drop_hits;
+  static constexpr bool PICK = false;
+  __host__ __device__ int count() const { return S; }
+  __device__ int64_t row(int n) const {
+    if (n >= S) return -1;
+    const int64_t id = ids[n];
+    return (id >= 0 && id < N) ? id : -1;
+  }
+  __device__ float bias(int n, int64_t r) const { return (c ? c[r] : 0.f) - (log_q ? log_q[n] : 0.f); }
+};
+
 template <typename T>
 struct Stage;
 // fp32: 32 k per stage; the 16-byte chunk j (of 8) of a row holds k 4j .. 4j + 3
@@ -26,8 +56,9 @@ template <>
 struct Stage<float> {
   static constexpr int BK = ROWB / 4;
   uint4 xr[4], wr[WCH];
-  __device__ void fetch(const float* __restrict__ x, int64_t ldx, int B, int b0, const float* __restrict__ W, int64_t ldw, int N, int n0,
-                        int k0, int tid) {
+  template <class Cols>
+  __device__ void fetch(const float* __restrict__ x, int64_t ldx, int B, int b0, const float* __restrict__ W, int64_t ldw, const Cols& cols,
+                        int n0, int k0, int tid) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
@@ -37,8 +68,8 @@ struct Stage<float> {
 #pragma unroll
     for (int i = 0; i < WCH; ++i) {
       const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-      const int n = n0 + row;
-      wr[i] = n < N ? *(const uint4*)(W + (int64_t)n * ldw + k0 + 4 * j) : make_uint4(0, 0, 0, 0);
+      const int64_t n = cols.row(n0 + row);
+      wr[i] = n >= 0 ? *(const uint4*)(W + n * ldw + k0 + 4 * j) : make_uint4(0, 0, 0, 0);
     }
   }
 };
@@ -47,8 +78,9 @@ template <>
 struct Stage<bf16_t> {
   static constexpr int BK = ROWB / 2;
   uint4 xr[4], wr[WCH];
-  __device__ void fetch(const float* __restrict__ x, int64_t ldx, int B, int b0, const bf16_t* __restrict__ W, int64_t ldw, int N, int n0,
-                        int k0, int tid) {
+  template <class Cols>
+  __device__ void fetch(const float* __restrict__ x, int64_t ldx, int B, int b0, const bf16_t* __restrict__ W, int64_t ldw, const Cols& cols,
+                        int n0, int k0, int tid) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
@@ -64,8 +96,8 @@ struct Stage<bf16_t> {
 #pragma unroll
     for (int i = 0; i < WCH; ++i) {
       const int ch = tid + 256 * i, row = ch >> 3, j = ch & 7;
-      const int n = n0 + row;
-      wr[i] = n < N ? *(const uint4*)(W + (int64_t)n * ldw + k0 + 8 * j) : make_uint4(0, 0, 0, 0);
+      const int64_t n = cols.row(n0 + row);
+      wr[i] = n >= 0 ? *(const uint4*)(W + n * ldw + k0 + 8 * j) : make_uint4(0, 0, 0, 0);
     }
   }
 };

@@ -49,6 +49,46 @@ __global__ __launch_bounds__(1024) void scatter_scan_kernel(const int* __restric
   }
   if (threadIdx.x == 1023) start[n] = sums[1023];
 }
+// The same scan for a large n, where one workgroup's bandwidth is the whole cost: chunks of SCAN_CHUNK counts, their sums, the scan above
+// over those sums, then every chunk scanned from its offset.  Integer sums: the result is the single-workgroup scan's, bit for bit.
+constexpr int SCAN_CHUNK = 4096;
+inline int scatter_scan_chunks(int n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK; }
+__global__ __launch_bounds__(256) void scatter_chunk_sum_kernel(const int* __restrict__ count, int n, int* __restrict__ csum) {
+  __shared__ int part[256];
+  const int t = threadIdx.x, i0 = blockIdx.x * SCAN_CHUNK, i1 = min(n, i0 + SCAN_CHUNK);
+  int s = 0;
+  for (int i = i0 + t; i < i1; i += 256) s += count[i];
+  part[t] = s;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (t < off) part[t] += part[t + off];
+    __syncthreads();
+  }
+  if (t == 0) csum[blockIdx.x] = part[0];
+}
+// thread t of chunk b owns counts b SCAN_CHUNK + 16 t .. + 15; coff[b] is the chunk's offset, coff[n_chunks] the total
+__global__ __launch_bounds__(256) void scatter_chunk_scan_kernel(const int* __restrict__ count, int n, const int* __restrict__ coff,
+                                                                 int n_chunks, int* __restrict__ start) {
+  __shared__ int sums[256];
+  constexpr int PER = SCAN_CHUNK / 256;
+  const int t = threadIdx.x, i0 = min(n, blockIdx.x * SCAN_CHUNK + t * PER), i1 = min(n, i0 + PER);
+  int s = 0;
+  for (int i = i0; i < i1; ++i) s += count[i];
+  sums[t] = s;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const int v = t >= off ? sums[t - off] : 0;
+    __syncthreads();
+    sums[t] += v;
+    __syncthreads();
+  }
+  int run = coff[blockIdx.x] + sums[t] - s;
+  for (int i = i0; i < i1; ++i) {
+    start[i] = run;
+    run += count[i];
+  }
+  if (blockIdx.x == n_chunks - 1 && t == 255) start[n] = coff[n_chunks];
+}
 template <class IdOf>
 __global__ void scatter_place_kernel(const IdOf id_of, int M, const int* __restrict__ start, const int* __restrict__ slot,
                                      int* __restrict__ placed) {
@@ -60,13 +100,28 @@ __global__ void scatter_place_kernel(const IdOf id_of, int M, const int* __restr
 // or more entries.  Lists of up to 256 entries: in LDS, rank = number of smaller j in the list.  Longer lists (the popular items): a
 // bitmap of the list's j over [0, M) in LDS, rank = popcount below j -- linear in M / 32 + L instead of quadratic in L.  (M beyond the
 // bitmap: the quadratic count over LDS chunks.)
+//
+// Which destination a workgroup takes is a functor `int operator()(int block) const` (-1: none).  BlockIsDest: workgroup d takes
+// destination d, a grid of n_dest.  FirstOfList: workgroup j takes the destination of contribution j if j arrived first in its list, a
+// grid of M -- for few contributions into many destinations (sampled.hip: a few thousand ids into a catalogue of a million), where a
+// workgroup per destination would be nearly all empty launches.  The sorted lists are the same either way.
 constexpr int RANK_SMALL = 256, RANK_WORDS = 16384;
-__global__ __launch_bounds__(256) void scatter_rank_kernel(const int* __restrict__ start, int n_dest, const int* __restrict__ placed,
-                                                           int M, int* __restrict__ sorted) {
+struct BlockIsDest {
+  __device__ int operator()(int block) const { return block; }
+};
+template <class IdOf>
+struct FirstOfList {
+  IdOf id_of;
+  const int* slot;
+  __device__ int operator()(int block) const { return slot[block] == 0 ? (int)id_of(block) : -1; }
+};
+template <class DestOf>
+__global__ __launch_bounds__(256) void scatter_rank_kernel(const DestOf dest_of, const int* __restrict__ start, int n_dest,
+                                                           const int* __restrict__ placed, int M, int* __restrict__ sorted) {
   __shared__ uint32_t bits[RANK_WORDS];
   __shared__ int tsum[256];
-  const int d = blockIdx.x, t = threadIdx.x;
-  if (d >= n_dest) return;
+  const int d = dest_of(blockIdx.x), t = threadIdx.x;
+  if (d < 0 || d >= n_dest) return;
   const int s = start[d], L = start[d + 1] - s;
   if (L <= 1) {
     if (L == 1 && t == 0) sorted[s] = placed[s];
@@ -134,15 +189,33 @@ inline ScatterIndex scatter_index_carve(char*& p, int64_t M, int n_dest) {
 }
 // the launches of one index build, in stream order: clear the counts, histogram, scan, placement, rank.  M == 0: every list is empty
 // (start is all zeros).  The pieces of the callers' float passes cover the first start[n_dest] sorted entries.
+// rank_by_contribution: the rank pass runs a workgroup per contribution (FirstOfList) instead of one per destination.
+// scan_scratch: 2 scatter_scan_chunks(n_dest) + 1 ints (scatter_scan_scratch_bytes); when given, n_dest > SCAN_CHUNK is scanned in chunks.
+inline int64_t scatter_scan_scratch_bytes(int n_dest) { return (4LL * (2 * scatter_scan_chunks(n_dest) + 1) + 255) / 256 * 256; }
 template <class IdOf>
-inline hipError_t scatter_index_build(const ScatterIndex& w, const IdOf& id_of, int M, int n_dest, hipStream_t s) {
+inline hipError_t scatter_index_build(const ScatterIndex& w, const IdOf& id_of, int M, int n_dest, hipStream_t s,
+                                      bool rank_by_contribution = false, int* scan_scratch = nullptr) {
   const hipError_t e = hipMemsetAsync(w.count, 0, 4LL * n_dest, s);
   if (e != hipSuccess) return e;
   if (M) hipLaunchKernelGGL((scatter_hist_kernel<IdOf>), dim3((M + 255) / 256), dim3(256), 0, s, id_of, M, n_dest, w.count, w.slot);
-  hipLaunchKernelGGL(scatter_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, n_dest, w.start);
+  if (scan_scratch && n_dest > SCAN_CHUNK) {
+    const int nc = scatter_scan_chunks(n_dest);
+    int* csum = scan_scratch;
+    int* coff = scan_scratch + nc;
+    hipLaunchKernelGGL(scatter_chunk_sum_kernel, dim3(nc), dim3(256), 0, s, (const int*)w.count, n_dest, csum);
+    hipLaunchKernelGGL(scatter_scan_kernel, dim3(1), dim3(1024), 0, s, (const int*)csum, nc, coff);
+    hipLaunchKernelGGL(scatter_chunk_scan_kernel, dim3(nc), dim3(256), 0, s, (const int*)w.count, n_dest, (const int*)coff, nc, w.start);
+  } else {
+    hipLaunchKernelGGL(scatter_scan_kernel, dim3(1), dim3(1024), 0, s, w.count, n_dest, w.start);
+  }
   if (M) {
     hipLaunchKernelGGL((scatter_place_kernel<IdOf>), dim3((M + 255) / 256), dim3(256), 0, s, id_of, M, w.start, w.slot, w.placed);
-    hipLaunchKernelGGL(scatter_rank_kernel, dim3(n_dest), dim3(256), 0, s, w.start, n_dest, w.placed, M, w.sorted);
+    if (rank_by_contribution)
+      hipLaunchKernelGGL((scatter_rank_kernel<FirstOfList<IdOf>>), dim3(M), dim3(256), 0, s, FirstOfList<IdOf>{id_of, w.slot}, w.start,
+                         n_dest, w.placed, M, w.sorted);
+    else
+      hipLaunchKernelGGL((scatter_rank_kernel<BlockIsDest>), dim3(n_dest), dim3(256), 0, s, BlockIsDest{}, w.start, n_dest, w.placed, M,
+                         w.sorted);
   }
   return hipSuccess;
 }

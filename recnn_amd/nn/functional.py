@@ -914,8 +914,9 @@ def catalogue_log_prob(x, weight, bias, actions, *, dtype=None, items_per_slice=
     return _catalogue_forward(_catalogue_operands(x, weight, bias, actions, dtype, items_per_slice, _x_padded))[:2]
 
 
-def _catalogue_operands(x, weight, bias, actions, dtype, items_per_slice, _x_padded=False):
-    """The checked, padded operands of one `recnn_catalogue_logprob` call: (xp, wp, c, act, B, N, K, Kp, bf16, ips)."""
+def _catalogue_operands(x, weight, bias, actions, dtype, items_per_slice, _x_padded=False, _null_bias=False):
+    """The checked, padded operands of one `recnn_catalogue_logprob` call: (xp, wp, c, act, B, N, K, Kp, bf16, ips).  `_null_bias`
+    (the sampled kernels, which take NULL for it): no bias gives c = None instead of [N] zeros."""
     if not (x.is_cuda and weight.is_cuda):
         raise L.RecnnHipError("recnn_amd catalogue_log_prob: needs GPU tensors (no CPU fallback)")
     dtype = _catalogue_dtype if dtype is None else dtype
@@ -951,7 +952,7 @@ def _catalogue_operands(x, weight, bias, actions, dtype, items_per_slice, _x_pad
         wp = _derived_of(weight, "padded", padded)
     else:
         wp = weight.detach()
-    c = torch.zeros(N, device=dev) if bias is None else bias.detach().float().contiguous()
+    c = (None if _null_bias else torch.zeros(N, device=dev)) if bias is None else bias.detach().float().contiguous()
     act = actions.detach().to(device=dev, dtype=torch.int64).contiguous()
     if act.shape != (B,):
         raise ValueError(f"catalogue_log_prob: {B} rows but actions of shape {tuple(act.shape)}")
@@ -1094,6 +1095,164 @@ def catalogue_cross_entropy(x, weight, bias, targets, *, reduction="mean", ignor
     if bool((keep & ((t < 0) | (t >= N))).any()):
         raise ValueError(f"catalogue_cross_entropy: a target lies outside [0, {N}) and is not ignore_index = {ignore_index}")
     lp, _ = catalogue_log_prob_train(x, weight, bias, torch.where(keep, t, torch.full_like(t, -1)), dtype=dtype)
+    loss = torch.where(keep, -lp, torch.zeros_like(lp))
+    if reduction == "none":
+        return loss
+    return loss.sum() if reduction == "sum" else loss.sum() / keep.sum()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Sampled softmax with negatives shared by the batch (csrc/sampled.hip): the target against S sampled items, with
+# the log-Q correction and accidental-hit removal.  Neither pass stores a [B, S] matrix or a gathered [S, K] copy of the table.
+
+def _sampled_operands(x, weight, bias, targets, negatives, target_log_q, negative_log_q, dtype, items_per_slice):
+    """The checked operands of the sampled kernels: `_catalogue_operands`' padding and weight shadows, then the negatives and
+    corrections.  (xp, wp, c or None, act, neg, tq, nq, B, S, N, K, Kp, bf16)."""
+    if not (isinstance(negatives, torch.Tensor) and negatives.is_cuda):
+        raise L.RecnnHipError("recnn_amd sampled_log_prob_train: needs GPU tensors (no CPU fallback)")
+    xp, wp, c, act, B, N, K, Kp, bf16, _ = _catalogue_operands(x, weight, bias, targets, dtype, 128, _null_bias=True)
+    dev = xp.device
+    if negatives.dim() != 1 or negatives.dtype.is_floating_point or negatives.dtype == torch.bool:
+        raise ValueError(f"sampled_log_prob_train: negatives must be integer ids [S], got {negatives.dtype} {tuple(negatives.shape)}")
+    neg = negatives.detach().to(device=dev, dtype=torch.int64).contiguous()
+    S = neg.shape[0]
+    if S == 0:
+        raise ValueError("sampled_log_prob_train: S = 0: the list of negatives is empty (at least one is needed)")
+
+    def corr(t, n, name):
+        if t is None:
+            return None
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"sampled_log_prob_train: {name} of shape {tuple(t.shape)} does not match its {n} ids")
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    tq, nq = corr(target_log_q, B, "target_log_q"), corr(negative_log_q, S, "negative_log_q")
+    if items_per_slice is not None and (int(items_per_slice) < 128 or int(items_per_slice) % 128):
+        raise ValueError(f"sampled_log_prob_train: items_per_slice must be a positive multiple of 128, got {items_per_slice}")
+    return xp, wp, c, act, neg, tq, nq, B, S, N, K, Kp, bf16
+
+
+class SampledLogProbFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, targets, negatives, target_log_q, negative_log_q, remove_hits, dtype, items_per_slice, sparse_grad):
+        ops = _sampled_operands(x, weight, bias, targets, negatives, target_log_q, negative_log_q, dtype, items_per_slice)
+        xp, wp, c, act, neg, tq, nq, B, S, N, K, Kp, bf16 = ops
+        dev = xp.device
+        lp, lse, zt = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
+        if B:
+            ips = default_items_per_slice(B, S) if items_per_slice is None else int(items_per_slice)
+            ws = L.workspace("recnn_sampled_logprob_workspace_bytes", B, S, ips, device=dev)
+            L.call("recnn_sampled_logprob", L.ptr(xp), xp.stride(0), B, Kp, L.ptr(wp), wp.stride(0), int(bf16), L.ptr(c), N, L.ptr(act),
+                   L.ptr(neg), S, L.ptr(tq), L.ptr(nq), int(bool(remove_hits)), ips, L.ptr(lp), L.ptr(lse), L.ptr(zt), L.ptr(ws),
+                   L.current_stream())
+        ctx.ops, ctx.lse, ctx.zt, ctx.user_ips = ops, lse.detach(), zt, items_per_slice
+        ctx.remove_hits, ctx.sparse = bool(remove_hits), bool(sparse_grad)
+        ctx.dtypes = (x.dtype, weight.dtype, None if bias is None else bias.dtype)
+        ctx.save_for_backward(x, weight)       # (for autograd's check that neither was written in between)
+        ctx.set_materialize_grads(False)
+        return lp, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_lp, g_lse):
+        ctx.saved_tensors
+        xp, wp, c, act, neg, tq, nq, B, S, N, K, Kp, bf16 = ctx.ops
+        need_x, need_w, need_c = ctx.needs_input_grad[:3]
+        need_c = need_c and ctx.dtypes[2] is not None
+        none = (None,) * 11
+        if (g_lp is None and g_lse is None) or not (need_x or need_w or need_c):
+            return none
+        dev = xp.device
+
+        def strip(t, dt):
+            t = t if K == Kp else t[:, :K].contiguous()
+            return t if t.dtype == dt else t.to(dt)
+        if B == 0:      # nothing to launch: exact zeros
+            gw = None
+            if need_w:
+                gw = (torch.sparse_coo_tensor(torch.empty(1, 0, dtype=torch.int64, device=dev), torch.empty(0, K, device=dev), (N, K))
+                      if ctx.sparse else torch.zeros(N, K, device=dev)).to(ctx.dtypes[1])
+            return (torch.zeros(0, K, device=dev, dtype=ctx.dtypes[0]) if need_x else None, gw,
+                    torch.zeros(N, device=dev, dtype=ctx.dtypes[2]) if need_c else None) + none[3:]
+        g_lp = None if g_lp is None else g_lp.float().contiguous()
+        g_lse = None if g_lse is None else g_lse.float().contiguous()
+        ips = catalogue_bwd_items_per_slice(B, S, K) if ctx.user_ips is None else int(ctx.user_ips)
+        sparse_w = need_w and ctx.sparse
+        dx = torch.empty(B, Kp, device=dev) if need_x else None
+        dws = torch.empty(S, Kp, device=dev) if need_w else None
+        dcs = torch.empty(S, device=dev) if need_c else None
+        dt = torch.empty(B, device=dev)
+        dwt = torch.empty(B, Kp, device=dev) if sparse_w else None
+        ws = L.workspace("recnn_sampled_logprob_bwd_workspace_bytes", B, S, Kp, ips, device=dev)
+        L.call("recnn_sampled_logprob_bwd", L.ptr(xp), xp.stride(0), B, Kp, L.ptr(wp), wp.stride(0), int(bf16), L.ptr(c), N, L.ptr(act),
+               L.ptr(neg), S, L.ptr(nq), int(ctx.remove_hits), L.ptr(ctx.lse), L.ptr(ctx.zt), L.ptr(g_lp), L.ptr(g_lse), ips,
+               L.ptr(dx), Kp, L.ptr(dws), Kp, L.ptr(dcs), L.ptr(dt), L.ptr(dwt), Kp, L.ptr(ws), L.current_stream())
+        gw = gc = None
+        dense_w = need_w and not ctx.sparse
+        if dense_w or need_c:
+            dw = torch.empty(N, Kp, device=dev) if dense_w else None
+            gc = torch.empty(N, device=dev) if need_c else None
+            ws2 = L.workspace("recnn_sampled_scatter_workspace_bytes", B, S, N, Kp, device=dev)
+            L.call("recnn_sampled_scatter", L.ptr(neg), S, L.ptr(act), B, L.ptr(dws), Kp, L.ptr(dcs), L.ptr(xp), xp.stride(0), int(bf16),
+                   L.ptr(dt), Kp, N, L.ptr(dw), Kp, L.ptr(gc), L.ptr(ws2), L.current_stream())
+            if dense_w:
+                gw = strip(dw, ctx.dtypes[1])
+            if need_c:
+                gc = gc.to(ctx.dtypes[2])
+        if sparse_w:
+            # uncoalesced: one entry per valid negative, then one per valid target; nothing of size n_items is written
+            keep_n, keep_t = (neg >= 0) & (neg < N), (act >= 0) & (act < N)
+            idx = torch.cat([neg[keep_n], act[keep_t]])
+            val = torch.cat([dws[keep_n], dwt[keep_t]])
+            gw = torch.sparse_coo_tensor(idx[None], strip(val, ctx.dtypes[1]), (N, K))
+        return (strip(dx, ctx.dtypes[0]) if need_x else None, gw, gc) + none[3:]
+
+
+def sampled_log_prob_train(x, weight, bias, targets, negatives, *, target_log_q=None, negative_log_q=None, remove_accidental_hits=True,
+                           dtype=None, items_per_slice=None, sparse_grad=False):
+    """(log_prob, lse), float32 [B] each, of the sampled softmax of x [B, K] over `targets` [B] and the negatives [S] that every row
+    shares (repeats allowed), with gradients to x, weight [N, K] and bias ([N] or None):
+
+        z_t[b] = x_b . W[a_b] + c[a_b] - target_log_q[b]        z[b, s] = x_b . W[n_s] + c[n_s] - negative_log_q[s]
+        lse[b] = log(exp z_t[b] + sum_s exp z[b, s])            log_prob[b] = min(z_t[b] - lse[b], 0)
+
+    `remove_accidental_hits`: a negative equal to a row's target is left out of that row (no probability, no gradient).  A negative
+    outside [0, N) is left out of every row (-1 padding).  A target outside [0, N) gives NaN in its log_prob only, its lse is taken
+    over the negatives, its log_prob gradient counts as 0 and its lse gradient still flows.  S = 0 and a K that pads above 256
+    are refused by name before any launch.  In-batch negatives are `negatives=targets`.
+    Forward: `recnn_sampled_logprob`; backward: `recnn_sampled_logprob_bwd` (dx and one compact gradient row per negative) and
+    `recnn_sampled_scatter`, which sums the S + B contributions by item id into the dense [N, K] / [N] gradients (csrc/sampled.hip);
+    the rows of the table are read through the ids, so neither a [B, S] matrix nor a gathered [S, K] copy exists.  Operands are
+    padded and shadowed as `catalogue_log_prob` pads them; `dtype` 'fp32' or 'bf16' as there, gradients fp32 either way.
+    `sparse_grad=True`: the weight gradient is an uncoalesced `torch.sparse_coo_tensor` [N, K] with indices cat(valid negatives,
+    valid targets) and the compact rows as values -- for `torch.optim.SparseAdam`; no [N, K] tensor is made, and no scatter launch
+    unless the bias needs its (dense) gradient.  `items_per_slice` (a multiple of 128) cuts the negatives; it defaults to
+    `default_items_per_slice(B, S)` forward and `catalogue_bwd_items_per_slice(B, S, K)` backward, and with it fixed a row's
+    log_prob, lse and dx bits do not depend on the batch around it.  No float atomics: equal calls give equal bits.  Not twice
+    differentiable."""
+    if weight.dim() == 2 and _padded_width(weight.shape[1], dtype) > CATALOGUE_BWD_KMAX:
+        raise ValueError(f"sampled_log_prob_train: K = {weight.shape[1]} pads to {_padded_width(weight.shape[1], dtype)}, above the "
+                         f"kernels' limit of {CATALOGUE_BWD_KMAX} (their output tile is register-resident; there is no K-chunked path)")
+    return SampledLogProbFunction.apply(x, weight, bias, targets, negatives, target_log_q, negative_log_q, remove_accidental_hits, dtype,
+                                        items_per_slice, sparse_grad)
+
+
+def sampled_cross_entropy(x, weight, bias, targets, negatives, *, target_log_q=None, negative_log_q=None, reduction="mean",
+                          ignore_index=-100, remove_accidental_hits=True, dtype=None, items_per_slice=None, sparse_grad=False):
+    """Sampled-softmax cross-entropy: -`sampled_log_prob_train(...)[0]`, reduced by `reduction` ('mean', 'sum' or 'none') with
+    `catalogue_cross_entropy`'s semantics: rows whose target equals `ignore_index` contribute 0 and are left out of the mean; any
+    other target outside [0, n_items) raises ValueError."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"sampled_cross_entropy: reduction {reduction!r} is not 'mean', 'sum' or 'none'")
+    if not (x.is_cuda and weight.is_cuda):
+        raise L.RecnnHipError("recnn_amd sampled_cross_entropy: needs GPU tensors (no CPU fallback)")
+    t = action_ids(targets).to(x.device)
+    keep = t != int(ignore_index)
+    N = weight.shape[0]
+    if bool((keep & ((t < 0) | (t >= N))).any()):
+        raise ValueError(f"sampled_cross_entropy: a target lies outside [0, {N}) and is not ignore_index = {ignore_index}")
+    lp, _ = sampled_log_prob_train(x, weight, bias, torch.where(keep, t, torch.full_like(t, -1)), negatives, target_log_q=target_log_q,
+                                   negative_log_q=negative_log_q, remove_accidental_hits=remove_accidental_hits, dtype=dtype,
+                                   items_per_slice=items_per_slice, sparse_grad=sparse_grad)
     loss = torch.where(keep, -lp, torch.zeros_like(lp))
     if reduction == "none":
         return loss

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import functional as F_hip
 
-__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead"]
+__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead", "NegativeSampler"]
 
 
 class DuelDQN(nn.Module):
@@ -454,6 +454,38 @@ class NextItemHead:
         return F_hip.catalogue_cross_entropy(x, self.weight, self.bias, targets, reduction=reduction, ignore_index=ignore_index,
                                              dtype=dtype)
 
+    def sampled_loss(self, x, targets, *, sampler=None, n_negatives=None, negatives=None, in_batch=False, reduction="mean",
+                     ignore_index=-100, dtype=None, sparse_grad=False):
+        """`sampled_cross_entropy` of x [rows, K] against `targets` (csrc/sampled.hip).  The negatives, shared by every
+        row, are either `negatives` (int64 [S], no corrections), or `n_negatives` draws from `sampler` (a `NegativeSampler`) with its
+        log-Q corrections for negatives and targets.  `in_batch=True`: the batch's own targets are the negatives (ignored rows
+        leave as -1), joined with the sampler's draws if a sampler is given; corrections come from the sampler when there is one.
+        Accidental hits are removed."""
+        if negatives is not None and (sampler is not None or in_batch):
+            raise ValueError("NextItemHead.sampled_loss: pass explicit negatives, or a sampler with n_negatives and / or in_batch")
+        if (sampler is None) != (n_negatives is None):
+            raise ValueError("NextItemHead.sampled_loss: sampler and n_negatives go together")
+        if negatives is None and sampler is None and not in_batch:
+            raise ValueError("NextItemHead.sampled_loss: needs negatives, a sampler with n_negatives, or in_batch=True")
+        t = F_hip.action_ids(targets).to(x.device)
+        tq = nq = None
+        if negatives is None:
+            parts, qs = [], []
+            if in_batch:
+                own = torch.where(t == int(ignore_index), torch.full_like(t, -1), t)
+                parts.append(own)
+                if sampler is not None:
+                    qs.append(sampler.log_q(own))
+            if sampler is not None:
+                ids, lq = sampler.sample(int(n_negatives))
+                parts.append(ids.to(x.device))
+                qs.append(lq.to(x.device))
+                tq = sampler.log_q(t).to(x.device)
+                nq = torch.cat(qs)
+            negatives = torch.cat(parts)
+        return F_hip.sampled_cross_entropy(x, self.weight, self.bias, t, negatives, target_log_q=tq, negative_log_q=nq,
+                                           reduction=reduction, ignore_index=ignore_index, dtype=dtype, sparse_grad=sparse_grad)
+
     def log_prob(self, x, targets):
         """(log_prob, lse) of `catalogue_log_prob`: detached, for the off-policy meters."""
         return F_hip.catalogue_log_prob(x, self.weight, self.bias, F_hip.action_ids(targets))
@@ -466,3 +498,54 @@ class NextItemHead:
                              "does; evaluate a bias-free head, or rank by the logits yourself")
         from ..retrieval import FlatIndex
         return FlatIndex(self.weight, "IP")
+
+
+class NegativeSampler:
+    """Draws item ids with replacement from a fixed distribution q over the catalogue and reports log q, the correction of the
+    sampled softmax (`NextItemHead.sampled_loss`, `functional.sampled_log_prob_train`).  q is uniform when `counts` is None, else
+    q proportional to (counts + smoothing)^power (word2vec's 0.75 by default).  Torch plumbing, not a kernel: a float64 inverse CDF,
+    `torch.searchsorted`, and a `torch.Generator` on `device` seeded with `seed` -- equal seeds give equal draws.  An item with
+    q = 0 could never be corrected for and is refused at construction."""
+
+    def __init__(self, n_items, counts=None, power=0.75, smoothing=1.0, seed=0, device="cuda"):
+        n_items = int(n_items)
+        if n_items < 1:
+            raise ValueError(f"NegativeSampler: n_items = {n_items}")
+        self.device = torch.device(device)
+        if counts is None:
+            w = torch.ones(n_items, dtype=torch.float64, device=self.device)
+        else:
+            counts = torch.as_tensor(counts).to(device=self.device, dtype=torch.float64)
+            if tuple(counts.shape) != (n_items,) or bool((counts < 0).any()):
+                raise ValueError(f"NegativeSampler: counts must be {n_items} non-negative numbers, got shape {tuple(counts.shape)}")
+            w = (counts + float(smoothing)) ** float(power)
+        if not bool(torch.isfinite(w).all()) or bool((w <= 0).any()):
+            raise ValueError("NegativeSampler: an item has q = 0 (a zero count with smoothing = 0): its log q is -inf and no "
+                             "correction exists; use smoothing > 0")
+        q = w / w.sum()
+        self.n_items = n_items
+        self._log_q = torch.log(q).to(torch.float32)
+        cdf = torch.cumsum(q, 0)
+        cdf[-1] = 1.0
+        self._cdf = cdf
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+
+    @classmethod
+    def from_store(cls, store, n_items, **kw):
+        """counts = how often each item occurs in `store.items` (a `recnn_amd.data.store.ReplayStore`-like object)."""
+        items = torch.as_tensor(store.items).reshape(-1).to(torch.int64)
+        items = items[(items >= 0) & (items < int(n_items))]
+        return cls(n_items, counts=torch.bincount(items, minlength=int(n_items)), **kw)
+
+    def sample(self, n):
+        """(ids int64 [n], log_q float32 [n]): n independent draws."""
+        u = torch.rand(int(n), dtype=torch.float64, device=self.device, generator=self._gen)
+        ids = torch.searchsorted(self._cdf, u, right=True).clamp_(max=self.n_items - 1)
+        return ids, self._log_q[ids]
+
+    def log_q(self, ids):
+        """log q of any ids, float32; 0 for an id outside [0, n_items) (padding, ignored targets: such entries take no part)."""
+        ids = torch.as_tensor(ids).to(device=self.device, dtype=torch.int64)
+        ok = (ids >= 0) & (ids < self.n_items)
+        return torch.where(ok, self._log_q[ids.clamp(0, self.n_items - 1)], torch.zeros((), device=self.device))

@@ -21,7 +21,9 @@ def next_item_update(batch, params, nets, optimizer, device=torch.device("cuda")
                      step=-1):
     """
     :param batch: dict with state [rows, K] (may require grad) and target int64 [rows] (`SeqEnv.target_items(batch)`)
-    :param params: dict, optional entries ignore_index (default -100) and dtype ('fp32' / 'bf16'; default: set_catalogue_dtype's)
+    :param params: dict, optional entries ignore_index (default -100) and dtype ('fp32' / 'bf16'; default: set_catalogue_dtype's);
+        sampler (a NegativeSampler) with n_negatives, and / or in_batch=True, switch the loss to the sampled softmax
+        (`NextItemHead.sampled_loss`); without them the loss is the full softmax
     :param nets: dict(head: NextItemHead, proj: optional module applied to state before the head)
     :param optimizer: dict(optimizer): one torch optimizer over whatever is trained (head, proj, encoder, table)
     :param device: accepted for signature compatibility; the step runs where the head lives (the GPU)
@@ -47,7 +49,12 @@ def next_item_update(batch, params, nets, optimizer, device=torch.device("cuda")
         raise ValueError(f"next_item_update: {state.shape[0]} state rows but target of shape {tuple(target.shape)}")
     with torch.set_grad_enabled(bool(learn)):
         x = state if proj is None else proj(state)
-        rows = head.loss(x, target, reduction="none", ignore_index=params.get("ignore_index", -100), dtype=params.get("dtype"))
+        if params.get("sampler") is not None or params.get("in_batch"):
+            rows = head.sampled_loss(x, target, sampler=params.get("sampler"), n_negatives=params.get("n_negatives"),
+                                     in_batch=bool(params.get("in_batch")), reduction="none",
+                                     ignore_index=params.get("ignore_index", -100), dtype=params.get("dtype"))
+        else:
+            rows = head.loss(x, target, reduction="none", ignore_index=params.get("ignore_index", -100), dtype=params.get("dtype"))
         kept = (target.to(rows.device) != params.get("ignore_index", -100)).sum()
         loss = rows.sum() / kept
     if debug is not None:

@@ -981,6 +981,67 @@ int recnn_gru_backward_table(const int32_t* items, const float* ratings, const i
                              const float* g_hT, float* d_w_ih, float* d_w_hh, float* d_b_ih, float* d_b_hh, float* d_h0,
                              float* d_table, void* workspace, void* table_workspace, void* stream);
 
+/* Causal self-attention as the state encoder (csrc/attn.hip): one multi-head attention layer over the steps of a call.
+ * Per user, for the call's steps t = 0 .. T - 1 (history positions t0 .. t0 + T - 1; positions before t0 are not seen):
+ *   x_t = [table[item_t] | rating_t],   [q_t | k_t | v_t] = w_in x_t + b_in      w_in float[3 hidden, emb_dim + 1], b_in float[3 hidden]
+ *   s_a(t, j) = (q_t^a . k_j^a) / sqrt(d) - m_a (t - j)   for j in [max(0, t - window + 1), t], head a of n_heads, d = hidden / n_heads
+ *   p_a(t, .) = softmax_j s_a(t, .),   o_t^a = sum_j p_a(t, j) v_j^a,   h_t = w_o o_t + b_o      w_o float[hidden, hidden], b_o float[hidden]
+ * with m_a = 2^(-8 (a + 1) / n_heads) when `alibi` is non-zero, else 0; `window` = 0 means no window (j in [0, t]).  The store, slots,
+ * t0, T, table and the limits on emb_dim and hidden are those of recnn_lstm_encode; besides, hidden % n_heads == 0, d in {16, 32, 64},
+ * n_users <= 65535, n_users * T < 2^31, T >= 1.  Everything is fp32 on v_mfma_f32_16x16x4_f32 in fixed summation orders and without float
+ * atomics: equal calls give equal bits; a user's h does not depend on the other users of the batch or on its place among them; h[:, 0:a]
+ * of a call with T = a + b equals the call with T = a bit for bit.  Key tiles of 64 lie on multiples of 64 from the call's step 0; tiles
+ * above the diagonal or left of the window are not visited, masked keys inside a visited tile are a select on the score (probability
+ * exactly 0), so h_t does not depend on the bits of a masked position -- as long as they are finite:
+ * an item id outside [0, n_items) at position j of a user makes that user's q_j, k_j, v_j NaN (nothing is read out of bounds); h_t is NaN
+ * for every t >= j that has j in its window, and ALSO for the user's other steps t that visit the key tile holding j (t in the same block
+ * of 64 steps, or j left of t's window inside a visited tile): 0 * NaN in P V is NaN.  Other users are bitwise unaffected.
+ * With round256(x) = x rounded up to 256:
+ *   recnn_attn_workspace_bytes        round256(12 n_users T hidden) (qkv [n_users, T, 3 hidden]) + round256(4 n_users T hidden) (o)
+ *                                     + round256(8 n_users n_heads T) (the log-sum-exp per user, head and step, held as its two
+ *                                     parts: the row maximum m and l = sum exp(s - m))
+ *   recnn_attn_train_workspace_bytes  saved_bytes = the same three tensors, kept for the backward;
+ *                                     bwd_bytes = round256(4 hidden^2) (w_o^T) + round256(4 n_users T hidden) (dO)
+ *                                                 + round256(4 n_users n_heads T) (delta) + round256(12 n_users T hidden) (dqkv)
+ *                                                 + round256(4 nsplit max(3 hidden (emb_dim + 2), hidden (hidden + 1))) (the parts of the
+ *                                                 weight gradients: the call's n_users T samples are summed in
+ *                                                 nsplit = clamp(ceil(n_users T / 1024), 1, 64) segments, the parts added in order)
+ *   recnn_attn_table_grad_workspace_bytes  as recnn_gru_table_grad_workspace_bytes (3 hidden rows of w_in).
+ * All three are host-only.
+ *
+ * recnn_attn_encode writes h_out float[n_users, T, hidden]; `workspace` as above, 16-byte aligned like table, w_o and h_out.
+ * recnn_attn_encode_train is the same call -- the same h_out bit for bit -- that keeps qkv, o and the log-sum-exp in `saved`.
+ * recnn_attn_backward is the backward of ONE such call (same store, slots, t0, T, table, n_heads, window, alibi, w_o; `saved` as that
+ * call wrote it) for the upstream gradient g_h float[n_users, T, hidden] (required, 16-byte aligned).  Outputs, each may be NULL (not
+ * wanted: its launch is skipped), written, not added to: d_w_in float[3 hidden, emb_dim + 1], d_b_in float[3 hidden], d_w_o
+ * float[hidden, hidden], d_b_o float[hidden].  P is recomputed from q, k and the log-sum-exp; delta = sum_j p dP comes from a first
+ * sweep over the queries, dK and dV from a launch that owns keys, dQ from one that owns queries: no float atomics.
+ * recnn_attn_backward_table is recnn_attn_backward -- the same bits in the outputs they share -- that also writes d_table
+ * float[n_items, emb_dim] (required; EVERY row, exact zeros for items the call's positions do not hold) as recnn_lstm_backward_table
+ * does, with da = [dq | dk | dv]; w_in is read in place (its rating column is not used).  Item ids outside the table contribute to no row.
+ * Errors: RECNN_E_INVALID with a message, before any launch. */
+int recnn_attn_workspace_bytes(int n_users, int T, int hidden, int n_heads, int64_t* bytes);
+int recnn_attn_encode(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users, int t0,
+                      int T, const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window, int alibi,
+                      const float* w_in, const float* b_in, const float* w_o, const float* b_o, float* h_out, void* workspace,
+                      void* stream);
+int recnn_attn_train_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_heads, int64_t* saved_bytes,
+                                     int64_t* bwd_bytes);
+int recnn_attn_encode_train(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                            int t0, int T, const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window, int alibi,
+                            const float* w_in, const float* b_in, const float* w_o, const float* b_o, float* h_out, void* saved,
+                            void* stream);
+int recnn_attn_backward(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users, int t0,
+                        int T, const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window, int alibi,
+                        const float* w_o, const void* saved, const float* g_h, float* d_w_in, float* d_b_in, float* d_w_o,
+                        float* d_b_o, void* workspace, void* stream);
+int recnn_attn_table_grad_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_items, int64_t* bytes);
+int recnn_attn_backward_table(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                              int t0, int T, const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window,
+                              int alibi, const float* w_in, const float* w_o, const void* saved, const float* g_h, float* d_w_in,
+                              float* d_b_in, float* d_w_o, float* d_b_o, float* d_table, void* workspace, void* table_workspace,
+                              void* stream);
+
 /* =====================================================================================
  * 11. Offline ranking evaluation (csrc/rank.hip, csrc/topk.hip, csrc/evalrank.hip): where the item the user took
  *    next lands in the ranking a generated action induces over the catalogue, and the hit rate / NDCG / MRR of a batch of such ranks.

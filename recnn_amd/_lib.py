@@ -260,6 +260,13 @@ SIGNATURES = {
     "recnn_gru_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 13),
     "recnn_gru_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
     "recnn_gru_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I] + [_P] * 16),
+    "recnn_attn_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_attn_encode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 6 + [_P] * 7),
+    "recnn_attn_train_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L), C.POINTER(_L)]),
+    "recnn_attn_encode_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 6 + [_P] * 7),
+    "recnn_attn_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 6 + [_P] * 9),
+    "recnn_attn_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_attn_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 6 + [_P] * 12),
     "recnn_dist_target_rank_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
     "recnn_dist_target_rank": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P]),
     "recnn_topk_target_rank_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),

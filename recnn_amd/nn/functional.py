@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .attention import AttentionEncoder
 
 _call_counter = itertools.count(1)
 
@@ -1976,10 +1977,163 @@ def gru_encode_train(gru, store, table, slots, T, h0=None, *, t0=0, train_table=
     return GRUEncodeFunction.apply(*params, h0, store, table, torch.from_numpy(slots).to(dev), T, t0)
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# Causal self-attention as the state encoder (csrc/attn.hip): the one encoder whose work is parallel over the steps.
+_ATTN_PARAMS = ("in_proj_weight", "in_proj_bias", "out_proj.weight", "out_proj.bias")
+
+
+def _attn_call_args(name, enc, store, table, slots, T, t0):
+    """The checks of `attn_encode` / `attn_encode_train`, on the host and by argument name, before any launch:
+    (dev, E, H, U, T, t0, slots, params)."""
+    if not isinstance(enc, AttentionEncoder):
+        t = type(enc)
+        raise L.RecnnHipError(f"{name}: the state encoder is a {t.__module__}.{t.__qualname__}, not a recnn_amd.nn.AttentionEncoder "
+                              "(a torch.nn.LSTM goes to lstm_encode, a torch.nn.GRU to gru_encode)")
+    params = (enc.in_proj_weight, enc.in_proj_bias, enc.out_proj.weight, enc.out_proj.bias)
+    dev = params[0].device
+    for pname, p in zip(_ATTN_PARAMS, params):
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+            raise L.RecnnHipError(f"{name}: {pname} must be a contiguous float32 tensor on {dev} (got {p.dtype} on {p.device}, "
+                                  f"{'contiguous' if p.is_contiguous() else 'strided'})")
+    if not (isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype == torch.float32 and table.is_contiguous()):
+        raise L.RecnnHipError(f"{name}: table must be a contiguous float32 [n_items, E] tensor")
+    E, H, heads = table.shape[1], enc.hidden_size, enc.num_heads
+    if enc.input_size != E + 1:
+        raise L.RecnnHipError(f"{name}: input_size={enc.input_size} but the table has {E} columns (needs E + 1: the rating)")
+    if heads < 1 or H % heads:
+        raise L.RecnnHipError(f"{name}: hidden_size={H} is not a multiple of num_heads={heads}")
+    if H // heads not in (16, 32, 64):
+        raise L.RecnnHipError(f"{name}: head_dim={H // heads} is not supported (hidden_size / num_heads must be 16, 32 or 64)")
+    if H % 16 or H > 256:
+        raise L.RecnnHipError(f"{name}: hidden_size={H} must be a multiple of 16 up to 256")
+    if E % 8 or E > 128 or E < 8:
+        raise L.RecnnHipError(f"{name}: the table's width E={E} must be a multiple of 8 up to 128")
+    if enc.window is not None and int(enc.window) < 1:
+        raise L.RecnnHipError(f"{name}: window={enc.window} must be at least 1 (or None)")
+    if tuple(params[0].shape) != (3 * H, E + 1) or tuple(params[1].shape) != (3 * H,) or tuple(params[2].shape) != (H, H) \
+            or tuple(params[3].shape) != (H,):
+        raise L.RecnnHipError(f"{name}: the parameters do not have the shapes of hidden_size={H}, input_size={E + 1}")
+    slots = store.checked_slots(slots, name, dev)
+    U, T, t0 = len(slots), int(T), int(t0)
+    if T < 1 or t0 < 0:
+        raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
+    if U * T >= 1 << 31 or U > 65535:
+        raise ValueError(f"{name}: U * T = {U * T} must stay below 2^31 and U = {U} below 65536")
+    if U and int(store.lengths[slots].min()) < t0 + T:
+        raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
+    if not params[0].is_cuda:
+        raise L.RecnnHipError(f"{name}: the module lives on {dev} (in_proj_weight.device); it needs a GPU module "
+                              "(recnn_amd has no CPU fallback)")
+    if table.device != dev:
+        raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
+    return dev, E, H, U, T, t0, slots, params
+
+
+def _attn_head(enc, store, slots_d, U, t0, T, table, E, H):
+    """The leading arguments of every recnn_attn_* launch: `_store_args`, then heads, window (0: none) and alibi."""
+    return (*_store_args(store, slots_d, U, t0, T, table, E, H), enc.num_heads, enc.window or 0, int(enc.alibi))
+
+
+@torch.no_grad()
+def attn_encode(enc, store, table, slots, T, *, t0=0):
+    """h float32[U, T, H] of a `recnn_amd.nn.AttentionEncoder` for the users `slots` (store slots) over the steps t0 .. t0 + T - 1 of
+    their histories: step t attends to steps max(0, t - window + 1) .. t of THIS call (positions before t0 are not seen; there is no
+    carried state), its input being [table[item_t] | rating_t] read through the replay `store`.  Three launches: the in-projection
+    (rows gathered through the store), the flash-style attention, the out-projection; fp32 on the exact-f32 MFMA.
+
+    Equal calls give equal bits; a user's rows do not depend on the other users or on its place in the batch; the first `a` steps
+    of a longer call are bit for bit the call with T = a; h_t does not depend on the bits of any position it does not attend to.
+    Runs under no_grad (`attn_encode_train` is the same call with a graph); the parameters are read live from the module.  Refused
+    with RecnnHipError naming what is wrong: another module type, a CPU module, a non-contiguous or non-float32 parameter,
+    input_size != E + 1, hidden_size % num_heads, head_dim outside {16, 32, 64}, hidden_size not a multiple of 16 up to 256, E not a
+    multiple of 8 up to 128, window < 1; with ValueError: a history shorter than t0 + T, U * T >= 2^31."""
+    dev, E, H, U, T, t0, slots, params = _attn_call_args("attn_encode", enc, store, table, slots, T, t0)
+    ws = L.workspace("recnn_attn_workspace_bytes", U, T, H, enc.num_heads, device=dev)
+    h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+    slots_d = torch.from_numpy(slots).to(dev)
+    L.call("recnn_attn_encode", *_attn_head(enc, store, slots_d, U, t0, T, table, E, H), *(L.ptr(p) for p in params), L.ptr(h),
+           L.ptr(ws), L.current_stream())
+    return h
+
+
+class AttnEncodeFunction(torch.autograd.Function):
+    """h of the attention encoder with qkv, o and the log-sum-exp kept, and its backward (`recnn_attn_encode_train` /
+    `recnn_attn_backward`).  Differentiable in the four parameters and in the embedding `table` (`recnn_attn_backward_table`: the
+    dense [n_items, E] gradient, allocated only when `needs_input_grad` asks for it); once."""
+
+    @staticmethod
+    def forward(ctx, w_in, b_in, w_o, b_o, enc, store, table, slots_d, T, t0):
+        U, E, H = slots_d.shape[0], table.shape[1], w_o.shape[0]
+        dev = w_in.device
+        nsaved, nbwd = C.c_int64(), C.c_int64()
+        L.call("recnn_attn_train_workspace_bytes", U, T, H, E, enc.num_heads, C.byref(nsaved), C.byref(nbwd))
+        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+        h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+        head = _attn_head(enc, store, slots_d, U, t0, T, table, E, H)
+        L.call("recnn_attn_encode_train", *head, L.ptr(w_in), L.ptr(b_in), L.ptr(w_o), L.ptr(b_o), L.ptr(h), L.ptr(saved),
+               L.current_stream())
+        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
+        ctx.layer = (enc.num_heads, enc.window or 0, int(enc.alibi))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(w_in, w_o, table, slots_d, saved)
+        return h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h):
+        w_in, w_o, table, slots_d, saved = ctx.saved_tensors
+        U, T, t0, E, H = ctx.dims
+        need = ctx.needs_input_grad
+        if g_h is None:
+            return (None,) * 10
+        dev = saved.device
+        g_h = g_h.to(torch.float32).contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        d_w_in = new(3 * H, E + 1) if need[0] else None
+        d_b_in = new(3 * H) if need[1] else None
+        d_w_o = new(H, H) if need[2] else None
+        d_b_o = new(H) if need[3] else None
+        d_table = new(table.shape[0], E) if need[6] else None
+        ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
+        head = (*_store_args(ctx.store, slots_d, U, t0, T, table, E, H), *ctx.layer)
+        mid = (L.ptr(w_o), L.ptr(saved), L.ptr(g_h), L.ptr(d_w_in), L.ptr(d_b_in), L.ptr(d_w_o), L.ptr(d_b_o))
+        if d_table is None:
+            L.call("recnn_attn_backward", *head, *mid, L.ptr(ws), L.current_stream())
+        else:
+            tws = L.workspace("recnn_attn_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
+            L.call("recnn_attn_backward_table", *head, L.ptr(w_in), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
+        return d_w_in, d_b_in, d_w_o, d_b_o, None, None, d_table, None, None, None
+
+
+def attn_encode_train(enc, store, table, slots, T, *, t0=0, train_table=False):
+    """`attn_encode` with a graph: the same arguments, checks and h -- bit for bit -- differentiable with respect to
+    in_proj_weight, in_proj_bias, out_proj.weight and out_proj.bias.  The forward keeps qkv [U, T, 3H], o [U, T, H] and the
+    log-sum-exp per (user, head, step); the backward recomputes the probabilities from them in three launches (a sweep that sums
+    delta = sum_j p dP, one that owns keys and gives dK and dV, one that owns queries and gives dQ), then the weight-gradient tile
+    of the recurrent encoders over segments of the samples: fixed summation orders and no float atomics, so equal calls give equal
+    gradients bit for bit.  Once differentiable.
+
+    The embedding table is handled as in `lstm_encode_train`: a `table` that requires grad is refused with RecnnHipError unless
+    `train_table=True`, and then `table.grad` receives the dense [n_items, E] gradient, exact zeros in the rows of items the batch's
+    steps do not hold -- also with every encoder parameter frozen.  The parameter gradients keep their bits.
+
+    Under `torch.no_grad()`, or when nothing requires grad, this IS `attn_encode`: nothing is kept."""
+    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
+        raise L.RecnnHipError("attn_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
+                              "computed only on request; pass train_table=True to train it, or table.detach()")
+    dev, E, H, U, T, t0, slots, params = _attn_call_args("attn_encode_train", enc, store, table, slots, T, t0)
+    if not (torch.is_grad_enabled() and (table.requires_grad or any(p.requires_grad for p in params))):
+        return attn_encode(enc, store, table.detach(), slots, T, t0=t0)
+    return AttnEncodeFunction.apply(*params, enc, store, table, torch.from_numpy(slots).to(dev), T, t0)
+
+
 def state_encode(encoder, store, table, slots, T, *, train=False, train_table=False):
     """h float32[U, T, H] of whichever state encoder `encoder` is -- the one place that dispatches on the module's type (SeqEnv goes
     through it): a torch.nn.LSTM runs `lstm_encode` / `lstm_encode_train`, a torch.nn.GRU `gru_encode` / `gru_encode_train`, from a
-    zero state at step 0.  Any other module is refused by name."""
+    zero state at step 0, a recnn_amd.nn.AttentionEncoder `attn_encode` / `attn_encode_train`.  Any other module is refused by name."""
+    kw = dict(train_table=train_table) if train else {}
+    if isinstance(encoder, AttentionEncoder):
+        return (attn_encode_train if train else attn_encode)(encoder, store, table, slots, T, **kw)
     if isinstance(encoder, torch.nn.LSTM):
         fn = lstm_encode_train if train else lstm_encode
     elif isinstance(encoder, torch.nn.GRU):
@@ -1987,8 +2141,9 @@ def state_encode(encoder, store, table, slots, T, *, train=False, train_table=Fa
     else:
         t = type(encoder)
         raise L.RecnnHipError(f"state encoder: a {t.__module__}.{t.__qualname__} is not supported; the HIP encoders are a single-layer "
-                              "torch.nn.LSTM(E + 1, H) and a single-layer torch.nn.GRU(E + 1, H)")
-    return fn(encoder, store, table, slots, T, **(dict(train_table=train_table) if train else {}))[0]
+                              "torch.nn.LSTM(E + 1, H), a single-layer torch.nn.GRU(E + 1, H) and a recnn_amd.nn.AttentionEncoder(E + 1, H, "
+                              "heads)")
+    return fn(encoder, store, table, slots, T, **kw)[0]
 
 
 class SeqCollectFunction(torch.autograd.Function):

@@ -14,8 +14,9 @@ import torch
 import torch.nn as nn
 
 from . import functional as F_hip
+from .attention import AttentionEncoder  # noqa: F401
 
-__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead", "NegativeSampler"]
+__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead", "NegativeSampler", "AttentionEncoder"]
 
 
 class DuelDQN(nn.Module):

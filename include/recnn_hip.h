@@ -1042,6 +1042,83 @@ int recnn_attn_backward_table(const int32_t* items, const float* ratings, const 
                               float* d_b_in, float* d_w_o, float* d_b_o, float* d_table, void* workspace, void* table_workspace,
                               void* stream);
 
+/* The transformer state encoder (csrc/block.hip): a gathered embedding, pre-LN transformer blocks on a dense residual
+ * stream x float[n_users, T, hidden], and a final LayerNorm.  The calls are cut along the autograd nodes; between them only
+ * [n_users, T, hidden] tensors cross.  Per user, for the call's steps t = 0 .. T - 1 (nothing is carried between calls):
+ *   embedding   x_t = w_e [table[item_t] | rating_t] + b_e                       w_e float[hidden, emb_dim + 1], b_e float[hidden]
+ *   block       u = x + w_o Attn(LN1(x)) + b_o                                   Attn: the layer above on a dense input, w_in
+ *                                                                                float[3 hidden, hidden] (q | k | v), b_in float[3 hidden]
+ *               y = u + w2 act(w1 LN2(u) + b1) + b2                              w1 float[ffn, hidden], w2 float[hidden, ffn]
+ *   LayerNorm   LN(z) = (z - mean(z)) / sqrt(var_biased(z) + eps) gamma + beta   (g1, be1), (g2, be2): float[hidden] each
+ * act: 0 = relu, 1 = gelu in its exact erf form.  n_heads, window, alibi, the limits on hidden, head width, emb_dim, n_users and T are
+ * those of recnn_attn_encode; besides, ffn is a multiple of 16 in 16 .. 1024 and eps > 0.  Everything is fp32 on
+ * v_mfma_f32_16x16x4_f32 in fixed summation orders, no float atomics.  A row's mean and variance are summed by four lanes (lane q:
+ * columns q, q + 4, .. upwards; then (s0 + s1) + (s2 + s3)), the mean first, then the centred squares.  Every product chain starts
+ * from its bias and walks the contraction index upwards; a residual is added after the chain is finished: u = x + (b_o + ..),
+ * y = u + (b2 + ..).  So equal calls give equal bits, a user's rows do not depend on the batch, and the first `a` steps of a longer call
+ * are the shorter call's.  An item id outside the table makes x_t NaN for that row (nothing is read out of bounds); the NaN then follows
+ * the attention's rule above through every block, and other users are bitwise unaffected.
+ *
+ * recnn_seq_embed writes x_out float[n_users, T, hidden] (16-byte aligned, like table); store, slots, t0, T, table as recnn_lstm_encode.
+ * recnn_seq_embed_backward: g_x float[n_users, T, hidden] (required) -> d_w_e float[hidden, emb_dim + 1], d_b_e float[hidden]; each may be
+ * NULL (not wanted: its launch is skipped), written, not added to.  workspace: recnn_seq_embed_backward_workspace_bytes =
+ * round256(4 nsplit hidden (emb_dim + 2)), nsplit as for recnn_attn_backward.  recnn_seq_embed_backward_table also writes d_table
+ * float[n_items, emb_dim] (required; every row) as recnn_attn_backward_table does, with da = g_x and w_e read in place;
+ * recnn_seq_embed_table_grad_workspace_bytes as recnn_gru_table_grad_workspace_bytes (hidden rows of w_e).
+ *
+ * recnn_block_forward: x -> y (y must not be x; both 16-byte aligned, like the four weight matrices and the workspace).
+ *   recnn_block_workspace_bytes = recnn_attn_workspace_bytes (qkv, o, log-sum-exp) + round256(4 n_users T hidden) (u).  It does not
+ *   depend on ffn: the [n_users T, ffn] activation lives in LDS, 64 rows by 32 columns at a time.  Host-only.
+ * recnn_block_forward_train is the same call -- the same y bit for bit -- that keeps in `saved` what the backward needs: qkv, o, the
+ *   log-sum-exp, u and the pre-activation a = w1 LN2(u) + b1 float[n_users T, ffn].  The LayerNorm statistics, the normalised rows and
+ *   act(a) are NOT kept: the backward recomputes them (the same functions, the same bits).
+ *   recnn_block_train_workspace_bytes: saved_bytes = recnn_block_workspace_bytes + round256(4 n_users T ffn); with W = max(ffn, 3 hidden),
+ *   bwd_bytes = round256(4 W hidden) (a transposed weight) + 2 round256(4 n_users T hidden) + round256(4 n_users T W)
+ *               + round256(4 n_users n_heads T) (delta) + round256(4 nsplit W (hidden + 1)) (the parts of the weight gradients)
+ *               + round256(8 hidden (ceil(n_users T / 64) + ceil(ceil(n_users T / 64) / 64))) (the parts of d_gamma / d_beta).
+ * recnn_block_backward is the backward of ONE recnn_block_forward_train call (the same x, sizes, parameters; `saved` as that call wrote
+ *   it) for g_y float[n_users, T, hidden] (required).  Outputs, each may be NULL (not wanted: its launch is skipped -- and everything
+ *   upstream of it that nothing else needs), written, not added to: d_x float[n_users, T, hidden] and the twelve parameter gradients in
+ *   the shapes of their parameters.  d_gamma / d_beta: each workgroup of 64 rows sums its columns in row order, the parts are added in
+ *   groups of 64 consecutive workgroups and then group after group.  The weight gradients are recnn_attn_backward's segmented tile.
+ *
+ * recnn_layernorm_rows: out = LN(x) for x float[rows, hidden] (the final LayerNorm); recnn_layernorm_rows_backward: g_out float[rows,
+ * hidden] -> d_x, d_gamma, d_beta (each may be NULL), workspace of recnn_layernorm_rows_backward_workspace_bytes (the d_gamma / d_beta
+ * parts above).  Errors: RECNN_E_INVALID with a message, before any launch. */
+int recnn_seq_embed(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users, int t0, int T,
+                    const float* table, int n_items, int emb_dim, int hidden, const float* w_e, const float* b_e, float* x_out,
+                    void* stream);
+int recnn_seq_embed_backward_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int64_t* bytes);
+int recnn_seq_embed_backward(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_users,
+                             int t0, int T, const float* table, int n_items, int emb_dim, int hidden, const float* g_x, float* d_w_e,
+                             float* d_b_e, void* workspace, void* stream);
+int recnn_seq_embed_table_grad_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_items, int64_t* bytes);
+int recnn_seq_embed_backward_table(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots,
+                                   int n_users, int t0, int T, const float* table, int n_items, int emb_dim, int hidden,
+                                   const float* w_e, const float* g_x, float* d_w_e, float* d_b_e, float* d_table, void* workspace,
+                                   void* table_workspace, void* stream);
+int recnn_block_workspace_bytes(int n_users, int T, int hidden, int n_heads, int64_t* bytes);
+int recnn_block_forward(const float* x, int n_users, int T, int hidden, int n_heads, int ffn, int act, int window, int alibi, float eps,
+                        const float* w_in, const float* b_in, const float* w_o, const float* b_o, const float* w1, const float* b1,
+                        const float* w2, const float* b2, const float* g1, const float* be1, const float* g2, const float* be2, float* y,
+                        void* workspace, void* stream);
+int recnn_block_train_workspace_bytes(int n_users, int T, int hidden, int n_heads, int ffn, int64_t* saved_bytes, int64_t* bwd_bytes);
+int recnn_block_forward_train(const float* x, int n_users, int T, int hidden, int n_heads, int ffn, int act, int window, int alibi,
+                              float eps, const float* w_in, const float* b_in, const float* w_o, const float* b_o, const float* w1,
+                              const float* b1, const float* w2, const float* b2, const float* g1, const float* be1, const float* g2,
+                              const float* be2, float* y, void* saved, void* stream);
+int recnn_block_backward(const float* x, int n_users, int T, int hidden, int n_heads, int ffn, int act, int window, int alibi, float eps,
+                         const float* w_in, const float* b_in, const float* w_o, const float* b_o, const float* w1, const float* b1,
+                         const float* w2, const float* b2, const float* g1, const float* be1, const float* g2, const float* be2,
+                         const void* saved, const float* g_y, float* d_x, float* d_w_in, float* d_b_in, float* d_w_o, float* d_b_o,
+                         float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_g1, float* d_be1, float* d_g2, float* d_be2,
+                         void* workspace, void* stream);
+int recnn_layernorm_rows(const float* x, int rows, int hidden, const float* gamma, const float* beta, float eps, float* out,
+                         void* stream);
+int recnn_layernorm_rows_backward_workspace_bytes(int rows, int hidden, int64_t* bytes);
+int recnn_layernorm_rows_backward(const float* x, int rows, int hidden, const float* gamma, float eps, const float* g_out, float* d_x,
+                                  float* d_gamma, float* d_beta, void* workspace, void* stream);
+
 /* =====================================================================================
  * 11. Offline ranking evaluation (csrc/rank.hip, csrc/topk.hip, csrc/evalrank.hip): where the item the user took
  *    next lands in the ranking a generated action induces over the catalogue, and the hit rate / NDCG / MRR of a batch of such ranks.

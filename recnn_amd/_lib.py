@@ -267,6 +267,19 @@ SIGNATURES = {
     "recnn_attn_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 6 + [_P] * 9),
     "recnn_attn_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
     "recnn_attn_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 6 + [_P] * 12),
+    "recnn_seq_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 3 + [_P] * 4),
+    "recnn_seq_embed_backward_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_seq_embed_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 3 + [_P] * 5),
+    "recnn_seq_embed_table_grad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_seq_embed_backward_table": (_I, [_P, _P, _P, _P, _I, _I, _I, _P] + [_I] * 3 + [_P] * 8),
+    "recnn_block_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_L)]),
+    "recnn_block_forward": (_I, [_P] + [_I] * 8 + [_F] + [_P] * 15),
+    "recnn_block_train_workspace_bytes": (_I, [_I, _I, _I, _I, _I, C.POINTER(_L), C.POINTER(_L)]),
+    "recnn_block_forward_train": (_I, [_P] + [_I] * 8 + [_F] + [_P] * 15),
+    "recnn_block_backward": (_I, [_P] + [_I] * 8 + [_F] + [_P] * 29),
+    "recnn_layernorm_rows": (_I, [_P, _I, _I, _P, _P, _F, _P, _P]),
+    "recnn_layernorm_rows_backward_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
+    "recnn_layernorm_rows_backward": (_I, [_P, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P]),
     "recnn_dist_target_rank_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
     "recnn_dist_target_rank": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P]),
     "recnn_topk_target_rank_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),

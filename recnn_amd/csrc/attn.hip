@@ -32,565 +32,9 @@
 //                    the table gradient is seq_grad.h's dX contraction and scatter-sum with da = dqkv.
 // Every sum has a fixed order that depends on nothing but (t, j): equal calls give equal bits, a user's bits do not depend on the batch,
 // and h[:, :a] of a longer call equals the shorter call's.
-#include <algorithm>
-
-#include "seq_bwd.h"
+#include "attn_dev.h"
 
 namespace {
-
-constexpr int AT_Q = 64;            // query rows per workgroup, keys per tile
-constexpr int AT_PAD = 4;
-constexpr int AT_MAXHEADS = 16;
-constexpr int LIN_ROWS = 64;
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
-
-// ------------------------------------------------------------------------------------------------ linear
-struct LinArgs {
-  SeqStore s;                       // GATHER: x rows are [table[item] | rating] through the store
-  int t0, T;
-  int rows;                         // samples s = u T + t
-  const float* x;                   // dense: [rows][K]
-  int K;                            // contraction width without the rating column (a multiple of 8; dense: of 16)
-  const float* w;                   // [N][ldw]
-  int ldw;
-  const float* b;                   // [N] or NULL
-  float* out;                       // [rows][N]
-  int N;                            // a multiple of 16
-};
-
-inline size_t lin_lds(int K) { return (size_t)(LIN_ROWS * (((K + 15) & ~15) + AT_PAD) + LIN_ROWS) * sizeof(float); }
-
-template <bool GATHER>
-__global__ __launch_bounds__(256) void attn_linear_kernel(const LinArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int K = a.K, KX = (K + 15) & ~15, ldx = KX + AT_PAD, C4 = KX >> 2;
-  float* xs = smem;                 // [64][ldx]
-  float* rs = xs + LIN_ROWS * ldx;  // [64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int s0 = blockIdx.x * LIN_ROWS;
-  for (int idx = tid; idx < LIN_ROWS * C4; idx += 256) {
-    const int row = idx / C4, c = idx - row * C4, s = s0 + row;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (s < a.rows && 4 * c < K) {
-      if constexpr (GATHER) {
-        const int u = s / a.T, t = s - u * a.T;
-        const int slot = a.s.slots[u];
-        const int64_t off = a.s.user_off[slot];
-        const int len = (int)(a.s.user_off[slot + 1] - off);
-        const int64_t pos = off + max(min(a.t0 + t, len - 1), 0);       // (the host refuses steps past a history's end)
-        v = len > 0 ? table_chunk(a.s, a.s.items[pos], c) : nan4();
-        if (c == 0) rs[row] = len > 0 ? a.s.ratings[pos] : __builtin_nanf("");
-      } else {
-        v = *(const float4*)(a.x + (int64_t)s * K + 4 * c);
-      }
-    } else if (GATHER && c == 0) {
-      rs[row] = 0.f;
-    }
-    *(float4*)(xs + row * ldx + 4 * c) = v;
-  }
-  __syncthreads();
-  const int ntiles = a.N >> 4;
-  for (int jt = wave; jt < ntiles; jt += 4) {
-    const int col = jt * 16 + r;
-    const float* wrow = a.w + (int64_t)col * a.ldw;
-    const float bias = a.b ? a.b[col] : 0.f;
-    f32x4 acc[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (GATHER) acc[mt][i] = fmaf(rs[16 * mt + 4 * g + i], wrow[K], bias);
-        else acc[mt][i] = bias;
-      }
-    for (int k0 = 0; k0 < K; k0 += 16) {
-      const bool kin = k0 + 4 * g < K;        // K a multiple of 8: the last k block may be half empty (x there is zero)
-      const f32x4 bv = kin ? (f32x4)(*(const f32x4u*)(wrow + k0 + 4 * g)) : f32x4{0.f, 0.f, 0.f, 0.f};
-      f32x4 av[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) av[mt] = *(const f32x4*)(xs + (16 * mt + r) * ldx + k0 + 4 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][e], bv[e], acc[mt], 0, 0, 0);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int s = s0 + 16 * mt + 4 * g + i;
-        if (s < a.rows) a.out[(int64_t)s * a.N + col] = acc[mt][i];
-      }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ attention
-struct AttnArgs {
-  int U, T, H, heads, window;       // window: 1 .. T (T: no window)
-  float scale;                      // 1 / sqrt(d)
-  float slope[AT_MAXHEADS];
-  const float* qkv;                 // [U][T][3H]
-  float* o;                         // [U][T][H]
-  float* lse;                       // [2][U][heads][T]: the log-sum-exp of a row in two parts, its maximum m and the sum l of exp(s - m)
-  const float* d_o;                 // backward: [U][T][H]
-  const float* delta;               // backward: [U][heads][T]
-  float* delta_out;                 // MODE 1 writes it
-  float* dqkv;                      // backward: [U][T][3H]
-};
-
-// a 64 x D tile of rows t0 .. t0 + 63 of one head's columns (src points at row 0 of the user, the head's first column; row stride ld)
-// into LDS [64][D + 4]; rows at or past T are zeros
-template <int D>
-__device__ __forceinline__ void stage_tile(float* dst, const float* src, int64_t ld, int t0, int T, int tid) {
-  constexpr int C4 = D / 4, LD = D + AT_PAD;
-  for (int idx = tid; idx < AT_Q * C4; idx += 256) {
-    const int row = idx / C4, c = idx - row * C4, t = t0 + row;
-    *(float4*)(dst + row * LD + 4 * c) = t < T ? *(const float4*)(src + (int64_t)t * ld + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-__device__ __forceinline__ float fold4(float v) {   // the sum over the four lane groups of a query, in every lane
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
-// grid (query blocks, heads, users), 256 threads.  MODE 0: the forward, o and the log-sum-exp.  MODE 1 and 2: the query owner of the
-// backward -- 1: delta[t] = sum_j p(t, j) dP(t, j), 2: dQ.
-template <int D, int MODE>
-__global__ __launch_bounds__(256) void attn_query_kernel(const AttnArgs a) {
-  constexpr int LD = D + AT_PAD, DT = D / 16;
-  constexpr bool BWD = MODE != 0;
-  __shared__ __attribute__((aligned(16))) float Ks[AT_Q * LD];
-  __shared__ __attribute__((aligned(16))) float Vs[AT_Q * LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int qb = gridDim.x - 1 - blockIdx.x, head = blockIdx.y, u = blockIdx.z;      // the heaviest blocks first
-  const int T = a.T, H = a.H, H3 = 3 * H, w = a.window;
-  const int q0 = qb * AT_Q, tq = q0 + 16 * wave + r;   // the lane's query
-  const bool qlive = tq < T;
-  const float* base = a.qkv + (int64_t)u * T * H3 + head * D;
-  const float slope = a.slope[head], scale = a.scale;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 qf[DT];
-  [[maybe_unused]] f32x4 dof[DT];
-#pragma unroll
-  for (int kb = 0; kb < DT; ++kb) {
-    qf[kb] = qlive ? *(const f32x4*)(base + (int64_t)tq * H3 + 16 * kb + 4 * g) : zero4;
-    if constexpr (BWD) dof[kb] = qlive ? *(const f32x4*)(a.d_o + ((int64_t)u * T + tq) * H + head * D + 16 * kb + 4 * g) : zero4;
-  }
-  const int64_t lplane = (int64_t)a.U * a.heads * T;          // l sits one plane behind m
-  [[maybe_unused]] float m_q = 0.f, il_q = 0.f, delta_q = 0.f;
-  if constexpr (BWD) {
-    if (qlive) {
-      m_q = a.lse[((int64_t)u * a.heads + head) * T + tq];
-      il_q = 1.f / a.lse[lplane + ((int64_t)u * a.heads + head) * T + tq];
-      if constexpr (MODE == 2) delta_q = a.delta[((int64_t)u * a.heads + head) * T + tq];
-    }
-  }
-  f32x4 oacc[DT];                    // O^T (BWD: dQ^T): columns 16 dt + 4 g + i of query tq
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) oacc[dt] = zero4;
-  float m = neg_inf(), l = 0.f;
-  [[maybe_unused]] float dsum = 0.f;
-  const int tq_lo = q0 + 16 * wave, tq_hi = tq_lo + 15;      // the wave's rows
-  const int tile_lo = max(0, q0 - w + 1) / AT_Q;
-
-  for (int kt = tile_lo; kt <= qb; ++kt) {
-    const int k0 = kt * AT_Q;
-    __syncthreads();
-    stage_tile<D>(Ks, base + H, H3, k0, T, tid);
-    stage_tile<D>(Vs, base + 2 * H, H3, k0, T, tid);
-    __syncthreads();
-    if (k0 > tq_hi || k0 + AT_Q - 1 < tq_lo - w + 1) continue;      // nothing of the tile is in the wave's reach (wave-uniform)
-    f32x4 s[4] = {zero4, zero4, zero4, zero4};
-    [[maybe_unused]] f32x4 dp[4] = {zero4, zero4, zero4, zero4};
-#pragma unroll
-    for (int kb = 0; kb < DT; ++kb) {
-      f32x4 kf[4];
-      [[maybe_unused]] f32x4 vf[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        kf[c] = *(const f32x4*)(Ks + (16 * c + r) * LD + 16 * kb + 4 * g);
-        if constexpr (BWD) vf[c] = *(const f32x4*)(Vs + (16 * c + r) * LD + 16 * kb + 4 * g);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          s[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[c][e], qf[kb][e], s[c], 0, 0, 0);
-          if constexpr (BWD) dp[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[c][e], dof[kb][e], dp[c], 0, 0, 0);
-        }
-    }
-    // s[c][i]: key k0 + 16 c + 4 g + i against query tq
-    if constexpr (!BWD) {
-      float tmax = neg_inf();
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int dist = tq - (k0 + 16 * c + 4 * g + i);
-          const bool valid = dist >= 0 && dist < w;
-          const float sc = valid ? fmaf(-slope, (float)dist, s[c][i] * scale) : neg_inf();
-          s[c][i] = sc;
-          tmax = fmaxf(tmax, sc);
-        }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float m_new = fmaxf(m, tmax);
-      const float m_use = m_new == neg_inf() ? 0.f : m_new;       // a row nothing has reached yet: exp(-inf - 0) = 0, never inf - inf
-      const float alpha = expf(m - m_use);
-      float psum = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float p = expf(s[c][i] - m_use);
-          s[c][i] = p;
-          psum += p;
-        }
-      psum = fold4(psum);
-      l = fmaf(l, alpha, psum);
-      m = m_new;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) oacc[dt] *= alpha;
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int dist = tq - (k0 + 16 * c + 4 * g + i);
-          const bool valid = qlive && dist >= 0 && dist < w;
-          const float sc = fmaf(-slope, (float)dist, s[c][i] * scale);
-          const float p = valid ? expf(sc - m_q) * il_q : 0.f;
-          if constexpr (MODE == 1) dsum = fmaf(p, dp[c][i], dsum);
-          else s[c][i] = p * (dp[c][i] - delta_q) * scale;         // dS, with the 1 / sqrt(d) of dQ = dS K / sqrt(d)
-        }
-    }
-    if constexpr (MODE == 1) continue;
-    const float* Bs = BWD ? Ks : Vs;                               // O^T += V^T P^T;  dQ^T += K^T dS^T
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-          oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Bs[(16 * c + 4 * g + e) * LD + 16 * dt + r], s[c][e], oacc[dt], 0, 0, 0);
-  }
-  if (!qlive) return;
-  if constexpr (!BWD) {
-    const float inv = 1.f / l;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-      *(f32x4*)(a.o + ((int64_t)u * T + tq) * H + head * D + 16 * dt + 4 * g) = oacc[dt] * inv;
-    if (g == 0) {
-      a.lse[((int64_t)u * a.heads + head) * T + tq] = m;
-      a.lse[lplane + ((int64_t)u * a.heads + head) * T + tq] = l;
-    }
-  } else if constexpr (MODE == 1) {
-    dsum = fold4(dsum);
-    if (g == 0) a.delta_out[((int64_t)u * a.heads + head) * T + tq] = dsum;
-  } else {
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) *(f32x4*)(a.dqkv + ((int64_t)u * T + tq) * H3 + head * D + 16 * dt + 4 * g) = oacc[dt];
-  }
-}
-
-// the key owner of the backward: grid (key blocks, heads, users), 256 threads; wave w owns keys 16 w .. 16 w + 15 of the block
-template <int D>
-__global__ __launch_bounds__(256) void attn_key_kernel(const AttnArgs a) {
-  constexpr int LD = D + AT_PAD, DT = D / 16;
-  __shared__ __attribute__((aligned(16))) float Qs[AT_Q * LD];
-  __shared__ __attribute__((aligned(16))) float Os[AT_Q * LD];      // dO
-  __shared__ __attribute__((aligned(16))) float Ls[AT_Q];      // m
-  __shared__ __attribute__((aligned(16))) float Is[AT_Q];      // 1 / l
-  __shared__ __attribute__((aligned(16))) float Ds[AT_Q];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int kb_ = blockIdx.x, head = blockIdx.y, u = blockIdx.z;    // (key block 0 is the heaviest)
-  const int T = a.T, H = a.H, H3 = 3 * H, w = a.window;
-  const int k0 = kb_ * AT_Q, jk = k0 + 16 * wave + r;               // the lane's key
-  const bool klive = jk < T;
-  const float* base = a.qkv + (int64_t)u * T * H3 + head * D;
-  const float* dobase = a.d_o + (int64_t)u * T * H + head * D;
-  const float* lrow = a.lse + ((int64_t)u * a.heads + head) * T;
-  const float* srow = lrow + (int64_t)a.U * a.heads * T;
-  const float* drow = a.delta + ((int64_t)u * a.heads + head) * T;
-  const float slope = a.slope[head], scale = a.scale;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 kf[DT], vf[DT], dk[DT], dv[DT];
-#pragma unroll
-  for (int kb = 0; kb < DT; ++kb) {
-    kf[kb] = klive ? *(const f32x4*)(base + (int64_t)jk * H3 + H + 16 * kb + 4 * g) : zero4;
-    vf[kb] = klive ? *(const f32x4*)(base + (int64_t)jk * H3 + 2 * H + 16 * kb + 4 * g) : zero4;
-    dk[kb] = zero4;
-    dv[kb] = zero4;
-  }
-  const int jk_lo = k0 + 16 * wave, jk_hi = jk_lo + 15;             // the wave's keys
-  const int nqb = (T + AT_Q - 1) / AT_Q;
-  const int qt_hi = min(nqb - 1, (k0 + AT_Q - 1 + w - 1) / AT_Q);
-
-  for (int qt = kb_; qt <= qt_hi; ++qt) {
-    const int t0 = qt * AT_Q;
-    __syncthreads();
-    stage_tile<D>(Qs, base, H3, t0, T, tid);
-    stage_tile<D>(Os, dobase, H, t0, T, tid);
-    if (tid < AT_Q) {
-      const bool in = t0 + tid < T;
-      Ls[tid] = in ? lrow[t0 + tid] : 0.f;
-      Is[tid] = in ? 1.f / srow[t0 + tid] : 0.f;
-      Ds[tid] = in ? drow[t0 + tid] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int c = 0; c < 4; ++c) {
-      const int tc = t0 + 16 * c;                                   // queries tc .. tc + 15
-      if (tc + 15 < jk_lo || tc - jk_hi >= w || tc >= T) continue;  // out of the wave's reach (wave-uniform)
-      f32x4 s = zero4, dp = zero4;
-#pragma unroll
-      for (int kb = 0; kb < DT; ++kb) {
-        const f32x4 qa = *(const f32x4*)(Qs + (16 * c + r) * LD + 16 * kb + 4 * g);
-        const f32x4 oa = *(const f32x4*)(Os + (16 * c + r) * LD + 16 * kb + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          s = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[e], kf[kb][e], s, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x4f32(oa[e], vf[kb][e], dp, 0, 0, 0);
-        }
-      }
-      // s[i]: query tc + 4 g + i against key jk
-      const f32x4 l4 = *(const f32x4*)(Ls + 16 * c + 4 * g), i4 = *(const f32x4*)(Is + 16 * c + 4 * g);
-      const f32x4 d4 = *(const f32x4*)(Ds + 16 * c + 4 * g);
-      f32x4 pv, dsv;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int t = tc + 4 * g + i, dist = t - jk;
-        const bool valid = klive && t < T && dist >= 0 && dist < w;
-        const float sc = fmaf(-slope, (float)dist, s[i] * scale);
-        const float p = valid ? expf(sc - l4[i]) * i4[i] : 0.f;
-        pv[i] = p;
-        dsv[i] = p * (dp[i] - d4[i]) * scale;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          dv[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Os[(16 * c + 4 * g + e) * LD + 16 * dt + r], pv[e], dv[dt], 0, 0, 0);
-          dk[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Qs[(16 * c + 4 * g + e) * LD + 16 * dt + r], dsv[e], dk[dt], 0, 0, 0);
-        }
-    }
-  }
-  if (!klive) return;
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
-    float* dst = a.dqkv + ((int64_t)u * T + jk) * H3 + head * D + 16 * dt + 4 * g;
-    *(f32x4*)(dst + H) = dk[dt];
-    *(f32x4*)(dst + 2 * H) = dv[dt];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ weight gradients
-// dW[m, n] = sum_s da[s, m] X[s, n] over the call's samples s = u T + t: the tile of seq_dw_kernel (seq_grad.h: 64 x 64 of dW per
-// workgroup, 16 samples per LDS stage, exact-f32 MFMA, the rating column and db as plain sums of the same stage) with one more grid
-// dimension.  There a workgroup walks ALL samples of a chunk of 32 steps; here the whole call is one "chunk" of U T samples, and
-// 12 x 2 workgroups walking 25 000 samples one after the other took 7 of the backward's 9 ms.  So the samples are cut
-// into `nsplit` segments of `seg` samples (a function of U T alone), workgroup z sums its segment in sample order into part[z], and
-// attn_sum_parts_kernel adds the parts in the order z = 0, 1, ..: still no atomics, still one fixed order for equal calls.
-struct AdwArgs {
-  SeqStore s;                       // GATHER: X rows are table rows through the store, and the rating is one more column
-  int t0, T;
-  int S, seg;                       // samples of the call; samples per segment (a multiple of 16)
-  const float* da;                  // [S][lda], columns 0 .. G - 1
-  int lda;
-  const float* x;                   // dense X rows [S][ldx]
-  int ldx;
-  int G, N;                         // rows of dW (a multiple of 16), columns without the rating column (a multiple of 4)
-  float* part;                      // [nsplit][G][ldp], ldp = N (+ 1: the rating column, GATHER); NULL: dW is not wanted
-  int ldp;
-  float* part_b;                    // [nsplit][G]; NULL: db is not wanted
-};
-
-// grid (ceil(G / 64), ceil(N / 64) or 1, nsplit), 256 threads
-template <bool GATHER>
-__global__ __launch_bounds__(256) void attn_dw_kernel(const AdwArgs a) {
-  __shared__ __attribute__((aligned(16))) float As[2][DW_S][DW_LD];
-  __shared__ __attribute__((aligned(16))) float Xs[2][DW_S][DW_LD];
-  __shared__ float Rs[2][DW_S];
-  const int G = a.G, N = a.N;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * DW_T, n0 = blockIdx.y * DW_T;
-  const int s_lo = blockIdx.z * a.seg, s_hi = min(a.S, s_lo + a.seg), nb = (s_hi - s_lo + DW_S - 1) / DW_S;
-  const int sr = tid >> 4, sc = tid & 15;     // the stager: sample row sr of a stage, 16-byte chunk sc of both operands
-  const bool xcol = n0 + 4 * sc < N, arow = m0 + 4 * sc < G;
-  const bool extras = blockIdx.y == 0 && (a.part_b || (GATHER && a.part));
-
-  auto fetch = [&](int b, float4& av, float4& xv, float& rv) {
-    const int s = s_lo + b * DW_S + sr;
-    av = make_float4(0.f, 0.f, 0.f, 0.f);
-    xv = av;
-    rv = 0.f;
-    if (s >= s_hi) return;
-    if (arow) av = *(const float4*)(a.da + (int64_t)s * a.lda + m0 + 4 * sc);
-    if constexpr (GATHER) {
-      const int u = s / a.T, t = s - u * a.T;
-      const int slot = a.s.slots[u];
-      const int64_t off = a.s.user_off[slot];
-      const int len = (int)(a.s.user_off[slot + 1] - off);
-      const int64_t pos = off + max(min(a.t0 + t, len - 1), 0);       // (the host refuses steps past a history's end)
-      if (xcol) xv = len > 0 ? table_chunk(a.s, a.s.items[pos], (n0 >> 2) + sc) : nan4();
-      if (sc == 0) rv = len > 0 ? a.s.ratings[pos] : __builtin_nanf("");
-    } else {
-      if (xcol) xv = *(const float4*)(a.x + (int64_t)s * a.ldx + n0 + 4 * sc);
-    }
-  };
-  auto put = [&](int buf, const float4& av, const float4& xv, float rv) {
-    *(float4*)&As[buf][sr][4 * sc] = av;
-    *(float4*)&Xs[buf][sr][4 * sc] = xv;
-    if (GATHER && sc == 0) Rs[buf][sr] = rv;
-  };
-
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[4] = {zero4, zero4, zero4, zero4};
-  float bsum = 0.f, rsum = 0.f;
-  float4 av, xv;
-  float rv;
-  if (nb > 0) {
-    fetch(0, av, xv, rv);
-    put(0, av, xv, rv);
-  }
-  __syncthreads();
-  for (int b = 0; b < nb; ++b) {
-    const int buf = b & 1;
-    if (b + 1 < nb) fetch(b + 1, av, xv, rv);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float am = As[buf][4 * g + e][16 * wave + r];
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) {
-        if (n0 + 16 * tn >= N) continue;
-        acc[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(am, Xs[buf][4 * g + e][16 * tn + r], acc[tn], 0, 0, 0);
-      }
-    }
-    if (extras && tid < DW_T) {       // db and the rating column of this tile's rows: plain sums in sample order
-#pragma unroll
-      for (int s = 0; s < DW_S; ++s) {
-        const float d = As[buf][s][tid];
-        bsum += d;
-        if constexpr (GATHER) rsum = fmaf(d, Rs[buf][s], rsum);
-      }
-    }
-    if (b + 1 < nb) put(buf ^ 1, av, xv, rv);
-    __syncthreads();
-  }
-  if (a.part) {
-    float* out = a.part + (int64_t)blockIdx.z * G * a.ldp;
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn) {
-      const int n = n0 + 16 * tn + r;
-      if (n >= N) continue;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = m0 + 16 * wave + 4 * g + i;
-        if (m < G) out[(int64_t)m * a.ldp + n] = acc[tn][i];
-      }
-    }
-    if (GATHER && extras && tid < DW_T && m0 + tid < G) out[(int64_t)(m0 + tid) * a.ldp + N] = rsum;
-  }
-  if (a.part_b && extras && tid < DW_T && m0 + tid < G) a.part_b[(int64_t)blockIdx.z * G + m0 + tid] = bsum;
-}
-
-// out[i] = part[0][i] + part[1][i] + .., in that order
-__global__ __launch_bounds__(256) void attn_sum_parts_kernel(const float* __restrict__ part, int nsplit, int64_t n, float* __restrict__ out) {
-  flat_walk<1>(n, [&](int64_t i, Width<1>) {
-    float acc = part[i];
-    for (int z = 1; z < nsplit; ++z) acc += part[(int64_t)z * n + i];
-    out[i] = acc;
-  });
-}
-
-constexpr int ADW_MAX_SPLIT = 64, ADW_MIN_SEG = 1024;
-inline int adw_nsplit(int64_t S) { return (int)std::max<int64_t>(1, std::min<int64_t>(ADW_MAX_SPLIT, (S + ADW_MIN_SEG - 1) / ADW_MIN_SEG)); }
-inline int adw_seg(int64_t S) {
-  const int n = adw_nsplit(S);
-  return (int)(((S + n - 1) / n + DW_S - 1) / DW_S * DW_S);
-}
-
-// ------------------------------------------------------------------------------------------------ host
-// what the forward keeps (the workspace of recnn_attn_encode, `saved` of recnn_attn_encode_train): qkv, o, and the log-sum-exp as (m, l)
-struct AttnWs {
-  int64_t qkv, o, lse, total;
-};
-inline AttnWs attn_ws(int U, int T, int H, int heads) {
-  const int64_t M = (int64_t)U * T;
-  AttnWs w;
-  w.qkv = 0;
-  w.o = scatter_index_round(M * 3 * H * 4);
-  w.lse = w.o + scatter_index_round(M * H * 4);
-  w.total = w.lse + scatter_index_round((int64_t)U * heads * T * 8);
-  return w;
-}
-// workspace of a backward call: W_o^T, dO, delta, dqkv, the parts of the weight gradients (W_in's [3H][E + 1] + [3H], reused by W_o's)
-struct AttnBwdWs {
-  int64_t wt, d_o, delta, dqkv, parts, total;
-};
-inline AttnBwdWs attn_bwd_ws(int U, int T, int H, int E, int heads) {
-  const int64_t M = (int64_t)U * T;
-  AttnBwdWs w;
-  w.wt = 0;
-  w.d_o = scatter_index_round((int64_t)H * H * 4);
-  w.delta = w.d_o + scatter_index_round(M * H * 4);
-  w.dqkv = w.delta + scatter_index_round((int64_t)U * heads * T * 4);
-  w.parts = w.dqkv + scatter_index_round(M * 3 * H * 4);
-  const int64_t per_part = std::max<int64_t>((int64_t)3 * H * (E + 2), (int64_t)H * (H + 1));      // [3H][E + 1] + [3H], or [H][H] + [H]
-  w.total = w.parts + scatter_index_round((int64_t)adw_nsplit(M) * per_part * 4);
-  return w;
-}
-
-#define RECNN_ATTN_DIMS_OK(what, emb_dim, hidden, n_heads)                                                                      \
-  RECNN_LSTM_DIMS_OK(what, emb_dim, hidden);                                                                                    \
-  RECNN_REQUIRE(n_heads >= 1 && hidden % n_heads == 0, "%s: hidden must be a multiple of n_heads (got hidden=%d, n_heads=%d)", \
-                what, hidden, n_heads);                                                                                         \
-  RECNN_REQUIRE(hidden / n_heads == 16 || hidden / n_heads == 32 || hidden / n_heads == 64,                                     \
-                "%s: head_dim = hidden / n_heads must be 16, 32 or 64 (got %d)", what, hidden / n_heads)
-#define RECNN_ATTN_SIZE_OK(what, n_users, T)                                                                     \
-  RECNN_REQUIRE(n_users >= 0 && T >= 0 && (int64_t)n_users * T < (1LL << 31) && n_users <= 65535,                \
-                "%s: need n_users in 0 .. 65535, T >= 0 and n_users * T < 2^31", what)
-
-AttnArgs attn_args(int U, int T, int H, int heads, int window, int alibi) {
-  AttnArgs a{};
-  a.U = U; a.T = T; a.H = H; a.heads = heads;
-  a.window = window <= 0 || window > T ? T : window;
-  a.scale = (float)(1.0 / sqrt((double)(H / heads)));
-  for (int h = 0; h < heads; ++h) a.slope[h] = alibi ? (float)exp2(-8.0 * (h + 1) / heads) : 0.f;
-  return a;
-}
-
-template <int MODE>
-void launch_query(const AttnArgs& a, hipStream_t s) {
-  const dim3 grid((a.T + AT_Q - 1) / AT_Q, a.heads, a.U);
-  switch (a.H / a.heads) {
-    case 16: hipLaunchKernelGGL((attn_query_kernel<16, MODE>), grid, dim3(256), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((attn_query_kernel<32, MODE>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((attn_query_kernel<64, MODE>), grid, dim3(256), 0, s, a); break;
-  }
-}
-void launch_key(const AttnArgs& a, hipStream_t s) {
-  const dim3 grid((a.T + AT_Q - 1) / AT_Q, a.heads, a.U);
-  switch (a.H / a.heads) {
-    case 16: hipLaunchKernelGGL((attn_key_kernel<16>), grid, dim3(256), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((attn_key_kernel<32>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((attn_key_kernel<64>), grid, dim3(256), 0, s, a); break;
-  }
-}
-template <bool GATHER>
-int launch_linear(const LinArgs& l, hipStream_t s) {
-  const size_t lds = lin_lds(l.K);
-  if (lds > 48 * 1024)
-    RECNN_HIP(hipFuncSetAttribute((const void*)attn_linear_kernel<GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((attn_linear_kernel<GATHER>), dim3((l.rows + LIN_ROWS - 1) / LIN_ROWS), dim3(256), lds, s, l);
-  return 0;
-}
 
 int attn_encode_impl(const char* what, const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots,
                      int n_users, int t0, int T, const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window,

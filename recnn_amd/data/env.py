@@ -381,7 +381,8 @@ class SeqEnv(StoreEnv):
     All T steps of a user batch are ONE HIP launch chain (`recnn_amd.nn.functional.lstm_encode` or `gru_encode`), the kept rows one
     more (`seq_collect`); the padded [U, Lmax, E] tensor is not built on this path.  `state_encoder` must be a single-layer
     unidirectional `torch.nn.LSTM(E + 1, H)` or `torch.nn.GRU(E + 1, H)`, or a `recnn_amd.nn.AttentionEncoder(E + 1, H, heads)`
-    (`attn_encode`: causal self-attention over the steps of the batch), on the GPU; `batch_first` is ignored (users are always
+    (`attn_encode`: causal self-attention over the steps of the batch) or a `recnn_amd.nn.TransformerStateEncoder(E + 1, H, heads)`
+    (`transformer_encode`: pre-LN transformer blocks over the steps of the batch), on the GPU; `batch_first` is ignored (users are always
     the batch).  A module of any other type (a `torch.nn.RNN`, say) is refused at construction, naming the type.
 
     The encoder is a FROZEN feature extractor for the replay buffer: the states in the buffer carry no autograd graph, and the
@@ -395,11 +396,14 @@ class SeqEnv(StoreEnv):
     def __init__(self, path, state_encoder, batch_size=25, device=torch.device("cuda"), layout=None, max_buf_size=1000,
                  num_workers=1, embed_batch=utils.batch_tensor_embeddings, *args, **kwargs):
         from ..nn.attention import AttentionEncoder
-        if state_encoder is not None and not isinstance(state_encoder, (torch.nn.LSTM, torch.nn.GRU, AttentionEncoder)):
+        from ..nn.transformer import TransformerStateEncoder
+        if state_encoder is not None and not isinstance(state_encoder, (torch.nn.LSTM, torch.nn.GRU, AttentionEncoder,
+                                                                        TransformerStateEncoder)):
             t = type(state_encoder)
             raise TypeError(f"SeqEnv: state_encoder is a {t.__module__}.{t.__qualname__}; the HIP encoders are a single-layer "
-                            "torch.nn.LSTM(E + 1, H), a single-layer torch.nn.GRU(E + 1, H) and a "
-                            "recnn_amd.nn.AttentionEncoder(E + 1, H, heads)")
+                            "torch.nn.LSTM(E + 1, H), a single-layer torch.nn.GRU(E + 1, H), a "
+                            "recnn_amd.nn.AttentionEncoder(E + 1, H, heads) and a "
+                            "recnn_amd.nn.TransformerStateEncoder(E + 1, H, heads)")
         super().__init__(path, min_seq_size=10, embed_batch=embed_batch, *args, **kwargs)
         self.state_encoder = state_encoder
         self.batch_size = batch_size

@@ -12,8 +12,8 @@ class AttentionEncoder(nn.Module):
         h_t = out_proj(sum_j softmax_j(s_a)(t, j) v_j^a)                            out_proj: Linear(H, H)
 
     m_a = 2^(-8 (a + 1) / num_heads) with `alibi` (a recency bias without parameters or a maximum length), else 0; `window=None`
-    attends to every earlier step of the call.  No residual, LayerNorm or feed-forward block: stack those in the head that reads
-    h.  Initialised as torch.nn.MultiheadAttention is (xavier_uniform_ weights, zero biases).
+    attends to every earlier step of the call.  No residual, LayerNorm or feed-forward block: `TransformerStateEncoder`
+    (nn/transformer.py) is this layer inside pre-LN blocks with all three.  Initialised as torch.nn.MultiheadAttention is (xavier_uniform_ weights, zero biases).
 
     The module only holds the parameters, as a torch.nn.LSTM does for `lstm_encode`: the layer runs in
     `recnn_amd.nn.functional.attn_encode` / `attn_encode_train` (or `state_encode`, or a `SeqEnv`), which read the store."""

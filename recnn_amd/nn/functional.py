@@ -16,6 +16,7 @@ import torch
 
 from .. import _lib as L
 from .attention import AttentionEncoder
+from .transformer import ACTIVATIONS as TRANSFORMER_ACTIVATIONS, TransformerStateEncoder
 
 _call_counter = itertools.count(1)
 
@@ -1990,8 +1991,14 @@ def _attn_call_args(name, enc, store, table, slots, T, t0):
         raise L.RecnnHipError(f"{name}: the state encoder is a {t.__module__}.{t.__qualname__}, not a recnn_amd.nn.AttentionEncoder "
                               "(a torch.nn.LSTM goes to lstm_encode, a torch.nn.GRU to gru_encode)")
     params = (enc.in_proj_weight, enc.in_proj_bias, enc.out_proj.weight, enc.out_proj.bias)
+    return _attn_checked(name, enc, _ATTN_PARAMS, params, lambda E, H: ((3 * H, E + 1), (3 * H,), (H, H), (H,)), "in_proj_weight",
+                         store, table, slots, T, t0)
+
+
+def _attn_checked(name, enc, pnames, params, shapes_of, first, store, table, slots, T, t0):
+    """The checks that `AttentionEncoder` and `TransformerStateEncoder` share: (dev, E, H, U, T, t0, slots, params)."""
     dev = params[0].device
-    for pname, p in zip(_ATTN_PARAMS, params):
+    for pname, p in zip(pnames, params):
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
             raise L.RecnnHipError(f"{name}: {pname} must be a contiguous float32 tensor on {dev} (got {p.dtype} on {p.device}, "
                                   f"{'contiguous' if p.is_contiguous() else 'strided'})")
@@ -2010,8 +2017,7 @@ def _attn_call_args(name, enc, store, table, slots, T, t0):
         raise L.RecnnHipError(f"{name}: the table's width E={E} must be a multiple of 8 up to 128")
     if enc.window is not None and int(enc.window) < 1:
         raise L.RecnnHipError(f"{name}: window={enc.window} must be at least 1 (or None)")
-    if tuple(params[0].shape) != (3 * H, E + 1) or tuple(params[1].shape) != (3 * H,) or tuple(params[2].shape) != (H, H) \
-            or tuple(params[3].shape) != (H,):
+    if any(tuple(p.shape) != shape for p, shape in zip(params, shapes_of(E, H))):
         raise L.RecnnHipError(f"{name}: the parameters do not have the shapes of hidden_size={H}, input_size={E + 1}")
     slots = store.checked_slots(slots, name, dev)
     U, T, t0 = len(slots), int(T), int(t0)
@@ -2022,7 +2028,7 @@ def _attn_call_args(name, enc, store, table, slots, T, t0):
     if U and int(store.lengths[slots].min()) < t0 + T:
         raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
     if not params[0].is_cuda:
-        raise L.RecnnHipError(f"{name}: the module lives on {dev} (in_proj_weight.device); it needs a GPU module "
+        raise L.RecnnHipError(f"{name}: the module lives on {dev} ({first}.device); it needs a GPU module "
                               "(recnn_amd has no CPU fallback)")
     if table.device != dev:
         raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
@@ -2127,13 +2133,231 @@ def attn_encode_train(enc, store, table, slots, T, *, t0=0, train_table=False):
     return AttnEncodeFunction.apply(*params, enc, store, table, torch.from_numpy(slots).to(dev), T, t0)
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# The transformer state encoder (csrc/block.hip): embedding, pre-LN blocks on a dense [U, T, H] stream, final LayerNorm.
+_BLOCK_PARAMS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                 "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight",
+                 "norm2.bias")
+
+
+def _block_params(blk):
+    sa = blk.self_attn
+    return (sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, blk.linear1.weight, blk.linear1.bias,
+            blk.linear2.weight, blk.linear2.bias, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias)
+
+
+def _transformer_call_args(name, enc, store, table, slots, T, t0):
+    """The checks of `transformer_encode` / `transformer_encode_train`, on the host and by argument name, before any launch: those of
+    `_attn_call_args`, then num_layers, dim_feedforward, activation and eps.  (dev, E, H, U, T, t0, slots, params, cfg) with params
+    = embed's two, twelve per block, norm's two, and cfg = (heads, F, act, window or 0, alibi, eps)."""
+    if not isinstance(enc, TransformerStateEncoder):
+        t = type(enc)
+        raise L.RecnnHipError(f"{name}: the state encoder is a {t.__module__}.{t.__qualname__}, not a "
+                              "recnn_amd.nn.TransformerStateEncoder (an AttentionEncoder goes to attn_encode, a torch.nn.LSTM to "
+                              "lstm_encode, a torch.nn.GRU to gru_encode)")
+    if int(enc.num_layers) < 1 or len(enc.layers) != int(enc.num_layers):
+        raise L.RecnnHipError(f"{name}: num_layers={enc.num_layers} must be at least 1 and the length of `layers` ({len(enc.layers)})")
+    F = int(enc.dim_feedforward)
+    if F % 16 or not 16 <= F <= 1024:
+        raise L.RecnnHipError(f"{name}: dim_feedforward={F} must be a multiple of 16 in 16 .. 1024")
+    if enc.activation not in TRANSFORMER_ACTIVATIONS:
+        raise L.RecnnHipError(f"{name}: activation={enc.activation!r} is not one of {sorted(TRANSFORMER_ACTIVATIONS)}")
+    if not float(enc.eps) > 0:
+        raise L.RecnnHipError(f"{name}: eps={enc.eps} must be positive")
+    pnames = ["embed.weight", "embed.bias"] + [f"layers.{i}.{n}" for i in range(len(enc.layers)) for n in _BLOCK_PARAMS] \
+        + ["norm.weight", "norm.bias"]
+    params = (enc.embed.weight, enc.embed.bias) + tuple(p for blk in enc.layers for p in _block_params(blk)) \
+        + (enc.norm.weight, enc.norm.bias)
+
+    def shapes_of(E, H):
+        block = ((3 * H, H), (3 * H,), (H, H), (H,), (F, H), (F,), (H, F), (H,), (H,), (H,), (H,), (H,))
+        return ((H, E + 1), (H,)) + block * len(enc.layers) + ((H,), (H,))
+    dev, E, H, U, T, t0, slots, params = _attn_checked(name, enc, pnames, params, shapes_of, "embed.weight", store, table, slots, T, t0)
+    cfg = (enc.num_heads, F, TRANSFORMER_ACTIVATIONS[enc.activation], enc.window or 0, int(enc.alibi), float(enc.eps))
+    return dev, E, H, U, T, t0, slots, params, cfg
+
+
+def _block_head(x, cfg):
+    """The leading arguments of every recnn_block_* launch on x [U, T, H]."""
+    U, T, H = x.shape
+    heads, F, act, window, alibi, eps = cfg
+    return (L.ptr(x), U, T, H, heads, F, act, window, alibi, C.c_float(eps))
+
+
+@torch.no_grad()
+def transformer_encode(enc, store, table, slots, T, *, t0=0):
+    """h float32[U, T, H] of a `recnn_amd.nn.TransformerStateEncoder` for the users `slots` (store slots) over the steps
+    t0 .. t0 + T - 1 of their histories (nothing is carried between calls: step t sees steps of THIS call only).  One gathered
+    embedding launch, four launches per block -- LN1 fused into the in-projection, the flash-style attention, the out-projection
+    with the residual in its epilogue, and the fused feed-forward (LN2, linear1, activation, linear2, residual), whose [U T, F]
+    activation never reaches memory -- and the final LayerNorm; fp32 on the exact-f32 MFMA.
+
+    Equal calls give equal bits; a user's rows do not depend on the other users or on its place in the batch; the first `a` steps
+    of a longer call are bit for bit the call with T = a; h_t does not depend on any position after t, nor, under a window w, on
+    positions more than num_layers (w - 1) steps back.  Runs under no_grad (`transformer_encode_train` is the same call with a
+    graph).  Refused with RecnnHipError naming what is wrong: everything `attn_encode` refuses, and num_layers < 1, dim_feedforward
+    not a multiple of 16 in 16 .. 1024, an unknown activation, eps <= 0."""
+    dev, E, H, U, T, t0, slots, params, cfg = _transformer_call_args("transformer_encode", enc, store, table, slots, T, t0)
+    slots_d = torch.from_numpy(slots).to(dev)
+    x = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+    y = torch.empty_like(x)
+    L.call("recnn_seq_embed", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(params[0]), L.ptr(params[1]), L.ptr(x),
+           L.current_stream())
+    ws = L.workspace("recnn_block_workspace_bytes", U, T, H, cfg[0], device=dev)
+    for i in range(len(enc.layers)):
+        L.call("recnn_block_forward", *_block_head(x, cfg), *(L.ptr(p) for p in params[2 + 12 * i:14 + 12 * i]), L.ptr(y), L.ptr(ws),
+               L.current_stream())
+        x, y = y, x
+    L.call("recnn_layernorm_rows", L.ptr(x), U * T, H, L.ptr(params[-2]), L.ptr(params[-1]), C.c_float(cfg[5]), L.ptr(y),
+           L.current_stream())
+    return y
+
+
+class SeqEmbedFunction(torch.autograd.Function):
+    """x^0 = embed([table[item] | rating]) through the store, and its backward (`recnn_seq_embed*`): differentiable in the two
+    parameters and, when asked, in the table."""
+
+    @staticmethod
+    def forward(ctx, w_e, b_e, store, table, slots_d, T, t0):
+        U, E, H = slots_d.shape[0], table.shape[1], w_e.shape[0]
+        x = torch.empty(U, T, H, dtype=torch.float32, device=w_e.device)
+        L.call("recnn_seq_embed", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(w_e), L.ptr(b_e), L.ptr(x),
+               L.current_stream())
+        ctx.store, ctx.dims = store, (U, T, t0, E, H)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(w_e, table, slots_d)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x):
+        w_e, table, slots_d = ctx.saved_tensors
+        U, T, t0, E, H = ctx.dims
+        need = ctx.needs_input_grad
+        if g_x is None:
+            return (None,) * 7
+        dev = w_e.device
+        g_x = g_x.to(torch.float32).contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        d_w = new(H, E + 1) if need[0] else None
+        d_b = new(H) if need[1] else None
+        d_table = new(table.shape[0], E) if need[3] else None
+        head = _store_args(ctx.store, slots_d, U, t0, T, table, E, H)
+        ws = L.workspace("recnn_seq_embed_backward_workspace_bytes", U, T, H, E, device=dev)
+        if d_table is None:
+            L.call("recnn_seq_embed_backward", *head, L.ptr(g_x), L.ptr(d_w), L.ptr(d_b), L.ptr(ws), L.current_stream())
+        else:
+            tws = L.workspace("recnn_seq_embed_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
+            L.call("recnn_seq_embed_backward_table", *head, L.ptr(w_e), L.ptr(g_x), L.ptr(d_w), L.ptr(d_b), L.ptr(d_table), L.ptr(ws),
+                   L.ptr(tws), L.current_stream())
+        return d_w, d_b, None, d_table, None, None, None
+
+
+class TransformerBlockFunction(torch.autograd.Function):
+    """y of one block with qkv, o, the log-sum-exp, u and the pre-activation kept, and its backward (`recnn_block_forward_train` /
+    `recnn_block_backward`): differentiable in x and the twelve parameters; a gradient nobody needs is not computed."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        U, T, H = x.shape
+        dev = x.device
+        y = torch.empty_like(x)
+        ctx.set_materialize_grads(False)
+        if not any(ctx.needs_input_grad):
+            ws = L.workspace("recnn_block_workspace_bytes", U, T, H, cfg[0], device=dev)
+            L.call("recnn_block_forward", *_block_head(x, cfg), *(L.ptr(p) for p in params), L.ptr(y), L.ptr(ws), L.current_stream())
+            return y
+        nsaved, nbwd = C.c_int64(), C.c_int64()
+        L.call("recnn_block_train_workspace_bytes", U, T, H, cfg[0], cfg[1], C.byref(nsaved), C.byref(nbwd))
+        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+        L.call("recnn_block_forward_train", *_block_head(x, cfg), *(L.ptr(p) for p in params), L.ptr(y), L.ptr(saved), L.current_stream())
+        ctx.cfg, ctx.bwd_bytes = cfg, nbwd.value
+        ctx.save_for_backward(x, saved, *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y):
+        if g_y is None:
+            return (None,) * 14
+        x, saved, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_y = g_y.to(torch.float32).contiguous()
+        d_x = torch.empty_like(x) if need[0] else None
+        grads = [torch.empty_like(p) if need[2 + i] else None for i, p in enumerate(params)]
+        ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=x.device)
+        L.call("recnn_block_backward", *_block_head(x, ctx.cfg), *(L.ptr(p) for p in params), L.ptr(saved), L.ptr(g_y), L.ptr(d_x),
+               *(L.ptr(g) for g in grads), L.ptr(ws), L.current_stream())
+        return (d_x, None, *grads)
+
+
+class LayerNormRowsFunction(torch.autograd.Function):
+    """LN(x) over the last axis of x [U, T, H] and its backward (`recnn_layernorm_rows*`)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        out = torch.empty_like(x)
+        H = x.shape[-1]
+        L.call("recnn_layernorm_rows", L.ptr(x), x.numel() // H, H, L.ptr(gamma), L.ptr(beta), C.c_float(eps), L.ptr(out),
+               L.current_stream())
+        ctx.eps = eps
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, gamma)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        x, gamma = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        H = x.shape[-1]
+        rows = x.numel() // H
+        g = g.to(torch.float32).contiguous()
+        d_x = torch.empty_like(x) if need[0] else None
+        d_g = torch.empty_like(gamma) if need[1] else None
+        d_b = torch.empty_like(gamma) if need[2] else None
+        ws = L.workspace("recnn_layernorm_rows_backward_workspace_bytes", rows, H, device=x.device)
+        L.call("recnn_layernorm_rows_backward", L.ptr(x), rows, H, L.ptr(gamma), C.c_float(ctx.eps), L.ptr(g), L.ptr(d_x), L.ptr(d_g),
+               L.ptr(d_b), L.ptr(ws), L.current_stream())
+        return d_x, d_g, d_b, None
+
+
+def transformer_encode_train(enc, store, table, slots, T, *, t0=0, train_table=False):
+    """`transformer_encode` with a graph: the same arguments, checks and h -- bit for bit -- differentiable with respect to every
+    parameter of the module.  Three kinds of autograd node are chained (the embedding, one per block, the final LayerNorm); between
+    them only [U, T, H] tensors cross.  A block keeps qkv, o, the log-sum-exp, u and the feed-forward's pre-activation [U T, F]; its
+    backward recomputes the normalised rows, the activation and the attention probabilities.  Fixed summation orders and no float
+    atomics: equal calls give equal gradients bit for bit.  A frozen parameter's gradient is not computed.  Once differentiable.
+
+    The embedding table is handled as in `attn_encode_train`: a `table` that requires grad is refused with RecnnHipError unless
+    `train_table=True`, and then `table.grad` receives the dense [n_items, E] gradient, exact zeros in the rows of items the batch's
+    steps do not hold -- also with every encoder parameter frozen.
+
+    Under `torch.no_grad()`, or when nothing requires grad, this IS `transformer_encode`: nothing is kept."""
+    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
+        raise L.RecnnHipError("transformer_encode_train: table.requires_grad is set, but gradients with respect to the embedding table "
+                              "are computed only on request; pass train_table=True to train it, or table.detach()")
+    dev, E, H, U, T, t0, slots, params, cfg = _transformer_call_args("transformer_encode_train", enc, store, table, slots, T, t0)
+    if not (torch.is_grad_enabled() and (table.requires_grad or any(p.requires_grad for p in params))):
+        return transformer_encode(enc, store, table.detach(), slots, T, t0=t0)
+    x = SeqEmbedFunction.apply(params[0], params[1], store, table, torch.from_numpy(slots).to(dev), T, t0)
+    for i in range(len(enc.layers)):
+        x = TransformerBlockFunction.apply(x, cfg, *params[2 + 12 * i:14 + 12 * i])
+    return LayerNormRowsFunction.apply(x, params[-2], params[-1], cfg[5])
+
+
 def state_encode(encoder, store, table, slots, T, *, train=False, train_table=False):
     """h float32[U, T, H] of whichever state encoder `encoder` is -- the one place that dispatches on the module's type (SeqEnv goes
     through it): a torch.nn.LSTM runs `lstm_encode` / `lstm_encode_train`, a torch.nn.GRU `gru_encode` / `gru_encode_train`, from a
-    zero state at step 0, a recnn_amd.nn.AttentionEncoder `attn_encode` / `attn_encode_train`.  Any other module is refused by name."""
+    zero state at step 0, a recnn_amd.nn.AttentionEncoder `attn_encode` / `attn_encode_train`, a
+    recnn_amd.nn.TransformerStateEncoder `transformer_encode` / `transformer_encode_train`.  Any other module is refused by name."""
     kw = dict(train_table=train_table) if train else {}
     if isinstance(encoder, AttentionEncoder):
         return (attn_encode_train if train else attn_encode)(encoder, store, table, slots, T, **kw)
+    if isinstance(encoder, TransformerStateEncoder):
+        return (transformer_encode_train if train else transformer_encode)(encoder, store, table, slots, T, **kw)
     if isinstance(encoder, torch.nn.LSTM):
         fn = lstm_encode_train if train else lstm_encode
     elif isinstance(encoder, torch.nn.GRU):
@@ -2141,8 +2365,8 @@ def state_encode(encoder, store, table, slots, T, *, train=False, train_table=Fa
     else:
         t = type(encoder)
         raise L.RecnnHipError(f"state encoder: a {t.__module__}.{t.__qualname__} is not supported; the HIP encoders are a single-layer "
-                              "torch.nn.LSTM(E + 1, H), a single-layer torch.nn.GRU(E + 1, H) and a recnn_amd.nn.AttentionEncoder(E + 1, H, "
-                              "heads)")
+                              "torch.nn.LSTM(E + 1, H), a single-layer torch.nn.GRU(E + 1, H), a recnn_amd.nn.AttentionEncoder(E + 1, H, "
+                              "heads) and a recnn_amd.nn.TransformerStateEncoder(E + 1, H, heads)")
     return fn(encoder, store, table, slots, T, **kw)[0]
 
 

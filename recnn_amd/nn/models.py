@@ -15,8 +15,9 @@ import torch.nn as nn
 
 from . import functional as F_hip
 from .attention import AttentionEncoder  # noqa: F401
+from .transformer import TransformerStateEncoder  # noqa: F401
 
-__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead", "NegativeSampler", "AttentionEncoder"]
+__all__ = ["DuelDQN", "AnomalyDetector", "Actor", "Critic", "DiscreteActor", "Beta", "bcqPerturbator", "bcqGenerator", "StateCritic", "SoftQ", "StochasticActor", "NextItemHead", "NegativeSampler", "AttentionEncoder", "TransformerStateEncoder"]
 
 
 class DuelDQN(nn.Module):

@@ -5,10 +5,8 @@
 //   the layer        x_t = [table[item_t] | rating_t], [q_t | k_t | v_t] = W_in x_t + b_in, per head a of width d = H / heads:
 //                      s(t, j) = (q_t . k_j) / sqrt(d) - m_a (t - j) for j in [max(0, t - window + 1), t], p = softmax_j s,
 //                      o_t = sum_j p(t, j) v_j,  h_t = W_o o_t + b_o.         m_a = 2^(-8 (a + 1) / heads) (ALiBi) or 0.
-//   linear kernel    out[s, n] = b[n] + sum_k x[s, k] w[n, k] for 64 rows s per workgroup, one fixed-order chain per element on the
-//                    exact-f32 MFMA: fma(rating, w[n, E], b[n]) first (the rank-1 link of seq_chain.h: K = E + 1 is never padded), then
-//                    k upwards in blocks of 16.  GATHER: the rows are table rows read through the store ([U, T, E] is never
-//                    materialised).  The same kernel is the out-projection and dO = g_h W_o (over a transposed copy of W_o).
+//   linear kernels   attn_dev.h describes them: the in-projection is its gathered linear (rows read through the store, the rating
+//                    as the chain's first link), the out-projection and dO = g_h W_o (over a transposed copy of W_o) its dense linear.
 //   forward          one workgroup per (user, head, 64 query rows), heaviest blocks first; wave w owns 16 query rows.  Key tiles of 64
 //                    lie on absolute multiples of 64 from the call's step 0 and are walked upwards from the first one the block's window
 //                    reaches to the diagonal one; K and V tiles pass through LDS.  The products are computed transposed -- S^T = K Q^T,
@@ -28,7 +26,7 @@
 //                    workgroups: the query owner (the forward's loop; dQ^T += K^T dS^T) and the key owner (one workgroup per 64 keys,
 //                    its K and V fragments in registers, sweeping the query tiles in its reach upwards; Q, dO, lse and delta tiles in
 //                    LDS; dV^T += dO^T P, dK^T += Q^T dS).  dqkv is written [U, T, 3H]; the weight gradients are the tile of
-//                    seq_dw_kernel (seq_grad.h) over segments of the call's samples, the parts added in order (attn_dw_kernel below);
+//                    seq_dw_kernel (seq_grad.h) over segments of the call's samples, the parts added in order (attn_dw_kernel of attn_dev.h);
 //                    the table gradient is seq_grad.h's dX contraction and scatter-sum with da = dqkv.
 // Every sum has a fixed order that depends on nothing but (t, j): equal calls give equal bits, a user's bits do not depend on the batch,
 // and h[:, :a] of a longer call equals the shorter call's.
@@ -54,17 +52,17 @@ int attn_encode_impl(const char* what, const int32_t* items, const float* rating
   l.t0 = t0; l.T = T; l.rows = n_users * T;
   l.K = emb_dim; l.w = w_in; l.ldw = emb_dim + 1; l.b = b_in;
   l.out = (float*)(kp + w.qkv); l.N = 3 * hidden;
-  if (int rc = launch_linear<true>(l, s)) return rc;
+  if (int rc = launch_linear(l, s)) return rc;
   AttnArgs a = attn_args(n_users, T, hidden, n_heads, window, alibi);
   a.qkv = (const float*)(kp + w.qkv);
   a.o = (float*)(kp + w.o);
   a.lse = (float*)(kp + w.lse);
   launch_query<0>(a, s);
-  LinArgs p{};
-  p.rows = n_users * T; p.T = T;
-  p.x = a.o; p.K = hidden; p.w = w_o; p.ldw = hidden; p.b = b_o;
-  p.out = h_out; p.N = hidden;
-  if (int rc = launch_linear<false>(p, s)) return rc;
+  DenseLinArgs p{};
+  p.rows = n_users * T; p.K = hidden; p.N = hidden;
+  p.x = a.o; p.w = w_o; p.ldw = hidden; p.b = b_o;
+  p.out = h_out;
+  if (int rc = launch_dense_linear(p, false, s)) return rc;
   return recnn_check_hip(hipGetLastError(), what);
 }
 
@@ -100,33 +98,17 @@ int attn_backward_impl(const int32_t* items, const float* ratings, const int64_t
   TableGrad tg{};
   if (with_table) RECNN_HIP(table_grad_prepare(tg, st, t0, T, G, G, T, dqkv, w_in, table_workspace, s));
   // the weight gradients: the parts of one tensor's tile launch are summed before the next launch reuses the buffer (stream order)
-  const int S = n_users * T, nsplit = adw_nsplit(S), seg = adw_seg(S);
+  const int S = n_users * T;
   float* part = (float*)(ws + w.parts);
-  auto weight_grad = [&](bool gather, const float* da, int lda, const float* x, int Gr, int N, float* d_w, float* d_b) {
-    AdwArgs x_{};
-    x_.s = st; x_.t0 = t0; x_.T = T; x_.S = S; x_.seg = seg;
-    x_.da = da; x_.lda = lda; x_.x = x; x_.ldx = N;
-    x_.G = Gr; x_.N = N; x_.ldp = N + (gather ? 1 : 0);
-    x_.part = d_w ? part : nullptr;
-    x_.part_b = d_b ? part + (int64_t)nsplit * Gr * x_.ldp : nullptr;
-    const dim3 grid((Gr + DW_T - 1) / DW_T, d_w ? (N + DW_T - 1) / DW_T : 1, nsplit);
-    if (gather) hipLaunchKernelGGL((attn_dw_kernel<true>), grid, dim3(256), 0, s, x_);
-    else hipLaunchKernelGGL((attn_dw_kernel<false>), grid, dim3(256), 0, s, x_);
-    if (d_w) {
-      const int64_t n = (int64_t)Gr * x_.ldp;
-      hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, x_.part, nsplit, n, d_w);
-    }
-    if (d_b) hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(Gr, 256, 2048)), dim3(256), 0, s, x_.part_b, nsplit, (int64_t)Gr, d_b);
-  };
   // d_w_o[m, n] = sum_s g_h[s, m] o[s, n] and d_b_o[m] = sum_s g_h[s, m]
-  if (d_w_o || d_b_o) weight_grad(false, g_h, H, o, H, H, d_w_o, d_b_o);
+  launch_weight_grad(nullptr, t0, T, S, g_h, H, o, H, H, H, part, d_w_o, d_b_o, s);
   if (d_w_in || d_b_in || with_table) {
     hipLaunchKernelGGL(whh_transpose_kernel, dim3(grid_for((int64_t)H * H, 256, 2048)), dim3(256), 0, s, w_o, H, H, (float*)(ws + w.wt));
-    LinArgs p{};
-    p.rows = n_users * T; p.T = T;
-    p.x = g_h; p.K = H; p.w = (const float*)(ws + w.wt); p.ldw = H; p.b = nullptr;
-    p.out = (float*)(ws + w.d_o); p.N = H;
-    if (int rc = launch_linear<false>(p, s)) return rc;
+    DenseLinArgs p{};
+    p.rows = S; p.K = H; p.N = H;
+    p.x = g_h; p.w = (const float*)(ws + w.wt); p.ldw = H;
+    p.out = (float*)(ws + w.d_o);
+    if (int rc = launch_dense_linear(p, false, s)) return rc;
     AttnArgs a = attn_args(n_users, T, H, n_heads, window, alibi);
     a.qkv = (const float*)(sp + sv.qkv);
     a.lse = (float*)(sp + sv.lse);                  // (read only)
@@ -142,7 +124,7 @@ int attn_backward_impl(const int32_t* items, const float* ratings, const int64_t
       table_grad_finish(tg, d_table, s);
     }
     // d_w_in (its rating column included) and d_b_in: da = dqkv, X rows gathered through the store
-    if (d_w_in || d_b_in) weight_grad(true, dqkv, G, nullptr, G, emb_dim, d_w_in, d_b_in);
+    launch_weight_grad(&st, t0, T, S, dqkv, G, nullptr, emb_dim, G, emb_dim, part, d_w_in, d_b_in, s);
   }
   return recnn_check_hip(hipGetLastError(), what);
 }

@@ -1,7 +1,20 @@
 // attn_dev.h -- the device half of the causal self-attention encoder, shared by attn.hip (the layer over the store)
-// and block.hip (the same layer on a dense [U, T, H] input inside a transformer block): the 64-row linear kernel, the
+// and block.hip (the same layer on a dense [U, T, H] input inside a transformer block): the two 64-row linear kernels, the
 // attention kernels with their arguments, the segmented weight-gradient tile, the workspace layouts and the launchers.  attn.hip
-// describes the layer and the kernels.
+// describes the layer and the attention kernels.
+//
+//   linear kernels   out[s, n] = b[n] + sum_k x[s, k] w[n, k] for 64 rows s per workgroup, one fixed-order chain per element on the
+//                    exact-f32 MFMA: the bias first, then k upwards in blocks of 16, MFMA e = 0 .. 3 inside a block.  Two kernels:
+//     gathered       (attn_linear_kernel) the rows are [table[item] | rating] read through the store -- [U, T, E] is never
+//                    materialised -- and the chain starts with fma(rating, w[n, E], b[n]), the rank-1 link of seq_chain.h (K = E + 1
+//                    is never padded).  The in-projection of attn.hip and the embedding of block.hip.
+//     dense          (dense_linear_kernel<LN>) the rows are x [rows][K]; every other product of both encoders, those with a
+//                    transposed weight (over a transposed copy) included.  A workgroup owns 64 rows and 256 columns, wave w column
+//                    tiles w, w + 4, w + 8, w + 12 of them, so a staged row block is read once for four column tiles.  K > 256 is
+//                    staged in blocks of 256, upwards, into the same accumulators (still one chain per element).  LN: the staged
+//                    rows are normalised in place before the products (ln_rows), so the no-grad encode writes no normalised copy.
+//                    Two epilogues: out = res + acc (the residual link; the chain is finished before the residual is added) and
+//                    out = acc act'(aux) (the activation's derivative at the saved pre-activation).
 #pragma once
 #include <algorithm>
 
@@ -16,13 +29,12 @@ constexpr int LIN_ROWS = 64;
 
 __device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
 
-// ------------------------------------------------------------------------------------------------ linear
+// ------------------------------------------------------------------------------------------------ gathered linear
 struct LinArgs {
-  SeqStore s;                       // GATHER: x rows are [table[item] | rating] through the store
+  SeqStore s;                       // x rows are [table[item] | rating] through the store
   int t0, T;
   int rows;                         // samples s = u T + t
-  const float* x;                   // dense: [rows][K]
-  int K;                            // contraction width without the rating column (a multiple of 8; dense: of 16)
+  int K;                            // contraction width without the rating column (a multiple of 8)
   const float* w;                   // [N][ldw]
   int ldw;
   const float* b;                   // [N] or NULL
@@ -32,7 +44,7 @@ struct LinArgs {
 
 inline size_t lin_lds(int K) { return (size_t)(LIN_ROWS * (((K + 15) & ~15) + AT_PAD) + LIN_ROWS) * sizeof(float); }
 
-template <bool GATHER>
+// grid ceil(rows / 64), 256 threads; wave w owns column tiles w, w + 4, ..
 __global__ __launch_bounds__(256) void attn_linear_kernel(const LinArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int K = a.K, KX = (K + 15) & ~15, ldx = KX + AT_PAD, C4 = KX >> 2;
@@ -45,18 +57,11 @@ __global__ __launch_bounds__(256) void attn_linear_kernel(const LinArgs a) {
     const int row = idx / C4, c = idx - row * C4, s = s0 + row;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (s < a.rows && 4 * c < K) {
-      if constexpr (GATHER) {
-        const int u = s / a.T, t = s - u * a.T;
-        const int slot = a.s.slots[u];
-        const int64_t off = a.s.user_off[slot];
-        const int len = (int)(a.s.user_off[slot + 1] - off);
-        const int64_t pos = off + max(min(a.t0 + t, len - 1), 0);       // (the host refuses steps past a history's end)
-        v = len > 0 ? table_chunk(a.s, a.s.items[pos], c) : nan4();
-        if (c == 0) rs[row] = len > 0 ? a.s.ratings[pos] : __builtin_nanf("");
-      } else {
-        v = *(const float4*)(a.x + (int64_t)s * K + 4 * c);
-      }
-    } else if (GATHER && c == 0) {
+      const int u = s / a.T, t = s - u * a.T;
+      const StorePos p = store_pos(a.s, u, a.t0 + t);
+      v = p.live() ? table_chunk(a.s, a.s.items[p.pos], c) : nan4();
+      if (c == 0) rs[row] = p.live() ? a.s.ratings[p.pos] : __builtin_nanf("");
+    } else if (c == 0) {
       rs[row] = 0.f;
     }
     *(float4*)(xs + row * ldx + 4 * c) = v;
@@ -71,10 +76,7 @@ __global__ __launch_bounds__(256) void attn_linear_kernel(const LinArgs a) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (GATHER) acc[mt][i] = fmaf(rs[16 * mt + 4 * g + i], wrow[K], bias);
-        else acc[mt][i] = bias;
-      }
+      for (int i = 0; i < 4; ++i) acc[mt][i] = fmaf(rs[16 * mt + 4 * g + i], wrow[K], bias);
     for (int k0 = 0; k0 < K; k0 += 16) {
       const bool kin = k0 + 4 * g < K;        // K a multiple of 8: the last k block may be half empty (x there is zero)
       const f32x4 bv = kin ? (f32x4)(*(const f32x4u*)(wrow + k0 + 4 * g)) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -92,6 +94,133 @@ __global__ __launch_bounds__(256) void attn_linear_kernel(const LinArgs a) {
       for (int i = 0; i < 4; ++i) {
         const int s = s0 + 16 * mt + 4 * g + i;
         if (s < a.rows) a.out[(int64_t)s * a.N + col] = acc[mt][i];
+      }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ rows in LDS
+constexpr int LIN_KB = 256;         // contraction columns per LDS stage of the dense linear kernel
+constexpr int LIN_COLS = 256;       // output columns per workgroup of the dense linear kernel
+
+enum { ACT_RELU = 0, ACT_GELU = 1 };
+
+__device__ __forceinline__ float act_fwd(float a, int act) {
+  if (act == ACT_RELU) return a < 0.f ? 0.f : a;                   // (a NaN stays a NaN)
+  return 0.5f * a * (1.f + erff(a * 0.70710678118654752440f));
+}
+__device__ __forceinline__ float act_grad(float a, int act) {
+  if (act == ACT_RELU) return a > 0.f ? 1.f : (a != a ? a : 0.f);
+  const float cdf = 0.5f * (1.f + erff(a * 0.70710678118654752440f));
+  return fmaf(a * 0.39894228040143267794f, expf(-0.5f * a * a), cdf);      // Phi(a) + a phi(a)
+}
+
+// rows s0 .. s0 + 63 of x [rows][ld], columns 0 .. kw - 1 (a multiple of 4), into xs [64][ldx]; rows at or past `rows` are zeros
+__device__ __forceinline__ void stage_rows(float* xs, int ldx, const float* x, int64_t ld, int s0, int rows, int kw, int tid) {
+  const int C4 = kw >> 2;
+  for (int idx = tid; idx < LIN_ROWS * C4; idx += 256) {
+    const int row = idx / C4, c = idx - row * C4, s = s0 + row;
+    *(float4*)(xs + row * ldx + 4 * c) = s < rows ? *(const float4*)(x + (int64_t)s * ld + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+__device__ __forceinline__ float row4_sum(float v) {      // the sum over the four lanes of a row, in every one of them
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  return v;
+}
+// mean and 1 / sqrt(var + eps) of a row of K values in LDS; lane q of the row's four (tid & 3)
+__device__ __forceinline__ void ln_stats(const float* xrow, int K, float eps, int q, float& mean, float& rstd) {
+  float s = 0.f;
+  for (int c = q; c < K; c += 4) s += xrow[c];
+  mean = row4_sum(s) / (float)K;
+  float v = 0.f;
+  for (int c = q; c < K; c += 4) {
+    const float d = xrow[c] - mean;
+    v = fmaf(d, d, v);
+  }
+  rstd = 1.f / sqrtf(row4_sum(v) / (float)K + eps);
+}
+// xs [64][ldx] -> LN(xs) in place; thread tid owns columns (tid & 3) + 4 i of row tid >> 2.  The caller puts a barrier on both sides.
+__device__ __forceinline__ void ln_rows(float* xs, int ldx, int K, const float* gamma, const float* beta, float eps, int tid) {
+  float* xrow = xs + (tid >> 2) * ldx;
+  const int q = tid & 3;
+  float mean, rstd;
+  ln_stats(xrow, K, eps, q, mean, rstd);
+  for (int c = q; c < K; c += 4) xrow[c] = fmaf((xrow[c] - mean) * rstd, gamma[c], beta[c]);
+}
+
+// ------------------------------------------------------------------------------------------------ dense linear
+struct DenseLinArgs {
+  int rows, K, N;                   // K and N multiples of 16
+  const float* x;                   // [rows][K]
+  const float* w;                   // [N][ldw]
+  int ldw;
+  const float* b;                   // [N] or NULL
+  const float *gamma, *beta;        // LN: [K], K <= LIN_KB
+  float eps;
+  const float* res;                 // [rows][N] or NULL: out = res + acc
+  const float* aux;                 // [rows][N] or NULL: out = acc act'(aux)
+  int act;
+  float* out;                       // [rows][N]
+};
+inline size_t dense_lin_lds(int K) { return (size_t)LIN_ROWS * (std::min(K, LIN_KB) + AT_PAD) * sizeof(float); }
+
+// grid (ceil(rows / 64), ceil(N / 256)), 256 threads
+template <bool LN>
+__global__ __launch_bounds__(256) void dense_linear_kernel(const DenseLinArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int K = a.K, KB = K < LIN_KB ? K : LIN_KB, ldx = KB + AT_PAD;
+  float* xs = smem;                 // [64][ldx]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int s0 = blockIdx.x * LIN_ROWS;
+  const int ntiles = a.N >> 4, jt0 = blockIdx.y * (LIN_COLS / 16) + wave;
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool on = jt0 + 4 * j < ntiles;
+    const float bias = on && a.b ? a.b[(jt0 + 4 * j) * 16 + r] : 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) acc[j][mt] = f32x4{bias, bias, bias, bias};
+  }
+  for (int kb = 0; kb < K; kb += KB) {
+    const int kw = min(KB, K - kb);
+    if (kb) __syncthreads();
+    stage_rows(xs, ldx, a.x + kb, K, s0, a.rows, kw, tid);
+    __syncthreads();
+    if constexpr (LN) {
+      ln_rows(xs, ldx, K, a.gamma, a.beta, a.eps, tid);
+      __syncthreads();
+    }
+    for (int k0 = 0; k0 < kw; k0 += 16) {
+      f32x4 av[4];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) av[mt] = *(const f32x4*)(xs + (16 * mt + r) * ldx + k0 + 4 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (jt0 + 4 * j >= ntiles) continue;                    // (wave-uniform)
+        const f32x4 bv = *(const f32x4*)(a.w + (int64_t)((jt0 + 4 * j) * 16 + r) * a.ldw + kb + k0 + 4 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt) acc[j][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][e], bv[e], acc[j][mt], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (jt0 + 4 * j >= ntiles) continue;
+    const int col = (jt0 + 4 * j) * 16 + r;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int s = s0 + 16 * mt + 4 * g + i;
+        if (s >= a.rows) continue;
+        const int64_t at = (int64_t)s * a.N + col;
+        float v = acc[j][mt][i];
+        if (a.res) v = a.res[at] + v;
+        if (a.aux) v = v * act_grad(a.aux[at], a.act);
+        a.out[at] = v;
       }
   }
 }
@@ -405,12 +534,9 @@ __global__ __launch_bounds__(256) void attn_dw_kernel(const AdwArgs a) {
     if (arow) av = *(const float4*)(a.da + (int64_t)s * a.lda + m0 + 4 * sc);
     if constexpr (GATHER) {
       const int u = s / a.T, t = s - u * a.T;
-      const int slot = a.s.slots[u];
-      const int64_t off = a.s.user_off[slot];
-      const int len = (int)(a.s.user_off[slot + 1] - off);
-      const int64_t pos = off + max(min(a.t0 + t, len - 1), 0);       // (the host refuses steps past a history's end)
-      if (xcol) xv = len > 0 ? table_chunk(a.s, a.s.items[pos], (n0 >> 2) + sc) : nan4();
-      if (sc == 0) rv = len > 0 ? a.s.ratings[pos] : __builtin_nanf("");
+      const StorePos p = store_pos(a.s, u, a.t0 + t);
+      if (xcol) xv = p.live() ? table_chunk(a.s, a.s.items[p.pos], (n0 >> 2) + sc) : nan4();
+      if (sc == 0) rv = p.live() ? a.s.ratings[p.pos] : __builtin_nanf("");
     } else {
       if (xcol) xv = *(const float4*)(a.x + (int64_t)s * a.ldx + n0 + 4 * sc);
     }
@@ -554,13 +680,48 @@ void launch_key(const AttnArgs& a, hipStream_t s) {
     default: hipLaunchKernelGGL((attn_key_kernel<64>), grid, dim3(256), 0, s, a); break;
   }
 }
-template <bool GATHER>
 int launch_linear(const LinArgs& l, hipStream_t s) {
   const size_t lds = lin_lds(l.K);
-  if (lds > 48 * 1024)
-    RECNN_HIP(hipFuncSetAttribute((const void*)attn_linear_kernel<GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((attn_linear_kernel<GATHER>), dim3((l.rows + LIN_ROWS - 1) / LIN_ROWS), dim3(256), lds, s, l);
+  if (int rc = raise_lds(attn_linear_kernel, lds)) return rc;
+  hipLaunchKernelGGL(attn_linear_kernel, dim3((l.rows + LIN_ROWS - 1) / LIN_ROWS), dim3(256), lds, s, l);
   return 0;
+}
+int launch_dense_linear(const DenseLinArgs& l, bool ln, hipStream_t s) {
+  const size_t lds = dense_lin_lds(l.K);
+  const dim3 grid((l.rows + LIN_ROWS - 1) / LIN_ROWS, (l.N + LIN_COLS - 1) / LIN_COLS);
+  if (ln) {
+    if (int rc = raise_lds(dense_linear_kernel<true>, lds)) return rc;
+    hipLaunchKernelGGL((dense_linear_kernel<true>), grid, dim3(256), lds, s, l);
+  } else {
+    if (int rc = raise_lds(dense_linear_kernel<false>, lds)) return rc;
+    hipLaunchKernelGGL((dense_linear_kernel<false>), grid, dim3(256), lds, s, l);
+  }
+  return 0;
+}
+
+// dW[m, n] = sum_s da[s, m] X[s, n] (G rows, N columns) and db[m] = sum_s da[s, m] over the S = U T samples of a call, either may be
+// NULL: the tile launch over the segments of the samples into `part`, then the parts summed into d_w and d_b.  `st`: X rows are
+// gathered through the store at steps t0 .. t0 + T - 1 and d_w [G][N + 1] has the rating column; NULL: X is x [S][ldx].  `part` holds
+// nsplit ([G][ldp] + [G]) floats, free again when the launches have run (stream order).
+void launch_weight_grad(const SeqStore* st, int t0, int T, int S, const float* da, int lda, const float* x, int ldx, int G, int N,
+                        float* part, float* d_w, float* d_b, hipStream_t s) {
+  if (!d_w && !d_b) return;
+  const int nsplit = adw_nsplit(S);
+  AdwArgs a{};
+  if (st) a.s = *st;
+  a.t0 = t0; a.T = T; a.S = S; a.seg = adw_seg(S);
+  a.da = da; a.lda = lda; a.x = x; a.ldx = ldx;
+  a.G = G; a.N = N; a.ldp = N + (st ? 1 : 0);
+  a.part = d_w ? part : nullptr;
+  a.part_b = d_b ? part + (int64_t)nsplit * G * a.ldp : nullptr;
+  const dim3 grid((G + DW_T - 1) / DW_T, d_w ? (N + DW_T - 1) / DW_T : 1, nsplit);
+  if (st) hipLaunchKernelGGL((attn_dw_kernel<true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_dw_kernel<false>), grid, dim3(256), 0, s, a);
+  if (d_w) {
+    const int64_t n = (int64_t)G * a.ldp;
+    hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, a.part, nsplit, n, d_w);
+  }
+  if (d_b) hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(G, 256, 2048)), dim3(256), 0, s, a.part_b, nsplit, (int64_t)G, d_b);
 }
 
 }  // namespace

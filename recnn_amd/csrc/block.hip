@@ -7,12 +7,8 @@
 //                    are folded (s0 + s1) + (s2 + s3); the mean first, then the centred squares the same way (two passes: no
 //                    E[x^2] - E[x]^2), rstd = 1 / sqrt(var + eps), n = fma((x - mean) rstd, gamma, beta).  One function (ln_rows) on
 //                    rows held in LDS serves every kernel that normalises, so a row's normalised bits are the same wherever it is met.
-//   linear kernel    attn_dev.h's 64-row linear with three additions: LN (the staged rows are normalised in place before the
-//                    products, so the no-grad encode writes no normalised copy), a K-blocked walk (K > 256 is staged in blocks of 256,
-//                    upwards, into the same accumulators: one chain per element, bias first, then k = 0, 1, ..), and two epilogues:
-//                    out = res + acc (the residual link; the chain is finished before the residual is added) and
-//                    out = acc act'(aux) (the activation's derivative at the saved pre-activation).  A workgroup owns 64 rows and
-//                    256 columns; wave w owns column tiles w, w + 4, w + 8, w + 12 of them.
+//   linear kernels   attn_dev.h describes them: the embedding is its gathered linear, every other product its dense linear -- with LN
+//                    for the in-projection, the residual epilogue for the out-projection, the act' epilogue for d_a.
 //   feed-forward     one workgroup per 64 rows: LN2 in place in LDS, then F is walked in chunks of 32: wave w computes 32 rows by 16
 //                    columns of the chunk's a = W_1 n + b_1 (bias first, k upwards), act(a) goes to a [64][32] tile in LDS, and that
 //                    tile feeds y's accumulators (wave w owns column tiles w, w + 4, .. of H: 64 accumulator registers at H = 256),
@@ -20,7 +16,7 @@
 //                    residual is added last.  The [rows, F] activation reaches memory only when the training forward asks for the
 //                    pre-activation a (the backward needs its sign / its value).
 //   backward         what the training forward keeps per block: qkv, o, the log-sum-exp parts, u and a.  The normalised rows and
-//                    act(a) are recomputed.  Weight gradients are attn_dw_kernel<false> + attn_sum_parts_kernel over segments of the
+//                    act(a) are recomputed.  Weight gradients are attn_dev.h's launch_weight_grad over segments of the
 //                    samples; products with a transposed weight run the linear kernel over a transposed copy; the LayerNorm backward
 //                    is row-wise with the forward's lane layout and also sums, per 64 rows, the columns of dn xhat and dn -- those
 //                    parts are added in groups of 64 consecutive workgroups and then group after group (no atomics, one order).
@@ -30,135 +26,9 @@
 
 namespace {
 
-constexpr int BL_KB = 256;          // contraction columns per LDS stage of the linear kernel
-constexpr int BL_COLS = 256;        // output columns per workgroup of the linear kernel
 constexpr int FF_C = 32;            // feed-forward: columns of F per chunk (two workgroups per CU fit at H = 256: 75.8 KB of LDS each)
 constexpr int FF_LD = FF_C + AT_PAD;
 constexpr int BLK_GROUP = 64;       // LayerNorm backward: workgroup parts per first-level sum
-
-enum { ACT_RELU = 0, ACT_GELU = 1 };
-
-__device__ __forceinline__ float act_fwd(float a, int act) {
-  if (act == ACT_RELU) return a < 0.f ? 0.f : a;                   // (a NaN stays a NaN)
-  return 0.5f * a * (1.f + erff(a * 0.70710678118654752440f));
-}
-__device__ __forceinline__ float act_grad(float a, int act) {
-  if (act == ACT_RELU) return a > 0.f ? 1.f : (a != a ? a : 0.f);
-  const float cdf = 0.5f * (1.f + erff(a * 0.70710678118654752440f));
-  return fmaf(a * 0.39894228040143267794f, expf(-0.5f * a * a), cdf);      // Phi(a) + a phi(a)
-}
-
-// ------------------------------------------------------------------------------------------------ rows in LDS
-// rows s0 .. s0 + 63 of x [rows][ld], columns 0 .. kw - 1 (a multiple of 4), into xs [64][ldx]; rows at or past `rows` are zeros
-__device__ __forceinline__ void stage_rows(float* xs, int ldx, const float* x, int64_t ld, int s0, int rows, int kw, int tid) {
-  const int C4 = kw >> 2;
-  for (int idx = tid; idx < LIN_ROWS * C4; idx += 256) {
-    const int row = idx / C4, c = idx - row * C4, s = s0 + row;
-    *(float4*)(xs + row * ldx + 4 * c) = s < rows ? *(const float4*)(x + (int64_t)s * ld + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-__device__ __forceinline__ float row4_sum(float v) {      // the sum over the four lanes of a row, in every one of them
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  return v;
-}
-// mean and 1 / sqrt(var + eps) of a row of K values in LDS; lane q of the row's four (tid & 3)
-__device__ __forceinline__ void ln_stats(const float* xrow, int K, float eps, int q, float& mean, float& rstd) {
-  float s = 0.f;
-  for (int c = q; c < K; c += 4) s += xrow[c];
-  mean = row4_sum(s) / (float)K;
-  float v = 0.f;
-  for (int c = q; c < K; c += 4) {
-    const float d = xrow[c] - mean;
-    v = fmaf(d, d, v);
-  }
-  rstd = 1.f / sqrtf(row4_sum(v) / (float)K + eps);
-}
-// xs [64][ldx] -> LN(xs) in place; thread tid owns columns (tid & 3) + 4 i of row tid >> 2.  The caller puts a barrier on both sides.
-__device__ __forceinline__ void ln_rows(float* xs, int ldx, int K, const float* gamma, const float* beta, float eps, int tid) {
-  float* xrow = xs + (tid >> 2) * ldx;
-  const int q = tid & 3;
-  float mean, rstd;
-  ln_stats(xrow, K, eps, q, mean, rstd);
-  for (int c = q; c < K; c += 4) xrow[c] = fmaf((xrow[c] - mean) * rstd, gamma[c], beta[c]);
-}
-
-// ------------------------------------------------------------------------------------------------ linear
-struct BlkLinArgs {
-  int rows, K, N;                   // K and N multiples of 16
-  const float* x;                   // [rows][K]
-  const float* w;                   // [N][ldw]
-  int ldw;
-  const float* b;                   // [N] or NULL
-  const float *gamma, *beta;        // LN: [K], K <= BL_KB
-  float eps;
-  const float* res;                 // [rows][N] or NULL: out = res + acc
-  const float* aux;                 // [rows][N] or NULL: out = acc act'(aux)
-  int act;
-  float* out;                       // [rows][N]
-};
-inline size_t blk_lin_lds(int K) { return (size_t)LIN_ROWS * (std::min(K, BL_KB) + AT_PAD) * sizeof(float); }
-
-// grid (ceil(rows / 64), ceil(N / 256)), 256 threads
-template <bool LN>
-__global__ __launch_bounds__(256) void blk_linear_kernel(const BlkLinArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int K = a.K, KB = K < BL_KB ? K : BL_KB, ldx = KB + AT_PAD;
-  float* xs = smem;                 // [64][ldx]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int s0 = blockIdx.x * LIN_ROWS;
-  const int ntiles = a.N >> 4, jt0 = blockIdx.y * (BL_COLS / 16) + wave;
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool on = jt0 + 4 * j < ntiles;
-    const float bias = on && a.b ? a.b[(jt0 + 4 * j) * 16 + r] : 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) acc[j][mt] = f32x4{bias, bias, bias, bias};
-  }
-  for (int kb = 0; kb < K; kb += KB) {
-    const int kw = min(KB, K - kb);
-    if (kb) __syncthreads();
-    stage_rows(xs, ldx, a.x + kb, K, s0, a.rows, kw, tid);
-    __syncthreads();
-    if constexpr (LN) {
-      ln_rows(xs, ldx, K, a.gamma, a.beta, a.eps, tid);
-      __syncthreads();
-    }
-    for (int k0 = 0; k0 < kw; k0 += 16) {
-      f32x4 av[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) av[mt] = *(const f32x4*)(xs + (16 * mt + r) * ldx + k0 + 4 * g);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (jt0 + 4 * j >= ntiles) continue;                    // (wave-uniform)
-        const f32x4 bv = *(const f32x4*)(a.w + (int64_t)((jt0 + 4 * j) * 16 + r) * a.ldw + kb + k0 + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) acc[j][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][e], bv[e], acc[j][mt], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (jt0 + 4 * j >= ntiles) continue;
-    const int col = (jt0 + 4 * j) * 16 + r;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int s = s0 + 16 * mt + 4 * g + i;
-        if (s >= a.rows) continue;
-        const int64_t at = (int64_t)s * a.N + col;
-        float v = acc[j][mt][i];
-        if (a.res) v = a.res[at] + v;
-        if (a.aux) v = v * act_grad(a.aux[at], a.act);
-        a.out[at] = v;
-      }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ feed-forward
 struct FfnArgs {
@@ -343,23 +213,6 @@ __global__ __launch_bounds__(256) void blk_act_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-template <class Kern>
-int raise_lds(Kern kern, size_t lds) {
-  if (lds > 48 * 1024) RECNN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return 0;
-}
-int launch_blk_linear(const BlkLinArgs& l, bool ln, hipStream_t s) {
-  const size_t lds = blk_lin_lds(l.K);
-  const dim3 grid((l.rows + LIN_ROWS - 1) / LIN_ROWS, (l.N + BL_COLS - 1) / BL_COLS);
-  if (ln) {
-    if (int rc = raise_lds(blk_linear_kernel<true>, lds)) return rc;
-    hipLaunchKernelGGL((blk_linear_kernel<true>), grid, dim3(256), lds, s, l);
-  } else {
-    if (int rc = raise_lds(blk_linear_kernel<false>, lds)) return rc;
-    hipLaunchKernelGGL((blk_linear_kernel<false>), grid, dim3(256), lds, s, l);
-  }
-  return 0;
-}
 int launch_ln_rows(const float* x, int rows, int H, const float* gamma, const float* beta, float eps, float* out, hipStream_t s) {
   const size_t lds = lin_lds(H);
   if (int rc = raise_lds(blk_ln_rows_kernel, lds)) return rc;
@@ -395,23 +248,9 @@ int launch_ln_bwd(const float* x, const float* dn, const float* gamma, float eps
   return 0;
 }
 
-// dW[m, n] = sum_s da[s, m] x[s, n] and db[m] = sum_s da[s, m] over S samples, dense operands: attn.hip's segmented tile
+// dW[m, n] = sum_s da[s, m] x[s, n] and db[m] = sum_s da[s, m] over S samples, dense operands x [S][N]
 void dense_weight_grad(const float* da, int lda, const float* x, int Gr, int N, int S, float* part, float* d_w, float* d_b, hipStream_t s) {
-  if (!d_w && !d_b) return;
-  const int nsplit = adw_nsplit(S), seg = adw_seg(S);
-  AdwArgs x_{};
-  x_.T = 1; x_.S = S; x_.seg = seg;
-  x_.da = da; x_.lda = lda; x_.x = x; x_.ldx = N;
-  x_.G = Gr; x_.N = N; x_.ldp = N;
-  x_.part = d_w ? part : nullptr;
-  x_.part_b = d_b ? part + (int64_t)nsplit * Gr * N : nullptr;
-  const dim3 grid((Gr + DW_T - 1) / DW_T, d_w ? (N + DW_T - 1) / DW_T : 1, nsplit);
-  hipLaunchKernelGGL((attn_dw_kernel<false>), grid, dim3(256), 0, s, x_);
-  if (d_w) {
-    const int64_t n = (int64_t)Gr * N;
-    hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, x_.part, nsplit, n, d_w);
-  }
-  if (d_b) hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(Gr, 256, 2048)), dim3(256), 0, s, x_.part_b, nsplit, (int64_t)Gr, d_b);
+  launch_weight_grad(nullptr, 0, 1, S, da, lda, x, N, Gr, N, part, d_w, d_b, s);
 }
 
 // what a block's forward keeps: attn.hip's three tensors, u, and (training only) the pre-activation a [rows][F]
@@ -473,18 +312,18 @@ int block_forward_impl(const char* what, const float* x, int n_users, int T, int
   const BlockWs w = block_ws(n_users, T, H, n_heads, ffn, train);
   char* kp = (char*)keep;
   float* u = (float*)(kp + w.u);
-  BlkLinArgs l{};
+  DenseLinArgs l{};
   l.rows = M; l.K = H; l.N = 3 * H; l.x = x; l.w = p.w_in; l.ldw = H; l.b = p.b_in;
   l.gamma = p.g1; l.beta = p.be1; l.eps = eps; l.out = (float*)(kp + w.at.qkv);
-  if (int rc = launch_blk_linear(l, true, s)) return rc;
+  if (int rc = launch_dense_linear(l, true, s)) return rc;
   AttnArgs a = attn_args(n_users, T, H, n_heads, window, alibi);
   a.qkv = (const float*)(kp + w.at.qkv);
   a.o = (float*)(kp + w.at.o);
   a.lse = (float*)(kp + w.at.lse);
   launch_query<0>(a, s);
-  BlkLinArgs o{};
+  DenseLinArgs o{};
   o.rows = M; o.K = H; o.N = H; o.x = a.o; o.w = p.w_o; o.ldw = H; o.b = p.b_o; o.res = x; o.out = u;
-  if (int rc = launch_blk_linear(o, false, s)) return rc;
+  if (int rc = launch_dense_linear(o, false, s)) return rc;
   FfnArgs f{};
   f.rows = M; f.H = H; f.F = ffn; f.act = act; f.u = u;
   f.w1 = p.w1; f.b1 = p.b1; f.w2 = p.w2; f.b2 = p.b2; f.gamma = p.g2; f.beta = p.be2; f.eps = eps;
@@ -542,9 +381,9 @@ int block_backward_impl(const float* x, int n_users, int T, int hidden, int n_he
   if (!need_da1) return recnn_check_hip(hipGetLastError(), what);
   // d_a = (g_y W_2) act'(a)   [rows][F]
   transpose(p.w2, F, H);
-  BlkLinArgs l{};
+  DenseLinArgs l{};
   l.rows = M; l.K = H; l.N = F; l.x = g_y; l.w = wt; l.ldw = H; l.aux = a1; l.act = act; l.out = big;
-  if (int rc = launch_blk_linear(l, false, s)) return rc;
+  if (int rc = launch_dense_linear(l, false, s)) return rc;
   if (d.w1 || d.b1) {
     if (d.w1)
       if (int rc = launch_ln_rows(u, M, H, p.g2, p.be2, eps, nb, s)) return rc;
@@ -553,17 +392,17 @@ int block_backward_impl(const float* x, int n_users, int T, int hidden, int n_he
   if (!need_du) return recnn_check_hip(hipGetLastError(), what);
   // d(LN2 u) = d_a W_1, then d_u = g_y + LN2's backward
   transpose(p.w1, H, F);
-  l = BlkLinArgs{};
+  l = DenseLinArgs{};
   l.rows = M; l.K = F; l.N = H; l.x = big; l.w = wt; l.ldw = F; l.out = nb;
-  if (int rc = launch_blk_linear(l, false, s)) return rc;
+  if (int rc = launch_dense_linear(l, false, s)) return rc;
   if (int rc = launch_ln_bwd(u, nb, p.g2, eps, g_y, M, H, du, d.g2, d.be2, lnpart, s)) return rc;
   // the out-projection
   dense_weight_grad(du, H, o, H, H, M, part, d.w_o, d.b_o, s);
   if (!need_attn) return recnn_check_hip(hipGetLastError(), what);
   transpose(p.w_o, H, H);
-  l = BlkLinArgs{};
+  l = DenseLinArgs{};
   l.rows = M; l.K = H; l.N = H; l.x = du; l.w = wt; l.ldw = H; l.out = nb;          // dO
-  if (int rc = launch_blk_linear(l, false, s)) return rc;
+  if (int rc = launch_dense_linear(l, false, s)) return rc;
   AttnArgs a = attn_args(n_users, T, H, n_heads, window, alibi);
   a.qkv = (const float*)(sp + sv.at.qkv);
   a.lse = (float*)(sp + sv.at.lse);                  // (read only)
@@ -582,9 +421,9 @@ int block_backward_impl(const float* x, int n_users, int T, int hidden, int n_he
   }
   if (!need_ln1) return recnn_check_hip(hipGetLastError(), what);
   transpose(p.w_in, H, 3 * H);
-  l = BlkLinArgs{};
+  l = DenseLinArgs{};
   l.rows = M; l.K = 3 * H; l.N = H; l.x = big; l.w = wt; l.ldw = 3 * H; l.out = nb;
-  if (int rc = launch_blk_linear(l, false, s)) return rc;
+  if (int rc = launch_dense_linear(l, false, s)) return rc;
   if (int rc = launch_ln_bwd(x, nb, p.g1, eps, du, M, H, d_x, d.g1, d.be1, lnpart, s)) return rc;
   return recnn_check_hip(hipGetLastError(), what);
 }
@@ -615,23 +454,7 @@ int seq_embed_backward_impl(const int32_t* items, const float* ratings, const in
     table_grad_chunk(tg, 0, T, s);
     table_grad_finish(tg, d_table, s);
   }
-  if (d_w_e || d_b_e) {
-    const int nsplit = adw_nsplit(S);
-    float* part = (float*)workspace;
-    AdwArgs x_{};
-    x_.s = st; x_.t0 = t0; x_.T = T; x_.S = S; x_.seg = adw_seg(S);
-    x_.da = g_x; x_.lda = H; x_.ldx = emb_dim;
-    x_.G = H; x_.N = emb_dim; x_.ldp = emb_dim + 1;
-    x_.part = d_w_e ? part : nullptr;
-    x_.part_b = d_b_e ? part + (int64_t)nsplit * H * x_.ldp : nullptr;
-    const dim3 grid((H + DW_T - 1) / DW_T, d_w_e ? (emb_dim + DW_T - 1) / DW_T : 1, nsplit);
-    hipLaunchKernelGGL((attn_dw_kernel<true>), grid, dim3(256), 0, s, x_);
-    if (d_w_e) {
-      const int64_t n = (int64_t)H * x_.ldp;
-      hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, x_.part, nsplit, n, d_w_e);
-    }
-    if (d_b_e) hipLaunchKernelGGL(attn_sum_parts_kernel, dim3(grid_for(H, 256, 2048)), dim3(256), 0, s, x_.part_b, nsplit, (int64_t)H, d_b_e);
-  }
+  launch_weight_grad(&st, t0, T, S, g_x, H, nullptr, emb_dim, H, emb_dim, (float*)workspace, d_w_e, d_b_e, s);
   return recnn_check_hip(hipGetLastError(), what);
 }
 
@@ -652,7 +475,7 @@ extern "C" int recnn_seq_embed(const int32_t* items, const float* ratings, const
   l.t0 = t0; l.T = T; l.rows = n_users * T;
   l.K = emb_dim; l.w = w_e; l.ldw = emb_dim + 1; l.b = b_e;
   l.out = x_out; l.N = hidden;
-  if (int rc = launch_linear<true>(l, (hipStream_t)stream)) return rc;
+  if (int rc = launch_linear(l, (hipStream_t)stream)) return rc;
   return recnn_check_hip(hipGetLastError(), what);
 }
 

@@ -121,7 +121,7 @@ int backward_impl(void (*chain1)(BwdArgs<Cell>), void (*chain2)(BwdArgs<Cell>), 
   float* dh = (float*)(ws + w.dh);
   const bool want_w = d_w_ih || d_w_hh || d_b_ih || d_b_hh;
   const size_t lds = bwd_lds(H);
-  if (lds > 48 * 1024) RECNN_HIP(hipFuncSetAttribute((const void*)chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (int rc = raise_lds(chain, lds)) return rc;
   hipLaunchKernelGGL(whh_transpose_kernel, dim3(grid_for((int64_t)H * G, 256, 2048)), dim3(256), 0, s, w_hh, H, G, wt);
 
   BwdArgs<Cell> a{};

@@ -78,6 +78,22 @@ struct EncArgs {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
+// Position t of user u's history through the store, for the kernels that meet a (user, step) sample at a time: where it lies in
+// items / ratings -- past the history's end it is clamped to the last element (the host refuses such a step; nothing is read out of
+// bounds) -- and whether the history holds anything at all (an empty one gives NaN rows and is in no list).
+struct StorePos {
+  int64_t pos;
+  int len;
+  __device__ __forceinline__ bool live() const { return len > 0; }
+};
+__device__ __forceinline__ StorePos store_pos(const int32_t* slots, const int64_t* user_off, int u, int t) {
+  const int slot = slots[u];
+  const int64_t off = user_off[slot];
+  const int len = (int)(user_off[slot + 1] - off);
+  return StorePos{off + max(min(t, len - 1), 0), len};
+}
+__device__ __forceinline__ StorePos store_pos(const SeqStore& s, int u, int t) { return store_pos(s.slots, s.user_off, u, t); }
+
 // The stager: thread (su = tid >> 5, sc = tid & 31) owns 16-byte chunk sc of user row su of the x panel.  Positions past a history's
 // end are clamped to its last element (the host refuses such a T; nothing is read out of bounds).
 struct Stager {
@@ -328,6 +344,13 @@ __global__ __launch_bounds__(NT) void seq_project_kernel(const EncArgs a) {
 #pragma unroll
       for (int q = 0; q < Cell::PRE_Q; ++q)
         ((f32x4*)a.pre)[acc_index(blockIdx.x, a.T, t, ntiles, jt[j], Cell::PRE_Q, q, lane)] = acc[j][q];
+}
+
+// a launch with more than 48 KB of dynamic LDS has to be opted in, kernel by kernel
+template <class Kern>
+int raise_lds(Kern kern, size_t lds) {
+  if (lds > 48 * 1024) RECNN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return 0;
 }
 
 inline size_t encode_lds(int E, int H) { return (size_t)(2 * MT * (((E + 15) & ~15) + PAD) + 2 * MT * (H + PAD) + 2 * MT) * sizeof(float); }

@@ -82,12 +82,9 @@ __global__ __launch_bounds__(256) void seq_dw_kernel(const DwArgs a) {
     const int u = s / a.Tc, tl = s - u * a.Tc, t = a.tb + tl;
     if (arow) av = *(const float4*)(a.da + ((int64_t)u * a.da_T + tl) * a.lda + acol);
     if constexpr (IH) {
-      const int slot = a.s.slots[u];
-      const int64_t off = a.s.user_off[slot];
-      const int len = (int)(a.s.user_off[slot + 1] - off);
-      const int64_t pos = off + max(min(a.t0 + t, len - 1), 0);       // (the host refuses steps past a history's end)
-      if (xcol) xv = len > 0 ? table_chunk(a.s, a.s.items[pos], (n0 >> 2) + sc) : nan4();
-      if (sc == 0) rv = len > 0 ? a.s.ratings[pos] : __builtin_nanf("");
+      const StorePos p = store_pos(a.s, u, a.t0 + t);
+      if (xcol) xv = p.live() ? table_chunk(a.s, a.s.items[p.pos], (n0 >> 2) + sc) : nan4();
+      if (sc == 0) rv = p.live() ? a.s.ratings[p.pos] : __builtin_nanf("");
     } else {
       if (xcol) {
         if (t >= 1) xv = *(const float4*)(a.h_out + ((int64_t)u * a.T + t - 1) * H + n0 + 4 * sc);
@@ -241,10 +238,8 @@ struct StoreId {
   int T, t0;
   __device__ int64_t operator()(int j) const {
     const int u = j / T, t = j - u * T;
-    const int slot = slots[u];
-    const int64_t off = user_off[slot];
-    const int len = (int)(user_off[slot + 1] - off);
-    return len > 0 ? (int64_t)items[off + max(min(t0 + t, len - 1), 0)] : -1;
+    const StorePos p = store_pos(slots, user_off, u, t0 + t);
+    return p.live() ? (int64_t)items[p.pos] : -1;
   }
 };
 

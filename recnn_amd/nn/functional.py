@@ -1709,17 +1709,47 @@ def _encode_call_args(name, cell, module, store, table, slots, T, states, t0):
     return dev, E, H, U, T, t0, slots, states
 
 
-def _train_call_args(name, cell, module, store, table, slots, T, states, t0, train_table):
-    """The prologue of `lstm_encode_train` / `gru_encode_train`: the refusal of a table gradient nobody asked for, then
-    `_encode_call_args`' tuple with (params, live) appended -- the four weights, and whether anything wants a graph."""
+def _refuse_table_grad(name, table, train_table):
+    """What every `*_encode_train` opens with: the refusal of a table gradient nobody asked for."""
     if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
         raise L.RecnnHipError(f"{name}: table.requires_grad is set, but gradients with respect to the embedding table are "
                               "computed only on request; pass train_table=True to train it, or table.detach()")
+
+
+def _wants_graph(table, tensors):
+    """Whether a `*_encode_train` call records anything: grad mode, and the table (only with train_table) or one of `tensors`."""
+    return torch.is_grad_enabled() and (table.requires_grad or any(t.requires_grad for t in tensors))
+
+
+def _f32_on(dev):
+    """`new(*shape)`: an uninitialised float32 tensor on `dev`."""
+    return lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+
+
+def _train_buffers(query, dev, *dims):
+    """(`saved`, bytes of the backward's workspace) of a training forward, sized by the entry point `query`."""
+    nsaved, nbwd = C.c_int64(), C.c_int64()
+    L.call(query, *dims, C.byref(nsaved), C.byref(nbwd))
+    return torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev), nbwd.value
+
+
+def _call_backward(kind, head, w_table, mid, d_table, ws, table_dims, dev):
+    """recnn_<kind>_backward, or -- `d_table` wanted -- recnn_<kind>_backward_table, which also takes the weight next to the table
+    (`w_table`) and the table workspace of recnn_<kind>_table_grad_workspace_bytes(*table_dims)."""
+    if d_table is None:
+        L.call(f"recnn_{kind}_backward", *head, *mid, L.ptr(ws), L.current_stream())
+    else:
+        tws = L.workspace(f"recnn_{kind}_table_grad_workspace_bytes", *table_dims, device=dev)
+        L.call(f"recnn_{kind}_backward_table", *head, L.ptr(w_table), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
+
+
+def _train_call_args(name, cell, module, store, table, slots, T, states, t0, train_table):
+    """The prologue of `lstm_encode_train` / `gru_encode_train`: `_refuse_table_grad`, then `_encode_call_args`' tuple with
+    (params, live) appended -- the four weights, and whether anything wants a graph."""
+    _refuse_table_grad(name, table, train_table)
     *head, states = _encode_call_args(name, cell, module, store, table, slots, T, states, t0)
     params = (module.weight_ih_l0, module.weight_hh_l0, module.bias_ih_l0, module.bias_hh_l0)
-    live = torch.is_grad_enabled() and (table.requires_grad               # (the table: only with train_table)
-                                        or any(t.requires_grad for t in (*params, *(states or ()))))
-    return (*head, states, params, live)
+    return (*head, states, params, _wants_graph(table, (*params, *(states or ()))))
 
 
 def _store_args(store, slots_d, U, t0, T, table, E, H):
@@ -1732,13 +1762,10 @@ def _encode_buffers(cell, nstate, dev, U, T, E, H, train=False):
     """What one encode call allocates: (variant, projection workspace, `saved` record, bytes of the backward's workspace, h [U, T, H],
     a tuple of the `nstate` final states [U, H] each); `saved` is None and the bytes 0 unless `train`."""
     variant = LSTM_VARIANTS[_lstm_variant]
-    saved, nsaved, nbwd = None, C.c_int64(), C.c_int64()
-    if train:
-        L.call(f"recnn_{cell}_train_workspace_bytes", U, T, H, E, variant, C.byref(nsaved), C.byref(nbwd))
-        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+    saved, nbwd = _train_buffers(f"recnn_{cell}_train_workspace_bytes", dev, U, T, H, E, variant) if train else (None, 0)
     ws = L.workspace(f"recnn_{cell}_workspace_bytes", U, T, H, variant, device=dev)
-    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-    return variant, ws, saved, nbwd.value, new(U, T, H), tuple(new(U, H) for _ in range(nstate))
+    new = _f32_on(dev)
+    return variant, ws, saved, nbwd, new(U, T, H), tuple(new(U, H) for _ in range(nstate))
 
 
 @torch.no_grad()
@@ -1840,7 +1867,7 @@ class LSTMEncodeFunction(torch.autograd.Function):
         if g_h is None and g_hT is None and g_cT is None:
             return (None,) * 11
         g_h, g_hT, g_cT = (None if g is None else g.to(torch.float32).contiguous() for g in (g_h, g_hT, g_cT))
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        new = _f32_on(dev)
         d_w_ih = new(4 * H, E + 1) if need[0] else None
         d_w_hh = new(4 * H, H) if need[1] else None
         d_b = new(4 * H) if need[2] or need[3] else None
@@ -1851,11 +1878,7 @@ class LSTMEncodeFunction(torch.autograd.Function):
         head = _store_args(store, slots_d, U, t0, T, table, E, H)
         mid = (L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(c0), L.ptr(g_h), L.ptr(g_hT), L.ptr(g_cT), L.ptr(d_w_ih),
                L.ptr(d_w_hh), L.ptr(d_b), L.ptr(d_h0), L.ptr(d_c0))
-        if d_table is None:
-            L.call("recnn_lstm_backward", *head, *mid, L.ptr(ws), L.current_stream())
-        else:
-            tws = L.workspace("recnn_lstm_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
-            L.call("recnn_lstm_backward_table", *head, L.ptr(w_ih), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
+        _call_backward("lstm", head, w_ih, mid, d_table, ws, (U, T, H, E, table.shape[0]), dev)
         return (d_w_ih, d_w_hh, d_b if need[2] else None, (d_b.clone() if need[2] else d_b) if need[3] else None, d_h0, d_c0,
                 None, d_table, None, None, None)
 
@@ -1936,7 +1959,7 @@ class GRUEncodeFunction(torch.autograd.Function):
         if g_h is None and g_hT is None:
             return (None,) * 10
         g_h, g_hT = (None if g is None else g.to(torch.float32).contiguous() for g in (g_h, g_hT))
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        new = _f32_on(dev)
         d_w_ih = new(3 * H, E + 1) if need[0] else None
         d_w_hh = new(3 * H, H) if need[1] else None
         d_b_ih = new(3 * H) if need[2] else None
@@ -1947,11 +1970,7 @@ class GRUEncodeFunction(torch.autograd.Function):
         head = _store_args(store, slots_d, U, t0, T, table, E, H)
         mid = (L.ptr(w_hh), L.ptr(saved), L.ptr(h), L.ptr(h0), L.ptr(g_h), L.ptr(g_hT), L.ptr(d_w_ih), L.ptr(d_w_hh), L.ptr(d_b_ih),
                L.ptr(d_b_hh), L.ptr(d_h0))
-        if d_table is None:
-            L.call("recnn_gru_backward", *head, *mid, L.ptr(ws), L.current_stream())
-        else:
-            tws = L.workspace("recnn_gru_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
-            L.call("recnn_gru_backward_table", *head, L.ptr(w_ih), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
+        _call_backward("gru", head, w_ih, mid, d_table, ws, (U, T, H, E, table.shape[0]), dev)
         return d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_h0, None, d_table, None, None, None
 
 
@@ -2055,7 +2074,7 @@ def attn_encode(enc, store, table, slots, T, *, t0=0):
     multiple of 8 up to 128, window < 1; with ValueError: a history shorter than t0 + T, U * T >= 2^31."""
     dev, E, H, U, T, t0, slots, params = _attn_call_args("attn_encode", enc, store, table, slots, T, t0)
     ws = L.workspace("recnn_attn_workspace_bytes", U, T, H, enc.num_heads, device=dev)
-    h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+    h = _f32_on(dev)(U, T, H)
     slots_d = torch.from_numpy(slots).to(dev)
     L.call("recnn_attn_encode", *_attn_head(enc, store, slots_d, U, t0, T, table, E, H), *(L.ptr(p) for p in params), L.ptr(h),
            L.ptr(ws), L.current_stream())
@@ -2071,15 +2090,12 @@ class AttnEncodeFunction(torch.autograd.Function):
     def forward(ctx, w_in, b_in, w_o, b_o, enc, store, table, slots_d, T, t0):
         U, E, H = slots_d.shape[0], table.shape[1], w_o.shape[0]
         dev = w_in.device
-        nsaved, nbwd = C.c_int64(), C.c_int64()
-        L.call("recnn_attn_train_workspace_bytes", U, T, H, E, enc.num_heads, C.byref(nsaved), C.byref(nbwd))
-        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
-        h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+        saved, ctx.bwd_bytes = _train_buffers("recnn_attn_train_workspace_bytes", dev, U, T, H, E, enc.num_heads)
+        h = _f32_on(dev)(U, T, H)
         head = _attn_head(enc, store, slots_d, U, t0, T, table, E, H)
         L.call("recnn_attn_encode_train", *head, L.ptr(w_in), L.ptr(b_in), L.ptr(w_o), L.ptr(b_o), L.ptr(h), L.ptr(saved),
                L.current_stream())
-        ctx.store, ctx.dims, ctx.bwd_bytes = store, (U, T, t0, E, H), nbwd.value
-        ctx.layer = (enc.num_heads, enc.window or 0, int(enc.alibi))
+        ctx.enc, ctx.store, ctx.dims = enc, store, (U, T, t0, E, H)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(w_in, w_o, table, slots_d, saved)
         return h
@@ -2094,20 +2110,16 @@ class AttnEncodeFunction(torch.autograd.Function):
             return (None,) * 10
         dev = saved.device
         g_h = g_h.to(torch.float32).contiguous()
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        new = _f32_on(dev)
         d_w_in = new(3 * H, E + 1) if need[0] else None
         d_b_in = new(3 * H) if need[1] else None
         d_w_o = new(H, H) if need[2] else None
         d_b_o = new(H) if need[3] else None
         d_table = new(table.shape[0], E) if need[6] else None
         ws = torch.empty(max(ctx.bwd_bytes, 16), dtype=torch.uint8, device=dev)
-        head = (*_store_args(ctx.store, slots_d, U, t0, T, table, E, H), *ctx.layer)
+        head = _attn_head(ctx.enc, ctx.store, slots_d, U, t0, T, table, E, H)
         mid = (L.ptr(w_o), L.ptr(saved), L.ptr(g_h), L.ptr(d_w_in), L.ptr(d_b_in), L.ptr(d_w_o), L.ptr(d_b_o))
-        if d_table is None:
-            L.call("recnn_attn_backward", *head, *mid, L.ptr(ws), L.current_stream())
-        else:
-            tws = L.workspace("recnn_attn_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
-            L.call("recnn_attn_backward_table", *head, L.ptr(w_in), *mid, L.ptr(d_table), L.ptr(ws), L.ptr(tws), L.current_stream())
+        _call_backward("attn", head, w_in, mid, d_table, ws, (U, T, H, E, table.shape[0]), dev)
         return d_w_in, d_b_in, d_w_o, d_b_o, None, None, d_table, None, None, None
 
 
@@ -2124,11 +2136,9 @@ def attn_encode_train(enc, store, table, slots, T, *, t0=0, train_table=False):
     steps do not hold -- also with every encoder parameter frozen.  The parameter gradients keep their bits.
 
     Under `torch.no_grad()`, or when nothing requires grad, this IS `attn_encode`: nothing is kept."""
-    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
-        raise L.RecnnHipError("attn_encode_train: table.requires_grad is set, but gradients with respect to the embedding table are "
-                              "computed only on request; pass train_table=True to train it, or table.detach()")
+    _refuse_table_grad("attn_encode_train", table, train_table)
     dev, E, H, U, T, t0, slots, params = _attn_call_args("attn_encode_train", enc, store, table, slots, T, t0)
-    if not (torch.is_grad_enabled() and (table.requires_grad or any(p.requires_grad for p in params))):
+    if not _wants_graph(table, params):
         return attn_encode(enc, store, table.detach(), slots, T, t0=t0)
     return AttnEncodeFunction.apply(*params, enc, store, table, torch.from_numpy(slots).to(dev), T, t0)
 
@@ -2199,7 +2209,7 @@ def transformer_encode(enc, store, table, slots, T, *, t0=0):
     not a multiple of 16 in 16 .. 1024, an unknown activation, eps <= 0."""
     dev, E, H, U, T, t0, slots, params, cfg = _transformer_call_args("transformer_encode", enc, store, table, slots, T, t0)
     slots_d = torch.from_numpy(slots).to(dev)
-    x = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+    x = _f32_on(dev)(U, T, H)
     y = torch.empty_like(x)
     L.call("recnn_seq_embed", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(params[0]), L.ptr(params[1]), L.ptr(x),
            L.current_stream())
@@ -2220,7 +2230,7 @@ class SeqEmbedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, w_e, b_e, store, table, slots_d, T, t0):
         U, E, H = slots_d.shape[0], table.shape[1], w_e.shape[0]
-        x = torch.empty(U, T, H, dtype=torch.float32, device=w_e.device)
+        x = _f32_on(w_e.device)(U, T, H)
         L.call("recnn_seq_embed", *_store_args(store, slots_d, U, t0, T, table, E, H), L.ptr(w_e), L.ptr(b_e), L.ptr(x),
                L.current_stream())
         ctx.store, ctx.dims = store, (U, T, t0, E, H)
@@ -2238,18 +2248,13 @@ class SeqEmbedFunction(torch.autograd.Function):
             return (None,) * 7
         dev = w_e.device
         g_x = g_x.to(torch.float32).contiguous()
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        new = _f32_on(dev)
         d_w = new(H, E + 1) if need[0] else None
         d_b = new(H) if need[1] else None
         d_table = new(table.shape[0], E) if need[3] else None
         head = _store_args(ctx.store, slots_d, U, t0, T, table, E, H)
         ws = L.workspace("recnn_seq_embed_backward_workspace_bytes", U, T, H, E, device=dev)
-        if d_table is None:
-            L.call("recnn_seq_embed_backward", *head, L.ptr(g_x), L.ptr(d_w), L.ptr(d_b), L.ptr(ws), L.current_stream())
-        else:
-            tws = L.workspace("recnn_seq_embed_table_grad_workspace_bytes", U, T, H, E, table.shape[0], device=dev)
-            L.call("recnn_seq_embed_backward_table", *head, L.ptr(w_e), L.ptr(g_x), L.ptr(d_w), L.ptr(d_b), L.ptr(d_table), L.ptr(ws),
-                   L.ptr(tws), L.current_stream())
+        _call_backward("seq_embed", head, w_e, (L.ptr(g_x), L.ptr(d_w), L.ptr(d_b)), d_table, ws, (U, T, H, E, table.shape[0]), dev)
         return d_w, d_b, None, d_table, None, None, None
 
 
@@ -2267,11 +2272,9 @@ class TransformerBlockFunction(torch.autograd.Function):
             ws = L.workspace("recnn_block_workspace_bytes", U, T, H, cfg[0], device=dev)
             L.call("recnn_block_forward", *_block_head(x, cfg), *(L.ptr(p) for p in params), L.ptr(y), L.ptr(ws), L.current_stream())
             return y
-        nsaved, nbwd = C.c_int64(), C.c_int64()
-        L.call("recnn_block_train_workspace_bytes", U, T, H, cfg[0], cfg[1], C.byref(nsaved), C.byref(nbwd))
-        saved = torch.empty(max(nsaved.value, 16), dtype=torch.uint8, device=dev)
+        saved, ctx.bwd_bytes = _train_buffers("recnn_block_train_workspace_bytes", dev, U, T, H, cfg[0], cfg[1])
         L.call("recnn_block_forward_train", *_block_head(x, cfg), *(L.ptr(p) for p in params), L.ptr(y), L.ptr(saved), L.current_stream())
-        ctx.cfg, ctx.bwd_bytes = cfg, nbwd.value
+        ctx.cfg = cfg
         ctx.save_for_backward(x, saved, *params)
         return y
 
@@ -2336,11 +2339,9 @@ def transformer_encode_train(enc, store, table, slots, T, *, t0=0, train_table=F
     steps do not hold -- also with every encoder parameter frozen.
 
     Under `torch.no_grad()`, or when nothing requires grad, this IS `transformer_encode`: nothing is kept."""
-    if isinstance(table, torch.Tensor) and table.requires_grad and not train_table:
-        raise L.RecnnHipError("transformer_encode_train: table.requires_grad is set, but gradients with respect to the embedding table "
-                              "are computed only on request; pass train_table=True to train it, or table.detach()")
+    _refuse_table_grad("transformer_encode_train", table, train_table)
     dev, E, H, U, T, t0, slots, params, cfg = _transformer_call_args("transformer_encode_train", enc, store, table, slots, T, t0)
-    if not (torch.is_grad_enabled() and (table.requires_grad or any(p.requires_grad for p in params))):
+    if not _wants_graph(table, params):
         return transformer_encode(enc, store, table.detach(), slots, T, t0=t0)
     x = SeqEmbedFunction.apply(params[0], params[1], store, table, torch.from_numpy(slots).to(dev), T, t0)
     for i in range(len(enc.layers)):
@@ -2392,7 +2393,7 @@ class SeqCollectFunction(torch.autograd.Function):
             return None, None, None, None, None
         g_state, g_next = (None if g is None else g.to(torch.float32).contiguous() for g in (g_state, g_next))
         dev = (g_state if g_state is not None else g_next).device
-        g_h = torch.empty(U, T, H, dtype=torch.float32, device=dev)
+        g_h = _f32_on(dev)(U, T, H)
         steps_d = torch.from_numpy(ctx.steps).to(dev)
         L.call("recnn_seq_collect_bwd", L.ptr(g_state), L.ptr(g_next), U, T, H, L.ptr(steps_d), len(ctx.steps), L.ptr(g_h),
                L.current_stream())

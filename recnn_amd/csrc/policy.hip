@@ -35,6 +35,8 @@ __device__ inline float4 load4_tail(const float* row, int i4, int n, float fill)
 //            probabilities and is left untouched.
 //   sample : draw actions[row] ~ p / sum(p);  else actions[row] is read (or ignored when actions == NULL).
 // logprob[row] = log(clamp(p[a] / sum(p), eps, 1 - eps)), rowstat[row] = {max, sum exp, sum p, clamped}.
+// A logit of -inf is a masked item: its probability is exactly 0 and the sampler never draws it (a row of nothing but -inf is NaN,
+// like torch.softmax).
 template <bool SOFTMAX>
 __global__ __launch_bounds__(PT) void categorical_kernel(float* __restrict__ x, int64_t ld, int n, int sample, uint32_t key,
                                                          int64_t* __restrict__ actions, float* __restrict__ logprob,
@@ -55,7 +57,8 @@ __global__ __launch_bounds__(PT) void categorical_kernel(float* __restrict__ x, 
       const float4 v = load4_tail(xr, i, n, -INFINITY);
       const float vm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
       if (vm > m) { s *= expf(m - vm); m = vm; }
-      s += expf(v.x - m) + expf(v.y - m) + expf(v.z - m) + expf(v.w - m);
+      // nothing finite seen yet (masked items are -inf logits): -inf - -inf is NaN, and a NaN in s outlives every later rescale
+      if (m != -INFINITY) s += expf(v.x - m) + expf(v.y - m) + expf(v.z - m) + expf(v.w - m);
     }
     mx = block_max<NWAVE>(m, red);
     s = (m == -INFINITY) ? 0.f : s * expf(m - mx);

@@ -656,6 +656,13 @@ typedef struct recnn_engine_tuning {
                                loads every embedding line of a user's run once and writes 16 bytes per store (csrc/gather.hip) where the
                                rows' alignment allows; 0: the generic gather body, four rows per workgroup.  Took the last reserved slot:
                                the struct's size is unchanged.  Bit-identical */
+  int policy_fused;         /* the policy step's own launches on the single-GPU plain-bf16 engine (policy_chain, no communicator), a bit set:
+                               bit 0: layer 1 of the policy-loss critic runs on the per-step tiled kernel (csrc/l1gemm.hip) wherever the
+                               step's learning critics do; bit 1: the actor's three weight gradients are summed over their batch slices on
+                               chip and written to the flat gradient arena by ONE launch without slabs (csrc/dwadam.hip dw_grad_kernel),
+                               the clip quirk's |g| sums then come from that arena -- where the tile plan fits (batches of 1024, 2048, ...
+                               rows), else the dW launch + slab reduction stay.  0: the generic launches.  Default 3.  Bit-identical.
+                               (Grows the struct by one int: recnn_abi_sizeof(5).) */
 } recnn_engine_tuning;
 void recnn_engine_tuning_init(recnn_engine_tuning* h_t);
 int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* h_t);
@@ -679,7 +686,8 @@ int recnn_engine_unit_backward(recnn_engine* e);
  * policy step's batch of a batched segment is written), "cycle_target_q1" / "2", "cycle_next_action0" / "1" (the target actor's output of window mode, per copy) and
  * "cycle_xn0" / "1" (the packed next rows whose action slot holds it otherwise: the engine's own allocation, NULL while it has none);
  * what the cycle gather writes, per copy: "cycle_xs0" / "1" (packed [action | state] rows), "cycle_tail_n0" / "1" (window mode's next
- * ratings; NULL where the dims do not allow that mode), "cycle_reward0" / "1", "cycle_done0" / "1". */
+ * ratings; NULL where the dims do not allow that mode), "cycle_reward0" / "1", "cycle_done0" / "1".  "actor_l1part": the clip quirk's
+ * |g| sum per optimizer workgroup of the actor as the last policy step left them (fp32, one row per workgroup). */
 const void* recnn_engine_buffer(recnn_engine* e, const char* name, int64_t* h_rows, int64_t* h_cols,
                                 int64_t* h_ld, int* h_is_f32);
 

@@ -104,7 +104,7 @@ class Sampler(C.Structure):
 TUNING_FIELDS = ("fused_mlp", "chain_target_critic", "bwd_panel", "policy_chain", "split_fwd", "cycle_min_len", "cycle_min_seg",
                  "frozen_fused", "frozen_gemm", "graph_run", "pregather", "defer_policy_fwd", "sampler_f32_rows", "dw_splits", "comm_fused",
                  "l1_big", "gemm_variant", "gemm_v0_threshold", "gemm_dma", "gemm_dma_depth", "gemm_dma_waves", "gemm_waves", "dw_dma", "x3_tail", "x3_fwd", "dw_fuse", "tail_half", "l1_ws", "frozen_half",
-                 "frozen_window", "run_align", "frozen_acts_policy_only", "gather_cycle")
+                 "frozen_window", "run_align", "frozen_acts_policy_only", "gather_cycle", "policy_fused")
 
 
 RUN_MAX = 64

@@ -21,6 +21,7 @@ ENV_FIELDS = {
     "RECNN_X3_TAIL": "x3_tail", "RECNN_X3_FWD": "x3_fwd", "RECNN_DW_FUSE": "dw_fuse", "RECNN_TAIL_HALF": "tail_half", "RECNN_L1_WS": "l1_ws", "RECNN_FROZEN_HALF": "frozen_half",
     "RECNN_FROZEN_WINDOW": "frozen_window", "RECNN_RUN_ALIGN": "run_align",
     "RECNN_FROZEN_ACTS_POLICY_ONLY": "frozen_acts_policy_only", "RECNN_GATHER_CYCLE": "gather_cycle",
+    "RECNN_POLICY_FUSED": "policy_fused",
 }
 # process-level settings of the peer communicators (shared by engines: not part of an engine's tuning) and debug hooks
 # (RECNN_COMM_MEMORY / RECNN_COMM_WORKGROUPS are read by each PeerComm for ITSELF: recnn_amd/parallel.py)

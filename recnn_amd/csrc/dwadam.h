@@ -29,3 +29,19 @@ int dwadam_init();
 // whether tensor `ti` of layout L can be a tile problem of this kernel at `rows` batch rows
 bool dwadam_tensor_ok(const NetLayout& L, int ti, int rows, int x3 = 0);
 int dwadam_launch(DwAdamBatch& b, int nnet, hipStream_t s);
+
+// ---- the gradient-only form (dw_grad_kernel): ONE network's three weight matrices, the same tiles and slab order, the summed tile
+// straight into the flat gradient arena; the biases' panel sums reduced as grad_reduce_kernel does.  For a network whose optimizer
+// cannot ride in the epilogue: the actor's clip quirk needs the whole gradient's L1 norm first.
+constexpr int DWGRAD_MAX_W = 3;
+struct DwGradNet {
+  NetLayout L;
+  ApplyArgs a;           // filled by dwgrad_launch: only g_out is read
+  DwAdamProb w[DWGRAD_MAX_W];   // launch order (tensors W1 / W2 / W3 of the layout, each once)
+  int rows;
+  int nsmall;
+  int ntile[DWGRAD_MAX_W];
+};
+// whether the layout's three matrices fit the tile plan at `rows` rows and its three biases are panel-summed small tensors
+bool dwgrad_ok(const NetLayout& L, int rows);
+int dwgrad_launch(DwGradNet& n, float* gflat, hipStream_t s);

@@ -26,6 +26,11 @@
 // swap places in rows 8..15 of every 16, so that the 8 rows x 32 B of a half-wave read fall on 64 different banks).
 // The tensors that are not tiled (b1, b2, w3, b3: 769 elements, panel sums from mlpt.hip) are updated by apply_body workgroups of the
 // same launch, first in the launch order.
+//
+// dw_grad_kernel: the same tiles for a network whose optimizer cannot ride in the epilogue -- the actor on a policy step, whose
+// clip_grad_norm_(-1, 1) (ddpg.py:92, td3.py:133) needs the L1 norm of the WHOLE gradient first.  The summed tile goes to the flat gradient
+// arena instead (tile_role<.., GRAD>), replacing gemm_dw_dma_kernel's slabs + grad_reduce_kernel bit for bit; l1_blocks_kernel and
+// apply_kernel follow (engine_plan.hip ph_policy, tuning.policy_fused bit 1).
 #include "dwadam.h"
 #include "optim_dev.h"
 #include "x3.h"
@@ -73,9 +78,10 @@ __device__ __forceinline__ bf16x8 x3_frag_z(const unsigned char* s, int col0, in
   return f.to_bf16x8();
 }
 
-// SPW = slabs per consumer wave (nslab / 8); X3: split-bf16 operands and shadows
-template <int SPW, bool X3>
-__device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& P, const int tile, unsigned char* lds, unsigned long long* trow) {
+// SPW = slabs per consumer wave (nslab / 8); X3: split-bf16 operands and shadows; GRAD: the gradient-only epilogue (dw_grad_kernel: the
+// summed tile goes to the flat gradient arena N.a.g_out, no optimizer state is read or written) on a DwGradNet
+template <int SPW, bool X3, bool GRAD = false, class NetT = DwAdamNet>
+__device__ __forceinline__ void tile_role(const NetT& N, const DwAdamProb& P, const int tile, unsigned char* lds, unsigned long long* trow) {
   const unsigned lds0 = (unsigned)(size_t)lds;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -204,12 +210,14 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
   // under a branch makes hipcc wait for it at the join (vmcnt(0) per pair: two serial memory latencies in front of the first stage)
   Pair e[2];
   const float* tsrc = a.tgt_p ? a.tgt_p : a.p;
+  if constexpr (!GRAD) {
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    e[h].p = *(const float2*)(a.p + idx[h]);
-    e[h].m = *(const float2*)(a.m + idx[h]);
-    e[h].v = *(const float2*)(a.v + idx[h]);
-    e[h].tp = *(const float2*)(tsrc + idx[h]);
+    for (int h = 0; h < 2; ++h) {
+      e[h].p = *(const float2*)(a.p + idx[h]);
+      e[h].m = *(const float2*)(a.m + idx[h]);
+      e[h].v = *(const float2*)(a.v + idx[h]);
+      e[h].tp = *(const float2*)(tsrc + idx[h]);
+    }
   }
   // everything the epilogue reads from the kernel-argument block, ONCE, into registers (read at their use sites these were 17 scalar
   // loads + waits and the optimizer arithmetic's branches waited on them: in-kernel trace, 3.4k clocks for four elements per thread)
@@ -230,9 +238,11 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
     a_sh = (bf16_t*)q6; a_tsh = (bf16_t*)q7;
   }
   // the step's optimizer scalars (an fp64 chain, optim.h): ONE wave evaluates them under the launch's first memory latency
-  if (cw == NC - 1) {
-    const OptScalars S = opt_scalars(a);
-    if (lane == 0) *(OptScalars*)(lds + SCAL_OFF) = S;
+  if constexpr (!GRAD) {
+    if (cw == NC - 1) {
+      const OptScalars S = opt_scalars(a);
+      if (lane == 0) *(OptScalars*)(lds + SCAL_OFF) = S;
+    }
   }
   TRACE_STAMP(trow, 1);
 
@@ -374,6 +384,12 @@ __device__ __forceinline__ void tile_role(const DwAdamNet& N, const DwAdamProb& 
       }
     }
   }
+  if constexpr (GRAD) {   // the finished sums, where grad_reduce_kernel would have put them
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      if (ok[h]) *(float2*)(a_g + idx[h]) = make_float2(g[2 * h], g[2 * h + 1]);
+    return;
+  }
   const OptScalars S = *(const OptScalars*)(lds + SCAL_OFF);
   const float gs = a_gs;
   float pn[4], tn4[4];
@@ -464,13 +480,46 @@ __global__ __launch_bounds__((NC + NL) * 64) void dw_adam_kernel(const DwAdamBat
   else tile_role<2, false>(N, P, tile, lds, trow);
 }
 
+// The same tiles with the gradient-only epilogue: one network's weight matrices (the actor's three on a policy step) summed over their
+// batch slabs in grad_reduce_kernel's order straight into the flat gradient arena -- no slabs in memory.  The tensors that are not tiled
+// (b1, b2, b3: panel column sums from the chain launch) are reduced by grad_reduce_kernel's own code in the launch's first workgroups.
+__global__ __launch_bounds__((NC + NL) * 64) void dw_grad_kernel(const DwGradNet N) {
+  const int nwg = N.nsmall + N.ntile[0] + N.ntile[1] + N.ntile[2];
+  if ((int)blockIdx.x >= nwg) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int lid = xcd_remap(blockIdx.x, nwg);
+  if (lid < N.nsmall) {
+    if (threadIdx.x >= 256) return;
+    __shared__ float sp[4][OPT_SMALL_ELEMS];
+    const int nb1 = N.L.t[2].blk0 - N.L.t[1].blk0, nb2 = N.L.t[4].blk0 - N.L.t[3].blk0;   // blocks of b1, b2; the rest: b3
+    int bt = lid, ti = 1;
+    if (bt >= nb1) {
+      bt -= nb1; ti = 3;
+      if (bt >= nb2) { bt -= nb2; ti = 5; }
+    }
+    const TensorSeg& T = N.L.t[ti];
+    const Own o = own_elems(T, bt);
+    float g[4];
+    slab_grads(T, bt, o, g, sp);
+    if (o.cnt) store_own(N.a.g_out + T.p_off + o.e, o, g);
+    return;
+  }
+  int tile = lid - N.nsmall, wi = 0;
+  while (wi < DWGRAD_MAX_W - 1 && tile >= N.ntile[wi]) { tile -= N.ntile[wi]; ++wi; }
+  const DwAdamProb& P = N.w[wi];
+  if (P.nslab == 8) tile_role<1, false, true>(N, P, tile, lds, nullptr);
+  else tile_role<2, false, true>(N, P, tile, lds, nullptr);
+}
+
 unsigned long long* g_dwadam_trace = nullptr;
 }  // namespace
 
 extern "C" void recnn_debug_dwadam_trace(void* p) { g_dwadam_trace = (unsigned long long*)p; }   // [workgroup][8] uint64 shader-clock stamps
 
 int dwadam_init() {
-  return recnn_check_hip(hipFuncSetAttribute((const void*)dw_adam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL), "dw_adam attr");
+  int rc = recnn_check_hip(hipFuncSetAttribute((const void*)dw_adam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL), "dw_adam attr");
+  if (!rc) rc = recnn_check_hip(hipFuncSetAttribute((const void*)dw_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL), "dw_grad attr");
+  return rc;
 }
 
 bool dwadam_tensor_ok(const NetLayout& L, int ti, int rows, int x3) {
@@ -526,4 +575,36 @@ int dwadam_launch(DwAdamBatch& b, int nnet, hipStream_t s) {
   }
   hipLaunchKernelGGL(dw_adam_kernel, dim3(maxwg, nnet), dim3((NC + NL) * 64), LDS_TOTAL, s, b, g_dwadam_trace);
   return recnn_check_hip(hipGetLastError(), "dw_adam_kernel");
+}
+
+bool dwgrad_ok(const NetLayout& L, int rows) {
+  for (int t = 0; t < 6; t += 2)
+    if (L.t[t].small || !L.t[t].vec4 || !L.t[t].gpart || !dwadam_tensor_ok(L, t, rows, 0)) return false;
+  for (int t = 1; t < 6; t += 2)
+    if (!L.t[t].small || L.t[t].pair || !L.t[t].gpart) return false;
+  return true;
+}
+
+int dwgrad_launch(DwGradNet& n, float* gflat, hipStream_t s) {
+  RECNN_REQUIRE(gflat && !((uintptr_t)gflat & 7), "dw_grad: the flat gradient arena must be 8-byte aligned");
+  RECNN_REQUIRE(dwgrad_ok(n.L, n.rows), "dw_grad: the network does not fit the tile plan at %d rows", n.rows);
+  memset(&n.a, 0, sizeof(n.a));
+  n.a.g_out = gflat;
+  for (int w = 0; w < DWGRAD_MAX_W; ++w) {
+    DwAdamProb& p = n.w[w];
+    RECNN_REQUIRE(p.tensor == 0 || p.tensor == 2 || p.tensor == 4, "dw_grad: problem %d names tensor %d", w, p.tensor);
+    for (int u = 0; u < w; ++u) RECNN_REQUIRE(n.w[u].tensor != p.tensor, "dw_grad: tensor %d twice", p.tensor);
+    const TensorSeg& T = n.L.t[p.tensor];
+    RECNN_REQUIRE(p.dz && p.x && p.ldz >= T.rows && p.ldx >= (T.cols + 63) / 64 * 64 && !(((uintptr_t)p.dz | (uintptr_t)p.x) & 15) &&
+                      p.ldz % 8 == 0 && p.ldx % 8 == 0 && (int64_t)n.rows * p.ldx * 2 < (1ll << 31),
+                  "dw_grad: bad operands");
+    p.nslab = T.nslab;
+    p.tiles_m = T.rows / 32;
+    p.tiles_n = (T.cols + 63) / 64;
+    n.ntile[w] = p.tiles_m * p.tiles_n;
+  }
+  n.nsmall = (n.L.t[2].blk0 - n.L.t[1].blk0) + (n.L.t[4].blk0 - n.L.t[3].blk0) + (n.L.nblk - n.L.t[5].blk0);
+  const int nwg = n.nsmall + n.ntile[0] + n.ntile[1] + n.ntile[2];
+  hipLaunchKernelGGL(dw_grad_kernel, dim3(nwg), dim3((NC + NL) * 64), LDS_TOTAL, s, n);
+  return recnn_check_hip(hipGetLastError(), "dw_grad_kernel");
 }

@@ -563,6 +563,7 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
       {"pc_h1", e->pc.h1, e->H, Hp, 0},            {"pc_h2", e->pc.h2, e->H, Hp, 0},
       {"dze2", e->dze2, e->H, Hp, 0},              {"dze1", e->dze1, e->H, Hp, 0},
       {"dzp2", e->dzp2, e->H, Hp, 0},              {"dzp1", e->dzp1, e->H, Hp, 0},            {"noise", e->noise_buf, e->A, e->A, 1},
+      {"actor_l1part", e->net[RECNN_NET_POLICY].l1part, 1, 1, 1},   // the clip quirk's |g| sum per optimizer workgroup of the last policy step
   };
   // cycle mode's arrays (all MSET_MAX * Bc rows; the two copies alternate between the segments of a run graph): the target actor's
   // output is the action slot of the packed next rows "cycle_xn<b>", or -- window mode, which has no such rows (NULL) -- its own array
@@ -590,6 +591,7 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
   for (const Ent& t : tab)
     if (!strcmp(t.n, name)) {
       if (rows) *rows = (!strcmp(name, "losses") || !strcmp(name, "clip_coef")) ? 1 : (!strcmp(name, "loss_ring") ? LOSS_RING : e->cfg.max_rows);
+      if (rows && !strcmp(name, "actor_l1part")) *rows = e->net[RECNN_NET_POLICY].n_rows_blk;
       if (cols) *cols = t.c;
       if (ld) *ld = t.l;
       if (is_f32) *is_f32 = t.f;

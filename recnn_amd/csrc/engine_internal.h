@@ -134,6 +134,7 @@ struct recnn_engine {
   float* noise_buf;                        // fp32 [Bc, A]
   float *expected, *target_q, *q[2], *delta[2], *qpi;
   bool panel_bwd_done = false;             // this step's critic head + dX ran in the bwd.hip launch
+  bool split_critics = false;              // this step's learning critics ran the split forward (l1gemm.hip + mlpt.hip)
   float* tc_part[2];                       // chained target critics: fp32 [Bc, 256] layer-1 state parts
   int32_t* tc_flag[2];                     // ... their per-panel completion flags
   float* tqv[2];

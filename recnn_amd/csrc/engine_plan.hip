@@ -460,6 +460,7 @@ extern "C" void recnn_engine_tuning_init(recnn_engine_tuning* t) {
   t->frozen_window = 1;
   t->run_align = 1; t->frozen_acts_policy_only = 1;
   t->gather_cycle = 1;
+  t->policy_fused = 3;
 }
 extern "C" int recnn_engine_set_tuning(recnn_engine* e, const recnn_engine_tuning* t) {
   RECNN_REQUIRE(e && t, "set_tuning: null pointer");
@@ -696,6 +697,7 @@ int ph_forward_split(recnn_engine* e, int rows, bool value_side, bool actor_side
     if (np && (rc = slot(e, "tail_actors", tfl, s, [&] { return mlpt_launch(tb, np, s); }))) return rc;
   }
   e->panel_bwd_done = false;
+  e->split_critics = false;
   e->unit_bwd = false;
   e->half_panels = false;
   if (!value_side) return 0;
@@ -748,6 +750,7 @@ int ph_forward_split(recnn_engine* e, int rows, bool value_side, bool actor_side
     if ((rc = slot(e, "tail_critic", tfl, s, [&] { return mlpt_launch(tb, np, s); }))) return rc;
   }
   e->panel_bwd_done = true;     // dz2 / dz1 (already times the per-row loss seed) and the small tensors' panel sums exist
+  e->split_critics = true;
   e->half_panels = half;
   return 0;
 }
@@ -839,6 +842,7 @@ int ph_forward_x3(recnn_engine* e, int rows, bool value_side, bool actor_side, b
     if ((rc = fwd_layer(e, rows, 3, net, nn, "fwd_l3_actors", s))) return rc;
   }
   e->panel_bwd_done = false;
+  e->split_critics = false;
   e->half_panels = false;
   e->unit_bwd = false;
   if (!value_side) return 0;
@@ -979,6 +983,7 @@ int ph_forward(recnn_engine* e, int rows, bool value_side, bool actor_side, bool
     }
   }
   e->panel_bwd_done = false;
+  e->split_critics = false;
   e->half_panels = false;
   e->unit_bwd = false;
   if (value_side && fwd_did_bwd) {
@@ -1084,8 +1089,19 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
     const double fl = fill_mlp(e, pcr, rows, &mb.p[0]);
     if ((rc = slot(e, "mlp_fwd_pcritic", fl, s, [&] { return mlp_launch(mb, 1, s); }))) return rc;
   } else {
-    if ((rc = fwd_layer(e, rows, 1, &pcr, 1, "fwd_l1_pcritic", s))) return rc;
-    if (use_dot) {            // the loss from the layer-2 epilogue's partial dots, into the step's pl_part slot
+    // tuning.policy_fused bit 0: layer 1 on the per-step tiled kernel wherever the step's learning critics ran on it (one problem of
+    // 64 x 64 tiles, the deferred forward's problem of the "l1_critic" launch on this step's batch: the same h1 bit for bit)
+    const bool l1_tiled = (e->tune.policy_fused & 1) && use_dot && !e->x3 && !e->comm && e->tune.policy_chain && e->split_critics &&
+                          e->tune.bwd_panel >= 2 && H % 8 == 0;
+    if (l1_tiled) {
+      L1Batch lb;
+      fill_l1(e, &lb.p[0], pcr, rows);
+      const double fl = 2.0 * rows * (double)H * (e->S + A);
+      if ((rc = slot(e, "l1_pcritic", fl, s, [&] { return l1gemm_launch(lb, 1, 0, s, e->tune.l1_ws); }))) return rc;
+    } else if ((rc = fwd_layer(e, rows, 1, &pcr, 1, "fwd_l1_pcritic", s))) {
+      return rc;
+    }
+    if (use_dot) {          // the loss from the layer-2 epilogue's partial dots, into the step's pl_part slot
       pcr.q = e->pl_part;
       if ((rc = fwd_layer(e, rows, 2, nullptr, 0, "fwd_l2_pcritic", s, &pcr, &e->pl_dot_parts))) return rc;
       if ((rc = note_policy_parts(e, e->run_off, e->pl_dot_parts))) return rc;
@@ -1156,6 +1172,21 @@ int ph_policy(recnn_engine* e, int rows, bool backward, bool with_l1, hipStream_
   if ((rc = dx1("dx_actor_l2", e->dzp2, Hp, Hp, POL, W2, H, e->dzp1, Hp, e->pa.h1, pn.gp[B1]))) return rc;
   }
   NetLayout L = make_layout(e, POL, rows);
+  // tuning.policy_fused bit 1: the three weight gradients without slabs -- dwadam.hip's tiles with a gradient-only epilogue sum the batch
+  // slices on chip in grad_reduce_kernel's order and write the flat gradient; the clip quirk's per-block |g| sums then come from that
+  // arena (l1_blocks_kernel: grad_reduce_kernel's block map and summation order).  Same eligibility as the row-panel chain above.
+  if ((e->tune.policy_fused & 2) && chain_done && !e->x3 && !e->comm && e->cfg.dtype == RECNN_BF16 && dwgrad_ok(L, rows)) {
+    DwGradNet n;
+    memset(&n, 0, sizeof(n));
+    n.L = L; n.rows = rows;
+    n.w[0].dz = e->dzp1; n.w[0].ldz = Hp; n.w[0].x = e->xcs + tc_off(e, A); n.w[0].ldx = e->ldx; n.w[0].tensor = W1;
+    n.w[1].dz = e->dzp2; n.w[1].ldz = Hp; n.w[1].x = e->pa.h1; n.w[1].ldx = Hp; n.w[1].tensor = W2;
+    n.w[2].dz = e->dag; n.w[2].ldz = Ap; n.w[2].x = e->pa.h2; n.w[2].ldx = Hp; n.w[2].tensor = W3;
+    const double fl = 2.0 * rows * ((double)H * e->S + (double)H * H + (double)A * H);
+    if ((rc = slot(e, "dwgrad_actor", fl, s, [&] { return dwgrad_launch(n, g_produce(e, RECNN_NET_POLICY), s); }))) return rc;
+    if (!with_l1) return 0;
+    return slot(e, "l1_norm_actor", 0, s, [&] { return l1_blocks_launch(L, g_produce(e, RECNN_NET_POLICY), pn.l1part, s); });
+  }
   {
     Group g(e, GEMM_DW, 0, 0);
     g.flops += fill_dw(e, g.add(), rows, e->dag, Ap, A, e->pa.h2, Hp, H, 0, pn.gp[W3], L.t[W3].nslab, L.t[W3].slab_stride);

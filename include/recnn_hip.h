@@ -1127,6 +1127,37 @@ int recnn_layernorm_rows_backward_workspace_bytes(int rows, int hidden, int64_t*
 int recnn_layernorm_rows_backward(const float* x, int rows, int hidden, const float* gamma, float eps, const float* g_out, float* d_x,
                                   float* d_gamma, float* d_beta, void* workspace, void* stream);
 
+/* Serving the two encoders above step by step (csrc/attn_dev.h): a per-session key/value cache and "append n steps".
+ * The cache of one attention layer is kv float[n_sessions, capacity, 2 hidden]: position p of a session holds [k_p | v_p] in slot
+ * p % capacity.  capacity is a multiple of 64; without a window a session holds at most capacity positions, with window = w the cache
+ * is a ring and capacity >= recnn_kv_min_capacity(w, n) = 64 ceil((w - 1) / 64) + 64 ceil((n + 63) / 64): the key tiles an append
+ * stages and the slots it writes then never share a slot (host-only; window, n >= 1).
+ * An append call extends n_rows DISTINCT sessions rows[i] (int32, in [0, n_sessions)) by n steps each, session i from its own position
+ * pos[i] (int32 >= 0: the number of positions it holds; without a window pos[i] + n <= capacity).  The caller owns pos: nothing on the
+ * device counts.  The call writes k and v of positions pos[i] .. pos[i] + n - 1 into the cache and returns rows pos[i] .. pos[i] + n - 1
+ * of the whole-history call over the session's pos[i] + n steps, BIT FOR BIT: the query blocks stay aligned to absolute multiples of 64,
+ * a key tile is staged from the cache with pos[i] + n in T's place, and every row-wise product is the whole-history kernel on n_rows n
+ * dense rows.  A staged row is a written, not yet overwritten position or zero: what other slots hold (stale rows, NaN) is never read.
+ * A session the checks above would refuse (row or pos out of range) is skipped on the device: nothing is written out of bounds.
+ * The new steps' inputs are given directly: items int32[n_rows, n] and ratings float[n_rows, n] are read as a store whose histories
+ * are the rows -- user_off int64[n_rows + 1] = {0, n, 2 n, ..}, slots int32[n_rows] = {0, 1, ..} -- so the input rows go down the
+ * gathered linear kernel's own chain (recnn_seq_embed with t0 = 0, T = n is the transformer's embedding of the new steps).
+ *   recnn_kv_append_workspace_bytes  round256(12 n_rows n hidden) (qkv) + 2 round256(4 n_rows n hidden) (o, u).  Host-only.
+ * recnn_attn_append: the layer of recnn_attn_encode; h_out float[n_rows, n, hidden].
+ * recnn_block_append: the block of recnn_block_forward on x float[n_rows, n, hidden] -> y (y must not be x); kv is this block's cache.
+ * Limits on hidden, n_heads, emb_dim, ffn, act, eps as in the whole-history calls; n_rows <= 65535, n_rows * n < 2^31; kv, table, the
+ * weight matrices, x, y, h_out and the workspace 16-byte aligned.  Errors: RECNN_E_INVALID with a message, before any launch. */
+int recnn_kv_min_capacity(int window, int n, int* capacity);
+int recnn_kv_append_workspace_bytes(int n_rows, int n, int hidden, int64_t* bytes);
+int recnn_attn_append(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_rows, int n,
+                      const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window, int alibi, const float* w_in,
+                      const float* b_in, const float* w_o, const float* b_o, float* kv, int n_sessions, int capacity, const int32_t* pos,
+                      const int32_t* rows, float* h_out, void* workspace, void* stream);
+int recnn_block_append(const float* x, int n_rows, int n, int hidden, int n_heads, int ffn, int act, int window, int alibi, float eps,
+                       const float* w_in, const float* b_in, const float* w_o, const float* b_o, const float* w1, const float* b1,
+                       const float* w2, const float* b2, const float* g1, const float* be1, const float* g2, const float* be2, float* kv,
+                       int n_sessions, int capacity, const int32_t* pos, const int32_t* rows, float* y, void* workspace, void* stream);
+
 /* =====================================================================================
  * 11. Offline ranking evaluation (csrc/rank.hip, csrc/topk.hip, csrc/evalrank.hip): where the item the user took
  *    next lands in the ranking a generated action induces over the catalogue, and the hit rate / NDCG / MRR of a batch of such ranks.

@@ -280,6 +280,10 @@ SIGNATURES = {
     "recnn_layernorm_rows": (_I, [_P, _I, _I, _P, _P, _F, _P, _P]),
     "recnn_layernorm_rows_backward_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),
     "recnn_layernorm_rows_backward": (_I, [_P, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P]),
+    "recnn_kv_min_capacity": (_I, [_I, _I, C.POINTER(_I)]),
+    "recnn_kv_append_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
+    "recnn_attn_append": (_I, [_P, _P, _P, _P, _I, _I, _P] + [_I] * 6 + [_P] * 5 + [_I, _I] + [_P] * 5),
+    "recnn_block_append": (_I, [_P] + [_I] * 8 + [_F] + [_P] * 13 + [_I, _I] + [_P] * 5),
     "recnn_dist_target_rank_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(_L)]),
     "recnn_dist_target_rank": (_I, [_P, _L, _I, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P]),
     "recnn_topk_target_rank_workspace_bytes": (_I, [_I, _I, C.POINTER(_L)]),

@@ -28,6 +28,9 @@
 //                    LDS; dV^T += dO^T P, dK^T += Q^T dS).  dqkv is written [U, T, 3H]; the weight gradients are the tile of
 //                    seq_dw_kernel (seq_grad.h) over segments of the call's samples, the parts added in order (attn_dw_kernel of attn_dev.h);
 //                    the table gradient is seq_grad.h's dX contraction and scatter-sum with da = dqkv.
+//   append           recnn_attn_append: the layer on the n new steps of sessions whose keys and values live in a KV cache;
+//                    the in-projection reads [n_rows, n] ids and ratings as a store whose histories are the rows, attn_dev.h's
+//                    attn_cache_kernel is the forward above with its key tiles staged from the cache.
 // Every sum has a fixed order that depends on nothing but (t, j): equal calls give equal bits, a user's bits do not depend on the batch,
 // and h[:, :a] of a longer call equals the shorter call's.
 #include "attn_dev.h"
@@ -146,6 +149,56 @@ extern "C" int recnn_attn_encode(const int32_t* items, const float* ratings, con
                                  void* workspace, void* stream) {
   return attn_encode_impl("attn_encode", items, ratings, user_off, slots, n_users, t0, T, table, n_items, emb_dim, hidden, n_heads, window,
                           alibi, w_in, b_in, w_o, b_o, h_out, workspace, stream);
+}
+
+extern "C" int recnn_kv_min_capacity(int window, int n, int* capacity) {
+  const char* what = "kv_min_capacity";
+  RECNN_REQUIRE(capacity, "%s: null pointer", what);
+  RECNN_REQUIRE(window >= 1 && window < AT_NO_WINDOW && n >= 1 && n < AT_NO_WINDOW, "%s: need window and n in 1 .. 2^30 - 1 (got window=%d, n=%d)",
+                what, window, n);
+  *capacity = kv_min_capacity(window, n);
+  return 0;
+}
+
+extern "C" int recnn_kv_append_workspace_bytes(int n_rows, int n, int hidden, int64_t* bytes) {
+  const char* what = "kv_append_workspace_bytes";
+  RECNN_REQUIRE(bytes, "%s: null pointer", what);
+  RECNN_REQUIRE(hidden >= 16 && hidden % 16 == 0 && hidden <= 256, "%s: hidden must be a multiple of 16 up to 256 (got %d)", what, hidden);
+  RECNN_REQUIRE(n >= 1 && n_rows >= 0 && n_rows <= 65535 && (int64_t)n_rows * n < (1LL << 31),
+                "%s: need n >= 1, n_rows in 0 .. 65535 and n_rows * n < 2^31 (got n_rows=%d, n=%d)", what, n_rows, n);
+  *bytes = append_ws(n_rows, n, hidden).total;
+  return 0;
+}
+
+extern "C" int recnn_attn_append(const int32_t* items, const float* ratings, const int64_t* user_off, const int32_t* slots, int n_rows,
+                                 int n, const float* table, int n_items, int emb_dim, int hidden, int n_heads, int window, int alibi,
+                                 const float* w_in, const float* b_in, const float* w_o, const float* b_o, float* kv, int n_sessions,
+                                 int capacity, const int32_t* pos, const int32_t* rows, float* h_out, void* workspace, void* stream) {
+  const char* what = "attn_append";
+  RECNN_REQUIRE(store_ok(items, ratings, user_off, slots, table) && w_in && b_in && w_o && b_o && h_out && workspace, "%s: null pointer", what);
+  RECNN_ATTN_DIMS_OK(what, emb_dim, hidden, n_heads);
+  RECNN_KV_CACHE_OK(what, n_rows, n, n_sessions, capacity, window, kv, pos, rows);
+  RECNN_REQUIRE(n_items > 0, "%s: need n_items > 0", what);
+  RECNN_REQUIRE(aligned16(table, w_o, h_out, workspace), "%s: table, w_o, h_out and the workspace must be 16-byte aligned", what);
+  if (n_rows == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  const AppendWs w = append_ws(n_rows, n, hidden);
+  char* ws = (char*)workspace;
+  float* qkv = (float*)(ws + w.qkv);
+  float* o = (float*)(ws + w.o);
+  LinArgs l{};
+  l.s = SeqStore{items, ratings, user_off, slots, n_rows, table, n_items, emb_dim};
+  l.t0 = 0; l.T = n; l.rows = n_rows * n;
+  l.K = emb_dim; l.w = w_in; l.ldw = emb_dim + 1; l.b = b_in;
+  l.out = qkv; l.N = 3 * hidden;
+  if (int rc = launch_linear(l, s)) return rc;
+  launch_cache_attention(qkv, o, n_rows, n, hidden, n_heads, window, alibi, kv, n_sessions, capacity, pos, rows, s);
+  DenseLinArgs p{};
+  p.rows = n_rows * n; p.K = hidden; p.N = hidden;
+  p.x = o; p.w = w_o; p.ldw = hidden; p.b = b_o;
+  p.out = h_out;
+  if (int rc = launch_dense_linear(p, false, s)) return rc;
+  return recnn_check_hip(hipGetLastError(), what);
 }
 
 extern "C" int recnn_attn_train_workspace_bytes(int n_users, int T, int hidden, int emb_dim, int n_heads, int64_t* saved_bytes,

@@ -1,7 +1,7 @@
 // attn_dev.h -- the device half of the causal self-attention encoder, shared by attn.hip (the layer over the store)
 // and block.hip (the same layer on a dense [U, T, H] input inside a transformer block): the two 64-row linear kernels, the
-// attention kernels with their arguments, the segmented weight-gradient tile, the workspace layouts and the launchers.  attn.hip
-// describes the layer and the attention kernels.
+// attention kernels with their arguments, the attention of appended steps over a per-session KV cache, the segmented
+// weight-gradient tile, the workspace layouts and the launchers.  attn.hip describes the layer and the attention kernels.
 //
 //   linear kernels   out[s, n] = b[n] + sum_k x[s, k] w[n, k] for 64 rows s per workgroup, one fixed-order chain per element on the
 //                    exact-f32 MFMA: the bias first, then k upwards in blocks of 16, MFMA e = 0 .. 3 inside a block.  Two kernels:
@@ -489,6 +489,160 @@ __global__ __launch_bounds__(256) void attn_key_kernel(const AttnArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ attention over the KV cache
+// The step-by-step path: a call appends n steps to each of R sessions; session u of the call extends cache row rows[u]
+// from its own position pos[u].  The cache row holds [k | v] (2H floats) per position, position p in slot p % cap; cap is a multiple
+// of 64, so a 64-aligned tile of positions is 64 consecutive slots.
+struct AttnCacheArgs {
+  int R, n, H, heads, window;       // window: 1 .. AT_NO_WINDOW
+  float scale;
+  float slope[AT_MAXHEADS];
+  const float* qkv;                 // [R][n][3H]: the new rows' in-projection (q is read here; k and v from the cache)
+  float* kv;                        // [n_sessions][cap][2H]
+  int n_sessions, cap, ring;        // ring: a position past cap wraps (the encoder has a window); else pos + n <= cap
+  const int32_t* pos;               // [R]
+  const int32_t* rows;              // [R]
+  float* o;                         // [R][n][H]
+};
+constexpr int AT_NO_WINDOW = 1 << 30;
+
+// a session the host's checks would have refused writes and reads nothing
+__device__ __forceinline__ bool cache_row_ok(const AttnCacheArgs& a, int row, int pos) {
+  return (unsigned)row < (unsigned)a.n_sessions && pos >= 0 && pos <= AT_NO_WINDOW && (a.ring || pos + a.n <= a.cap);
+}
+
+// the k and v columns of the new rows go to their slots: 16-byte vector stores, one thread per chunk
+__global__ __launch_bounds__(256) void kv_scatter_kernel(const AttnCacheArgs a) {
+  const int C4 = a.H >> 1;          // 2H / 4
+  const int64_t total = (int64_t)a.R * a.n * C4;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int64_t s = idx / C4;
+    const int c = (int)(idx - s * C4), u = (int)(s / a.n), j = (int)(s - (int64_t)u * a.n);
+    const int row = a.rows[u], pos = a.pos[u];
+    if (!cache_row_ok(a, row, pos)) continue;
+    const int slot = (pos + j) % a.cap;
+    *(float4*)(a.kv + ((int64_t)row * a.cap + slot) * 2 * a.H + 4 * c) = *(const float4*)(a.qkv + s * 3 * a.H + a.H + 4 * c);
+  }
+}
+
+// The forward of attn_query_kernel<D, 0> for the new rows of a session: query blocks stay aligned to ABSOLUTE positions (grid x runs
+// over the 64-aligned blocks [pos, pos + n) touches, the heaviest first; a lane is live iff pos <= tq < pos + n), the key tiles
+// tile_lo .. qb are staged from the cache with pos + n in T's place, and the score / softmax / P V code below is that kernel's, line
+// for line: a live lane computes the chain it computes in a whole-history call of pos + n steps.  A staged row is a live position or
+// zero -- a slot nothing has written, or one that holds an overwritten position, is never read (DESIGN.md 31 derives the ring size that
+// guarantees it), so stale or NaN bits never reach an MFMA.  The next tile's loads are in flight while the current one is computed
+// (at n = 1 the kernel is a stream over the session's keys and values: one workgroup per (session, head), 64 positions per stage).
+template <int D>
+__global__ __launch_bounds__(256) void attn_cache_kernel(const AttnCacheArgs a) {
+  constexpr int LD = D + AT_PAD, DT = D / 16, C4 = D / 4;
+  __shared__ __attribute__((aligned(16))) float Ks[AT_Q * LD];
+  __shared__ __attribute__((aligned(16))) float Vs[AT_Q * LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int head = blockIdx.y, u = blockIdx.z;
+  const int row = a.rows[u], pos = a.pos[u];
+  if (!cache_row_ok(a, row, pos)) return;
+  const int T = pos + a.n, H = a.H, H3 = 3 * H, w = a.window;
+  const int qb = (T - 1) / AT_Q - (int)blockIdx.x;
+  if (qb < pos / AT_Q) return;                         // (uniform over the workgroup: before any barrier)
+  const int q0 = qb * AT_Q, tq = q0 + 16 * wave + r;   // the lane's query, an absolute position
+  const bool qlive = tq >= pos && tq < T;
+  const float* qrow = a.qkv + ((int64_t)u * a.n + (tq - pos)) * H3 + head * D;
+  const float* kbase = a.kv + (int64_t)row * a.cap * 2 * H + head * D;
+  const float slope = a.slope[head], scale = a.scale;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 qf[DT];
+#pragma unroll
+  for (int kb = 0; kb < DT; ++kb) qf[kb] = qlive ? *(const f32x4*)(qrow + 16 * kb + 4 * g) : zero4;
+  f32x4 oacc[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) oacc[dt] = zero4;
+  float m = neg_inf(), l = 0.f;
+  const int tq_lo = q0 + 16 * wave, tq_hi = tq_lo + 15;
+  const int tile_lo = max(0, q0 - w + 1) / AT_Q;
+
+  float4 kr[DT], vr[DT];            // the tile in flight: chunk tid + 256 i of its [64][D / 4] chunks
+  auto fetch = [&](int kt) {
+    const int k0 = kt * AT_Q;
+    const float* src = kbase + (int64_t)(k0 % a.cap) * 2 * H;
+#pragma unroll
+    for (int i = 0; i < DT; ++i) {
+      const int idx = tid + 256 * i, rw = idx / C4, c = idx - rw * C4;
+      const bool in = k0 + rw < T;
+      kr[i] = in ? *(const float4*)(src + (int64_t)rw * 2 * H + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      vr[i] = in ? *(const float4*)(src + (int64_t)rw * 2 * H + H + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  fetch(tile_lo);
+  for (int kt = tile_lo; kt <= qb; ++kt) {
+    const int k0 = kt * AT_Q;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < DT; ++i) {
+      const int idx = tid + 256 * i, rw = idx / C4, c = idx - rw * C4;
+      *(float4*)(Ks + rw * LD + 4 * c) = kr[i];
+      *(float4*)(Vs + rw * LD + 4 * c) = vr[i];
+    }
+    __syncthreads();
+    if (kt < qb) fetch(kt + 1);
+    if (k0 > tq_hi || k0 + AT_Q - 1 < tq_lo - w + 1) continue;      // nothing of the tile is in the wave's reach (wave-uniform)
+    f32x4 s[4] = {zero4, zero4, zero4, zero4};
+#pragma unroll
+    for (int kb = 0; kb < DT; ++kb) {
+      f32x4 kf[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) kf[c] = *(const f32x4*)(Ks + (16 * c + r) * LD + 16 * kb + 4 * g);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[c][e], qf[kb][e], s[c], 0, 0, 0);
+    }
+    // s[c][i]: key k0 + 16 c + 4 g + i against query tq
+    float tmax = neg_inf();
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int dist = tq - (k0 + 16 * c + 4 * g + i);
+        const bool valid = dist >= 0 && dist < w;
+        const float sc = valid ? fmaf(-slope, (float)dist, s[c][i] * scale) : neg_inf();
+        s[c][i] = sc;
+        tmax = fmaxf(tmax, sc);
+      }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m, tmax);
+    const float m_use = m_new == neg_inf() ? 0.f : m_new;
+    const float alpha = expf(m - m_use);
+    float psum = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float p = expf(s[c][i] - m_use);
+        s[c][i] = p;
+        psum += p;
+      }
+    psum = fold4(psum);
+    l = fmaf(l, alpha, psum);
+    m = m_new;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) oacc[dt] *= alpha;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+          oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Vs[(16 * c + 4 * g + e) * LD + 16 * dt + r], s[c][e], oacc[dt], 0, 0, 0);
+  }
+  if (!qlive) return;
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+    *(f32x4*)(a.o + ((int64_t)u * a.n + (tq - pos)) * H + head * D + 16 * dt + 4 * g) = oacc[dt] * inv;
+}
+
 // ------------------------------------------------------------------------------------------------ weight gradients
 // dW[m, n] = sum_s da[s, m] X[s, n] over the call's samples s = u T + t: the tile of seq_dw_kernel (seq_grad.h: 64 x 64 of dW per
 // workgroup, 16 samples per LDS stage, exact-f32 MFMA, the rating column and db as plain sums of the same stage) with one more grid
@@ -680,6 +834,55 @@ void launch_key(const AttnArgs& a, hipStream_t s) {
     default: hipLaunchKernelGGL((attn_key_kernel<64>), grid, dim3(256), 0, s, a); break;
   }
 }
+// The append path.  What one append call keeps in its workspace: the new rows' qkv, o and (inside a block) u.
+struct AppendWs {
+  int64_t qkv, o, u, total;
+};
+inline AppendWs append_ws(int R, int n, int H) {
+  const int64_t M = (int64_t)R * n;
+  AppendWs w;
+  w.qkv = 0;
+  w.o = scatter_index_round(M * 3 * H * 4);
+  w.u = w.o + scatter_index_round(M * H * 4);
+  w.total = w.u + scatter_index_round(M * H * 4);
+  return w;
+}
+// the smallest ring that keeps every staged position apart from every slot the append writes: the key tiles of the first query block
+// q0 = 64 floor(pos / 64) start at q0 - 64 ceil((w - 1) / 64), and the last written position is at most q0 + 63 + n - 1
+inline int kv_min_capacity(int window, int n) { return 64 * ((window - 1 + 63) / 64) + 64 * ((n + 63 + 63) / 64); }
+
+#define RECNN_KV_CACHE_OK(what, n_rows, n, n_sessions, capacity, window, kv, pos, rows)                                              \
+  RECNN_REQUIRE(kv && pos && rows, "%s: null pointer (kv, pos, rows)", what);                                                        \
+  RECNN_REQUIRE(n >= 1 && n_rows >= 0 && n_rows <= 65535 && (int64_t)n_rows * n < (1LL << 31),                                       \
+                "%s: need n >= 1, n_rows in 0 .. 65535 and n_rows * n < 2^31 (got n_rows=%d, n=%d)", what, n_rows, n);               \
+  RECNN_REQUIRE(n_sessions >= n_rows, "%s: n_rows=%d distinct rows do not fit n_sessions=%d", what, n_rows, n_sessions);             \
+  RECNN_REQUIRE(capacity >= 64 && capacity % 64 == 0, "%s: capacity must be a positive multiple of 64 (got %d)", what, capacity);   \
+  RECNN_REQUIRE(window >= 0 && window < AT_NO_WINDOW, "%s: window must be in 0 .. 2^30 - 1 (0: none), got %d", what, window);        \
+  RECNN_REQUIRE(n <= capacity && (window == 0 || capacity >= kv_min_capacity(window, n)),                                            \
+                "%s: capacity=%d is too small for window=%d and n=%d (a ring needs %d; without a window n <= capacity)", what,       \
+                capacity, window, n, window ? kv_min_capacity(window, n) : n);                                                       \
+  RECNN_REQUIRE(aligned16(kv), "%s: kv must be 16-byte aligned", what)
+
+// k and v of the new rows into the cache, then the attention of the new rows over it: qkv [R][n][3H] -> o [R][n][H]
+void launch_cache_attention(const float* qkv, float* o, int R, int n, int H, int heads, int window, int alibi, float* kv, int n_sessions,
+                            int cap, const int32_t* pos, const int32_t* rows, hipStream_t s) {
+  const AttnArgs base = attn_args(R, n, H, heads, 0, alibi);      // scale and slopes as in the whole-history call
+  AttnCacheArgs a{};
+  a.R = R; a.n = n; a.H = H; a.heads = heads;
+  a.window = window > 0 ? window : AT_NO_WINDOW;
+  a.scale = base.scale;
+  for (int h = 0; h < AT_MAXHEADS; ++h) a.slope[h] = base.slope[h];
+  a.qkv = qkv; a.kv = kv; a.n_sessions = n_sessions; a.cap = cap; a.ring = window > 0;
+  a.pos = pos; a.rows = rows; a.o = o;
+  hipLaunchKernelGGL(kv_scatter_kernel, dim3(grid_for((int64_t)R * n * (H >> 1), 256, 2048)), dim3(256), 0, s, a);
+  const dim3 grid((n + AT_Q - 2) / AT_Q + 1, heads, R);            // the 64-aligned blocks n consecutive positions can touch
+  switch (H / heads) {
+    case 16: hipLaunchKernelGGL((attn_cache_kernel<16>), grid, dim3(256), 0, s, a); break;
+    case 32: hipLaunchKernelGGL((attn_cache_kernel<32>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((attn_cache_kernel<64>), grid, dim3(256), 0, s, a); break;
+  }
+}
+
 int launch_linear(const LinArgs& l, hipStream_t s) {
   const size_t lds = lin_lds(l.K);
   if (int rc = raise_lds(attn_linear_kernel, lds)) return rc;

@@ -20,6 +20,9 @@
 //                    samples; products with a transposed weight run the linear kernel over a transposed copy; the LayerNorm backward
 //                    is row-wise with the forward's lane layout and also sums, per 64 rows, the columns of dn xhat and dn -- those
 //                    parts are added in groups of 64 consecutive workgroups and then group after group (no atomics, one order).
+//   append           recnn_block_append: the block on the n new steps of sessions whose keys and values live in a KV cache
+//                    -- the forward's launches on R n dense rows, attn_dev.h's attention over the cache, and for few rows the
+//                    feed-forward in 16-row workgroups (blk_ffn_rows16_kernel: the same element chains).
 // Every sum has a fixed order that depends on nothing but the row's own data and (t, j): equal calls give equal bits, a user's bits
 // do not depend on the batch, and h[:, :a] of a longer call equals the shorter call's.
 #include "attn_dev.h"
@@ -126,6 +129,110 @@ __global__ __launch_bounds__(256) void blk_ffn_kernel(const FfnArgs a) {
         const int s = s0 + 16 * mt + 4 * g + i;
         if (s < a.rows) a.y[(int64_t)s * H + col] = a.u[(int64_t)s * H + col] + acc[j][mt][i];
       }
+  }
+}
+
+// The feed-forward for FEW rows (the append path, DESIGN.md 31: R n rows, often 25): blk_ffn_kernel's element chains in another
+// distribution of the work.  With one workgroup per 64 rows, 25 rows are ONE workgroup that walks F in 32 chunks, each a serial run of
+// dependent weight loads.  Here a workgroup owns 16 rows (one MFMA row tile) and walks F in chunks of 128: wave w computes column tiles
+// 2 w and 2 w + 1 of the chunk's a = W_1 n + b_1 (bias first, k upwards), act(a) goes to a [16][128] tile in LDS, and that tile feeds y's
+// accumulators (wave w owns column tiles w, w + 4, .. of H), k upwards inside the chunk and chunk after chunk.  Every element of a and
+// of y is the same chain of the same MFMAs as in blk_ffn_kernel -- the bias, then f = 0, 1, .. in blocks of 16, e = 0 .. 3 inside a
+// block, the residual last -- so the bits are that kernel's (tests/test_gpu_kv_cache.py compares them on both sides of FFN_FEW_ROWS).
+constexpr int FFR = 16;             // rows per workgroup
+constexpr int FFR_C = 128;          // columns of F per chunk
+constexpr int FFR_LD = FFR_C + AT_PAD;
+constexpr int FFN_FEW_ROWS = 4096;  // up to here the append path runs this kernel: 256 workgroups
+inline size_t ffn_rows16_lds(int H) { return (size_t)FFR * (H + AT_PAD + FFR_LD) * sizeof(float); }
+
+// grid ceil(rows / 16), 256 threads; a.a1 is not written (no backward follows an append)
+__global__ __launch_bounds__(256) void blk_ffn_rows16_kernel(const FfnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int H = a.H, F = a.F, ldx = H + AT_PAD, C4 = H >> 2;
+  float* xs = smem;                 // [16][ldx]: LN2(u)
+  float* hs = xs + FFR * ldx;       // [16][FFR_LD]: act(a) of the chunk
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int s0 = blockIdx.x * FFR;
+  const int ntiles = H >> 4;
+  for (int idx = tid; idx < FFR * C4; idx += 256) {
+    const int row = idx / C4, c = idx - row * C4, s = s0 + row;
+    *(float4*)(xs + row * ldx + 4 * c) = s < a.rows ? *(const float4*)(a.u + (int64_t)s * H + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  __syncthreads();
+  if (tid < 4 * FFR) ln_rows(xs, ldx, H, a.gamma, a.beta, a.eps, tid);      // (all of wave 0: row tid >> 2, lane tid & 3 of its four)
+  __syncthreads();
+  f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float bias = wave + 4 * j < ntiles ? a.b2[(wave + 4 * j) * 16 + r] : 0.f;
+    acc[j] = f32x4{bias, bias, bias, bias};
+  }
+  for (int f0 = 0; f0 < F; f0 += FFR_C) {
+    f32x4 t[2];
+    bool on[2];
+    const float* wrow[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int col = f0 + 16 * (2 * wave + c) + r;
+      on[c] = f0 + 16 * (2 * wave + c) < F;                       // F is a multiple of 16: a tile is whole or absent (wave-uniform)
+      const float bias = on[c] ? a.b1[col] : 0.f;
+      t[c] = f32x4{bias, bias, bias, bias};
+      wrow[c] = a.w1 + (int64_t)(on[c] ? col : 0) * H;
+    }
+    if (on[0]) {                                                  // (an absent tile reads row 0 of W_1 and is dropped below)
+      f32x4 b0 = *(const f32x4*)(wrow[0] + 4 * g), b1 = *(const f32x4*)(wrow[1] + 4 * g);
+      for (int k0 = 0; k0 < H; k0 += 16) {
+        const int kn = k0 + 16 < H ? k0 + 16 : k0;                // the next block's weights are in flight under this block's products
+        const f32x4 n0 = *(const f32x4*)(wrow[0] + kn + 4 * g), n1 = *(const f32x4*)(wrow[1] + kn + 4 * g);
+        const f32x4 av = *(const f32x4*)(xs + r * ldx + k0 + 4 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          t[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], b0[e], t[0], 0, 0, 0);
+          t[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], b1[e], t[1], 0, 0, 0);
+        }
+        b0 = n0;
+        b1 = n1;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) hs[(4 * g + i) * FFR_LD + 16 * (2 * wave + c) + r] = on[c] ? act_fwd(t[c][i], a.act) : 0.f;
+    __syncthreads();
+    const int kw = min(FFR_C, F - f0);
+    const float* w2row[4];
+    f32x4 bv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int tile = wave + 4 * j < ntiles ? wave + 4 * j : 0;        // (an absent tile reads tile 0 of W_2 and is not stored)
+      w2row[j] = a.w2 + (int64_t)(tile * 16 + r) * F + f0 + 4 * g;
+      bv[j] = *(const f32x4*)w2row[j];
+    }
+    for (int k0 = 0; k0 < kw; k0 += 16) {
+      const int kn = k0 + 16 < kw ? k0 + 16 : k0;
+      f32x4 nv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) nv[j] = *(const f32x4*)(w2row[j] + kn);
+      const f32x4 av = *(const f32x4*)(hs + r * FFR_LD + k0 + 4 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[j][e], acc[j], 0, 0, 0);
+        bv[j] = nv[j];
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (wave + 4 * j >= ntiles) continue;
+    const int col = (wave + 4 * j) * 16 + r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = s0 + 4 * g + i;
+      if (s < a.rows) a.y[(int64_t)s * H + col] = a.u[(int64_t)s * H + col] + acc[j][i];
+    }
   }
 }
 
@@ -528,6 +635,50 @@ extern "C" int recnn_block_forward(const float* x, int n_users, int T, int hidde
                                    const float* be2, float* y, void* workspace, void* stream) {
   return block_forward_impl("block_forward", x, n_users, T, hidden, n_heads, ffn, act, window, alibi, eps,
                             BlockParams{w_in, b_in, w_o, b_o, w1, b1, w2, b2, g1, be1, g2, be2}, y, workspace, false, stream);
+}
+
+// One block on the n new steps of n_rows sessions: recnn_block_forward's launches on x [n_rows, n, hidden], with the
+// attention reading its keys and values from this layer's cache `kv`, which first receives the new rows' k and v.
+extern "C" int recnn_block_append(const float* x, int n_rows, int n, int hidden, int n_heads, int ffn, int act, int window, int alibi,
+                                  float eps, const float* w_in, const float* b_in, const float* w_o, const float* b_o, const float* w1,
+                                  const float* b1, const float* w2, const float* b2, const float* g1, const float* be1, const float* g2,
+                                  const float* be2, float* kv, int n_sessions, int capacity, const int32_t* pos, const int32_t* rows,
+                                  float* y, void* workspace, void* stream) {
+  const char* what = "block_append";
+  const BlockParams p{w_in, b_in, w_o, b_o, w1, b1, w2, b2, g1, be1, g2, be2};
+  RECNN_REQUIRE(x && y && workspace && p.all(), "%s: null pointer", what);
+  RECNN_BLOCK_DIMS_OK(what, hidden, n_heads, ffn, act, eps);
+  RECNN_KV_CACHE_OK(what, n_rows, n, n_sessions, capacity, window, kv, pos, rows);
+  RECNN_REQUIRE(x != y, "%s: y must not be x", what);
+  RECNN_REQUIRE(aligned16(x, y, workspace, p.w_in, p.w_o, p.w1, p.w2), "%s: x, y, the weights and the workspace must be 16-byte aligned", what);
+  if (n_rows == 0) return 0;
+  const hipStream_t s = (hipStream_t)stream;
+  const int H = hidden, M = n_rows * n;
+  const AppendWs w = append_ws(n_rows, n, H);
+  char* ws = (char*)workspace;
+  float* qkv = (float*)(ws + w.qkv);
+  float* o = (float*)(ws + w.o);
+  float* u = (float*)(ws + w.u);
+  DenseLinArgs l{};
+  l.rows = M; l.K = H; l.N = 3 * H; l.x = x; l.w = p.w_in; l.ldw = H; l.b = p.b_in;
+  l.gamma = p.g1; l.beta = p.be1; l.eps = eps; l.out = qkv;
+  if (int rc = launch_dense_linear(l, true, s)) return rc;
+  launch_cache_attention(qkv, o, n_rows, n, H, n_heads, window, alibi, kv, n_sessions, capacity, pos, rows, s);
+  DenseLinArgs ol{};
+  ol.rows = M; ol.K = H; ol.N = H; ol.x = o; ol.w = p.w_o; ol.ldw = H; ol.b = p.b_o; ol.res = x; ol.out = u;
+  if (int rc = launch_dense_linear(ol, false, s)) return rc;
+  FfnArgs f{};
+  f.rows = M; f.H = H; f.F = ffn; f.act = act; f.u = u;
+  f.w1 = p.w1; f.b1 = p.b1; f.w2 = p.w2; f.b2 = p.b2; f.gamma = p.g2; f.beta = p.be2; f.eps = eps;
+  f.y = y;
+  if (M <= FFN_FEW_ROWS) {
+    hipLaunchKernelGGL(blk_ffn_rows16_kernel, dim3((M + FFR - 1) / FFR), dim3(256), ffn_rows16_lds(H), s, f);
+  } else {
+    const size_t lds = ffn_lds(H);
+    if (int rc = raise_lds(blk_ffn_kernel, lds)) return rc;
+    hipLaunchKernelGGL(blk_ffn_kernel, dim3((M + LIN_ROWS - 1) / LIN_ROWS), dim3(256), lds, s, f);
+  }
+  return recnn_check_hip(hipGetLastError(), what);
 }
 
 extern "C" int recnn_block_train_workspace_bytes(int n_users, int T, int hidden, int n_heads, int ffn, int64_t* saved_bytes,

@@ -2005,17 +2005,45 @@ _ATTN_PARAMS = ("in_proj_weight", "in_proj_bias", "out_proj.weight", "out_proj.b
 def _attn_call_args(name, enc, store, table, slots, T, t0):
     """The checks of `attn_encode` / `attn_encode_train`, on the host and by argument name, before any launch:
     (dev, E, H, U, T, t0, slots, params)."""
+    params, shapes_of = _attn_spec(name, enc)
+    return _attn_checked(name, enc, _ATTN_PARAMS, params, shapes_of, "in_proj_weight", store, table, slots, T, t0)
+
+
+def _attn_spec(name, enc):
+    """(params, shapes_of) of an `AttentionEncoder`; another module is refused by name."""
     if not isinstance(enc, AttentionEncoder):
         t = type(enc)
         raise L.RecnnHipError(f"{name}: the state encoder is a {t.__module__}.{t.__qualname__}, not a recnn_amd.nn.AttentionEncoder "
                               "(a torch.nn.LSTM goes to lstm_encode, a torch.nn.GRU to gru_encode)")
     params = (enc.in_proj_weight, enc.in_proj_bias, enc.out_proj.weight, enc.out_proj.bias)
-    return _attn_checked(name, enc, _ATTN_PARAMS, params, lambda E, H: ((3 * H, E + 1), (3 * H,), (H, H), (H,)), "in_proj_weight",
-                         store, table, slots, T, t0)
+    return params, lambda E, H: ((3 * H, E + 1), (3 * H,), (H, H), (H,))
 
 
 def _attn_checked(name, enc, pnames, params, shapes_of, first, store, table, slots, T, t0):
     """The checks that `AttentionEncoder` and `TransformerStateEncoder` share: (dev, E, H, U, T, t0, slots, params)."""
+    dev, E, H = _attn_module_checked(name, enc, pnames, params, shapes_of, table)
+    slots = store.checked_slots(slots, name, dev)
+    U, T, t0 = len(slots), int(T), int(t0)
+    if T < 1 or t0 < 0:
+        raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
+    if U * T >= 1 << 31 or U > 65535:
+        raise ValueError(f"{name}: U * T = {U * T} must stay below 2^31 and U = {U} below 65536")
+    if U and int(store.lengths[slots].min()) < t0 + T:
+        raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
+    _module_on_gpu(name, params, first, dev)
+    if table.device != dev:
+        raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
+    return dev, E, H, U, T, t0, slots, params
+
+
+def _module_on_gpu(name, params, first, dev):
+    if not params[0].is_cuda:
+        raise L.RecnnHipError(f"{name}: the module lives on {dev} ({first}.device); it needs a GPU module "
+                              "(recnn_amd has no CPU fallback)")
+
+
+def _attn_module_checked(name, enc, pnames, params, shapes_of, table):
+    """What `_attn_checked` asks of the module and the table alone (the append calls ask the same): (dev, E, H)."""
     dev = params[0].device
     for pname, p in zip(pnames, params):
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
@@ -2038,20 +2066,7 @@ def _attn_checked(name, enc, pnames, params, shapes_of, first, store, table, slo
         raise L.RecnnHipError(f"{name}: window={enc.window} must be at least 1 (or None)")
     if any(tuple(p.shape) != shape for p, shape in zip(params, shapes_of(E, H))):
         raise L.RecnnHipError(f"{name}: the parameters do not have the shapes of hidden_size={H}, input_size={E + 1}")
-    slots = store.checked_slots(slots, name, dev)
-    U, T, t0 = len(slots), int(T), int(t0)
-    if T < 1 or t0 < 0:
-        raise ValueError(f"{name}: need T >= 1 and t0 >= 0 (got T={T}, t0={t0})")
-    if U * T >= 1 << 31 or U > 65535:
-        raise ValueError(f"{name}: U * T = {U * T} must stay below 2^31 and U = {U} below 65536")
-    if U and int(store.lengths[slots].min()) < t0 + T:
-        raise ValueError(f"{name}: steps {t0} .. {t0 + T - 1} asked of a history of {int(store.lengths[slots].min())} elements")
-    if not params[0].is_cuda:
-        raise L.RecnnHipError(f"{name}: the module lives on {dev} ({first}.device); it needs a GPU module "
-                              "(recnn_amd has no CPU fallback)")
-    if table.device != dev:
-        raise ValueError(f"{name}: the table lives on {table.device}, the module on {dev}")
-    return dev, E, H, U, T, t0, slots, params
+    return dev, E, H
 
 
 def _attn_head(enc, store, slots_d, U, t0, T, table, E, H):
@@ -2062,8 +2077,9 @@ def _attn_head(enc, store, slots_d, U, t0, T, table, E, H):
 @torch.no_grad()
 def attn_encode(enc, store, table, slots, T, *, t0=0):
     """h float32[U, T, H] of a `recnn_amd.nn.AttentionEncoder` for the users `slots` (store slots) over the steps t0 .. t0 + T - 1 of
-    their histories: step t attends to steps max(0, t - window + 1) .. t of THIS call (positions before t0 are not seen; there is no
-    carried state), its input being [table[item_t] | rating_t] read through the replay `store`.  Three launches: the in-projection
+    their histories: step t attends to steps max(0, t - window + 1) .. t of THIS call (positions before t0 are not seen; this call
+    carries no state -- `attn_append` serves a session step by step from a `KVCache`, with this call's bits), its input being
+    [table[item_t] | rating_t] read through the replay `store`.  Three launches: the in-projection
     (rows gathered through the store), the flash-style attention, the out-projection; fp32 on the exact-f32 MFMA.
 
     Equal calls give equal bits; a user's rows do not depend on the other users or on its place in the batch; the first `a` steps
@@ -2160,6 +2176,13 @@ def _transformer_call_args(name, enc, store, table, slots, T, t0):
     """The checks of `transformer_encode` / `transformer_encode_train`, on the host and by argument name, before any launch: those of
     `_attn_call_args`, then num_layers, dim_feedforward, activation and eps.  (dev, E, H, U, T, t0, slots, params, cfg) with params
     = embed's two, twelve per block, norm's two, and cfg = (heads, F, act, window or 0, alibi, eps)."""
+    pnames, params, shapes_of, cfg = _transformer_spec(name, enc)
+    dev, E, H, U, T, t0, slots, params = _attn_checked(name, enc, pnames, params, shapes_of, "embed.weight", store, table, slots, T, t0)
+    return dev, E, H, U, T, t0, slots, params, cfg
+
+
+def _transformer_spec(name, enc):
+    """(pnames, params, shapes_of, cfg) of a `TransformerStateEncoder`, its own settings checked; another module is refused by name."""
     if not isinstance(enc, TransformerStateEncoder):
         t = type(enc)
         raise L.RecnnHipError(f"{name}: the state encoder is a {t.__module__}.{t.__qualname__}, not a "
@@ -2182,9 +2205,8 @@ def _transformer_call_args(name, enc, store, table, slots, T, t0):
     def shapes_of(E, H):
         block = ((3 * H, H), (3 * H,), (H, H), (H,), (F, H), (F,), (H, F), (H,), (H,), (H,), (H,), (H,))
         return ((H, E + 1), (H,)) + block * len(enc.layers) + ((H,), (H,))
-    dev, E, H, U, T, t0, slots, params = _attn_checked(name, enc, pnames, params, shapes_of, "embed.weight", store, table, slots, T, t0)
     cfg = (enc.num_heads, F, TRANSFORMER_ACTIVATIONS[enc.activation], enc.window or 0, int(enc.alibi), float(enc.eps))
-    return dev, E, H, U, T, t0, slots, params, cfg
+    return pnames, params, shapes_of, cfg
 
 
 def _block_head(x, cfg):
@@ -2197,7 +2219,8 @@ def _block_head(x, cfg):
 @torch.no_grad()
 def transformer_encode(enc, store, table, slots, T, *, t0=0):
     """h float32[U, T, H] of a `recnn_amd.nn.TransformerStateEncoder` for the users `slots` (store slots) over the steps
-    t0 .. t0 + T - 1 of their histories (nothing is carried between calls: step t sees steps of THIS call only).  One gathered
+    t0 .. t0 + T - 1 of their histories (nothing is carried between calls: step t sees steps of THIS call only; `transformer_append`
+    serves a session step by step from a `KVCache`, with this call's bits).  One gathered
     embedding launch, four launches per block -- LN1 fused into the in-projection, the flash-style attention, the out-projection
     with the residual in its epilogue, and the fused feed-forward (LN2, linear1, activation, linear2, residual), whose [U T, F]
     activation never reaches memory -- and the final LayerNorm; fp32 on the exact-f32 MFMA.
@@ -2347,6 +2370,129 @@ def transformer_encode_train(enc, store, table, slots, T, *, t0=0, train_table=F
     for i in range(len(enc.layers)):
         x = TransformerBlockFunction.apply(x, cfg, *params[2 + 12 * i:14 + 12 * i])
     return LayerNormRowsFunction.apply(x, params[-2], params[-1], cfg[5])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Serving the two attention encoders step by step (nn/kv_cache.py, csrc/attn_dev.h): append n steps to sessions
+# whose keys and values live in a KVCache; the returned rows are the whole-history call's, bit for bit.
+def _append_call_args(name, enc, pnames, params, shapes_of, first, cache, table, items, ratings, rows):
+    """The checks of `attn_append` / `transformer_append`, on the host and by argument name, before any launch (a refused call
+    leaves the cache as it was): (dev, E, H, R, n, rows int64 numpy, items int32, ratings)."""
+    from .kv_cache import KVCache, encoder_config
+    dev, E, H = _attn_module_checked(name, enc, pnames, params, shapes_of, table)
+    _module_on_gpu(name, params, first, dev)
+    if not isinstance(cache, KVCache):
+        raise L.RecnnHipError(f"{name}: cache must be a recnn_amd.nn.KVCache (got a {type(cache).__qualname__})")
+    config = encoder_config(name, enc)
+    if cache.config != config:
+        raise L.RecnnHipError(f"{name}: the cache was built for (E, H, heads, layers, window) = {cache.config}, the encoder has {config}")
+    kv = cache.kv
+    if not (isinstance(kv, torch.Tensor) and kv.is_cuda):
+        raise L.RecnnHipError(f"{name}: cache.kv must live on the GPU (recnn_amd has no CPU fallback)")
+    if kv.dtype != torch.float32 or not kv.is_contiguous() or tuple(kv.shape) != (config[3], cache.n_sessions, cache.capacity, 2 * H) \
+            or kv.device != dev:
+        raise L.RecnnHipError(f"{name}: cache.kv must be a contiguous float32 [{config[3]}, {cache.n_sessions}, {cache.capacity}, "
+                              f"{2 * H}] tensor on {dev} (got {kv.dtype} {tuple(kv.shape)} on {kv.device})")
+    for arg, t, dtypes in (("table", table, (torch.float32,)), ("items", items, (torch.int64, torch.int32)),
+                           ("ratings", ratings, (torch.float32,))):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise L.RecnnHipError(f"{name}: {arg} must be a GPU tensor (recnn_amd has no CPU fallback)")
+        if t.dtype not in dtypes:
+            raise L.RecnnHipError(f"{name}: {arg} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+        if t.device != dev:
+            raise ValueError(f"{name}: {arg} lives on {t.device}, the module on {dev}")
+    if items.dim() != 2 or ratings.shape != items.shape:
+        raise ValueError(f"{name}: items and ratings must both be [R, n] (got items {tuple(items.shape)}, ratings {tuple(ratings.shape)})")
+    R, n = items.shape
+    if not 1 <= n <= cache.max_append:
+        raise ValueError(f"{name}: n = items.shape[1] = {n} must be in 1 .. max_append = {cache.max_append}")
+    rows = cache.checked_rows(rows, name, count=R)
+    lengths = cache.lengths
+    if not (isinstance(lengths, np.ndarray) and lengths.shape == (cache.n_sessions,) and lengths.dtype == np.int64
+            and (lengths >= 0).all()):
+        raise ValueError(f"{name}: cache.lengths must be a non-negative int64 numpy array [{cache.n_sessions}]")
+    if R and config[4] is None and int(lengths[rows].max()) + n > cache.capacity:
+        raise ValueError(f"{name}: an append of n = {n} at position {int(lengths[rows].max())} runs past capacity = {cache.capacity} "
+                         "(the encoder has no window: the cache is no ring)")
+    if R and int(lengths[rows].max()) + n >= 1 << 30:
+        raise ValueError(f"{name}: a session of {int(lengths[rows].max()) + n} positions; positions stay below 2^30")
+    if items.dtype == torch.int64:      # an id outside the table stays outside it in 32 bits
+        items = torch.where((items < 0) | (items >= table.shape[0]), -1, items).to(torch.int32)
+    return dev, E, H, R, n, rows, items.contiguous(), ratings.contiguous()
+
+
+def _cache_tail(cache, layer, pos_rows):
+    """The trailing cache arguments of recnn_attn_append / recnn_block_append: this layer's kv, n_sessions, capacity, pos, rows."""
+    return (L.ptr(cache.kv[layer]), cache.n_sessions, cache.capacity, L.ptr(pos_rows[0]), L.ptr(pos_rows[1]))
+
+
+def _pos_rows(cache, rows, dev):
+    """int32 [2, R] on the device: each row's position, then the row."""
+    return torch.from_numpy(np.stack([cache.lengths[rows], rows]).astype(np.int32)).to(dev)
+
+
+@torch.no_grad()
+def attn_append(enc, cache, table, items, ratings, rows=None):
+    """Extend the sessions `rows` of a `recnn_amd.nn.KVCache` by n steps each and return their h float32[R, n, H]: for a session whose
+    appended inputs so far are x_0 .. x_{P + n - 1}, rows P .. P + n - 1 of `attn_encode` over those P + n steps, BIT FOR BIT -- however
+    the history was split into appends, whatever R, the row's place in `rows`, the other sessions, the capacity, or the bits of slots
+    the session has not written.  `items` int64 or int32 [R, n] and `ratings` float32 [R, n] are the new steps' inputs, given
+    directly (no ReplayStore); `rows` the R distinct cache rows (default: all, in order); a row is extended from its own position
+    `cache.lengths[row]`, and the call writes the new k and v into the cache and advances `lengths` by n.
+
+    Four launches: the in-projection of the new rows (the gathered linear kernel reading [R, n] as a store), k and v into their
+    slots, the attention of the new rows over the cache (query blocks aligned to absolute positions, key tiles staged from the ring),
+    the out-projection.  An item id outside the table gives NaN rows for that session from that step on, as the whole-history call
+    does for the steps it has not yet returned; other sessions keep their bits.
+
+    Refused before any launch, the cache untouched -- RecnnHipError: everything `attn_encode` refuses of the module, a cache that is
+    no KVCache or was built for another (E, H, heads, layers, window), a CPU cache, table, items or ratings, a wrong dtype;
+    ValueError: items and ratings not both [R, n], n outside 1 .. cache.max_append, rows duplicate, out of range or not R of them,
+    an append past capacity without a window."""
+    params, shapes_of = _attn_spec("attn_append", enc)
+    dev, E, H, R, n, rows, items, ratings = _append_call_args("attn_append", enc, _ATTN_PARAMS, params, shapes_of, "in_proj_weight",
+                                                              cache, table, items, ratings, rows)
+    h = _f32_on(dev)(R, n, H)
+    if R == 0:
+        return h
+    user_off, slots = cache.dense_store(n)
+    ws = L.workspace("recnn_kv_append_workspace_bytes", R, n, H, device=dev)
+    L.call("recnn_attn_append", L.ptr(items), L.ptr(ratings), L.ptr(user_off), L.ptr(slots), R, n, L.ptr(table), table.shape[0], E, H,
+           enc.num_heads, enc.window or 0, int(enc.alibi), L.ptr(enc.in_proj_weight), L.ptr(enc.in_proj_bias), L.ptr(enc.out_proj.weight),
+           L.ptr(enc.out_proj.bias), *_cache_tail(cache, 0, _pos_rows(cache, rows, dev)), L.ptr(h), L.ptr(ws), L.current_stream())
+    cache.lengths[rows] += n
+    return h
+
+
+@torch.no_grad()
+def transformer_append(enc, cache, table, items, ratings, rows=None):
+    """`attn_append` for a `recnn_amd.nn.TransformerStateEncoder`: h float32[R, n, H], rows P .. P + n - 1 of `transformer_encode`
+    over the session's P + n steps, bit for bit; the cache holds k and v of every block.  The embedding of the new steps (the
+    gathered linear kernel on [R, n] read as a store), per block the LN1 + in-projection, k and v into the block's slots, the
+    attention over the cache, the out-projection with its residual and the fused feed-forward, then the final LayerNorm: the
+    row-wise launches are `transformer_encode`'s kernels on R n dense rows.  Arguments, refusals and the NaN rule as `attn_append`,
+    with everything `transformer_encode` refuses of the module."""
+    name = "transformer_append"
+    pnames, params, shapes_of, cfg = _transformer_spec(name, enc)
+    dev, E, H, R, n, rows, items, ratings = _append_call_args(name, enc, pnames, params, shapes_of, "embed.weight", cache, table, items,
+                                                              ratings, rows)
+    x = _f32_on(dev)(R, n, H)
+    y = torch.empty_like(x)
+    if R == 0:
+        return y
+    user_off, slots = cache.dense_store(n)
+    L.call("recnn_seq_embed", L.ptr(items), L.ptr(ratings), L.ptr(user_off), L.ptr(slots), R, 0, n, L.ptr(table), table.shape[0], E, H,
+           L.ptr(params[0]), L.ptr(params[1]), L.ptr(x), L.current_stream())
+    ws = L.workspace("recnn_kv_append_workspace_bytes", R, n, H, device=dev)
+    pos_rows = _pos_rows(cache, rows, dev)
+    for i in range(len(enc.layers)):
+        L.call("recnn_block_append", *_block_head(x, cfg), *(L.ptr(p) for p in params[2 + 12 * i:14 + 12 * i]),
+               *_cache_tail(cache, i, pos_rows), L.ptr(y), L.ptr(ws), L.current_stream())
+        x, y = y, x
+    L.call("recnn_layernorm_rows", L.ptr(x), R * n, H, L.ptr(params[-2]), L.ptr(params[-1]), C.c_float(cfg[5]), L.ptr(y),
+           L.current_stream())
+    cache.lengths[rows] += n
+    return y
 
 
 def state_encode(encoder, store, table, slots, T, *, train=False, train_table=False):

@@ -434,6 +434,10 @@ int mlpf_launch(const FrozenBatch& b, int nprob, hipStream_t s, int panel_rows) 
     }
     RECNN_REQUIRE(k64 >= 2, "mlp_frozen: layer 1 needs at least 128 k");
     RECNN_REQUIRE(p.ldw1 % 8 == 0 && p.ldw2 % 8 == 0 && (((uintptr_t)p.W1 | (uintptr_t)p.W2) & 15) == 0, "mlp_frozen: bad weight pitches");
+    // (whatever H and out_dim: the stream reads HP rows of W1 / W2 and 128 of W3, HP columns of W2 / W3, and the panel stores write HP
+    //  columns of h1 / h2, those at and beyond H as +0 -- the arrays must be that large; their pitches are what can be checked here)
+    RECNN_REQUIRE(p.ldw2 >= HP, "mlp_frozen: W2 (and W3) must hold %d columns per row, zero or not beyond H", HP);
+    RECNN_REQUIRE((!p.h1 && !p.h2) || (p.ldh >= HP && p.ldh % 8 == 0), "mlp_frozen: stored activations take %d columns per row (a pitch that is a multiple of 8)", HP);
     RECNN_REQUIRE(p.mask_mode == RECNN_MASK_NONE || p.mask_mode == RECNN_MASK_HASH, "mlp_frozen: hash dropout masks only");
     RECNN_REQUIRE(p.store_row0 >= 0 && p.store_row0 <= p.rows, "mlp_frozen: the first stored activation row lies outside the problem");
     RECNN_REQUIRE(p.rows_per_set == 0 || p.rows_per_set % 32 == 0, "mlp_frozen: batches must be multiples of 32 rows");

@@ -23,7 +23,9 @@ void recnn_debug_l1_trace(void* device_u64_wg16);
  * w1_col[g] .. of W1 [H, ldw1]; W3 != NULL: an actor (out [rows, ldo] bf16 = h2 W3^T + b3 + clip(addend), out_dim <= 128), else a critic
  * (q [rows] fp32 = h2 . w3row + b3[0]).  mask_mode RECNN_MASK_NONE | RECNN_MASK_HASH with (seed, step + batch index, stream1 | stream2),
  * batches of rows_per_set rows (0: one batch); h1 / h2 optional bf16 [rows, ldh], rows store_row0 .. stored.  panel_rows 128 | 64 (the
- * same numbers).  sizeof_args = sizeof(recnn_debug_frozen_args) as the caller sees it (refused if it differs). */
+ * same numbers).  Whatever H and out_dim, the kernel streams 256 rows of W1 and W2, 128 rows of W3 and 256 columns of W2 / W3, and stores
+ * 256 columns of h1 / h2 (+0 at and beyond H): the arrays must be that large (ldw2, ldw3, ldh >= 256 are checked; the row counts cannot
+ * be); what lies at or beyond H never reaches a result.  sizeof_args = sizeof(recnn_debug_frozen_args) as the caller sees it (refused if it differs). */
 typedef struct recnn_debug_frozen_args {
   const void* A[4]; int64_t lda[4]; int K[4]; int w1_col[4]; int nseg;
   const void* W1; int64_t ldw1; const void* W2; int64_t ldw2; const void* W3; int64_t ldw3;

@@ -5,8 +5,9 @@ branches; the engine reaches only some of their combinations and always gives la
 (a) directly: segment lists that give 2, 2, 3, 4 and 23 layer-1 slabs -- a third slab exists or not, a boundary between contraction
     segments at every slab -- on a single panel, a ragged last panel and two panels, for an actor with hash masks, an actor with a
     clipped addend, a plain actor and a critic.  The 64-row and the 128-row workgroup forms compute every output element by the same
-    arithmetic, so their outputs are equal BIT FOR BIT; the direct entry has no third implementation to compare with, so the cases
-    also check that an option changes what it must change (masks, the addend, the first stored row), that a narrow output equals the
+    arithmetic, so their outputs are equal BIT FOR BIT.  The float64 reference of the kernel is tests/test_gpu_frozen_exact.py (lattice
+    operands, every stored stage equal bit for bit); this file remains the test of form against form on ordinary random operands,
+    where the cases also check that an option changes what it must change (masks, the addend, the first stored row), that a narrow output equals the
     matching columns of a full one, and that what lies beyond out_dim or below the first stored row is never written.
 (b) through the engine on the shapes of tests/test_gpu_frozen_window.py (128 rows per batch, users of 11-14 items, policy period 3,
     run(7) from step 5 = segments of 2 + 3 + 2, all batched: cycle_min_seg 2), 128-row and 64-row workgroups (frozen_half 0 | 1):
@@ -56,8 +57,12 @@ class _Net:
         self.addend = (torch.randn(rows, OUT + 4, generator=g) * 0.5).to(cuda)
 
 
-def _forward(net, kind, panel_rows, *, out_dim=OUT, store_row0=0, acts=True, rows_per_set=0):
-    """One launch; returns {"out" | "q", "h1", "h2"} as CPU tensors.  kind: "actor_hash", "actor_add", "actor_plain", "critic"."""
+def _forward(net, kind, panel_rows, *, out_dim=OUT, store_row0=0, acts=True, rows_per_set=0, hidden=H, add_clip=0.3, masks=None, add=None, ldh=H):
+    """One launch; returns {"out" | "q", "h1", "h2"} as CPU tensors.  kind: "actor_hash", "actor_add", "actor_plain", "critic".
+    (tests/test_gpu_frozen_exact.py drives the same plumbing with `hidden`, `add_clip`, a pitch `ldh` of the stored activations and
+    `masks` / `add` that override what the kind implies.)"""
+    masks = kind == "actor_hash" if masks is None else masks
+    add = kind == "actor_add" if add is None else add
     from recnn_amd import _lib as L
     lib = L.load()
     dev = net.W1.device
@@ -67,14 +72,14 @@ def _forward(net, kind, panel_rows, *, out_dim=OUT, store_row0=0, acts=True, row
     a.nseg = len(net.segs)
     a.W1, a.ldw1, a.W2, a.ldw2 = net.W1.data_ptr(), net.W1.stride(0), net.W2.data_ptr(), net.W2.stride(0)
     a.b1, a.b2, a.b3 = net.b1.data_ptr(), net.b2.data_ptr(), net.b3.data_ptr()
-    a.rows, a.H, a.out_dim = net.rows, H, out_dim
-    a.mask_mode = L.MASK_HASH if kind == "actor_hash" else L.MASK_NONE
+    a.rows, a.H, a.out_dim = net.rows, hidden, out_dim
+    a.mask_mode = L.MASK_HASH if masks else L.MASK_NONE
     a.seed, a.stream1, a.stream2, a.step, a.rows_per_set = 4711, 2, 3, 5, rows_per_set
     res = {}
     if acts:
-        res["h1"] = torch.full((net.rows, H), SENTINEL, dtype=torch.bfloat16, device=dev)
-        res["h2"] = torch.full((net.rows, H), SENTINEL, dtype=torch.bfloat16, device=dev)
-        a.h1, a.h2, a.ldh, a.store_row0 = res["h1"].data_ptr(), res["h2"].data_ptr(), H, store_row0
+        res["h1"] = torch.full((net.rows, ldh), SENTINEL, dtype=torch.bfloat16, device=dev)
+        res["h2"] = torch.full((net.rows, ldh), SENTINEL, dtype=torch.bfloat16, device=dev)
+        a.h1, a.h2, a.ldh, a.store_row0 = res["h1"].data_ptr(), res["h2"].data_ptr(), ldh, store_row0
     if kind == "critic":
         a.w3row = net.w3row.data_ptr()
         res["q"] = torch.full((net.rows,), SENTINEL, dtype=torch.float32, device=dev)
@@ -83,8 +88,8 @@ def _forward(net, kind, panel_rows, *, out_dim=OUT, store_row0=0, acts=True, row
         a.W3, a.ldw3 = net.W3.data_ptr(), net.W3.stride(0)
         res["out"] = torch.full((net.rows, OUT + 4), SENTINEL, dtype=torch.bfloat16, device=dev)
         a.out, a.ldo = res["out"].data_ptr(), res["out"].stride(0)
-        if kind == "actor_add":
-            a.addend, a.ld_add, a.add_clip = net.addend.data_ptr(), net.addend.stride(0), 0.3
+        if add:
+            a.addend, a.ld_add, a.add_clip = net.addend.data_ptr(), net.addend.stride(0), add_clip
     a.panel_rows = panel_rows
     L.check(lib.recnn_debug_frozen_forward(C.byref(a), C.sizeof(a), None), "recnn_debug_frozen_forward")
     torch.cuda.synchronize()

@@ -687,7 +687,11 @@ int recnn_engine_unit_backward(recnn_engine* e);
  * "cycle_xn0" / "1" (the packed next rows whose action slot holds it otherwise: the engine's own allocation, NULL while it has none);
  * what the cycle gather writes, per copy: "cycle_xs0" / "1" (packed [action | state] rows), "cycle_tail_n0" / "1" (window mode's next
  * ratings; NULL where the dims do not allow that mode), "cycle_reward0" / "1", "cycle_done0" / "1".  "actor_l1part": the clip quirk's
- * |g| sum per optimizer workgroup of the actor as the last policy step left them (fp32, one row per workgroup). */
+ * |g| sum per optimizer workgroup of the actor as the last policy step left them (fp32, one row per workgroup).
+ * "<net>_w1_shadow" / "<net>_w2_shadow" / (actors) "<net>_w3_shadow" with <net> one of policy, target_policy, value1, target_value1,
+ * value2, target_value2: the compute-type copy of that weight which the optimizer pass rewrites -- [out, ld] rows in the engine's compute
+ * type, zero padded; a critic's W1 columns rotated to [action | state]; split-bf16 rows in their physical layout (h_cols is the logical
+ * column count, h_ld the physical pitch). */
 const void* recnn_engine_buffer(recnn_engine* e, const char* name, int64_t* h_rows, int64_t* h_cols,
                                 int64_t* h_ld, int* h_is_f32);
 

@@ -580,6 +580,25 @@ extern "C" const void* recnn_engine_buffer(recnn_engine* e, const char* name, in
       {"cycle_reward0", e->m_reward_b[0], 1, 1, 1},                {"cycle_reward1", e->m_reward_b[1], 1, 1, 1},
       {"cycle_done0", e->m_done_b[0], 1, 1, 1},                    {"cycle_done1", e->m_done_b[1], 1, 1, 1},
   };
+  // the compute-type weight shadows the optimizer pass rewrites: "<net>_w1_shadow" / "_w2_shadow" / (actors) "_w3_shadow", whole padded
+  // rows in the engine's compute type (split rows: physical pitch, logical column count)
+  static const char* const net_name[RECNN_NET_COUNT] = {"policy", "target_policy", "value1", "target_value1", "value2", "target_value2"};
+  static const char* const sh_name[3] = {"_w1_shadow", "_w2_shadow", "_w3_shadow"};
+  for (int ni = 0; ni < RECNN_NET_COUNT; ++ni) {
+    const size_t len = strlen(net_name[ni]);
+    if (strncmp(name, net_name[ni], len) || !net_used(e, ni)) continue;
+    const Net& n = e->net[ni];
+    const int which[3] = {W1, W2, W3};
+    const int64_t r[3] = {e->H, e->H, e->A}, c[3] = {n.in_dim, e->H, e->H}, l[3] = {n.ld_w1, n.ld_w2, n.ld_w3};
+    for (int k = 0; k < 3; ++k) {
+      if (strcmp(name + len, sh_name[k]) || n.sh_off[which[k]] < 0 || !n.shadow) continue;
+      if (rows) *rows = r[k];
+      if (cols) *cols = c[k];
+      if (ld) *ld = l[k];
+      if (is_f32) *is_f32 = e->twins ? 0 : 1;
+      return n.shadow + n.sh_off[which[k]] * e->esz;
+    }
+  }
   for (const Ent& t : cyc)
     if (!strcmp(t.n, name)) {
       if (rows) *rows = MB;

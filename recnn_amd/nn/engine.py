@@ -394,8 +394,9 @@ class StepEngine:
             return {"value1": v[0], "value2": v[1], "policy": v[2]}
         return {"value": v[0], "policy": v[1]}
 
-    def buffer(self, name: str, rows: Optional[int] = None) -> torch.Tensor:
-        """Copy of an intermediate device buffer (debug / tests)."""
+    def buffer(self, name: str, rows: Optional[int] = None, raw: bool = False) -> torch.Tensor:
+        """Copy of an intermediate device buffer (debug / tests).  raw: the stored [rows, ld] array itself, padding included, in its
+        storage type (split-bf16 rows undecoded)."""
         r, c, ld, f = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
         p = self.lib.recnn_engine_buffer(self.handle, name.encode(), C.byref(r), C.byref(c), C.byref(ld), C.byref(f))
         if not p:
@@ -403,16 +404,18 @@ class StepEngine:
         rows = int(r.value) if rows is None else rows
         esz = 4 if f.value else (4 if self.dtype == "fp32" else 2)
         nbytes = rows * ld.value * esz
-        raw = None
+        raw_bytes = None
         for owner in (self.workspace, self.xn, self.xs) + tuple(getattr(self, "_bound", ())[:2]):
             base = owner.data_ptr()
             if base <= p < base + owner.numel() * owner.element_size():
-                raw = owner.view(-1).view(torch.uint8)[p - base: p - base + nbytes]
+                raw_bytes = owner.view(-1).view(torch.uint8)[p - base: p - base + nbytes]
                 break
-        if raw is None:
+        if raw_bytes is None:
             raise KeyError(name)
         dt = torch.float32 if esz == 4 else torch.bfloat16
-        t = raw.view(dt).view(rows, ld.value)
+        t = raw_bytes.view(dt).view(rows, ld.value)
+        if raw:
+            return t.clone()
         if esz == 2 and self.dtype == "bf16x3":
             # split-bf16 rows (csrc/x3.h): logical column c = hi at 2 (c & ~31) + (c & 31), lo 32 elements further
             col = torch.arange(c.value, device=t.device)
